@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- units/sec mapped by the MI355X gmapper hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4|cfg5] [--reads-per-step R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4|cfg5] [--reads-per-step R] [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path (seed lookup -> windows -> vector SW -> full SW -> SAM records) over one batch of R synthetic reads / pairs.
 Workloads:
@@ -15,9 +15,14 @@ N > 1: one rank per GPU (torch.distributed, backend nccl = RCCL); rank 0 builds 
 collective); every rank maps its own read shard (weak scaling: R units per rank per step).  Prints ONE JSON line on rank 0.  The ranks come either from
 the caller (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`: WORLD_SIZE must then equal --gpus) or from this script: a plain
 `python bench.py --gpus N` starts them itself as a CHILD torch.distributed.run (launch_ranks; the parent never touches the GPU and exits with the child's code).
-The default N = 1 line also carries `other_workloads`: cfg4 and cfg5, three steps each, with their own roofline and parity-sample fields.
+A plain run sets up, warms up, times the K steps and prints the line (plus --dump-outputs).  --full adds what the headline does not need: the CPU baseline
+with its parity sample (`cpu_baseline`), and on the default N = 1 line `other_workloads` (cfg5, cfg4, cfg2, text and file input, three steps each, with their
+own roofline and parity-sample fields) and `host_sensitivity`.
+--dump-outputs DIR: after the timed steps, the SAM text the last timed step returned, as arrays (sam_arrays): DIR/sam_records.npy, sam_record_crc32.npy,
+sam_totals.npy.
 """
-import argparse, json, os, sys, time
+import argparse, ctypes as C, json, os, sys, time, zlib
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -119,20 +124,25 @@ def selftest_ranks(steps: int = 3, units: int = 1000):
 
 
 def make_pools(synth, contigs, kind, R, L, rseed, rank, n_pool, dev):
-    """n_pool distinct synthetic batches for this rank (letter space: packed and resident in HBM; colour space / pairs: packed host buffers)"""
+    """n_pool distinct synthetic batches for this rank (letter space: packed and resident in HBM; colour space / pairs: packed host buffers).
+    The batches are generated on host threads (each from its own seed, so the same arrays as one after the other) and uploaded in order."""
     import torch
-    pools = []
-    for b in range(n_pool):
+
+    def one(b):
         sd = shard_seed(rseed, rank, n_pool, b)
         if kind == "ls":
             reads, _ = synth.make_reads(contigs, R, L, sd)
-            pools.append(torch.from_numpy(synth.pack_reads(reads).view(np.int32)).to(dev))          # resident in HBM
+            return synth.pack_reads(reads).view(np.int32)
         elif kind == "cs":
             reads, _ = synth.make_cs_reads(contigs, R, L, sd)
-            pools.append((np.ascontiguousarray(synth.pack_reads(np.ascontiguousarray(reads[:, 1:]))), np.ascontiguousarray(reads[:, 0])))
-        else:
-            reads, _ = synth.make_pairs(contigs, R, L, sd)
-            pools.append((np.ascontiguousarray(synth.pack_reads(np.ascontiguousarray(reads[0::2]))), np.ascontiguousarray(synth.pack_reads(np.ascontiguousarray(reads[1::2])))))
+            return (np.ascontiguousarray(synth.pack_reads(np.ascontiguousarray(reads[:, 1:]))), np.ascontiguousarray(reads[:, 0]))
+        reads, _ = synth.make_pairs(contigs, R, L, sd)
+        return (np.ascontiguousarray(synth.pack_reads(np.ascontiguousarray(reads[0::2]))), np.ascontiguousarray(synth.pack_reads(np.ascontiguousarray(reads[1::2]))))
+
+    with ThreadPoolExecutor(max(1, min(n_pool, usable_cores()))) as ex:
+        pools = list(ex.map(one, range(n_pool)))
+    if kind == "ls":
+        pools = [torch.from_numpy(p).to(dev) for p in pools]                                 # resident in HBM
     return pools
 
 
@@ -142,16 +152,47 @@ def make_sample(synth, contigs, kind, n, L, rseed):
     return synth.make_pairs(contigs, n, L, rseed + 104729)[0]
 
 
-def timed_steps(gm, sess, kind, pools, R, L, steps, warmup, world, dist, dev, emit_sam=True):
+def step_keep(gm, sess, kind, p, R, L, popts, emit_sam):
+    """one step through the same entry point as Session.map_device / map_cs_packed / map_pairs_packed, but the SAM text is left in the library's buffer:
+    returns (pointer, length), to be read and gm_free'd once the clock has stopped (--dump-outputs)"""
+    lib = gm.lib(); sam = C.c_void_p(); sl = C.c_size_t(); st = gm.MapStats()
+    u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+    if kind == "ls":
+        rc, what = lib.gm_map_reads_device(sess.h, R, L, C.c_void_p(p.data_ptr()), int(emit_sam), C.byref(sam), C.byref(sl), C.byref(st)), "gm_map_reads_device"
+    elif kind == "cs":
+        rc, what = lib.gm_map_reads_cs(sess.h, R, L, p[0].ctypes.data_as(u32p), p[1].ctypes.data_as(u8p), None, C.byref(sam), C.byref(sl), C.byref(st)), "gm_map_reads_cs"
+    else:
+        rc, what = lib.gm_map_pairs(sess.h, R, L, p[0].ctypes.data_as(u32p), L, p[1].ctypes.data_as(u32p), None, None, C.byref(popts),
+                                    C.byref(sam), C.byref(sl), C.byref(st)), "gm_map_pairs"
+    if rc != 0:
+        if sam.value: lib.gm_free(sam)
+        gm._check(rc, what)
+    sess.stats = st.as_dict()
+    return sam, sl.value
+
+
+def take_text(gm, kept) -> bytes:
+    """the text step_keep left in the library's buffer, copied out; the buffer is released"""
+    sam, n = kept
+    out = C.string_at(sam, n) if sam.value else b""
+    if sam.value: gm.lib().gm_free(sam)
+    return out
+
+
+def timed_steps(gm, sess, kind, pools, R, L, steps, warmup, world, dist, dev, emit_sam=True, keep_last=False):
     """W untimed steps, then EXACTLY `steps` timed ones between barrier + synchronize on both sides; the job's time is the slowest rank's.
-    Returns (seconds, K1 event milliseconds, K1 algorithmic bytes, K1 launches, summed stats)."""
+    Returns (seconds, K1 event milliseconds, K1 algorithmic bytes, K1 launches, summed stats, kept); with keep_last the last timed step goes through step_keep
+    and kept is its (pointer, length) -- the text stays in the library's buffer until take_text, so nothing is added inside the timed region -- else None."""
     import torch
     popts = gm.PairOpts.default("opp-in", 100, 600)
     n_pool = len(pools)
+    kept = None
 
-    def step(i):
+    def step(i, keep=False):
+        nonlocal kept
         p = pools[i % n_pool]
-        if kind == "ls": sess.map_device(p.data_ptr(), R, L, emit_sam=emit_sam, return_bytes=False)
+        if keep: kept = step_keep(gm, sess, kind, p, R, L, popts, emit_sam)
+        elif kind == "ls": sess.map_device(p.data_ptr(), R, L, emit_sam=emit_sam, return_bytes=False)
         elif kind == "cs": sess.map_cs_packed(p[0], p[1], R, L, return_bytes=False)
         else: sess.map_pairs_packed(p[0], p[1], R, L, L, popts, return_bytes=False)
         return sess.stats
@@ -165,7 +206,7 @@ def timed_steps(gm, sess, kind, pools, R, L, steps, warmup, world, dist, dev, em
     agg = {}
     t0 = time.perf_counter()
     for i in range(steps):
-        st = step(warmup + i)
+        st = step(warmup + i, keep=keep_last and i == steps - 1)
         ms, nb, nl = sess.lookup_timing()                    # K1's own HIP events on its stream (paired mode: both mate sets of every sub-batch)
         lk_ms += ms; lk_bytes += (nb or st["list_bytes"]); lk_launch += nl
         for k, v in st.items():
@@ -174,7 +215,58 @@ def timed_steps(gm, sess, kind, pools, R, L, steps, warmup, world, dist, dev, em
     if world > 1:
         dist.barrier()
     dt = reduce_max_time(time.perf_counter() - t0, world, dist, dev)
-    return dt, lk_ms, lk_bytes, lk_launch, agg
+    return dt, lk_ms, lk_bytes, lk_launch, agg, kept
+
+
+SAM_COLUMNS = ("unit", "flag", "rname", "pos", "mapq", "rnext", "pnext", "tlen", "AS", "NM")
+DUMP_UNITS = 131072          # reads (pairs for cfg5) of the last step whose records are dumped field by field: a fixed, seeded sample of larger steps
+
+
+def sam_arrays(text: bytes, n_units: int, seed: int = 12345) -> dict:
+    """The SAM text of one step as float64 arrays (--dump-outputs), so that two builds can be compared output for output:
+      sam_records       [records, 10]  per record of the sampled units: SAM_COLUMNS -- unit = the number in QNAME (r<i>, p<i>), rname / rnext = the
+                                       number in the contig name (-1 for '*'; '=' is rname), AS / NM = the tags' values (-1 when absent)
+      sam_record_crc32  [records]      CRC-32 of each of those records' whole line (CIGAR, SEQ, QUAL and every tag included)
+      sam_totals        [3]            of the WHOLE text: records, bytes, CRC-32
+    The sample: every record of DUMP_UNITS units drawn without replacement by a fixed seed (every unit when n_units <= DUMP_UNITS)."""
+    import re
+    num = re.compile(rb"(\d+)")
+    lines = [l for l in text.split(b"\n") if l and not l.startswith(b"@")]
+    totals = np.array([len(lines), len(text), zlib.crc32(text)], dtype=np.float64)
+    keep = None
+    if n_units > DUMP_UNITS:
+        keep = np.zeros(n_units, dtype=bool)
+        keep[np.random.Generator(np.random.PCG64(seed)).choice(n_units, DUMP_UNITS, replace=False)] = True
+
+    def unit_of(qname):
+        m = num.search(qname)
+        return int(m.group(1)) if m else -1
+
+    def ref_of(name, same):
+        if name == b"*": return -1
+        if name == b"=": return same
+        m = num.search(name[::-1])
+        return int(m.group(1)[::-1]) if m else zlib.crc32(name)
+
+    rows, crcs = [], []
+    for l in lines:
+        u = unit_of(l[:l.find(b"\t")])
+        if keep is not None and not (0 <= u < n_units and keep[u]):
+            continue
+        f = l.split(b"\t")
+        tags = {t[:2]: t[5:] for t in f[11:] if t[2:5] == b":i:"}
+        rn = ref_of(f[2], -1)
+        rows.append((u, int(f[1]), rn, int(f[3]), int(f[4]), ref_of(f[6], rn), int(f[7]), int(f[8]), int(tags.get(b"AS", -1)), int(tags.get(b"NM", -1))))
+        crcs.append(zlib.crc32(l))
+    return {"sam_records": np.array(rows, dtype=np.float64).reshape(-1, len(SAM_COLUMNS)), "sam_record_crc32": np.array(crcs, dtype=np.float64),
+            "sam_totals": totals}
+
+
+def dump_outputs(d: str, arrays: dict) -> dict:
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def roofline_of(gm, lk_ms, lk_bytes, lk_launch, units):
@@ -211,16 +303,22 @@ def main():
     ap.add_argument("--workload", default=os.environ.get("GM_BENCH_WORKLOAD", "cfg3"), choices=sorted(WORKLOADS))
     ap.add_argument("--reads-per-step", type=int, default=0, help="units (reads, or pairs for cfg5) per rank per step; 0 = the workload's default")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the genome (debugging only; makes the result invalid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: cpu_baseline (+ parity sample), "
+                                                           "other_workloads and host_sensitivity (default N = 1 line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the SAM text of the last timed step as float64 arrays "
+                                                                         "(DIR/sam_records.npy, sam_record_crc32.npy, sam_totals.npy; see sam_arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=0, help="units in the CPU-baseline sample; 0 = the workload's default (10-30 s of CPU work)")
     ap.add_argument("--no-sam", action="store_true", help="skip SAM text emission on the host (alignment records only; letter-space unpaired only)")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the cfg4 / cfg5 entries of the default line")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: skip the other_workloads and host_sensitivity entries of the default line")
     ap.add_argument("--selftest-ranks", action="store_true", help="rank logic only (gloo, sleeps instead of GPU steps): what tests/test_dist_gloo.py drives through launch_ranks")
     args = ap.parse_args()
 
     have_ranks = "WORLD_SIZE" in os.environ
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if not have_ranks and args.gpus > 1:
         # plain `python bench.py --gpus N`: start the N ranks as a child job.  This process makes no GPU call of any kind (not even a device count): a rank without
         # a GPU fails by itself ("local rank k has no GPU") and the child's exit code is ours.
@@ -268,8 +366,6 @@ def main():
     t_gen = time.time() - t0
     n_pool = min(10, args.steps + args.warmup)           # distinct batches, cycled: 10 x 1 M reads = the 10 M reads of BASELINE configs[2] (round 3 cycled two)
     pools = make_pools(synth, contigs, kind, R, L, rseed, rank, n_pool, dev)
-    n_sample = args.cpu_sample or {"ls": 200_000, "cs": 50_000, "pairs": 20_000}[kind]
-    sample = make_sample(synth, contigs, kind, n_sample, L, rseed)
 
     # ---- index: built on rank 0's GPU, broadcast once ----
     params = gm.default_params_cs() if kind == "cs" else gm.default_params()
@@ -287,7 +383,14 @@ def main():
     sub_batch = lambda k: int(os.environ.get("GM_SUBBATCH", "131072" if k != "pairs" else "65536"))
     sess = gm.Session(ix, params=params, max_batch_reads=sub_batch(kind))
 
-    dt, lk_ms, lk_bytes, lk_launch, agg = timed_steps(gm, sess, kind, pools, R, L, args.steps, args.warmup, world, dist, dev, emit_sam=not args.no_sam)
+    dt, lk_ms, lk_bytes, lk_launch, agg, kept = timed_steps(gm, sess, kind, pools, R, L, args.steps, args.warmup, world, dist, dev, emit_sam=not args.no_sam,
+                                                            keep_last=args.dump_outputs is not None)
+    dumped = None
+    if kept is not None:
+        text = take_text(gm, kept)
+        if rank == 0:                                        # (rank 0's shard: its reads are the ones a one-GPU run maps)
+            dumped = dump_outputs(args.dump_outputs, sam_arrays(text, R))
+        del text
     total_units = R * args.steps * world
     value = total_units / dt
     threads_all = [host_threads]
@@ -327,11 +430,15 @@ def main():
                            "mapped_frac": agg["reads_matched"] / U, "exact_order_frac": agg["exact_order_reads"] / (2 * U),
                            "post_sw_host_redo": agg.get("post_sw_host_redo", 0) / U, "mp_unfiltered": agg.get("mp_unfiltered", 0) / U}
         out["setup_s"] = {"genome_gen": t_gen, "index_build": t_index, "index_bcast": t_bcast, "index_bytes": ix.nbytes}
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped, "sam_records_columns": list(SAM_COLUMNS)}
         o_ls = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the CPU restatement (oracle, "port") on this box's host cores over a bounded sample of the same workload -- on as many threads as the GPU run's
             # host side used (this process's CPU affinity share), so that the two numbers sit on the same cores
             from tests import oracle_api as oa
+            n_sample = args.cpu_sample or {"ls": 200_000, "cs": 50_000, "pairs": 20_000}[kind]
+            sample = make_sample(synth, contigs, kind, n_sample, L, rseed)
             ncores = int(os.environ.get("GM_CPU_THREADS", min(host_threads, usable_cores())))      # the CPU leg runs flat out: its threads = the cores the container grants
             oa.load().gmo_set_threads(ncores)
             t0 = time.time(); o = oa.Session(contigs, opts="colour=1" if kind == "cs" else None); t_oidx = time.time() - t0
@@ -358,7 +465,7 @@ def main():
             # parity spot check on the sample while we are here
             out["cpu_baseline"]["sample_sam_identical"] = bool(product_sample(sess, kind, sample) == sam)
         # ---- the other single-GPU configurations, three steps each, so that their numbers are measured by whoever runs the default line ----
-        if world == 1 and args.workload == "cfg3" and args.scale == 1.0 and not args.no_other_workloads and not args.no_sam:
+        if args.full and world == 1 and args.workload == "cfg3" and args.scale == 1.0 and not args.no_other_workloads and not args.no_sam:
             others = {}
             for wname in ("cfg5", "cfg4"):
                 k2, _, _, L2, rs2, R2, m2, u2, d2 = WORKLOADS[wname]
@@ -369,7 +476,7 @@ def main():
                     t_ix2 = time.time() - t0
                     s2 = gm.Session(ix2, params=p2, max_batch_reads=sub_batch(k2))
                     pools2 = make_pools(synth, contigs, k2, R2, L2, rs2, 0, 2, dev)
-                    dt2, ms2, by2, nl2, agg2 = timed_steps(gm, s2, k2, pools2, R2, L2, 3, 1, 1, dist, dev)
+                    dt2, ms2, by2, nl2, agg2, _ = timed_steps(gm, s2, k2, pools2, R2, L2, 3, 1, 1, dist, dev)
                     e = {"metric": m2, "unit": u2, "workload": d2, "value": R2 * 3 / dt2, "steps": 3, "warmup": 1, "ms_per_step": 1e3 * dt2 / 3,
                          "roofline": {k: v for k, v in roofline_of(gm, ms2, by2, nl2, R2 * 3).items() if k in ("kernel", "achieved", "frac", "avg_launch_ms", "launches", "alg_bytes_per_unit")},
                          "stages_ms_per_step": {k: agg2[k] / 3 for k in agg2 if k.startswith("ms_")}}
@@ -395,7 +502,7 @@ def main():
                 t0 = time.time(); contigs2 = synth.make_genome(synth.contig_lengths(g2, 1.0), gs2); ix2 = gm.Index(contigs2, device=local, params=params); t_ix2 = time.time() - t0
                 s2 = gm.Session(ix2, params=params, max_batch_reads=sub_batch(k2))
                 pools2 = make_pools(synth, contigs2, k2, R2, L2, rs2, 0, 2, dev)
-                dt2, ms2, by2, nl2, agg2 = timed_steps(gm, s2, k2, pools2, R2, L2, 3, 1, 1, dist, dev)
+                dt2, ms2, by2, nl2, agg2, _ = timed_steps(gm, s2, k2, pools2, R2, L2, 3, 1, 1, dist, dev)
                 e = {"metric": m2, "unit": u2, "workload": d2, "value": R2 * 3 / dt2, "steps": 3, "warmup": 1, "ms_per_step": 1e3 * dt2 / 3,
                      "roofline": {k: v for k, v in roofline_of(gm, ms2, by2, nl2, R2 * 3).items() if k in ("kernel", "achieved", "frac", "avg_launch_ms", "launches", "alg_bytes_per_unit")},
                      "stages_ms_per_step": {k: agg2[k] / 3 for k in agg2 if k.startswith("ms_")}, "genome_and_index_s": t_ix2}

@@ -1,8 +1,8 @@
 """gm_merge_sam (shrimp_amd/csrc/gm_merge.cpp) against the reference's mergesam (ref: mergesam/mergesam.c).
 
 Host-only text processing inside the C-ABI library, so these run without a GPU: every fixture under tests/golden/merge is the output of the
-reference's mergesam on SAM files the reference's gmapper wrote (tools/make_merge_golden.py).  When oracle/_ref/mergesam is present (build
-container) the same comparison is repeated on fresh shards cut a different way."""
+reference's mergesam on SAM files the reference's gmapper wrote (tools/make_merge_golden.py), or on shards of them
+(test_merge_against_reference_program_on_other_shards, which re-runs oracle/_ref/mergesam where it is built)."""
 import gzip, json, os, subprocess
 import numpy as np
 import pytest
@@ -80,9 +80,14 @@ def test_merge_rejects_bad_input():
     assert gm.merge_sam(b"", [b""]) == b""
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mergesam")), reason="reference mergesam not built (oracle/Makefile.ref)")
+SHARD_SETS = {"default": [], "single_best_all": ["--single-best-mapping", "--all-contigs"], "strata_o4": ["--strata", "-o", "4"],
+              "unal_no_half_paired": ["--sam-unaligned", "--no-half-paired"]}
+
+
 def test_merge_against_reference_program_on_other_shards(tmp_path):
-    """three-way split of the reads of a committed case by record (the reference's program run here, on inputs no fixture holds)"""
+    """three-way split of the reads of a committed case by record, against the reference's mergesam on those shards: its outputs are stored
+    (pairs_db2@shards4_<set>.out.gz, @PG's program path cut to "mergesam"); where oracle/_ref/mergesam is built, the program is run here as well
+    and must still write exactly the stored text"""
     from shrimp_amd import gmapper as gm
     case = "pairs_db2"
     reads = gz(case + ".reads.gz"); sams = [gz("%s.in%d.sam.gz" % (case, k)) for k in range(2)]
@@ -97,8 +102,11 @@ def test_merge_against_reference_program_on_other_shards(tmp_path):
     for i, p in enumerate(parts):
         (tmp_path / ("s%d.sam" % i)).write_bytes(p); names.append("s%d.sam" % i)
     exe = os.path.join(ROOT, "oracle", "_ref", "mergesam")
-    for args in ([], ["--single-best-mapping", "--all-contigs"], ["--strata", "-o", "4"], ["--sam-unaligned", "--no-half-paired"]):
-        ref = subprocess.run([exe, "--sam", *args, "r.fa", *names], cwd=tmp_path, capture_output=True, check=True).stdout
+    for tag, args in sorted(SHARD_SETS.items()):
+        want = gz("%s@shards4_%s.out.gz" % (case, tag))
+        if os.path.exists(exe):
+            ref = subprocess.run([exe, "--sam", *args, "r.fa", *names], cwd=tmp_path, capture_output=True, check=True).stdout
+            assert ref.replace(b"CL:" + exe.encode() + b" ", b"CL:mergesam ") == want, args
         kw, _ = options_of(args)
-        got = gm.merge_sam(reads, parts, command_line=" ".join([exe, "--sam", *args, "r.fa", *names]) + " ", threads=3, **kw)
-        assert got == ref, args
+        got = gm.merge_sam(reads, parts, command_line=" ".join(["mergesam", "--sam", *args, "r.fa", *names]) + " ", threads=3, **kw)
+        assert got == want, args
