@@ -584,11 +584,8 @@ int gm_launch_anchors(const GmIndexDev& ix, const GmScoreDev& sc, int n_reads, i
   const bool split = scap >= 2048 && !(gm_tune("GM_K2_WIDE") && atoi(gm_tune("GM_K2_WIDE")) == 0);
   const size_t lds = k2_lds_bytes(false, scap, NL, read_len), lds_a = k2_lds_bytes(false, split ? 1024 : scap, NL, read_len);
   if (lds > 64 * 1024) {
-    static GmLdsLimit lim_configured; size_t& configured = lim_configured.cur();
     if (lds > 160 * 1024) { gm_set_error("anchor kernel LDS %zu too large", lds); return GM_E_ARG; }
-    if (lds > configured) {
-      GM_HIP(hipFuncSetAttribute((const void*)k_anchors<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      GM_HIP(hipFuncSetAttribute((const void*)k_anchors<false, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); configured = lds; }
+    GM_HIP(gm_lds_at_least((const void*)k_anchors<false>, lds)); GM_HIP(gm_lds_at_least((const void*)k_anchors<false, 32>, lds));
   }
   hipLaunchKernelGGL(k_anchors<false>, dim3(n_reads * 2), dim3(GM_WAVE), lds_a, stream, ix, sc, n_reads, read_len, window_len, max_n_kmers, NL,
                      d_surv, d_surv_cnt, scap, 0, (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr,

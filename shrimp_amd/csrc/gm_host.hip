@@ -21,6 +21,7 @@
 #include <deque>
 #include <functional>
 #include <future>
+#include <map>
 #include <unordered_map>
 #include <zlib.h>
 #include "gm_common.h"
@@ -33,6 +34,18 @@ void gm_set_error(const char* fmt, ...) {
 }
 extern "C" const char* gm_last_error(void) { return g_err; }
 extern "C" int gm_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
+hipError_t gm_lds_at_least(const void* kernel, size_t bytes) {
+  if (bytes <= 48 * 1024) return hipSuccess;
+  int dev = 0; hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  static std::mutex m; static std::map<std::pair<int, const void*>, size_t> raised;     // (device, kernel) -> the limit set there so far
+  std::lock_guard<std::mutex> lk(m);
+  size_t& cur = raised[{dev, kernel}];
+  if (bytes <= cur) return hipSuccess;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) cur = bytes;
+  return e;
+}
 // The SAM text of a large call is hundreds of megabytes: allocating it afresh for every call (page faults on first touch) and unmapping it in gm_free cost 20+ ms per
 // 1 M reads that nothing overlaps.  One freed text buffer of >= 16 MB is therefore parked here and handed to the next call (gm_release_cache() drops it).
 static struct { std::mutex m; char* p = nullptr; size_t cap = 0; char* live = nullptr; size_t live_cap = 0; } g_outcache;
@@ -366,6 +379,7 @@ struct gm_session {
   unsigned long long* d_pstats[2] = {nullptr, nullptr};   // per buffer set: counters of one sub-batch
   uint32_t* h_pin = nullptr;                      // pinned words the front writes (heavy count per set); from word 16 on: K1's start flags
   uint32_t flag_epoch = 0, front_epoch[2] = {0, 0}; int front_flag_grid[2] = {0, 0};
+  GmK1Scratch k1;                                 // K1 / K1b launch scratch: every launch that touches it is queued on `stream`
   DevSet set[2];
   DevSet set2[2];                                 // paired mode: the second pair of buffer sets of the two-stream pipeline
   HostSlot slot[3];
@@ -644,6 +658,7 @@ extern "C" void gm_session_free(gm_session_t* s) {
   for (auto& v : s->pin_res) v.release();
   for (auto& v : s->pin_ops) v.release();
   free_buffers(s->set[0]); free_buffers(s->set[1]); free_buffers(s->set2[0]); free_buffers(s->set2[1]);
+  s->k1.release();
   for (auto& h : s->slot) slot_free(h);
   if (s->d_qtab) (void)hipFree(s->d_qtab);
   if (s->d_pairs) (void)hipFree(s->d_pairs);
@@ -1350,7 +1365,7 @@ static int prune_e_max(const gm_session* s, int read_len, int W) {
 static int launch_lookup(gm_session* s, DevSet& D, const GmIndexDev& dv, int n, int read_len, int read_words, int W, unsigned long long* d_stats, int* fused) {
   GmFusePrune f; f.d_surv2 = D.d_surv2; f.d_surv_cnt2 = D.d_surv_cnt2; f.scap2 = D.scap2; f.window_len = W; f.e_max = D.scap2 > 0 ? prune_e_max(s, read_len, W) : -1; f.fused = fused;
   *fused = 0;
-  return gm_launch_lookup(gm_view_of(dv, D), D.d_reads, n, read_len, read_words, D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, d_stats, s->stream, D.d_surv_seg, &f);
+  return gm_launch_lookup(gm_view_of(dv, D), D.d_reads, n, read_len, read_words, D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, d_stats, s->stream, &s->k1, D.d_surv_seg, &f);
 }
 
 // K1b + K2 on the survivors of K1
@@ -1360,7 +1375,7 @@ static int launch_prune_anchors(gm_session* s, DevSet& D, const GmIndexDev& dv, 
   if (D.scap2 > 0) {
     if (!fused) {
       const int e_max = prune_e_max(s, read_len, W);
-      int rc = gm_launch_prune(n, read_len, W, e_max, s->ix->n_slabs, s->ix->slab_bits, D.d_surv, D.d_surv_cnt, D.d_surv_seg, D.scap, D.d_surv2, D.d_surv_cnt2, D.scap2, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, d_stats, q);
+      int rc = gm_launch_prune(n, read_len, W, e_max, s->ix->n_slabs, s->ix->slab_bits, D.d_surv, D.d_surv_cnt, D.d_surv_seg, D.scap, D.d_surv2, D.d_surv_cnt2, D.scap2, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, d_stats, q, &s->k1);
       if (rc) return rc;
     }
     return gm_launch_anchors(dv, s->sc, n, read_len, W, D.d_surv2, D.d_surv_cnt2, D.scap2, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, d_stats, q);
@@ -1390,11 +1405,11 @@ static int pipeline_front(gm_session* s, int k, int n, int read_len) {
   GM_HIP(hipMemsetAsync(d_stats, 0, (size_t)GS_STRIPES * GS_STRIDE * 8, q));
   GM_HIP(hipEventRecord(s->pev[k][0], q));
   if (D.d_read_rna) { const int rc0 = gm_launch_read_rna_flags(D.d_reads, n, read_len, read_words, D.d_read_rna, q); if (rc0) return rc0; }      // which reads are RNA (ref: fasta.c:528-542)
-  gm_lookup_set_start_flags(s->h_pin + 16, 1024, ++s->flag_epoch);
+  s->k1.start_flags = s->h_pin + 16; s->k1.flag_cap = 1024; s->k1.epoch = ++s->flag_epoch;
   int fused = 0;
   int rc = launch_lookup(s, D, dv, n, read_len, read_words, W, d_stats, &fused);
-  s->front_epoch[k] = s->flag_epoch; s->front_flag_grid[k] = rc ? 0 : gm_lookup_start_flag_grid();
-  gm_lookup_set_start_flags(nullptr, 0, 0);
+  s->front_epoch[k] = s->flag_epoch; s->front_flag_grid[k] = rc ? 0 : s->k1.flag_grid;
+  s->k1.start_flags = nullptr; s->k1.flag_cap = 0;     // (the paired path's lookups raise no flags)
   if (rc) return rc;
   GM_HIP(hipEventRecord(s->pev[k][1], q));
   rc = launch_prune_anchors(s, D, dv, n, read_len, W, d_stats, fused);
@@ -1541,22 +1556,20 @@ static int run_device_pipeline(gm_session* s, DevSet& D, HostSlot& H, int n, int
   return pipeline_back(s, 0, H, n, read_len, st, lookup_ms);
 }
 
-// The lookup kernels keep per-DEVICE scratch (fall-back lists, start flags, the rounds kernel's rows: gm_lookup.hip, gm_lookup5.hip), shared by every session on that
-// device: mapping calls of different sessions on one device take turns (a single call already fills the GPU).  Sessions on different devices run side by side.
-// (round 4: that scratch exists twice per device -- gm_lookup_set_scratch_slot -- so TWO mapping calls may be in flight on a device, e.g. the two sessions the file entry
-// alternates its chunks between: the tail of one call, its last back half and host work, then runs under the other's lookups.  A third call waits for a free set.)
+// Admission of mapping calls per device: at most TWO in flight on a device (a single call already fills the GPU), e.g. the two sessions the file entry alternates its
+// chunks between -- the tail of one call, its last back half and host work, then runs under the other's lookups.  A third call waits until one of them returns.
+// Sessions on different devices run side by side.  (Each session owns its launch scratch, GmK1Scratch: the calls share no buffers.)
 struct GmDevTurn {
   static std::mutex& m(int d) { static std::mutex a[16]; return a[d]; }
   static std::condition_variable& cv(int d) { static std::condition_variable a[16]; return a[d]; }
-  static bool& busy(int d, int k) { static bool a[16][2] = {}; return a[d][k]; }
-  int dev, slot;
-  explicit GmDevTurn(const gm_session* s) : dev((int)((unsigned)s->ix->device & 15u)), slot(0) {
+  static int& in_flight(int d) { static int a[16] = {}; return a[d]; }
+  int dev;
+  explicit GmDevTurn(const gm_session* s) : dev((int)((unsigned)s->ix->device & 15u)) {
     std::unique_lock<std::mutex> lk(m(dev));
-    cv(dev).wait(lk, [&] { return !busy(dev, 0) || !busy(dev, 1); });
-    slot = busy(dev, 0) ? 1 : 0; busy(dev, slot) = true;
-    gm_lookup_set_scratch_slot(slot);
+    cv(dev).wait(lk, [&] { return in_flight(dev) < 2; });
+    in_flight(dev)++;
   }
-  ~GmDevTurn() { { std::lock_guard<std::mutex> lk(m(dev)); busy(dev, slot) = false; } cv(dev).notify_one(); }
+  ~GmDevTurn() { { std::lock_guard<std::mutex> lk(m(dev)); in_flight(dev)--; } cv(dev).notify_one(); }
   GmDevTurn(const GmDevTurn&) = delete; GmDevTurn& operator=(const GmDevTurn&) = delete;
 };
 
@@ -1923,7 +1936,7 @@ extern "C" int gm_last_lookup_timing(gm_session_t* s, double* ms, uint64_t* alg_
 // stage dump for parity tests: hits selected by pass 1, in ext-heap array order (before pass 2 / reverse_hit)
 extern "C" int gm_debug_tophits(gm_session_t* s, int n_reads, int read_len, const uint32_t* reads_packed, long long* rows, long cap, long* n_rows) {
   if (!s) return GM_E_ARG;
-  GmDevTurn dev_turn(s);     // (the device's lookup scratch is shared by its sessions: one call at a time, like the mapping entries)
+  GmDevTurn dev_turn(s);     // (admitted like the mapping entries)
   GM_HIP(hipSetDevice(s->ix->device));
   DevSet& D = s->set[0];
   if (D.cur_len != read_len || (D.caps_pair_mode != 0 && D.caps_pair_mode != 4)) { choose_caps(s, D, read_len); D.caps_pair_mode = 0; int rc = alloc_buffers(s, D, read_len); if (rc) return rc; }

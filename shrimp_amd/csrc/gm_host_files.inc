@@ -246,8 +246,9 @@ static int map_reads_file_cb_impl(gm_session_t* s, const char* path, int fastq, 
     return GM_OK;
   };
   // The chunks go alternately to this session and to its twin (made when the file turns out to hold more than one chunk), each mapped by a thread of its own: a mapping call
-  // ends with a tail -- the last sub-batch's SW passes and the host's text work, ~30 ms with nothing on the lookup stream -- and with two calls in flight (GmDevTurn) that tail
-  // runs under the other chunk's lookups.  Tickets keep the order: chunk t is written when chunks 0 .. t - 1 have been.
+  // ends with a tail -- the last sub-batch's SW passes and the host's text work, ~30 ms with nothing on the lookup stream -- and with two calls in flight (GmDevTurn admits
+  // two per device; each session owns its launch scratch) that tail runs under the other chunk's lookups.  Tickets keep the order: chunk t is written when chunks
+  // 0 .. t - 1 have been.
   struct Shared { std::mutex take_m, m; std::condition_variable cv; size_t next_ticket = 0, write_turn = 0; bool done = false; int rc = GM_OK; std::string err; gm_map_stats_t total; } S;
   memset(&S.total, 0, sizeof S.total);
   std::thread helper;

@@ -502,7 +502,7 @@ static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* 
           DevSet& D = *PS[k][m];
           GM_HIP(hipMemsetAsync(D.d_mp_cnt, 0, (size_t)2 * n * 4, qa));
           GmIndexDev d1 = dvm[m]; d1.mp.mode = 1; d1.mp.out_rows = D.d_mp_rows; d1.mp.out_cnt = D.d_mp_cnt;
-          rc = gm_launch_lookup(gm_view_of(d1, D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, nullptr, nullptr);
+          rc = gm_launch_lookup(gm_view_of(d1, D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, &s->k1, nullptr, nullptr);
           if (rc) return rc;
         }
         for (int m = 0; m < 2; m++) {
@@ -517,14 +517,14 @@ static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* 
           for (int m = 0; m < 2; m++) {
             DevSet& D = *PS[k][m];
             GmIndexDev d3 = dkm[k][m]; d3.mp.mode = 3;
-            rc = gm_launch_lookup(gm_view_of(d3, D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, nullptr, nullptr);
+            rc = gm_launch_lookup(gm_view_of(d3, D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, &s->k1, nullptr, nullptr);
             if (rc) return rc;
           }
       }
       for (int m = 0; m < 2; m++) {
         DevSet& D = *PS[k][m];
         GM_HIP(hipEventRecord(s->pkev[k][2 * m], qa));
-        rc = gm_launch_lookup(gm_view_of(dkm[k][m], D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, D.d_surv_seg, nullptr);
+        rc = gm_launch_lookup(gm_view_of(dkm[k][m], D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, &s->k1, D.d_surv_seg, nullptr);
         if (rc) return rc;
         GM_HIP(hipEventRecord(s->pkev[k][2 * m + 1], qa));
       }
@@ -545,7 +545,7 @@ static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* 
         if (D.d_read_rna) { rc = gm_launch_read_rna_flags(D.d_reads, n, len[m], rwords[m], D.d_read_rna, qa); if (rc) return rc; }      // (before the mate is turned: its complement of U is A)
         if (in_st[m] && !cs) { rc = gm_launch_revcomp_reads(D.d_reads, n, len[m], rwords[m], qa, D.d_read_rna); if (rc) return rc; }
         GM_HIP(hipEventRecord(s->pkev[k][2 * m], qa));
-        rc = gm_launch_lookup(gm_view_of(dvm[m], D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, D.d_surv_seg, nullptr);
+        rc = gm_launch_lookup(gm_view_of(dvm[m], D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, &s->k1, D.d_surv_seg, nullptr);
         if (rc) return rc;
         GM_HIP(hipEventRecord(s->pkev[k][2 * m + 1], qa));
       }

@@ -60,34 +60,46 @@ int gm_index_build_device(GmIndexHost* ix, hipStream_t stream);
 int gm_index_colour_genome_device(GmIndexHost* ix, hipStream_t stream);   // derives d_genome_cs from d_genome
 int gm_index_from_lists_device(GmIndexHost* ix, int sn, const uint32_t* lens, const uint32_t* pos, uint32_t total);
 
-// The dynamic-LDS limit raised for a kernel so far, per device (hipFuncSetAttribute acts on the current device's code object: a process that maps on a
-// second device must raise it there too).  One static instance per kernel at its launch site: `static GmLdsLimit lim; size_t& configured = lim.cur();`
-struct GmLdsLimit { size_t v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; size_t& cur() { int d = 0; (void)hipGetDevice(&d); return v[(d >= 0 && d < 16) ? d : 0]; } };
+// Raises `kernel`'s dynamic-LDS limit on the current device to `bytes` where that is above 48 KB and above what was set there before (hipFuncSetAttribute acts on
+// the current device's code object: a process that maps on a second device raises it there too).  One lock and one high-water mark per (device, kernel): a limit
+// is never lowered, also when two threads launch the same kernel at once.
+hipError_t gm_lds_at_least(const void* kernel, size_t bytes);
 
+// The launch scratch of the seed lookup (K1) and its prune (K1b).  One per session: every launch that touches it is queued on the session's front stream
+// (s->stream), so its buffers are allocated on first use, grown only after that stream has drained, and freed with the session.
+struct GmK1Scratch {
+  int cus = 0;                                                    // the device's CU count (read once)
+  uint64_t* k4_bins = nullptr; size_t k4_words = 0;               // k_lookup_v4: candidate bins
+  uint32_t* k4_fb = nullptr;                                      // k_lookup_v4: fall-back list (+ its counter)
+  uint32_t* k5_fb = nullptr; uint32_t* k5_pl = nullptr; int k5_cap = 0;   // k_lookup_v5: read-strands for the lane-per-list kernel + K1b / for K1b only (+ a counter each)
+  uint2* k5_spill = nullptr; size_t k5_spill_n = 0;               // k_lookup_v5_rounds: candidate rows of the rounds after the first
+  uint32_t* k1b_list = nullptr; int k1b_cap = 0;                  // k_prune_v2: read-strands left to k_prune (+ their counter)
+  // in: pinned words the persistent K1 grid raises when its workgroups are resident (null: none), and this launch's epoch
+  uint32_t* start_flags = nullptr; int flag_cap = 0; uint32_t epoch = 0;
+  // out, of the last launch: workgroups that will raise a flag (0: none); k_lookup_v5's rounds and half-size shape; the K1 variant chosen
+  int flag_grid = 0, rounds = 1, half = 0; const char* kernel = nullptr;
+  void release() {
+    void* ptrs[] = {k4_bins, k4_fb, k5_fb, k5_pl, k5_spill, k1b_list};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    *this = GmK1Scratch();
+  }
+};
 
 // K1 seed lookup + region filter: one workgroup per read-strand; read-strands with more than scap
 // survivors are listed in d_heavy_list (count in d_surv_cnt) and re-run by gm_launch_lookup_redo
-void gm_lookup_set_scratch_slot(int slot);   // which of the device's two lookup-scratch sets the calling thread's launches use (0 / 1)
-void gm_lookup_set_start_flags(uint32_t* flags, int cap, uint32_t epoch);   // pinned words the persistent K1 grid raises when its workgroups are resident
-int gm_lookup_start_flag_grid(void);
 // Optional fusion of K1b into K1 (k_lookup_v5): when `fuse` is given and the chosen kernel can apply the prune rules itself, the kept
 // keys go straight to fuse->d_surv2 / d_surv_cnt2 and *fuse->fused is set to 1 (the caller then skips gm_launch_prune).
 struct GmFusePrune { uint64_t* d_surv2; uint32_t* d_surv_cnt2; int scap2; int window_len; int e_max; int* fused; };
 int gm_launch_lookup(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                      uint64_t* d_surv, uint32_t* d_surv_cnt, int scap, uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap,
-                     unsigned long long* d_stats, hipStream_t stream, uint32_t* d_surv_seg = nullptr,   // d_surv_seg[rs][S + 1]: survivors after each slab
+                     unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K, uint32_t* d_surv_seg = nullptr,   // d_surv_seg[rs][S + 1]: survivors after each slab
                      const GmFusePrune* fuse = nullptr);
 int gm_index_derive_rna(GmIndexHost* ix, hipStream_t stream);        // per-contig RNA flags (gm_index.hip); idempotent
 int gm_index_derive_strips(GmIndexHost* ix, hipStream_t stream);     // strip lists for k_lookup_v5 (gm_lookup5.hip); idempotent
-void gm_lookup5_set_start_flags(uint32_t* flags, int cap, uint32_t epoch);
-int gm_lookup5_start_flag_grid(void);
-int gm_lookup5_last_rounds(void);
-int gm_lookup5_last_half(void);
 int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words, int max_n_kmers, int NL,
                       uint64_t* d_out, uint32_t* d_out_cnt, int out_cap, uint32_t* d_surv_cnt, int prune, uint32_t D, int e_max,
-                      uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap, unsigned long long* d_stats, hipStream_t stream,
-                      uint32_t** fb_list, uint32_t** fb_cnt, int* fb_cap_out,
-                      uint64_t* d_raw = nullptr, int raw_cap = 0, uint32_t* d_surv_seg = nullptr, uint32_t** pl_list = nullptr, uint32_t** pl_cnt = nullptr);
+                      uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap, unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K,
+                      uint64_t* d_raw = nullptr, int raw_cap = 0, uint32_t* d_surv_seg = nullptr);   // (its fall-back lists: K->k5_fb, K->k5_pl)
 int gm_launch_lookup_redo(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                           int n_heavy, const uint32_t* d_redo_list, const uint64_t* d_redo_off, uint64_t* d_out,
                           unsigned long long* d_stats, hipStream_t stream);
@@ -98,7 +110,7 @@ size_t gm_lookup_lds_bytes(const GmIndexDev& ix, int read_len);
 int gm_launch_prune(int n_reads, int read_len, int window_len, int e_max, int n_slabs, int slab_bits, const uint64_t* d_surv, const uint32_t* d_surv_cnt,
                     const uint32_t* d_surv_seg, int scap,
                     uint64_t* d_surv2, uint32_t* d_surv_cnt2, int scap2, uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap,
-                    unsigned long long* d_stats, hipStream_t stream,
+                    unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K,
                     const uint32_t* d_rs_list = nullptr, const uint32_t* d_rs_cnt = nullptr, int rs_cap = 0);   // list mode: only the listed read-strands
 
 // K2 anchors + candidate windows: one wave per read-strand (LDS tier) + heavy tier on global arrays

@@ -1275,13 +1275,6 @@ k_lookup_v4(GmIndexDev ix, const uint32_t* __restrict__ reads, int n_reads, int 
   if ((tid & (GM_WAVE - 1)) == 0) { GS_ADD(stats, GS_LOOKUPS, my_lookups); GS_ADD(stats, GS_ENTRIES, my_entries); }
 }
 
-// start flags of the persistent K1 grid (see gm_host.hip, pipeline_back): set before a launch, consumed by it
-// Launch state of the CALLING THREAD (thread_local: a session's front pipeline sets the flags, launches and reads the grid back on one host thread; two threads that map
-// on two devices side by side each keep their own -- round 3 advisor: as process-wide statics one session could launch with the other's pinned flag pointer and epoch).
-static thread_local uint32_t* g_k4_flags = nullptr; static thread_local uint32_t g_k4_epoch = 0; static thread_local int g_k4_flag_cap = 0, g_k4_flag_grid = 0;
-void gm_lookup_set_start_flags(uint32_t* flags, int cap, uint32_t epoch) { g_k4_flags = flags; g_k4_flag_cap = cap; g_k4_epoch = epoch; g_k4_flag_grid = 0; }
-int gm_lookup_start_flag_grid(void) { return g_k4_flag_grid; }   // workgroups that will raise a flag for the last launch (0: none)
-
 static void k1_geometry(const GmIndexDev& ix, int read_len, int* max_n_kmers, int* NL, int* bm_words, size_t* lds) {
   *max_n_kmers = read_len - ix.min_seed_span + 1;
   if (*max_n_kmers < 0) *max_n_kmers = 0;
@@ -1294,18 +1287,10 @@ static void k1_geometry(const GmIndexDev& ix, int read_len, int* max_n_kmers, in
 }
 
 // v4 launch: returns false when the geometry does not fit (the caller falls back to the slab-sweep kernels)
-struct K4Scratch { uint64_t* scratch = nullptr; size_t words = 0; uint32_t* fb = nullptr; int cus = 0; };
-static K4Scratch g_k4[16][2];                                   // (two sets per device, see gm_lookup_set_scratch_slot)
-static thread_local int g_k4_slot = 0;
-void gm_lookup5_set_scratch_slot(int slot);
-// The lookup kernels' scratch (fall-back lists, the rounds kernel's rows, v4's candidate bins) exists twice per device: a mapping call runs all its launches with the set
-// its thread was given, so that two calls -- two sessions -- can be in flight on one device (gm_host.hip hands the sets out).
-void gm_lookup_set_scratch_slot(int slot) { g_k4_slot = slot & 1; gm_lookup5_set_scratch_slot(slot & 1); }
 static bool k4_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words, int max_n_kmers, int NL,
                       uint64_t* d_surv, uint32_t* d_surv_cnt, int scap, uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap,
-                      unsigned long long* d_stats, hipStream_t stream, uint32_t* d_surv_seg, size_t lds_generic, int bm_words) {
-  int dev = 0; if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
-  K4Scratch& K = g_k4[dev][g_k4_slot];
+                      unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K, uint32_t* d_surv_seg, size_t lds_generic, int bm_words) {
+  int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return false;
   const int S = ix.n_slabs;
   {  // v4's fixed cost per read-strand (two 128 KB table clears, per-bin passes) pays off from ~30 k list entries per read-strand
      // (measured: 45 k at 100 bp / 3 Gbp 7 % faster than the slab sweep, 17 k at 50 colours 40 % slower)
@@ -1330,32 +1315,29 @@ static bool k4_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads
   if (const char* e = gm_tune("GM_K4_LDS_PAD")) lds += (size_t)std::max(0, atoi(e));   // experiment: what the LDS footprint does to the co-residency with pass 1 / pass 2
   if (lds > 160 * 1024 - 64) return false;
   int wgs_per_cu = 1; if (const char* e = gm_tune("GM_K4_WGS")) wgs_per_cu = std::max(1, std::min(8, atoi(e)));
-  if (!K.cus) { if (hipDeviceGetAttribute(&K.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || K.cus < 1) K.cus = 256; }
-  int grid = std::min(2 * n_reads, K.cus * wgs_per_cu);
+  if (!K->cus) { if (hipDeviceGetAttribute(&K->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || K->cus < 1) K->cus = 256; }
+  int grid = std::min(2 * n_reads, K->cus * wgs_per_cu);
   if (const char* e = gm_tune("GM_K4_GRID")) grid = std::max(1, std::min(2 * n_reads, atoi(e)));
-  const size_t need = (size_t)std::max(grid, K.cus) * SC * bin_cap;
-  if (need > K.words) {
-    if (K.scratch) (void)hipFree(K.scratch);
-    K.scratch = nullptr; K.words = 0;
-    if (hipMalloc(&K.scratch, need * 8) != hipSuccess) return false;
-    K.words = need;
+  const size_t need = (size_t)std::max(grid, K->cus) * SC * bin_cap;
+  if (need > K->k4_words) {
+    if (K->k4_bins) { (void)hipStreamSynchronize(stream); (void)hipFree(K->k4_bins); }
+    K->k4_bins = nullptr; K->k4_words = 0;
+    if (hipMalloc(&K->k4_bins, need * 8) != hipSuccess) return false;
+    K->k4_words = need;
   }
-  if (!K.fb) { if (hipMalloc(&K.fb, (size_t)(fb_cap + 4) * 4) != hipSuccess) return false; }
-  if (hipMemsetAsync(K.fb + fb_cap, 0, 4, stream) != hipSuccess) return false;
-  static GmLdsLimit lim_configured4, lim_configured_g; size_t &configured4 = lim_configured4.cur(), &configured_g = lim_configured_g.cur();
-  if (lds > 48 * 1024 && lds > configured4) { if (hipFuncSetAttribute((const void*)k_lookup_v4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false; configured4 = lds; }
-  if (lds_generic > 48 * 1024 && lds_generic > configured_g) {
-    if (hipFuncSetAttribute((const void*)k_lookup<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_generic) != hipSuccess) return false; configured_g = lds_generic; }
+  if (!K->k4_fb) { if (hipMalloc(&K->k4_fb, (size_t)(fb_cap + 4) * 4) != hipSuccess) return false; }
+  if (hipMemsetAsync(K->k4_fb + fb_cap, 0, 4, stream) != hipSuccess) return false;
+  if (gm_lds_at_least((const void*)k_lookup_v4, lds) != hipSuccess || gm_lds_at_least((const void*)k_lookup<false>, lds_generic) != hipSuccess) return false;
   int k4_threads = 1024; if (const char* e = gm_tune("GM_K1_THREADS")) k4_threads = std::max(64, std::min(1024, atoi(e) & ~63));
-  const bool use_flags = g_k4_flags && grid <= g_k4_flag_cap;
-  g_k4_flag_grid = use_flags ? grid : 0;
+  const bool use_flags = K->start_flags && grid <= K->flag_cap;
+  K->flag_grid = use_flags ? grid : 0;
   hipLaunchKernelGGL(k_lookup_v4, dim3(grid), dim3(k4_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words, max_n_kmers, NL, tab_bits, cbits, SC, wcap,
-                     d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, d_surv_seg, K.scratch, bin_cap, K.fb, K.fb + fb_cap, fb_cap,
-                     gm_tune("GM_K1_ABLATE") ? atoi(gm_tune("GM_K1_ABLATE")) : 0, use_flags ? g_k4_flags : nullptr, g_k4_epoch);
+                     d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, d_surv_seg, K->k4_bins, bin_cap, K->k4_fb, K->k4_fb + fb_cap, fb_cap,
+                     gm_tune("GM_K1_ABLATE") ? atoi(gm_tune("GM_K1_ABLATE")) : 0, use_flags ? K->start_flags : nullptr, K->epoch);
   // read-strands whose candidates overflowed their bins: the slab-sweep kernel in list mode (blocks beyond the list's end return at once)
   hipLaunchKernelGGL(k_lookup<false>, dim3(std::min(fb_cap, 1024)), dim3(K1_THREADS), lds_generic, stream, ix, d_reads, n_reads, read_len, read_words,
                      max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                     (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)K.fb, (const uint32_t*)(K.fb + fb_cap), d_stats, 0, d_surv_seg);
+                     (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)K->k4_fb, (const uint32_t*)(K->k4_fb + fb_cap), d_stats, 0, d_surv_seg);
   return true;
 }
 
@@ -1363,43 +1345,33 @@ size_t gm_lookup_lds_bytes(const GmIndexDev& ix, int read_len) {
   int a, b, c; size_t l; k1_geometry(ix, read_len, &a, &b, &c, &l); return l;
 }
 
-// the mate-pair modes of the generic kernel: their dynamic LDS limit (set once per device for both instantiations)
+// the mate-pair modes of the generic kernel: their dynamic LDS limit
 static int k1_mp_lds(size_t& lds) {
   lds += (size_t)2 * GM_MP_CAP * 4;                                   // the mate's row and this read-strand's own
   if (lds + 64 > 160 * 1024) { gm_set_error("lookup kernel (mate-pair modes) needs %zu bytes of LDS", lds); return GM_E_ARG; }
-  static GmLdsLimit lim_mp; size_t& configured = lim_mp.cur();
-  if (lds > 48 * 1024 && lds > configured) {
-    GM_HIP(hipFuncSetAttribute((const void*)k_lookup<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GM_HIP(hipFuncSetAttribute((const void*)k_lookup<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GM_HIP(hipFuncSetAttribute((const void*)k_lookup<false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GM_HIP(hipFuncSetAttribute((const void*)k_lookup<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GM_HIP(hipFuncSetAttribute((const void*)k_lookup<false, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured = lds;
-  }
+  for (const void* k : {(const void*)k_lookup<false, 1>, (const void*)k_lookup<false, 2>, (const void*)k_lookup<false, 3>, (const void*)k_lookup<false, 4>, (const void*)k_lookup<false, 5>})
+    GM_HIP(gm_lds_at_least(k, lds));
   return GM_OK;
 }
 
-static thread_local const char* g_k1_name = "";
+static thread_local const char* g_k1_name = "";   // K->kernel of the calling thread's last launch
 extern "C" const char* gm_last_lookup_kernel(void) { return g_k1_name; }   // which K1 variant the calling thread's last gm_launch_lookup chose (for bench.py / profiles)
 
 int gm_launch_lookup(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                      uint64_t* d_surv, uint32_t* d_surv_cnt, int scap, uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap,
-                     unsigned long long* d_stats, hipStream_t stream, uint32_t* d_surv_seg, const GmFusePrune* fuse) {
+                     unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K, uint32_t* d_surv_seg, const GmFusePrune* fuse) {
   int max_n_kmers, NL, bm_words; size_t lds;
   k1_geometry(ix, read_len, &max_n_kmers, &NL, &bm_words, &lds);
+  K->flag_grid = 0;
   if (lds > 160 * 1024) { gm_set_error("lookup kernel needs %zu bytes of LDS (read_len %d, slab_bits %d)", lds, read_len, ix.slab_bits); return GM_E_ARG; }
   GM_HIP(hipMemsetAsync(d_heavy_cnt, 0, 4, stream));
   if (fuse && fuse->fused) *fuse->fused = 0;
   if (NL == 0 || n_reads == 0) { GM_HIP(hipMemsetAsync(d_surv_cnt, 0, (size_t)n_reads * 2 * 4, stream)); return GM_OK; }
-  static GmLdsLimit lim_configured; size_t& configured = lim_configured.cur();
-  if (lds > 48 * 1024 && lds > configured) {
-    GM_HIP(hipFuncSetAttribute((const void*)k_lookup<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured = lds;
-  }
+  GM_HIP(gm_lds_at_least((const void*)k_lookup<false>, lds));
   if (ix.mp.mode) {   // paired -n 3: the generic slab-sweep kernel in one of its mate-pair modes (GmMpDev)
     int rc = k1_mp_lds(lds); if (rc) return rc;
     const int k1_threads = std::min(1024, std::max(256, (NL + 63) & ~63));
-    g_k1_name = "k_lookup";
+    g_k1_name = K->kernel = "k_lookup";
     if (ix.mp.mode == 1)
       hipLaunchKernelGGL((k_lookup<false, 1>), dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
                          max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
@@ -1432,22 +1404,18 @@ int gm_launch_lookup(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads,
     const bool want_fuse = fuse && fuse->scap2 > 0;
     const uint32_t D = (uint32_t)std::max(want_fuse ? fuse->window_len : 0, read_len);
     const int e_max = want_fuse ? std::min(fuse->e_max, read_len) : -1;
-    uint32_t *fbl = nullptr, *fbc = nullptr, *pll = nullptr, *plc = nullptr; int fbcap = 0;
-    gm_lookup5_set_start_flags(g_k4_flags, g_k4_flag_cap, g_k4_epoch);
     bool fused = want_fuse;
     int r = gm_lookup5_launch(ix, d_reads, n_reads, read_len, read_words, max_n_kmers, NL, fused ? fuse->d_surv2 : d_surv, fused ? fuse->d_surv_cnt2 : d_surv_cnt,
-                              fused ? fuse->scap2 : scap, d_surv_cnt, fused ? 1 : 0, D, e_max, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, &fbl, &fbc, &fbcap,
-                              d_surv, scap, d_surv_seg, &pll, &plc);
+                              fused ? fuse->scap2 : scap, d_surv_cnt, fused ? 1 : 0, D, e_max, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, d_surv, scap, d_surv_seg);
     if (r == 0 && fused) {   // the prune rules do not fit region-sized bins (very long reads): v5 without them, K1b afterwards
       fused = false;
       r = gm_lookup5_launch(ix, d_reads, n_reads, read_len, read_words, max_n_kmers, NL, d_surv, d_surv_cnt, scap, d_surv_cnt, 0, D, -1,
-                            d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, &fbl, &fbc, &fbcap);
+                            d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K);
     }
-    g_k4_flag_grid = gm_lookup5_start_flag_grid();
-    gm_lookup5_set_start_flags(nullptr, 0, 0);
     if (r < 0) return r;
     if (r == 1) {
-      g_k1_name = gm_lookup5_last_half() ? "k_lookup_v5_half" : gm_lookup5_last_rounds() > 1 ? "k_lookup_v5_rounds" : "k_lookup_v5";
+      g_k1_name = K->kernel = K->half ? "k_lookup_v5_half" : K->rounds > 1 ? "k_lookup_v5_rounds" : "k_lookup_v5";
+      uint32_t* const fbl = K->k5_fb; uint32_t* const fbc = K->k5_fb + K->k5_cap; const int fbcap = K->k5_cap;
       // read-strands whose candidates did not fit the LDS tiers (none on the benchmark genome): the slab-sweep kernel in list mode (blocks beyond the list's end
       // return at once), then K1b for those.  (k_lookup_v4 in list mode was tried for them: no faster, and its 134 KB workgroups wait longer for a CU.)
       hipLaunchKernelGGL(k_lookup<false>, dim3(std::min(fbcap, 1024)), dim3(K1_THREADS), lds, stream, ix, d_reads, n_reads, read_len, read_words,
@@ -1456,28 +1424,26 @@ int gm_launch_lookup(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads,
       GM_HIP(hipGetLastError());
       if (fused) {
         const int rc = gm_launch_prune(n_reads, read_len, fuse->window_len, fuse->e_max, ix.n_slabs, ix.slab_bits, d_surv, d_surv_cnt, d_surv_seg, scap,
-                                       fuse->d_surv2, fuse->d_surv_cnt2, fuse->scap2, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, fbl, fbc, fbcap);
+                                       fuse->d_surv2, fuse->d_surv_cnt2, fuse->scap2, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, fbl, fbc, fbcap);
         if (rc) return rc;
-        if (pll) {   // read-strands whose members v5 left in their raw rows (more kept than K2's tier under region-sized bins): K1b only
-          const int rc2 = gm_launch_prune(n_reads, read_len, fuse->window_len, fuse->e_max, ix.n_slabs, ix.slab_bits, d_surv, d_surv_cnt, d_surv_seg, scap,
-                                          fuse->d_surv2, fuse->d_surv_cnt2, fuse->scap2, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, pll, plc, fbcap);
-          if (rc2) return rc2;
-        }
+        // read-strands whose members v5 left in their raw rows (more kept than K2's tier under region-sized bins): K1b only
+        const int rc2 = gm_launch_prune(n_reads, read_len, fuse->window_len, fuse->e_max, ix.n_slabs, ix.slab_bits, d_surv, d_surv_cnt, d_surv_seg, scap,
+                                        fuse->d_surv2, fuse->d_surv_cnt2, fuse->scap2, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, K->k5_pl, K->k5_pl + K->k5_cap, fbcap);
+        if (rc2) return rc2;
         if (fuse->fused) *fuse->fused = 1;
       }
       return GM_OK;
     }
   }
   if (bkt) {
-    g_k1_name = "k_lookup_bkt";
+    g_k1_name = K->kernel = "k_lookup_bkt";
     const size_t lds_b = (size_t)((((read_len + 3) / 4) + 3) & ~3) * 4 + (size_t)bm_words * 4;
     // the persistent form (probes one read-strand ahead) unless GM_BKT_V1 asks for one workgroup per read-strand; its grid: what fits a CU by waves and LDS, times the CUs
     const int threads_b = (NL + 63) & ~63;
     const size_t lds_p = lds_b + (size_t)((((read_len + 3) / 4) + 3) & ~3) * 4;
     int dev_b = 0, cus_b = 256; (void)hipGetDevice(&dev_b); if (hipDeviceGetAttribute(&cus_b, hipDeviceAttributeMultiprocessorCount, dev_b) != hipSuccess || cus_b < 1) cus_b = 256;
-    { static GmLdsLimit lim_b, lim_p; size_t &cb = lim_b.cur(), &cp = lim_p.cur();      // (a small region size on a bucket-sized genome: the bitmap can pass 48 KB)
-      if (lds_b > 48 * 1024 && lds_b > cb) { GM_HIP(hipFuncSetAttribute((const void*)k_lookup_bkt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b)); cb = lds_b; }
-      if (lds_p > 48 * 1024 && lds_p <= 64 * 1024 && lds_p > cp) { GM_HIP(hipFuncSetAttribute((const void*)k_lookup_bkt_p, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p)); cp = lds_p; } }
+    GM_HIP(gm_lds_at_least((const void*)k_lookup_bkt, lds_b));      // (a small region size on a bucket-sized genome: the bitmap can pass 48 KB)
+    if (lds_p <= 64 * 1024) GM_HIP(gm_lds_at_least((const void*)k_lookup_bkt_p, lds_p));
     int per_cu = 0;                                              // resident workgroups per CU (registers, waves, LDS): the persistent grid is exactly that
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_lookup_bkt_p, threads_b, lds_p) != hipSuccess || per_cu < 1) per_cu = 4;
     if (const char* e = gm_tune("GM_BKT_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < per_cu) { if (getenv("GM_TIMELINE")) fprintf(stderr, "[bkt] %d workgroups a CU fit, %d taken (%d threads, %zu B of LDS)\n", per_cu, v, threads_b, lds_p); per_cu = v; } }
@@ -1488,29 +1454,27 @@ int gm_launch_lookup(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads,
     hipLaunchKernelGGL(k_lookup_bkt_p, dim3(std::min(n_reads * 2, cus_b * per_cu)), dim3(threads_b), lds_p, stream, ix, d_reads, n_reads, read_len, read_words,
                        max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, d_surv_seg);
   } else if (!all && ix.n_slabs > 1 && NL < 65536 && !gm_tune("GM_K1_V2") && !gm_tune("GM_K1_V3") && k4_launch(ix, d_reads, n_reads, read_len, read_words, max_n_kmers, NL, d_surv, d_surv_cnt, scap,
-                                                                                                   d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, d_surv_seg, lds, bm_words)) {
+                                                                                                   d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, d_surv_seg, lds, bm_words)) {
     // k_lookup_v4 ran (hashed pre-count + exact count on the candidates); read-strands it could not hold were redone in list mode
-    g_k1_name = "k_lookup_v4";
+    g_k1_name = K->kernel = "k_lookup_v4";
   } else if (!all && ix.list_cutoff < 65536u && !gm_tune("GM_K1_V2") &&
              (size_t)((((read_len + 3) / 4) + 3 * NL + ix.n_slabs * NL + (ix.n_slabs + 1) / 2 + (NL * (ix.n_slabs + 1) + 1) / 2 + 3) & ~3) * 4 + (size_t)bm_words * 4 <= 160 * 1024) {
     // (long reads on many slabs: the per-slab window maps outgrow the LDS and the lane-per-list kernel below takes over)
-    g_k1_name = "k_lookup_v3";
+    g_k1_name = K->kernel = "k_lookup_v3";
     const size_t lds3 = (size_t)((((read_len + 3) / 4) + 3 * NL + ix.n_slabs * NL + (ix.n_slabs + 1) / 2 + (NL * (ix.n_slabs + 1) + 1) / 2 + 3) & ~3) * 4 + (size_t)bm_words * 4;
-    static GmLdsLimit lim_configured3; size_t& configured3 = lim_configured3.cur();
-    if (lds3 > 48 * 1024 && lds3 > configured3) { GM_HIP(hipFuncSetAttribute((const void*)k_lookup_v3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3)); configured3 = lds3; }
+    GM_HIP(gm_lds_at_least((const void*)k_lookup_v3, lds3));
     int k1_threads = 768;
     if (const char* e = gm_tune("GM_K1_THREADS")) k1_threads = std::max(64, std::min(768, atoi(e) & ~63));
     hipLaunchKernelGGL(k_lookup_v3, dim3(n_reads * 2), dim3(k1_threads), lds3, stream, ix, d_reads, n_reads, read_len, read_words,
                        max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats,
                        gm_tune("GM_K1_ABLATE") ? atoi(gm_tune("GM_K1_ABLATE")) : 0, d_surv_seg);
   } else {
-    g_k1_name = "k_lookup";
+    g_k1_name = K->kernel = "k_lookup";
     // one list per lane when the read-strand's lists fit a workgroup: every list slice is in flight at once
     int k1_threads = std::min(1024, (NL + 63) & ~63);
     if (const char* e = gm_tune("GM_K1_THREADS")) k1_threads = std::max(64, std::min(1024, atoi(e) & ~63));
     if (all) {
-      static GmLdsLimit lim6; size_t& c6 = lim6.cur();
-      if (lds > 48 * 1024 && lds > c6) { GM_HIP(hipFuncSetAttribute((const void*)k_lookup<false, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); c6 = lds; }
+      GM_HIP(gm_lds_at_least((const void*)k_lookup<false, 6>, lds));
       hipLaunchKernelGGL((k_lookup<false, 6>), dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
                          max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
                          (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, d_surv_seg);
@@ -1532,8 +1496,7 @@ int gm_launch_lookup_redo(const GmIndexDev& ix, const uint32_t* d_reads, int n_r
   k1_geometry(ix, read_len, &max_n_kmers, &NL, &bm_words, &lds);
   if (n_heavy == 0) return GM_OK;
   if (ix.no_region_counts) {
-    static GmLdsLimit lim6r; size_t& c6 = lim6r.cur();
-    if (lds > 48 * 1024 && lds > c6) { GM_HIP(hipFuncSetAttribute((const void*)k_lookup<false, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); c6 = lds; }
+    GM_HIP(gm_lds_at_least((const void*)k_lookup<false, 6>, lds));
     hipLaunchKernelGGL((k_lookup<false, 6>), dim3(n_heavy), dim3(K1_THREADS), lds, stream, ix, d_reads, n_reads, read_len, read_words,
                        max_n_kmers, NL, bm_words, d_out, (uint32_t*)nullptr, 0, (uint32_t*)nullptr, (uint32_t*)nullptr, 0,
                        d_redo_list, d_redo_off, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, (uint32_t*)nullptr);

@@ -211,26 +211,12 @@ int gm_index_derive_strips(GmIndexHost* ix, hipStream_t stream) {
 // ---------------------------------------------------------------------------------------------
 // launch: returns 1 when v5 ran (0: geometry does not fit, the caller takes another kernel; < 0: error)
 // ---------------------------------------------------------------------------------------------
-struct K5Scratch { uint32_t* fb = nullptr; uint32_t* pl = nullptr; int fb_cap = 0; int cus = 0; uint2* spill = nullptr; size_t spill_n = 0; };   // fb: read-strands for the lane-per-list kernel + K1b; pl: for K1b only
-static K5Scratch g_k5[16][2];                                   // per device, two sets: two mapping calls may be in flight on a device, each with the set its thread was given
-static thread_local int g_k5_slot = 0;
-void gm_lookup5_set_scratch_slot(int slot) { g_k5_slot = slot & 1; }
-// (launch state of the calling thread, like gm_lookup.hip's: set, used and read back by one host thread per launch)
-static thread_local uint32_t* g_k5_flags = nullptr; static thread_local uint32_t g_k5_epoch = 0; static thread_local int g_k5_flag_cap = 0, g_k5_flag_grid = 0;
-void gm_lookup5_set_start_flags(uint32_t* flags, int cap, uint32_t epoch) { g_k5_flags = flags; g_k5_flag_cap = cap; g_k5_epoch = epoch; g_k5_flag_grid = 0; }
-int gm_lookup5_start_flag_grid(void) { return g_k5_flag_grid; }
-static thread_local int g_k5_last_rounds = 1, g_k5_last_half = 0;
-int gm_lookup5_last_rounds(void) { return g_k5_last_rounds; }      // rounds of the last launch (> 1: k_lookup_v5_rounds)
-int gm_lookup5_last_half(void) { return g_k5_last_half; }            // the last launch was k_lookup_v5_half
-
 int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words, int max_n_kmers, int NL,
                       uint64_t* d_out, uint32_t* d_out_cnt, int out_cap, uint32_t* d_surv_cnt, int prune, uint32_t D, int e_max,
-                      uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap, unsigned long long* d_stats, hipStream_t stream,
-                      uint32_t** fb_list, uint32_t** fb_cnt, int* fb_cap_out,
-                      uint64_t* d_raw, int raw_cap, uint32_t* d_surv_seg, uint32_t** pl_list, uint32_t** pl_cnt) {
-  int dev = 0; if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
+                      uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap, unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K,
+                      uint64_t* d_raw, int raw_cap, uint32_t* d_surv_seg) {
+  int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return 0;
   if (!ix.seed[0].sdir || ix.region_bits < 9 || ix.region_bits > 16 || NL <= 0) return 0;
-  K5Scratch& K = g_k5[dev][g_k5_slot];
   const bool forced = gm_tune("GM_K1_V5") != nullptr;
   double entries = 0;                                          // expected list entries per read-strand
   for (int sn = 0; sn < ix.n_seeds; sn++) {
@@ -308,53 +294,47 @@ int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads
   if (prune && (D + (uint32_t)std::max(0, e_max) > (1u << ix.region_bits) || D > 0xFFFFu)) return 0;   // the prune rules need bins (= regions) of at least D + e_max positions
   const size_t lds = (half ? fixed_h : fixed) + (size_t)(4u << lsw) + (size_t)(4u << ltw);
   const int fb_cap = std::max(4096, 2 * n_reads);              // every read-strand may fall back (tiny tables in the tests, repeats)
-  if (!K.cus) { if (hipDeviceGetAttribute(&K.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || K.cus < 1) K.cus = 256; }
-  if (fb_cap > K.fb_cap) {
-    if (K.fb) { (void)hipDeviceSynchronize(); (void)hipFree(K.fb); (void)hipFree(K.pl); K.fb = nullptr; K.pl = nullptr; K.fb_cap = 0; }
-    if (hipMalloc(&K.fb, (size_t)(fb_cap + 4) * 4) != hipSuccess) return 0;
-    if (hipMalloc(&K.pl, (size_t)(fb_cap + 4) * 4) != hipSuccess) return 0;
-    K.fb_cap = fb_cap;
+  if (!K->cus) { if (hipDeviceGetAttribute(&K->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || K->cus < 1) K->cus = 256; }
+  if (fb_cap > K->k5_cap) {
+    if (K->k5_fb) { (void)hipStreamSynchronize(stream); (void)hipFree(K->k5_fb); (void)hipFree(K->k5_pl); K->k5_fb = nullptr; K->k5_pl = nullptr; K->k5_cap = 0; }
+    if (hipMalloc(&K->k5_fb, (size_t)(fb_cap + 4) * 4) != hipSuccess) return 0;
+    if (hipMalloc(&K->k5_pl, (size_t)(fb_cap + 4) * 4) != hipSuccess) return 0;
+    K->k5_cap = fb_cap;
   }
-  uint32_t* const fb_cnt_p = K.fb + K.fb_cap; uint32_t* const pl_cnt_p = K.pl + K.fb_cap;
+  uint32_t* const fb_cnt_p = K->k5_fb + K->k5_cap; uint32_t* const pl_cnt_p = K->k5_pl + K->k5_cap;
   if (hipMemsetAsync(fb_cnt_p, 0, 4, stream) != hipSuccess || hipMemsetAsync(pl_cnt_p, 0, 4, stream) != hipSuccess) return GM_E_NODEVICE;
-  static GmLdsLimit lim_configured; size_t& configured = lim_configured.cur();
-  if (lds > 48 * 1024 && lds > configured) {
-    if (hipFuncSetAttribute((const void*)k_lookup_v5<15>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_lookup_v5<14>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_lookup_v5_rounds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_lookup_v5_half, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+  if (gm_lds_at_least((const void*)k_lookup_v5<15>, lds) != hipSuccess || gm_lds_at_least((const void*)k_lookup_v5<14>, lds) != hipSuccess ||
+      gm_lds_at_least((const void*)k_lookup_v5_rounds, lds) != hipSuccess || gm_lds_at_least((const void*)k_lookup_v5_half, lds) != hipSuccess ||
 #ifdef GM_TUNING
-        hipFuncSetAttribute((const void*)k_lookup_v5_half_plain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+      gm_lds_at_least((const void*)k_lookup_v5_half_plain, lds) != hipSuccess ||
 #endif
-        hipFuncSetAttribute((const void*)k_lookup_v5<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
-    configured = lds;
-  }
+      gm_lds_at_least((const void*)k_lookup_v5<0>, lds) != hipSuccess) return 0;
   // (the half-size shapes: two workgroups a CU.  For the colour-space shape that leaves 16 KB of a CU's LDS, so the colour-space pass 2 runs beside it on the CUs the lookup
   // has not filled yet or has left already rather than on all of them -- but the lookup itself takes 7.1 instead of 11.5 ms per launch (66 k reads on average), and since pass 2 takes eight
   // windows a wave the step is shorter that way: 190 -> 179 ms per 1 M 50-colour reads, tools/k5_shape_cfg4.sh; with the four-window pass 2 of round 3 it made no difference)
-  int grid = std::min(2 * n_reads, (half || small_shape) ? 2 * K.cus : K.cus);
+  int grid = std::min(2 * n_reads, (half || small_shape) ? 2 * K->cus : K->cus);
   if (const char* e = gm_tune("GM_K5_GRID")) grid = std::max(1, std::min(2 * n_reads, atoi(e)));
   K5Args a;
   a.reads = d_reads; a.n_reads = n_reads; a.read_len = read_len; a.read_words = read_words; a.max_n_kmers = max_n_kmers; a.NL = NL;
   a.lsw = lsw; a.ltw = ltw; a.cand_cap = cand_cap; a.hbits = hbits; a.cand_limit = cand_limit; a.xrec = xrec; a.rounds = rounds; a.round_regs = round_regs;
   a.out = d_out; a.out_cnt = d_out_cnt; a.out_cap = out_cap; a.surv_cnt = d_surv_cnt; a.prune = prune; a.D = D; a.e_max = e_max;
   a.heavy_list = d_heavy_list; a.heavy_cnt = d_heavy_cnt; a.heavy_cap = heavy_cap; a.stats = d_stats;
-  a.fb_list = K.fb; a.fb_cnt = fb_cnt_p; a.fb_cap = fb_cap;
-  a.raw_out = prune ? d_raw : nullptr; a.raw_cap = raw_cap; a.surv_seg = d_surv_seg; a.n_slabs = ix.n_slabs; a.pl_list = K.pl; a.pl_cnt = pl_cnt_p; a.pl_cap = fb_cap;
-  const bool use_flags = g_k5_flags && grid <= g_k5_flag_cap;
-  g_k5_flag_grid = use_flags ? grid : 0;
-  a.start_flags = use_flags ? g_k5_flags : nullptr; a.start_epoch = g_k5_epoch;
-  g_k5_last_rounds = rounds; g_k5_last_half = half;
+  a.fb_list = K->k5_fb; a.fb_cnt = fb_cnt_p; a.fb_cap = fb_cap;
+  a.raw_out = prune ? d_raw : nullptr; a.raw_cap = raw_cap; a.surv_seg = d_surv_seg; a.n_slabs = ix.n_slabs; a.pl_list = K->k5_pl; a.pl_cnt = pl_cnt_p; a.pl_cap = fb_cap;
   a.spill = nullptr; a.spill_cap = cand_cap;
   if (rounds > 1) {
     const size_t need = (size_t)grid * (size_t)(rounds - 1) * (size_t)cand_cap;
-    if (need > K.spill_n) {
-      if (K.spill) { (void)hipDeviceSynchronize(); (void)hipFree(K.spill); K.spill = nullptr; K.spill_n = 0; }
-      if (hipMalloc(&K.spill, need * sizeof(uint2)) != hipSuccess) return 0;
-      K.spill_n = need;
+    if (need > K->k5_spill_n) {
+      if (K->k5_spill) { (void)hipStreamSynchronize(stream); (void)hipFree(K->k5_spill); K->k5_spill = nullptr; K->k5_spill_n = 0; }
+      if (hipMalloc(&K->k5_spill, need * sizeof(uint2)) != hipSuccess) return 0;
+      K->k5_spill_n = need;
     }
-    a.spill = K.spill;
+    a.spill = K->k5_spill;
   }
+  const bool use_flags = K->start_flags && grid <= K->flag_cap;
+  K->flag_grid = use_flags ? grid : 0;
+  a.start_flags = use_flags ? K->start_flags : nullptr; a.start_epoch = K->epoch;
+  K->rounds = rounds; K->half = half;
   if (half) {
 #ifdef GM_TUNING
     if (half == 2) hipLaunchKernelGGL(k_lookup_v5_half_plain, dim3(grid), dim3(threads), lds, stream, ix, a); else
@@ -365,6 +345,5 @@ int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads
   else if (lsw == 14) hipLaunchKernelGGL((k_lookup_v5<14>), dim3(grid), dim3(threads), lds, stream, ix, a);
   else hipLaunchKernelGGL((k_lookup_v5<0>), dim3(grid), dim3(threads), lds, stream, ix, a);
   if (hipGetLastError() != hipSuccess) return GM_E_NODEVICE;
-  *fb_list = K.fb; *fb_cnt = fb_cnt_p; *fb_cap_out = fb_cap; if (pl_list) *pl_list = K.pl; if (pl_cnt) *pl_cnt = pl_cnt_p;
   return 1;
 }

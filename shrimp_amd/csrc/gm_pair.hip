@@ -322,8 +322,7 @@ int gm_launch_mp_filter(int n_pairs, int region_bits, int region_overlap, uint64
   if (n_pairs == 0) return GM_OK;
   const MpDelta dl = gm_mp_region_deltas(region_bits, dmin1, dmax1, dmin2, dmax2);
   const size_t lds = (size_t)(2u << MPF_HBITS) * 4;
-  static GmLdsLimit lim_mp; size_t& configured = lim_mp.cur();
-  if (lds > configured) { GM_HIP(hipFuncSetAttribute((const void*)k_mp_filter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); configured = lds; }
+  GM_HIP(gm_lds_at_least((const void*)k_mp_filter, lds));
   const int grid = std::min(2 * n_pairs, 1024);
   hipLaunchKernelGGL(k_mp_filter, dim3(grid), dim3(MPF_THREADS), lds, stream, n_pairs, region_bits, (uint32_t)region_overlap, d_surv1, d_cnt1, scap1, d_surv2, d_cnt2, scap2,
                      dl, d_seg1, d_seg2, n_slabs, d_unfiltered);

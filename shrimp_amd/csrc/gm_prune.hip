@@ -247,31 +247,29 @@ k_prune_v2(int n_rs, const uint64_t* __restrict__ surv, const uint32_t* __restri
 int gm_launch_prune(int n_reads, int read_len, int window_len, int e_max, int n_slabs, int slab_bits, const uint64_t* d_surv, const uint32_t* d_surv_cnt,
                     const uint32_t* d_surv_seg, int scap,
                     uint64_t* d_surv2, uint32_t* d_surv_cnt2, int scap2, uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap,
-                    unsigned long long* d_stats, hipStream_t stream, const uint32_t* d_rs_list, const uint32_t* d_rs_cnt, int rs_cap) {
+                    unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K, const uint32_t* d_rs_list, const uint32_t* d_rs_cnt, int rs_cap) {
   if (n_reads == 0) return GM_OK;
   const uint32_t D = (uint32_t)std::max(window_len, read_len);
   if (e_max > read_len) e_max = read_len;
   if (!d_rs_cnt && !gm_tune("GM_PRUNE_V1") && D + (uint32_t)std::max(0, e_max) <= 65535u) {
     // k_prune_v2 for every read-strand; the few with more survivors than its table takes are listed and done by k_prune below (list mode)
-    int dev = 0; GM_HIP(hipGetDevice(&dev));
-    static uint32_t* ov[16] = {nullptr}; static int ov_cap[16] = {0};
-    if (dev >= 0 && dev < 16) {
-      const int need = std::max(4096, 2 * n_reads);
-      if (need > ov_cap[dev]) { if (ov[dev]) { GM_HIP(hipDeviceSynchronize()); (void)hipFree(ov[dev]); } GM_HIP(hipMalloc(&ov[dev], (size_t)(need + 4) * 4)); ov_cap[dev] = need; }
-      uint32_t* ovc = ov[dev] + ov_cap[dev];
-      GM_HIP(hipMemsetAsync(ovc, 0, 4, stream));
-      int bb = 11; while ((1u << bb) < D + (uint32_t)std::max(0, e_max)) bb++;
-      int hb = 12; if (const char* e = gm_tune("GM_PRUNE_HBITS")) hb = std::max(6, std::min(13, atoi(e)));
-      const uint32_t n_max = (3u << hb) / 4u;
-      const size_t lds2 = (size_t)12 << hb;
-      static GmLdsLimit lim_configured2; size_t& configured2 = lim_configured2.cur();
-      if (lds2 > 48 * 1024 && lds2 > configured2) { GM_HIP(hipFuncSetAttribute((const void*)k_prune_v2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2)); configured2 = lds2; }
-      hipLaunchKernelGGL(k_prune_v2, dim3(n_reads * 2), dim3(512), lds2, stream, n_reads * 2, d_surv, d_surv_cnt, scap, d_surv2, d_surv_cnt2, scap2, D, e_max, bb, hb, n_max,
-                         d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, ov[dev], ovc, ov_cap[dev]);
-      GM_HIP(hipGetLastError());
-      return gm_launch_prune(n_reads, read_len, window_len, e_max, n_slabs, slab_bits, d_surv, d_surv_cnt, d_surv_seg, scap, d_surv2, d_surv_cnt2, scap2,
-                             d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, ov[dev], ovc, ov_cap[dev]);
+    const int need = std::max(4096, 2 * n_reads);
+    if (need > K->k1b_cap) {
+      if (K->k1b_list) { GM_HIP(hipStreamSynchronize(stream)); (void)hipFree(K->k1b_list); K->k1b_list = nullptr; K->k1b_cap = 0; }
+      GM_HIP(hipMalloc(&K->k1b_list, (size_t)(need + 4) * 4)); K->k1b_cap = need;
     }
+    uint32_t* ovc = K->k1b_list + K->k1b_cap;
+    GM_HIP(hipMemsetAsync(ovc, 0, 4, stream));
+    int bb = 11; while ((1u << bb) < D + (uint32_t)std::max(0, e_max)) bb++;
+    int hb = 12; if (const char* e = gm_tune("GM_PRUNE_HBITS")) hb = std::max(6, std::min(13, atoi(e)));
+    const uint32_t n_max = (3u << hb) / 4u;
+    const size_t lds2 = (size_t)12 << hb;
+    GM_HIP(gm_lds_at_least((const void*)k_prune_v2, lds2));
+    hipLaunchKernelGGL(k_prune_v2, dim3(n_reads * 2), dim3(512), lds2, stream, n_reads * 2, d_surv, d_surv_cnt, scap, d_surv2, d_surv_cnt2, scap2, D, e_max, bb, hb, n_max,
+                       d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, K->k1b_list, ovc, K->k1b_cap);
+    GM_HIP(hipGetLastError());
+    return gm_launch_prune(n_reads, read_len, window_len, e_max, n_slabs, slab_bits, d_surv, d_surv_cnt, d_surv_seg, scap, d_surv2, d_surv_cnt2, scap2,
+                           d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, K->k1b_list, ovc, K->k1b_cap);
   }
   int bin_bits = 1; while ((1u << bin_bits) < D + (uint32_t)std::max(0, e_max)) bin_bits++;
   if (bin_bits > 12) { gm_set_error("prune: D = %u does not fit the 12-bit bin offsets", D); return GM_E_ARG; }
@@ -279,8 +277,7 @@ int gm_launch_prune(int n_reads, int read_len, int window_len, int e_max, int n_
   const int segs = d_surv_seg ? std::max(1, n_slabs) : 1;
   int hbits = 8; while ((1 << hbits) < 2 * std::max(128, (segs > 1 ? (2 * scap) / segs : scap))) hbits++;
   const size_t lds = (size_t)8 << hbits;
-  static GmLdsLimit lim_configured; size_t& configured = lim_configured.cur();
-  if (lds > 48 * 1024 && lds > configured) { GM_HIP(hipFuncSetAttribute((const void*)k_prune, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); configured = lds; }
+  GM_HIP(gm_lds_at_least((const void*)k_prune, lds));
   // latency-bound (hash probes): as many lanes per read-strand as a segment has work for
   const int pthreads = gm_tune("GM_PRUNE_THREADS") ? atoi(gm_tune("GM_PRUNE_THREADS")) : std::min(1024, std::max(128, (1 << hbits) / 8));
   hipLaunchKernelGGL(k_prune, dim3(d_rs_cnt ? std::min(rs_cap, 1024) : n_reads * 2), dim3(pthreads), lds, stream, n_reads * 2, d_surv, d_surv_cnt, d_surv_seg, scap, d_surv2, d_surv_cnt2, scap2,

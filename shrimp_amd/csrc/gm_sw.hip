@@ -1333,15 +1333,10 @@ int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* 
     const bool g8 = false; (void)reach; (void)lds8;
 #endif
     const size_t ldsn = g8 ? lds8 : lds4;
-    static GmLdsLimit lim4; size_t& conf4 = lim4.cur();
-    if (ldsn > 48 * 1024 && ldsn > conf4) {
-      GM_HIP(hipFuncSetAttribute((const void*)k_pass2_g4<16, int, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-      GM_HIP(hipFuncSetAttribute((const void*)k_pass2_g4<16, int, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
+    GM_HIP(gm_lds_at_least((const void*)k_pass2_g4<16, int, false>, ldsn)); GM_HIP(gm_lds_at_least((const void*)k_pass2_g4<16, int, true>, ldsn));
 #ifdef GM_TUNING
-      GM_HIP(hipFuncSetAttribute((const void*)k_pass2_g4<8, int16_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-      GM_HIP(hipFuncSetAttribute((const void*)k_pass2_g4<8, int16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
+    GM_HIP(gm_lds_at_least((const void*)k_pass2_g4<8, int16_t, false>, ldsn)); GM_HIP(gm_lds_at_least((const void*)k_pass2_g4<8, int16_t, true>, ldsn));
 #endif
-      conf4 = ldsn; }
     GM_HIP(hipMemsetAsync(d_cls_cnt, 0, 16, stream));
     hipLaunchKernelGGL(k_p2cs_classify, dim3(512), dim3(256), 0, stream, d_work, d_n_work, d_sel, input_strand, sc.tiebreak_rev ? 1 : 0, d_order, d_cls_cnt);
 #define GM_P2_G4L(GG, CT, LOC) hipLaunchKernelGGL((k_pass2_g4<GG, CT, LOC>), dim3(grid / (64 / GG)), dim3(GM_WAVE), ldsn, stream, ix, sc, d_reads, n_reads, read_len, read_words, d_hits, d_perm, hcap, d_sel, d_sel_sidx, \
@@ -2195,10 +2190,7 @@ int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs
   P.b_go = cs_params9[5]; P.b_ge = cs_params9[6]; P.anchor_width = cs_params9[7]; P.taboo = cs_params9[8];
   const size_t lds = 5 * (size_t)((read_len + 15) & ~15) + ((window_len + 15) & ~15) + (size_t)window_len * 48 + 64;
   if (lds > 160 * 1024) { gm_set_error("colour-space pass 2: window of %d does not fit LDS", window_len); return GM_E_ARG; }
-  static GmLdsLimit lim_configured; size_t& configured = lim_configured.cur();
-  if (lds > 48 * 1024 && lds > configured) {
-    GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); configured = lds; }
+  GM_HIP(gm_lds_at_least((const void*)k_pass2_cs<false>, lds)); GM_HIP(gm_lds_at_least((const void*)k_pass2_cs<true>, lds));
   // Four or eight windows per wave (k_pass2_cs_g4) unless GM_P2_G4=0 asks for the one-window kernel; a wave owns that many consecutive back-pointer scratches.
   // Eight (groups of 8 lanes: a stripe of 8 rows takes band width + 14 steps, against band width + 30 for 16 rows -- the chain north, west, north, ... through a band is two steps a
   // row whatever the lane count, so ~band width / 2 lanes a window is what the recurrence can feed) where the carry rows fit int16_t, see cs_carry_ld; GM_P2_G=16 keeps four.
@@ -2216,16 +2208,10 @@ int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs
     const bool g8 = reach < 16000 && lds8 <= 64 * 1024 && !(gm_tune("GM_P2_G") && atoi(gm_tune("GM_P2_G")) == 16);
     const size_t ldsn = g8 ? lds8 : lds4;
     if (ldsn <= 160 * 1024 && grid >= 8) {
-      static GmLdsLimit lim4; size_t& conf4 = lim4.cur();
-      if (ldsn > 48 * 1024 && ldsn > conf4) {
-        GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs_g4<16, int, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-        GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs_g4<16, int, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-        GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs_g4<16, int, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-        GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs_g4<16, int, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-        GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs_g4<8, int16_t, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-        GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs_g4<8, int16_t, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-        GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs_g4<8, int16_t, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn));
-        GM_HIP(hipFuncSetAttribute((const void*)k_pass2_cs_g4<8, int16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn)); conf4 = ldsn; }
+      for (const void* k : {(const void*)k_pass2_cs_g4<16, int, false, false>, (const void*)k_pass2_cs_g4<16, int, true, false>, (const void*)k_pass2_cs_g4<16, int, false, true>,
+                            (const void*)k_pass2_cs_g4<16, int, true, true>, (const void*)k_pass2_cs_g4<8, int16_t, false, false>, (const void*)k_pass2_cs_g4<8, int16_t, true, false>,
+                            (const void*)k_pass2_cs_g4<8, int16_t, false, true>, (const void*)k_pass2_cs_g4<8, int16_t, true, true>})
+        GM_HIP(gm_lds_at_least(k, ldsn));
 #define GM_P2CS_G4(GG, CT, TB, LOC) hipLaunchKernelGGL((k_pass2_cs_g4<GG, CT, TB, LOC>), dim3(grid / (64 / GG)), dim3(GM_WAVE), ldsn, stream, ix, sc, P, d_reads, d_initbp, n_reads, read_len, read_words, d_hits, hcap, d_sel, \
                            d_work, d_n_work, d_res, d_ops, ops_stride, d_back, back_words, window_len, d_stats, d_xover, d_sel_sidx, d_order, d_cls_cnt)
 #define GM_P2CS_GN(TB, LOC) do { if (g8) GM_P2CS_G4(8, int16_t, TB, LOC); else GM_P2CS_G4(16, int, TB, LOC); } while (0)
@@ -2334,9 +2320,8 @@ int gm_launch_sw_full_cs_single(const int* cs_params9, const uint32_t* d_genome_
   GmCsDev P; P.match = cs_params9[0]; P.mismatch = cs_params9[1]; P.xover = cs_params9[2]; P.a_go = cs_params9[3]; P.a_ge = cs_params9[4];
   P.b_go = cs_params9[5]; P.b_ge = cs_params9[6]; P.anchor_width = cs_params9[7]; P.taboo = cs_params9[8];
   const size_t lds = 5 * (size_t)((rlen + 15) & ~15) + ((glen + 15) & ~15) + (size_t)glen * 48 + 64;
-  static GmLdsLimit lim_configured; size_t& configured = lim_configured.cur();
   if (lds > 160 * 1024) { gm_set_error("sw_full_cs: window of %d does not fit LDS", glen); return GM_E_ARG; }
-  if (lds > 48 * 1024 && lds > configured) { GM_HIP(hipFuncSetAttribute((const void*)k_sw_full_cs_single, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); configured = lds; }
+  GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_single, lds));
   hipLaunchKernelGGL(k_sw_full_cs_single, dim3(1), dim3(GM_WAVE), lds, stream, P, d_genome_ls, goff, glen, d_read, rlen, initbp, thresh, ax, ay, alen, awidth,
                      revcmpl, d_back, d_out, d_ops, ops_cap, local, d_xrow);
   GM_HIP(hipGetLastError());

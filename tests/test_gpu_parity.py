@@ -331,8 +331,8 @@ def test_one_session_through_every_mode_in_turn(gm):
 
 
 def test_two_sessions_on_one_device_from_two_threads(gm):
-    """two sessions mapping at the same time from two host threads (ctypes drops the GIL during the calls): the lookup kernels' per-device scratch exists twice and
-    the library hands a set to each call in flight -- both outputs equal the golden, repeatedly"""
+    """two sessions mapping at the same time from two host threads (ctypes drops the GIL during the calls): two calls may be in flight on a device, each with the
+    launch scratch of its own session -- both outputs equal the golden, repeatedly"""
     import threading
     contigs, reads, sam = oa.load_golden("cfg2s_100bp_2Mbp")
     g = oa.load_golden_pairs("cfg5s_2x150_1Mbp")
@@ -350,24 +350,32 @@ def test_two_sessions_on_one_device_from_two_threads(gm):
     assert len(out["b"]) == 4 and all(o == g["sam"] for o in out["b"])
 
 
-def test_three_threads_share_the_two_scratch_sets_of_a_device(gm):
-    """three sessions mapping at once through k_lookup_v5 with tables so small that read-strands fall back (the fall-back lists are the per-device scratch): two calls are
-    in flight, the third waits for a set -- every output equals the golden, repeatedly"""
+THREE_SESSION_CASES = {
+    "v5_fallback": ({"GM_SLAB_BITS": "18", "GM_K1_V5": "1", "GM_K5_LSW": "11", "GM_K5_CANDLIMIT": "40"}, "k_lookup_v5"),   # v5 tables so small that read-strands fall back
+    "k1b_overflow": ({"GM_PRUNE_HBITS": "6"}, "k_lookup_bkt"),          # bucket kernel, then K1b unfused: most read-strands go through k_prune_v2's overflow list
+    "v4_fallback": ({"GM_SLAB_BITS": "18", "GM_K1_V4": "1", "GM_K4_BINCAP": "16"}, "k_lookup_v4"),   # v4 candidate bins overflow: its fall-back list
+}
+
+
+@pytest.mark.parametrize("case", sorted(THREE_SESSION_CASES))
+def test_three_sessions_on_one_device_from_three_threads(gm, case):
+    """three sessions mapping at once, each through a path that fills a fall-back or overflow list of its session's launch scratch: two calls are in flight on the
+    device, the third waits for one of them to return -- every output equals the golden, repeatedly, and every thread's last lookup took the case's kernel"""
     import threading
     contigs, reads, sam = oa.load_golden("cfg2s_100bp_2Mbp")
-    env = {"GM_SLAB_BITS": "18", "GM_K1_V5": "1", "GM_K5_LSW": "11", "GM_K5_CANDLIMIT": "40"}
+    env, want_kern = THREE_SESSION_CASES[case]
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
         ix = gm.Index(contigs)
         ss = [gm.Session(ix, max_batch_reads=1024) for _ in range(3)]
-        outs = [[] for _ in ss]
+        outs = [[] for _ in ss]; kerns = [None for _ in ss]
         def run(i):
             for _ in range(3): outs[i].append(oa.sam_header(contigs) + ss[i].map_reads(reads))
+            kerns[i] = gm.lib().gm_last_lookup_kernel().decode()
         th = [threading.Thread(target=run, args=(i,)) for i in range(3)]
         for x in th: x.start()
         for x in th: x.join()
-        kern = gm.lib().gm_last_lookup_kernel().decode()
         for s in ss: s.close()
         ix.close()
     finally:
@@ -375,6 +383,7 @@ def test_three_threads_share_the_two_scratch_sets_of_a_device(gm):
             if v is None: os.environ.pop(k, None)
             else: os.environ[k] = v
     for o in outs: assert len(o) == 3 and all(x == sam for x in o)
+    assert kerns == [want_kern] * 3, kerns
 
 
 def test_n1_on_noisy_reads_matches_reference_golden(gm):
