@@ -135,6 +135,30 @@ int  gm_index_build(gm_index_t **out, int device, int n_contigs, const uint32_t 
                     const uint32_t *contig_len, const char *const *contig_names,
                     int n_seeds, const char *const *seeds, const gm_params_t *params);
 void gm_index_free(gm_index_t *ix);
+/* S5 as the reference has it: load_genome(files, nfiles), ref: gmapper/genome.c:1012-1182.  FASTA, plain or gzip, one or more contigs a file, files in the
+ * given order; the text is packed into the resident bitfield on the device, then the index is built as by gm_index_build -- the two give the same index for
+ * the same contigs.  The genome is read in letter space, also for a colour-space index (genome.c:1053).  The reference's reader (common/fasta.c:316-553):
+ *   - a line whose first character is '>' starts a contig; its name is the header cut as the read files' names are cut (after the '>': up to the first tab,
+ *     trimmed, cut at the first blank -- so the tab test of genome.c:1079 on the name cannot fire); a line whose first character is '#' is skipped wherever
+ *     it stands; every other line is sequence; the last line may lack its '\n'; an empty line inside a sequence adds nothing (as in the reference);
+ *   - letters of either case A C G T U M R W S Y K V H D B N -> 0..15, X and '.' -> 15 (gm_sequence_to_bitfield's letter-space table); any other byte of a
+ *     sequence line ('\r', blank, tab, digit, a '>' that is not at a line start, ...) fails the call with GM_E_ARG and a message that names the file, the
+ *     contig and the byte offset (the reference: "invalid sequence; tag: [..]", genome.c:1094-1097);
+ *   - a genome of 2^32 bases or more fails as in gm_index_build.
+ * Deliberate divergence: a file that does not start with a '>' line (after '#' lines), a header with no name and no sequence before the next header or the
+ * end, a header line with nothing after the '>', and an unreadable or empty file return GM_E_ARG.  The reference prints a message and silently goes on with
+ * the contigs it has so far.  Lines longer than the reference's 8 MiB line buffer are out of scope.  gm_last_error() names the file. */
+int  gm_index_build_fasta(gm_index_t **out, int device, int n_files, const char *const *paths,
+                          int n_seeds, const char *const *seeds, const gm_params_t *params);
+/* names and lengths of the contigs of an index (for a caller that did not parse the genome itself); *name lives as long as the index */
+int  gm_index_n_contigs(const gm_index_t *ix);
+int  gm_index_contig(const gm_index_t *ix, int c, const char **name, uint32_t *len);
+/* the header gmapper prints before its records (ref: gmapper.c:2980-3008): @HD VN:1.0 SO:unsorted, one @SQ per contig, @RG ID/SM when rg_id is given,
+ * @PG ID:gmapper VN:2.2.3 CL:<command_line> when command_line is given.  *text: gm_free */
+int  gm_sam_header(const gm_index_t *ix, const char *rg_id, const char *rg_sample, const char *command_line, char **text, size_t *len);
+/* how long gm_index_build_fasta took for this index: seconds until the genome bitfield and the contig table were resident (where the device build of the
+ * lists starts), and seconds of the whole call; GM_E_ARG for an index made another way */
+int  gm_index_build_timing(const gm_index_t *ix, double *to_bitfield_s, double *total_s);
 /* The reference's on-disk index ("-S prefix" / "-L prefix": <prefix>.genome + <prefix>.seed.<n>, gzip; ref: gmapper/genome.c:15-270,
  * 670-831).  gm_index_save writes files stock gmapper can load; gm_index_load reads files stock gmapper wrote (letter or colour space, with or without -H: the mode and Hflag words of the files must match params)
  * and uploads them -- the lists are taken as they are, only the per-slab directory is derived on the device. */

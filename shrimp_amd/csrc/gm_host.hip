@@ -153,8 +153,8 @@ static void choose_slabs(GmIndexHost* ix) {
   if (ix->n_slabs < 1) ix->n_slabs = 1;
 }
 
-// shared by gm_index_build and gm_index_load: contig table, cutoff, slabs, genome re-packed into global coordinates and uploaded
-static int index_prepare(gm_index* ix, int n_contigs, const uint32_t* const* contigs, const uint32_t* contig_len, const char* const* contig_names) {
+// shared by gm_index_build, gm_index_load and gm_index_build_fasta: contig table (host and device), cutoff, slabs, size of the genome bitfield
+static int index_tables(gm_index* ix, int n_contigs, const uint32_t* contig_len, const char* const* contig_names) {
   ix->n_contigs = n_contigs;
   ix->contig_off.resize(n_contigs + 1);
   uint64_t tot = 0;
@@ -175,8 +175,15 @@ static int index_prepare(gm_index* ix, int n_contigs, const uint32_t* const* con
     ix->list_cutoff = cutoff;
   } else ix->list_cutoff = ix->params.list_cutoff;
   choose_slabs(ix);
-  // re-pack the per-contig bitfields into one bitfield in global coordinates
   ix->genome_words = (tot + 7) / 8 + 64;
+  GM_HIP(hipMalloc(&ix->d_contig_off, (size_t)(n_contigs + 1) * 4));
+  GM_HIP(hipMemcpy(ix->d_contig_off, ix->contig_off.data(), (size_t)(n_contigs + 1) * 4, hipMemcpyHostToDevice));
+  return GM_OK;
+}
+// gm_index_build and gm_index_load: the tables, then the genome re-packed into global coordinates on the host and uploaded
+static int index_prepare(gm_index* ix, int n_contigs, const uint32_t* const* contigs, const uint32_t* contig_len, const char* const* contig_names) {
+  { const int rc = index_tables(ix, n_contigs, contig_len, contig_names); if (rc != GM_OK) return rc; }
+  // re-pack the per-contig bitfields into one bitfield in global coordinates
   std::vector<uint32_t> g(ix->genome_words, 0);
   for (int c = 0; c < n_contigs; c++) {
     const uint64_t off = ix->contig_off[c]; const uint32_t* src = contigs[c]; const uint64_t len = contig_len[c];
@@ -190,12 +197,17 @@ static int index_prepare(gm_index* ix, int n_contigs, const uint32_t* const* con
   }
   GM_HIP(hipMalloc(&ix->d_genome, ix->genome_words * 4));
   GM_HIP(hipMemcpy(ix->d_genome, g.data(), ix->genome_words * 4, hipMemcpyHostToDevice));
-  GM_HIP(hipMalloc(&ix->d_contig_off, (size_t)(n_contigs + 1) * 4));
-  GM_HIP(hipMemcpy(ix->d_contig_off, ix->contig_off.data(), (size_t)(n_contigs + 1) * 4, hipMemcpyHostToDevice));
   return GM_OK;
 }
 
 extern "C" void gm_index_free(gm_index_t* ix);
+static int index_seeds(gm_index* ix, int n_seeds, const char* const* seeds) {
+  int rc = GM_OK;
+  if (n_seeds == 0) {   // load_default_seeds(0), letter space: ref gmapper-defaults.h:212-227
+    rc |= add_seed(ix, "11110111101111"); rc |= add_seed(ix, "1111011100100001111"); rc |= add_seed(ix, "1111000011001101111");
+  } else for (int i = 0; i < n_seeds; i++) rc |= add_seed(ix, seeds[i]);
+  return rc;
+}
 extern "C" int gm_index_build(gm_index_t** out, int device, int n_contigs, const uint32_t* const* contigs,
                               const uint32_t* contig_len, const char* const* contig_names,
                               int n_seeds, const char* const* seeds, const gm_params_t* params) {
@@ -205,10 +217,7 @@ extern "C" int gm_index_build(gm_index_t** out, int device, int n_contigs, const
   gm_index* ix = new gm_index();
   ix->device = device;
   if (params) ix->params = *params; else gm_params_default(&ix->params);
-  int rc = GM_OK;
-  if (n_seeds == 0) {   // load_default_seeds(0), letter space: ref gmapper-defaults.h:212-227
-    rc |= add_seed(ix, "11110111101111"); rc |= add_seed(ix, "1111011100100001111"); rc |= add_seed(ix, "1111000011001101111");
-  } else for (int i = 0; i < n_seeds; i++) rc |= add_seed(ix, seeds[i]);
+  int rc = index_seeds(ix, n_seeds, seeds);
   if (rc != GM_OK) { delete ix; gm_set_error("invalid spaced seed"); return GM_E_ARG; }
   rc = index_prepare(ix, n_contigs, contigs, contig_len, contig_names);
   if (rc != GM_OK) { gm_index_free(ix); return rc; }
@@ -217,6 +226,65 @@ extern "C" int gm_index_build(gm_index_t** out, int device, int n_contigs, const
   (void)hipStreamDestroy(stream);
   if (rc != GM_OK) { gm_index_free(ix); return rc; }
   *out = ix;
+  return GM_OK;
+}
+
+// S5 from the genome files themselves: the text is packed on the device (gm_fasta.hip), then the same tables and the same device build as gm_index_build
+extern "C" int gm_index_build_fasta(gm_index_t** out, int device, int n_files, const char* const* paths,
+                                    int n_seeds, const char* const* seeds, const gm_params_t* params) {
+  if (!out || n_files < 1 || !paths) { gm_set_error("gm_index_build_fasta: bad arguments"); return GM_E_ARG; }
+  if (gm_device_count() <= device) { gm_set_error("no HIP device %d (the seed index lives in HBM; there is no CPU path)", device); return GM_E_NODEVICE; }
+  GM_HIP(hipSetDevice(device));
+  const auto t0 = std::chrono::steady_clock::now();
+  gm_index* ix = new gm_index();
+  ix->device = device;
+  if (params) ix->params = *params; else gm_params_default(&ix->params);
+  int rc = index_seeds(ix, n_seeds, seeds);
+  if (rc != GM_OK) { delete ix; gm_set_error("invalid spaced seed"); return GM_E_ARG; }
+  GmFastaGenome G;
+  rc = gm_fasta_to_device(n_files, paths, &G);
+  if (rc != GM_OK) { delete ix; return rc; }
+  ix->d_genome = G.d_genome;                                       // (from here on gm_index_free releases it)
+  std::vector<const char*> nptr(G.names.size());
+  for (size_t c = 0; c < G.names.size(); c++) nptr[c] = G.names[c].c_str();
+  rc = index_tables(ix, (int)G.lens.size(), G.lens.data(), nptr.data());
+  if (rc == GM_OK && (ix->total_len != G.total || ix->genome_words != G.words)) { gm_set_error("gm_index_build_fasta: contig lengths do not add up to the bases packed"); rc = GM_E_ARG; }
+  if (rc != GM_OK) { gm_index_free(ix); return rc; }
+  const auto t1 = std::chrono::steady_clock::now();
+  hipStream_t stream = nullptr;
+  if (hipStreamCreate(&stream) != hipSuccess) { gm_index_free(ix); gm_set_error("hipStreamCreate failed"); return GM_E_NODEVICE; }
+  rc = gm_index_build_device(ix, stream);
+  (void)hipStreamDestroy(stream);
+  if (rc != GM_OK) { gm_index_free(ix); return rc; }
+  ix->fasta_to_bitfield_s = std::chrono::duration<double>(t1 - t0).count();
+  ix->fasta_total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  *out = ix;
+  return GM_OK;
+}
+extern "C" int gm_index_n_contigs(const gm_index_t* ix) { return ix ? ix->n_contigs : GM_E_ARG; }
+extern "C" int gm_index_contig(const gm_index_t* ix, int c, const char** name, uint32_t* len) {
+  if (!ix || c < 0 || c >= ix->n_contigs) { gm_set_error("gm_index_contig: no contig %d", c); return GM_E_ARG; }
+  if (name) *name = ix->names[c].c_str();
+  if (len) *len = ix->contig_off[c + 1] - ix->contig_off[c];
+  return GM_OK;
+}
+// the header gmapper prints before its records (ref: gmapper.c:2980-3008)
+extern "C" int gm_sam_header(const gm_index_t* ix, const char* rg_id, const char* rg_sample, const char* command_line, char** text, size_t* len) {
+  if (!ix || !text || !len) { gm_set_error("gm_sam_header: bad arguments"); return GM_E_ARG; }
+  std::string h = "@HD\tVN:1.0\tSO:unsorted\n";
+  for (int c = 0; c < ix->n_contigs; c++) h += "@SQ\tSN:" + ix->names[c] + "\tLN:" + std::to_string(ix->contig_off[c + 1] - ix->contig_off[c]) + "\n";
+  if (rg_id) h += std::string("@RG\tID:") + rg_id + "\tSM:" + (rg_sample ? rg_sample : "") + "\n";
+  if (command_line) h += std::string("@PG\tID:gmapper\tVN:2.2.3\tCL:") + command_line + "\n";
+  char* p = (char*)malloc(h.size() + 1);
+  if (!p) return GM_E_NOMEM;
+  memcpy(p, h.c_str(), h.size() + 1);
+  *text = p; *len = h.size();
+  return GM_OK;
+}
+extern "C" int gm_index_build_timing(const gm_index_t* ix, double* to_bitfield_s, double* total_s) {
+  if (!ix || ix->fasta_total_s <= 0) { gm_set_error("gm_index_build_timing: not an index built by gm_index_build_fasta"); return GM_E_ARG; }
+  if (to_bitfield_s) *to_bitfield_s = ix->fasta_to_bitfield_s;
+  if (total_s) *total_s = ix->fasta_total_s;
   return GM_OK;
 }
 

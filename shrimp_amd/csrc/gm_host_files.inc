@@ -94,10 +94,7 @@ struct ReadsFile {
       got = true; break;
     }
     if (!got || line.size() <= 1) { stopped = true; return 0; }
-    { size_t b = 1, e = line.find('\t', 1); if (e == std::string::npos) e = line.size();
-      while (b < e && isspace((unsigned char)line[b])) b++; while (e > b && isspace((unsigned char)line[e - 1])) e--;      // strtrim
-      size_t k = b; while (k < e && line[k] != ' ' && line[k] != '\t') k++;
-      R.name.assign(line, b, k - b); }
+    R.name = gm_extract_name(line);
     // ---- sequence ----
     bool plus = false;
     for (;;) {

@@ -125,6 +125,7 @@ int gm_index_from_lists_device(GmIndexHost* ix, int sn, const uint32_t* lens, co
   GM_HIP(hipMemset(sd.d_pos, 0xff, (size_t)(total + 64) * 4));
   if (total) GM_HIP(hipMemcpy(sd.d_pos, pos, (size_t)total * 4, hipMemcpyHostToDevice));
   GM_HIP(hipMalloc(&sd.d_dir, (size_t)(KS + 1 + 16) * 4));
+  GM_HIP(hipMemsetAsync(sd.d_dir + KS + 1, 0, 16 * 4, 0));
   hipLaunchKernelGGL(k_dir_from_lists, dim3(256 * 16), dim3(256), 0, 0, d_start, sd.d_pos, K, ix->n_slabs, ix->slab_bits, sd.d_dir);
   if (ix->n_slabs == 1 && (double)total / (double)K <= 12.0 && !gm_tune("GM_NO_BUCKETS")) {
     GM_HIP(hipMalloc(&sd.d_bkt, (size_t)K * 16 * 4));
@@ -262,6 +263,7 @@ int gm_index_build_device(GmIndexHost* ix, hipStream_t stream) {
     GM_HIP(hipMemsetAsync(sd.d_pos, 0xff, (size_t)(n_valid + 64) * 4, stream));   // tail pad: 0xffffffff sentinels
     GM_HIP(hipMemcpyAsync(sd.d_pos, vals_b, (size_t)n_valid * 4, hipMemcpyDeviceToDevice, stream));
     GM_HIP(hipMalloc(&sd.d_dir, (size_t)(KS + 1 + 16) * 4));
+    GM_HIP(hipMemsetAsync(sd.d_dir + KS + 1, 0, 16 * 4, stream));                  // the pad words travel with the array (gm_index_device_array): keep them defined
     hipLaunchKernelGGL(k_build_dir, dim3(grid), dim3(256), 0, stream, keys_b, vals_b, n_valid, ix->n_slabs, ix->slab_bits, KS, sd.d_dir);
     // small genomes (one slab, short lists): add the 64-byte buckets so that a lookup is a single HBM sector
     if (ix->n_slabs == 1 && (double)n_valid / (double)K <= 12.0 && !gm_tune("GM_NO_BUCKETS")) {

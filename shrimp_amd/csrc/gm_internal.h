@@ -29,6 +29,7 @@ struct GmIndexHost {
   gm_params_t params;
   uint32_t list_cutoff = 0;
   bool strips_ready = false;
+  double fasta_to_bitfield_s = 0, fasta_total_s = 0;   // gm_index_build_fasta: seconds until the device build of the lists started, and of the whole call
   GmIndexDev dev_view() const;
 };
 struct gm_index : GmIndexHost {};
@@ -47,6 +48,9 @@ enum { GS_LOOKUPS = 0, GS_ENTRIES, GS_SURVIVORS, GS_ANCHORS, GS_WINDOWS, GS_VEC_
 // the ablation bits of the lookup kernels exist only in builds with -DGM_TUNING (the Makefile's default; `make TUNING=0` is the release build: the knobs
 // read as unset and every ablation branch folds away).  GM_HOST_THREADS, GM_OVERLAP and GM_POST_SW_HOST are run-time options of every build.
 #include <cstdlib>
+#include <cctype>
+#include <string>
+#include <vector>
 #ifdef GM_TUNING
 static inline const char* gm_tune(const char* name) { return getenv(name); }
 #define GM_ABL(bits) (ablate & (bits))
@@ -57,6 +61,17 @@ static inline const char* gm_tune(const char*) { return nullptr; }
 
 // ---- kernel launchers (one per .hip file) -----------------------------------------------------
 int gm_index_build_device(GmIndexHost* ix, hipStream_t stream);
+// Genome FASTA files -> one bitfield in global coordinates, packed on the device (gm_fasta.hip).  On success d_genome ((total + 7) / 8 + 64 words, zero behind the
+// last base; the allocation may be up to an eighth larger) is the caller's; on failure nothing is left allocated.
+struct GmFastaGenome { uint32_t* d_genome = nullptr; uint64_t words = 0, total = 0; std::vector<std::string> names; std::vector<uint32_t> lens; };
+int gm_fasta_to_device(int n_files, const char* const* paths, GmFastaGenome* out);
+// extract_name (ref: common/fasta.c:242-283) on a '>' / '@' line without its '\n': what follows the mark up to the first tab, trimmed, cut at the first blank
+static inline std::string gm_extract_name(const std::string& line) {
+  size_t b = 1, e = line.find('\t', 1); if (e == std::string::npos) e = line.size();
+  while (b < e && isspace((unsigned char)line[b])) b++; while (e > b && isspace((unsigned char)line[e - 1])) e--;      // strtrim
+  size_t k = b; while (k < e && line[k] != ' ' && line[k] != '\t') k++;
+  return line.substr(b, k - b);
+}
 int gm_index_colour_genome_device(GmIndexHost* ix, hipStream_t stream);   // derives d_genome_cs from d_genome
 int gm_index_from_lists_device(GmIndexHost* ix, int sn, const uint32_t* lens, const uint32_t* pos, uint32_t total);
 

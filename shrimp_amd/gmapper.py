@@ -108,7 +108,7 @@ class SwFullResults(C.Structure):   # struct gm_sw_full_results == the reference
 
 
 # every entry point include/gmapper_hip.h declares
-EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", "gm_preprocess_read_text", "gm_map_pairs_cs_fastq", "gm_map_reads_file", "gm_merge_options_default", "gm_merge_sam", "gm_release_cache", "gm_map_pairs_cs", "gm_last_error", "gm_device_count", "gm_params_default", "gm_params_default_cs", "gm_index_build", "gm_index_free", "gm_index_list_cutoff",
+EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", "gm_preprocess_read_text", "gm_map_pairs_cs_fastq", "gm_map_reads_file", "gm_merge_options_default", "gm_merge_sam", "gm_release_cache", "gm_map_pairs_cs", "gm_last_error", "gm_device_count", "gm_params_default", "gm_params_default_cs", "gm_index_build", "gm_index_build_fasta", "gm_index_n_contigs", "gm_index_contig", "gm_sam_header", "gm_index_build_timing", "gm_index_free", "gm_index_list_cutoff",
            "gm_index_save", "gm_index_load", "gm_index_bytes", "gm_index_n_slabs", "gm_index_has_buckets", "gm_index_get_list", "gm_index_device_array", "gm_index_meta", "gm_index_alloc_like",
            "sw_vector_setup", "sw_vector", "sw_vector_stats", "sw_vector_cleanup", "gm_sw_vector_batch", "gm_sw_vector_batch_bounded",
            "sw_gapless_setup", "sw_gapless", "sw_gapless_stats", "gm_sw_gapless_batch",
@@ -137,6 +137,11 @@ def lib():
     L.gm_params_default.argtypes = [C.POINTER(Params)]
     L.gm_params_default_cs.argtypes = [C.POINTER(Params)]
     L.gm_index_build.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(u32p), u32p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.POINTER(Params)]
+    L.gm_index_build_fasta.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.POINTER(Params)]
+    L.gm_index_n_contigs.argtypes = [vp]; L.gm_index_n_contigs.restype = C.c_int
+    L.gm_index_contig.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), u32p]
+    L.gm_sam_header.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.gm_index_build_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.gm_index_free.argtypes = [vp]
     L.gm_index_save.argtypes = [vp, C.c_char_p]
     L.gm_index_load.argtypes = [C.POINTER(vp), C.c_int, C.c_char_p, C.POINTER(Params)]
@@ -245,6 +250,41 @@ class Index:
         self.h = C.c_void_p(); self.device = device; self._packed = []; self.contig_len = []
         _check(lib().gm_index_load(C.byref(self.h), device, prefix.encode(), C.byref(self.params)), "gm_index_load")
         return self
+
+    @classmethod
+    def from_fasta(cls, paths, seeds=None, params: "Params | None" = None, device: int = 0) -> "Index":
+        """load_genome(files, nfiles): the genome FASTA files (plain or gzip, in this order) packed on the device and indexed"""
+        if isinstance(paths, (str, bytes, os.PathLike)):
+            paths = [paths]
+        self = cls.__new__(cls)
+        self.params = params or default_params()
+        self.h = C.c_void_p(); self.device = device; self._packed = []; self.contig_len = []
+        ps = [os.fsencode(p) for p in paths]
+        arr = (C.c_char_p * len(ps))(*ps)
+        sd = None; ns = 0
+        if seeds:
+            ns = len(seeds); sd = (C.c_char_p * ns)(*[s.encode() for s in seeds])
+        _check(lib().gm_index_build_fasta(C.byref(self.h), device, len(ps), arr, ns, sd, C.byref(self.params)), "gm_index_build_fasta")
+        self.contig_len = [n for _, n in self.contigs()]
+        return self
+
+    def contigs(self):
+        """[(name, length)] of the index's contigs"""
+        L = lib(); out = []
+        for c in range(L.gm_index_n_contigs(self.h)):
+            nm = C.c_char_p(); ln = C.c_uint32()
+            _check(L.gm_index_contig(self.h, c, C.byref(nm), C.byref(ln)), "gm_index_contig")
+            out.append((nm.value, ln.value))
+        return out
+
+    def sam_header(self, rg_id=None, rg_sample=None, command_line=None) -> bytes:
+        """the header gmapper prints before its records: @HD, one @SQ per contig, @RG when rg_id is given, @PG when command_line is given"""
+        L = lib(); out = C.c_void_p(); n = C.c_size_t()
+        enc = lambda x: None if x is None else (x if isinstance(x, bytes) else str(x).encode())
+        _check(L.gm_sam_header(self.h, enc(rg_id), enc(rg_sample), enc(command_line), C.byref(out), C.byref(n)), "gm_sam_header")
+        text = C.string_at(out, n.value)
+        L.gm_free(out)
+        return text
 
     def save(self, prefix: str) -> None:
         """the reference's -S: files stock gmapper can load with -L"""
