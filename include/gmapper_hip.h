@@ -41,8 +41,8 @@ extern "C" {
 #define GM_E_NOMEM      -6
 
 const char *gm_last_error(void);
-/* sizeof of the structs that cross the ABI, for bindings to check their mirrors against: which = 0 gm_params_t, 1 gm_pair_opts_t, 2 gm_map_stats_t, 3 gm_merge_options_t
- * (-1 for any other value) */
+/* sizeof of the structs that cross the ABI, for bindings to check their mirrors against: which = 0 gm_params_t, 1 gm_pair_opts_t, 2 gm_map_stats_t, 3 gm_merge_options_t,
+ * 4 gm_sw_full_rec_t (-1 for any other value) */
 int gm_abi_sizeof(int which);
 /* number of visible HIP devices (0 when none); never initialises more than the runtime */
 int gm_device_count(void);
@@ -279,6 +279,42 @@ int  post_sw_stats(uint64_t *invocs, uint64_t *cells, double *secs);
 /* batch form of the colour-space vector filter: as gm_sw_vector_batch plus the letter-space genome and one initial base per read */
 int gm_sw_vector_batch_cs(int n, const uint32_t *genome_cs, const uint32_t *genome_ls, uint64_t genome_words, const int64_t *g_off,
                           const int *glen, const uint32_t *reads, int read_words, const int *rlen, const int *initbp, int *scores);
+
+/* ---------------------------------------------------------------------------------------------
+ * S2, batch forms: n independent sw_full_ls / sw_full_cs calls in one go, on this thread's sw_full_ls_setup / sw_full_cs_setup state (without it: GM_E_NOTSETUP).
+ * Input layout of gm_sw_vector_batch: one shared genome bitfield, g_off[i] a base offset into it, reads[i * read_words ..) read i.  One call makes a fixed
+ * number of device allocations, copies and kernel launches whatever n is (the back-pointer scratch belongs to the resident waves, not to the items).
+ *   anchors       n boxes (x, y, length, width as sw_full_ls / sw_full_cs take them), or NULL.  Letter space: NULL, or an item whose box has length <= 0, runs over the
+ *                 band the threshold allows (the single seam's anchors == NULL).  Colour space needs a box for every item, as the single seam does.
+ *   revcmpl       n flags or NULL (all 0);  threshscore n;  maxscore n (letter space, read in local mode only; may be NULL otherwise)
+ *   crossover_scores  colour space: NULL (the global penalty everywhere) or n rows of xover_stride >= rlen[i] per-position scores, the single seam's crossover_score[]
+ * Output: recs[i] for every item.  status 0: answered, with the values the single seam leaves in struct gm_sw_full_results (letter space, score 0: rmapped = gmapped = 1,
+ * genome_start = g_off[i]; colour space below threshscore: all 0).  status < 0 (GM_E_*): the device path cannot take this item -- sizes beyond the setup's, a window
+ * outside the bitfield, a colour-space box missing, a crossover score outside [-128, 127], a window that does not fit LDS beside the longest read of the call (colour space: 48 bytes a column) -- it is
+ * refused with score 0, the reason of the last such item is in gm_last_error(), and the other items of the call are answered all the same.
+ * *ops: one buffer of *ops_len bytes (gm_free), item i's edit operations at ops[ops_off .. ops_off + n_ops) in alignment order:
+ *   letter space   'M' match or mismatch, 'I' insertion (a genome letter against a gap in the read), 'D' deletion (a read letter against a gap in the genome)
+ *   colour space   low nibble 1 = insertion; 2..5 = deletion, 6..9 = match / mismatch, the read letter taken from letter translation 0..3 of the colour read
+ *                  (translation k starts from primer letter (initbp + k) % 4: the base called in that column); bit 7 = a crossover at this column (lower case in qralign)
+ * gm_sw_full_batch_strings: dbalign / qralign of one item exactly as the single seams return them, rebuilt on the host from the item's record, the ops buffer and the
+ * caller's own bitfields (genome: the shared one, genome_len positions; read: read i's words, rlen positions; ops_len: *ops_len of the batch call); both malloc()ed, gm_free.
+ * A record whose operations or alignment do not lie inside those lengths is refused with GM_E_ARG before anything is read through it.  Letter space without alignment: two empty strings; colour space: two NULLs.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gm_sw_full_rec {
+  int score, read_start, rmapped, gmapped, matches, mismatches, insertions, deletions, crossovers /* colour space only, else 0 */;
+  int status;                            /* 0 ok; < 0: this item was refused (GM_E_*), score = 0 */
+  int64_t genome_start;                  /* counted from the start of `genome`, i.e. includes g_off[i] */
+  uint64_t ops_off; uint32_t n_ops;      /* this item's edit operations: ops[ops_off .. ops_off + n_ops) */
+} gm_sw_full_rec_t;
+int gm_sw_full_ls_batch(int n, const uint32_t *genome, uint64_t genome_words, const int64_t *g_off, const int *glen,
+                        const uint32_t *reads, int read_words, const int *rlen, const struct gm_anchor *anchors, const uint8_t *revcmpl,
+                        const int *threshscore, const int *maxscore, int local_alignment, gm_sw_full_rec_t *recs, uint8_t **ops, uint64_t *ops_len);
+int gm_sw_full_cs_batch(int n, const uint32_t *genome_ls, uint64_t genome_words, const int64_t *g_off, const int *glen,
+                        const uint32_t *reads, int read_words, const int *rlen, const uint8_t *initbp, const struct gm_anchor *anchors, const uint8_t *revcmpl,
+                        const int *threshscore, const int *crossover_scores, int xover_stride, int is_rna, int local_alignment,
+                        gm_sw_full_rec_t *recs, uint8_t **ops, uint64_t *ops_len);
+int gm_sw_full_batch_strings(int colour_space, const gm_sw_full_rec_t *rec, const uint8_t *ops, uint64_t ops_len, const uint32_t *genome, uint64_t genome_len,
+                             const uint32_t *read, int rlen, int initbp, int is_rna, char **dbalign, char **qralign);
 
 /* ---------------------------------------------------------------------------------------------
  * S4: the per-read pipeline.  Replaces handle_read() for unpaired letter-space reads

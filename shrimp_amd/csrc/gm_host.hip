@@ -84,7 +84,7 @@ extern "C" void gm_params_default(gm_params_t* p) {
   p->trim_front = 0; p->trim_end = 0; p->trim_first = 1; p->trim_second = 1; p->trim_illumina = 0; p->min_avg_qv = 10; p->ignore_qvs = 0; p->no_qv_check = 0;      // ref: gmapper.h:63-67,75,81,104
 }
 extern "C" int gm_abi_sizeof(int which) {
-  switch (which) { case 0: return (int)sizeof(gm_params_t); case 1: return (int)sizeof(gm_pair_opts_t); case 2: return (int)sizeof(gm_map_stats_t); case 3: return (int)sizeof(gm_merge_options_t); }
+  switch (which) { case 0: return (int)sizeof(gm_params_t); case 1: return (int)sizeof(gm_pair_opts_t); case 2: return (int)sizeof(gm_map_stats_t); case 3: return (int)sizeof(gm_merge_options_t); case 4: return (int)sizeof(gm_sw_full_rec_t); }
   return -1;
 }
 // compute_mapping_qualities (ref: gmapper.c:2258,2325-2328): off with --no-mapping-qualities and in local mode -- then MAPQ 255, no Z tags, no post_sw (mapping.c:1648)
@@ -2338,6 +2338,209 @@ extern "C" void sw_full_cs(uint32_t* genome_ls, int goff, int glen, uint32_t* re
     else { const char d = LSTRANS[nib(genome_ls, pj++)]; if (c == 'n' || c == 'N') c = xov ? (char)tolower((int)d) : d; db.push_back(d); q.push_back(c); }
   }
   sfr->dbalign = strdup(db.c_str()); sfr->qralign = strdup(q.c_str());
+}
+
+// ---- S2 batch: gm_sw_full_ls_batch / gm_sw_full_cs_batch -----------------------------------------------------------------------------
+// One call = a fixed number of device buffers (genome, reads, items, results, ops, back-pointer scratch, crossover rows), copies and launches.  The scratch is
+// grid x (largest glen x rlen of the launch), never the sum over the items; when that passes GM_SWF_BACK_BUDGET with the grid the items would fill, the items are
+// sorted into at most three launches by matrix size (so that a few large windows do not starve the many small ones of waves) that share the one scratch.
+static const size_t GM_SWF_BACK_BUDGET = (size_t)512 << 20;
+static const int GM_SWF_MAX_GRID = 2048;
+struct SwfLaunch { int first = 0, count = 0, grid = 0, max_g = 0, max_r = 0; size_t stride = 0; };
+// items (accepted ones only) are reordered by class; unit = scratch bytes a cell; *pool = bytes of the shared scratch
+static void swf_plan(std::vector<GmFullItem>& items, size_t unit, std::vector<SwfLaunch>& launches, size_t* pool) {
+  launches.clear(); *pool = 0;
+  if (items.empty()) return;
+  auto cells = [](const GmFullItem& it) { return (size_t)it.glen * (size_t)it.rlen; };
+  size_t M = 0; for (const GmFullItem& it : items) M = std::max(M, cells(it));
+  int want = (int)std::min<size_t>(items.size(), (size_t)GM_SWF_MAX_GRID);
+  if (gm_tune("GM_SWF_SLOTS") && atoi(gm_tune("GM_SWF_SLOTS")) > 0) want = std::min(want, atoi(gm_tune("GM_SWF_SLOTS")));      // (tuning build: few slots, i.e. many items of all shapes through each)
+  std::vector<size_t> bound;                                  // a class takes the items of at most this many cells that no earlier class took
+  if ((size_t)want * (M * unit + 256) > GM_SWF_BACK_BUDGET) { bound = {M / 64, M / 8, M}; } else bound = {M};
+  std::vector<GmFullItem> sorted; sorted.reserve(items.size());
+  size_t lo = 0;
+  for (size_t b : bound) {
+    SwfLaunch L; L.first = (int)sorted.size(); size_t mc = 0;
+    for (const GmFullItem& it : items) { const size_t c = cells(it); if (c > lo && c <= b) { sorted.push_back(it); mc = std::max(mc, c); L.max_g = std::max(L.max_g, it.glen); L.max_r = std::max(L.max_r, it.rlen); } }
+    lo = b;
+    L.count = (int)sorted.size() - L.first;
+    if (!L.count) continue;
+    L.stride = (mc * unit + 256 + 15) & ~(size_t)15;
+    L.grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(want, L.count), GM_SWF_BACK_BUDGET / L.stride));
+    *pool = std::max(*pool, (size_t)L.grid * L.stride);
+    launches.push_back(L);
+  }
+  items.swap(sorted);
+}
+static inline int swf_nib(const uint32_t* b, long long i) { return (int)((b[i / 8] >> (4 * (i % 8))) & 0xf); }
+
+// shared body: colour = gm_sw_full_cs_batch
+static int sw_full_batch_impl(bool colour, int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen, const uint32_t* reads, int read_words,
+                              const int* rlen, const uint8_t* initbp, const struct gm_anchor* anchors, const uint8_t* revcmpl, const int* threshscore, const int* maxscore,
+                              const int* xover, int xover_stride, int is_rna, int local, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len) {
+  const char* who = colour ? "gm_sw_full_cs_batch" : "gm_sw_full_ls_batch";
+  if (ops) *ops = nullptr; if (ops_len) *ops_len = 0;
+  if (colour ? !g_sc.init : !g_sf.init) { gm_set_error("%s called before sw_full_%s_setup", who, colour ? "cs" : "ls"); return GM_E_NOTSETUP; }
+  if (n <= 0) return GM_OK;
+  if (!genome || !g_off || !glen || !reads || !rlen || !threshscore || !recs || !ops || !ops_len || read_words < 1 || (colour && !initbp) || (xover && xover_stride < 1) ||
+      (!colour && local && !maxscore)) { gm_set_error("%s: a required argument is missing", who); return GM_E_ARG; }
+  SeamTimer tm(colour ? &g_sc.secs : &g_sf.secs);
+  const int dblen = colour ? g_sc.dblen : g_sf.dblen, qrlen = colour ? g_sc.qrlen : g_sf.qrlen;
+  std::vector<GmFullItem> items; items.reserve(n);
+  std::vector<int8_t> xrows;
+  const int xstride = xover ? ((xover_stride + 15) & ~15) : 0;
+  if (xover) xrows.assign((size_t)n * xstride, 0);
+  unsigned long long ops_total = 0;
+  // LDS is laid out for the longest read and the longest window of a launch, which may belong to different items: an item is admitted when its window fits beside the
+  // longest read of the call that is otherwise in order (so whatever the launch classes turn out to be, each fits)
+  auto in_order = [&](int i) { return glen[i] >= 1 && rlen[i] >= 1 && g_off[i] >= 0 && (uint64_t)g_off[i] + (uint64_t)glen[i] <= genome_words * 8 &&
+                                      ((uint64_t)rlen[i] + 7) / 8 <= (uint64_t)read_words && glen[i] <= dblen && rlen[i] <= qrlen; };
+  int call_max_r = 1;
+  for (int i = 0; i < n; i++) if (in_order(i)) call_max_r = std::max(call_max_r, rlen[i]);
+  for (int i = 0; i < n; i++) {
+    gm_sw_full_rec_t& R = recs[i]; memset(&R, 0, sizeof R);
+    auto refuse = [&](int code, const char* why) { R.status = code; gm_set_error("%s: item %d refused: %s", who, i, why); };
+    if (glen[i] < 1 || rlen[i] < 1 || g_off[i] < 0 || (uint64_t)g_off[i] + (uint64_t)glen[i] > genome_words * 8 || ((uint64_t)rlen[i] + 7) / 8 > (uint64_t)read_words) {
+      refuse(GM_E_ARG, "window or read outside the bitfields"); continue; }
+    if (glen[i] > dblen || rlen[i] > qrlen) { refuse(GM_E_ARG, "window / read longer than the setup sizes"); continue; }
+    const bool has_anchor = anchors && anchors[i].length > 0;
+    if (colour) {
+      if (!has_anchor || g_sc.p[7] < 0) { refuse(GM_E_ARG, "colour space needs one anchor box (gmapper's call, ref: mapping.c:375-379)"); continue; }
+      if (initbp[i] > 3) { refuse(GM_E_ARG, "initbp outside 0..3"); continue; }
+      if (gm_sw_full_cs_batch_lds(glen[i], call_max_r) > GM_SWF_LDS_LIMIT) { refuse(GM_E_ARG, "the window does not fit LDS (48 bytes a column) beside the call's longest read"); continue; }
+      if (xover) {
+        if (xover_stride < rlen[i]) { refuse(GM_E_ARG, "xover_stride shorter than the read"); continue; }
+        bool ok = true;
+        for (int k = 0; k < rlen[i]; k++) { const int v = xover[(size_t)i * xover_stride + k]; if (v < -128 || v > 127) { ok = false; break; } xrows[(size_t)i * xstride + k] = (int8_t)v; }
+        if (!ok) { refuse(GM_E_RANGE, "a per-position crossover score outside [-128, 127] (the device keeps them in 8 bits)"); continue; }
+      }
+    } else if (gm_sw_full_batch_lds(glen[i], call_max_r) > GM_SWF_LDS_LIMIT) { refuse(GM_E_ARG, "the window does not fit LDS beside the call's longest read"); continue; }
+    GmFullItem it; memset(&it, 0, sizeof it);
+    it.goff = g_off[i]; it.glen = glen[i]; it.rlen = rlen[i];
+    if (has_anchor) { it.ax = anchors[i].x; it.ay = anchors[i].y; it.alen = anchors[i].length; it.awidth = anchors[i].width; } else { it.alen = it.awidth = 1; }
+    it.thresh = threshscore[i]; it.maxscore = maxscore ? maxscore[i] : 0;
+    it.flags = (has_anchor ? 1 : 0) | ((revcmpl && revcmpl[i]) ? 2 : 0);
+    it.initbp = colour ? ((int)initbp[i] | (is_rna ? GM_SEAM_RNA : 0)) : 0;
+    it.ops_cap = glen[i] + rlen[i] + 8; it.ops_off = ops_total; it.idx = i;           // exclusive scan of the caps, in item order
+    ops_total += (unsigned long long)it.ops_cap;
+    items.push_back(it);
+  }
+  if (items.empty()) return GM_OK;
+  std::vector<SwfLaunch> launches; size_t pool = 0;
+  swf_plan(items, colour ? 12 : 1, launches, &pool);
+  GmDevBufs bufs;
+  uint32_t *dg = nullptr, *dr = nullptr; GmFullItem* di = nullptr; GmFullOut* dout = nullptr; uint8_t *dops = nullptr, *dback = nullptr; int8_t* dx = nullptr;
+  GM_HIP(bufs.get(&dg, (genome_words + 8) * 4)); GM_HIP(bufs.get(&dr, (size_t)n * read_words * 4 + 32)); GM_HIP(bufs.get(&di, items.size() * sizeof(GmFullItem)));
+  GM_HIP(bufs.get(&dout, (size_t)n * sizeof(GmFullOut))); GM_HIP(bufs.get(&dops, (size_t)ops_total + 16)); GM_HIP(bufs.get(&dback, pool));
+  if (xover) GM_HIP(bufs.get(&dx, xrows.size() + 16));
+  GM_HIP(hipMemsetAsync(dg + genome_words, 0, 8 * 4, 0));
+  GM_HIP(hipMemcpyAsync(dg, genome, genome_words * 4, hipMemcpyHostToDevice, 0));
+  GM_HIP(hipMemcpyAsync(dr, reads, (size_t)n * read_words * 4, hipMemcpyHostToDevice, 0));
+  GM_HIP(hipMemcpyAsync(di, items.data(), items.size() * sizeof(GmFullItem), hipMemcpyHostToDevice, 0));
+  if (xover) GM_HIP(hipMemcpyAsync(dx, xrows.data(), xrows.size(), hipMemcpyHostToDevice, 0));
+  for (const SwfLaunch& L : launches) {
+    const int rc = colour ? gm_launch_sw_full_cs_batch(g_sc.p, L.first, L.count, L.grid, di, dg, dr, read_words, L.max_g, L.max_r, dx, xstride, (uint32_t*)dback, L.stride / 4, dout,
+                                                       dops, local ? 1 : 0, 0)
+                          : gm_launch_sw_full_batch(g_sf.sc, L.first, L.count, L.grid, di, dg, dr, read_words, L.max_g, L.max_r, dback, L.stride, dout, dops, local ? 1 : 0, 0);
+    if (rc != GM_OK) { (void)hipDeviceSynchronize(); return rc; }
+  }
+  std::vector<GmFullOut> out(n); std::vector<uint8_t> hops((size_t)ops_total);
+  GM_HIP(hipMemcpyAsync(hops.data(), dops, (size_t)ops_total, hipMemcpyDeviceToHost, 0));
+  GM_HIP(hipMemcpyAsync(out.data(), dout, (size_t)n * sizeof(GmFullOut), hipMemcpyDeviceToHost, 0));
+  GM_HIP(hipStreamSynchronize(0));
+  for (const GmFullItem& it : items) {                                               // (the items that ran: a refused item, or a call that failed before here, scored nothing)
+    if (colour) { g_sc.invocs++; g_sc.cells += 4ull * (uint64_t)it.glen * (uint64_t)it.rlen; }
+    else { g_sf.invocs++; g_sf.cells += (uint64_t)it.glen * (uint64_t)it.rlen; }
+  }
+  // the used lengths, compacted in item order
+  std::sort(items.begin(), items.end(), [](const GmFullItem& a, const GmFullItem& b) { return a.idx < b.idx; });
+  uint64_t used = 0;
+  for (const GmFullItem& it : items) { const int* v = out[it.idx].v; if (v[0] > 0) used += (uint64_t)std::min(v[10], it.ops_cap); }
+  uint8_t* obuf = (uint8_t*)malloc(used ? used : 1);
+  if (!obuf) { gm_set_error("%s: out of memory", who); return GM_E_NOMEM; }
+  uint64_t at = 0;
+  for (const GmFullItem& it : items) {
+    const int* v = out[it.idx].v; gm_sw_full_rec_t& R = recs[it.idx];
+    R.score = v[0];
+    if (v[0] > 0) {
+      R.read_start = v[1]; R.rmapped = v[2]; R.genome_start = (int64_t)it.goff + v[3]; R.gmapped = v[4];
+      R.matches = v[5]; R.mismatches = v[6]; R.insertions = v[7]; R.deletions = v[8]; R.crossovers = v[9];
+      R.n_ops = (uint32_t)std::min(v[10], it.ops_cap); R.ops_off = at;
+      memcpy(obuf + at, hops.data() + it.ops_off, R.n_ops); at += R.n_ops;
+    } else if (!colour) { R.score = v[0] < 0 ? 0 : v[0]; R.rmapped = 1; R.gmapped = 1; R.genome_start = it.goff; R.ops_off = at; }      // as sw_full_ls leaves a window without alignment
+    else { R.score = 0; R.ops_off = at; }
+  }
+  *ops = obuf; *ops_len = used;
+  return GM_OK;
+}
+extern "C" int gm_sw_full_ls_batch(int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen, const uint32_t* reads, int read_words,
+                                   const int* rlen, const struct gm_anchor* anchors, const uint8_t* revcmpl, const int* threshscore, const int* maxscore,
+                                   int local_alignment, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len) {
+  return sw_full_batch_impl(false, n, genome, genome_words, g_off, glen, reads, read_words, rlen, nullptr, anchors, revcmpl, threshscore, maxscore, nullptr, 0, 0,
+                            local_alignment, recs, ops, ops_len);
+}
+extern "C" int gm_sw_full_cs_batch(int n, const uint32_t* genome_ls, uint64_t genome_words, const int64_t* g_off, const int* glen, const uint32_t* reads, int read_words,
+                                   const int* rlen, const uint8_t* initbp, const struct gm_anchor* anchors, const uint8_t* revcmpl, const int* threshscore,
+                                   const int* crossover_scores, int xover_stride, int is_rna, int local_alignment, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len) {
+  return sw_full_batch_impl(true, n, genome_ls, genome_words, g_off, glen, reads, read_words, rlen, initbp, anchors, revcmpl, threshscore, nullptr, crossover_scores,
+                            xover_stride, is_rna, local_alignment, recs, ops, ops_len);
+}
+// pretty_print of one batch item (ref: sw-full-ls.c:524-560, sw-full-cs.c:945-1060), as sw_full_ls / sw_full_cs above build their strings.  Host only.
+extern "C" int gm_sw_full_batch_strings(int colour_space, const gm_sw_full_rec_t* rec, const uint8_t* ops, uint64_t ops_len, const uint32_t* genome, uint64_t genome_len,
+                                        const uint32_t* read, int rlen_in, int initbp, int is_rna, char** dbalign, char** qralign) {
+  if (!rec || !dbalign || !qralign) { gm_set_error("gm_sw_full_batch_strings: a required argument is missing"); return GM_E_ARG; }
+  *dbalign = *qralign = nullptr;
+  const bool aligned = rec->status == 0 && rec->score > 0;
+  if (!aligned) { if (!colour_space) { *dbalign = strdup(""); *qralign = strdup(""); } return GM_OK; }
+  if (!ops || !genome || !read || (colour_space && (initbp < 0 || initbp > 3))) { gm_set_error("gm_sw_full_batch_strings: a required argument is missing"); return GM_E_ARG; }
+  // a record that does not lie inside what the caller holds is refused before anything is read through it
+  uint64_t adv_g = 0, adv_r = 0;
+  if (rec->ops_off > ops_len || rec->n_ops > ops_len - rec->ops_off || rec->genome_start < 0 || rec->read_start < 0 || rlen_in < 0) {
+    gm_set_error("gm_sw_full_batch_strings: the record points outside the ops buffer or the bitfields"); return GM_E_ARG; }
+  const uint8_t* o = ops + rec->ops_off;
+  for (uint32_t k = 0; k < rec->n_ops; k++) {
+    const bool ins = colour_space ? (o[k] & 0x0f) == 1 : o[k] == 'I', del = colour_space ? ((o[k] & 0x0f) >= 2 && (o[k] & 0x0f) <= 5) : o[k] == 'D';
+    if (!del) adv_g++; if (!ins) adv_r++;
+  }
+  if ((uint64_t)rec->genome_start + adv_g > genome_len || (uint64_t)rec->read_start + adv_r > (uint64_t)rlen_in) {
+    gm_set_error("gm_sw_full_batch_strings: the record's alignment runs past the genome or the read"); return GM_E_ARG; }
+  std::string db, q;
+  long long pj = rec->genome_start; int pi = rec->read_start;
+  if (!colour_space) {
+    for (uint32_t k = 0; k < rec->n_ops; k++) {
+      if (o[k] == 'D') { db.push_back('-'); q.push_back(LSTRANS[swf_nib(read, pi++)]); }
+      else if (o[k] == 'I') { db.push_back(LSTRANS[swf_nib(genome, pj++)]); q.push_back('-'); }
+      else { db.push_back(LSTRANS[swf_nib(genome, pj++)]); q.push_back(LSTRANS[swf_nib(read, pi++)]); }
+    }
+  } else {
+    const int rlen = rlen_in;
+    std::vector<uint8_t> qr[4];
+    for (int k = 0; k < 4; k++) {
+      qr[k].resize(rlen); int letter = (k + initbp) % 4;
+      for (int j = 0; j < rlen; j++) {
+        const int base = swf_nib(read, j);
+        if (base == 15) { qr[k][j] = 15; letter = (k + initbp) % 4; }
+        else {                                                   // cstols(letter, base, is_rna), ref: util.h:157-180
+          const int lt = (is_rna && letter == 4) ? 3 : letter;
+          int l2 = (lt % 2 == 0) ? ((4 + lt + base) % 4) : ((4 + lt - base) % 4); if (is_rna && l2 == 3) l2 = 4;
+          qr[k][j] = (uint8_t)((letter == 15 || base > 3) ? 15 : l2); letter = qr[k][j];
+        }
+      }
+    }
+    for (uint32_t t = 0; t < rec->n_ops; t++) {
+      const int type = o[t] & 0x0f; const bool xov = (o[t] & 0x80) != 0;
+      if (type == 1) { db.push_back(LSTRANS[swf_nib(genome, pj++)]); q.push_back('-'); continue; }
+      const bool del = type >= 2 && type <= 5;
+      const int lay = del ? type - 2 : type - 6;
+      if (lay < 0 || lay > 3 || pi >= rlen) { gm_set_error("gm_sw_full_batch_strings: an operation byte that is none of the encoding"); return GM_E_ARG; }
+      char c = LSTRANS[qr[lay][pi++]];
+      if (xov) c = (char)tolower((int)c);
+      if (del) { db.push_back('-'); q.push_back(c); }
+      else { const char d = LSTRANS[swf_nib(genome, pj++)]; if (c == 'n' || c == 'N') c = xov ? (char)tolower((int)d) : d; db.push_back(d); q.push_back(c); }
+    }
+  }
+  *dbalign = strdup(db.c_str()); *qralign = strdup(q.c_str());
+  return GM_OK;
 }
 
 

@@ -214,3 +214,19 @@ int gm_launch_sw_vector_batch_cs(const GmScoreDev& sc, int n, const uint32_t* d_
 int gm_launch_sw_full_cs_single(const int* cs_params9, const uint32_t* d_genome_ls, long long goff, int glen, const uint32_t* d_read, int rlen, int initbp,
                                 int thresh, long long ax, long long ay, int alen, int awidth, int revcmpl, uint32_t* d_back, int* d_out, uint8_t* d_ops,
                                 int ops_cap, hipStream_t stream, int local = 0, const int8_t* d_xrow = nullptr);
+
+// S2 batch (gm_sw_full_ls_batch / gm_sw_full_cs_batch): one window as the batch kernels read it, and what they write back per window.
+// flags: 1 = anchor box given (else the threshold band), 2 = revcmpl; initbp: colour space only, the primer letter | GM_SEAM_RNA; idx: the caller's item
+// (row of reads[] and of the crossover rows, slot of out[]); ops_off / ops_cap: the item's segment of the device ops buffer.
+struct GmFullItem { long long goff, ax, ay; unsigned long long ops_off; int glen, rlen, alen, awidth, thresh, maxscore, flags, initbp, ops_cap, idx; };
+// v[0..10] = score read_start rmapped genome_start (window-relative) gmapped matches mismatches insertions deletions crossovers n_ops
+struct GmFullOut { int v[12]; };
+static const size_t GM_SWF_LDS_LIMIT = 160 * 1024;      // LDS of a CU: what one wave of the batch kernels may take; the admission test of the host entries and the launchers share it
+size_t gm_sw_full_batch_lds(int max_g, int max_r);
+size_t gm_sw_full_cs_batch_lds(int max_g, int max_r);
+// items[first .. first + n) by `grid` waves; wave b owns back-pointer scratch d_back + b * back_stride (bytes; colour space: uint32 words)
+int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
+                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream);
+int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
+                               int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
+                               uint8_t* d_ops, int local, hipStream_t stream);

@@ -1254,6 +1254,109 @@ int gm_launch_sw_full_single(const GmScoreDev& sc, const uint32_t* d_genome, lon
   return GM_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// S2 batch: n independent sw_full_ls calls on caller bitfields, grid-stride over the items, one wave per item at a time (k_sw_full_single per item:
+// same band arithmetic, same full_sw_wave, same walk on lane 0).  LDS is laid out for the call's longest read and window.
+//
+// Back-pointer scratch belongs to the wave (blockIdx.x), not to the item: a wave's items of any shape follow each other through the same bytes, row
+// stride = the current item's glen.  Why stale bytes of an earlier item are never taken for this item's:
+//  * the walk only visits cells (i, j) with 0 <= i < rlen, 0 <= j < glen, and full_sw_wave writes back[i * glen + j] for every cell of the band
+//    (`inband`), so a byte the current item did not write belongs to a cell OUTSIDE its band;
+//  * global mode: a cell outside the band holds FS_NEG in all three states, so a state that is finite was derived from finite states only, i.e. from
+//    band cells or the virtual row above the matrix.  The walk starts at a cell of positive score and follows the source of a finite state to a
+//    finite state: it cannot step outside the band.  (That is why the `!(bb & 0x80)` test alone was enough on freshly allocated memory, where
+//    it never fires for score > 0.)
+//  * local mode: a cell outside the band reads as (0, -b_open, -a_open), a band cell CAN derive from it, and the reference stops there on its
+//    null back pointer.  The walk tests the band box itself (band_range) before it believes a byte -- as k_pass2 / k_pass2_g4 do on their reused scratch.
+// The band test is applied in both modes here, so the stop never depends on what an earlier item left behind.  Reads of the scratch are
+// agent-scope atomic loads (no stale line of an earlier item in the vector cache); an item's stores precede its walk by a barrier, and the next
+// item's stores follow the walk in program order of the same wave.
+// ---------------------------------------------------------------------------------------------
+template <bool LOCAL>
+__global__ void __launch_bounds__(GM_WAVE)
+k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ items, const uint32_t* __restrict__ genome, const uint32_t* __restrict__ reads,
+                int read_words, int max_g, int max_r, uint8_t* __restrict__ back_pool, size_t back_stride, GmFullOut* __restrict__ out, uint8_t* __restrict__ ops_all) {
+  extern __shared__ __align__(16) uint8_t sm[];
+  const int lane = threadIdx.x;
+  uint8_t* qr = sm;
+  uint8_t* db = sm + ((max_r + 15) & ~15);
+  int* carry = (int*)(db + ((max_g + 15) & ~15));
+  uint8_t* back = back_pool + (size_t)blockIdx.x * back_stride;
+  for (int k = blockIdx.x; k < n; k += gridDim.x) {
+    const GmFullItem it = items[first + k];
+    const int glen = __builtin_amdgcn_readfirstlane(it.glen), rlen = __builtin_amdgcn_readfirstlane(it.rlen), flags = __builtin_amdgcn_readfirstlane(it.flags);
+    __syncthreads();                                                              // lane 0 may still read the previous item's db / qr
+    load_read(reads + (size_t)it.idx * read_words, rlen, false, qr, lane);
+    load_window(genome, (uint64_t)it.goff, glen, false, db, lane);
+    __syncthreads();
+    const bool has_anchor = (flags & 1) != 0, revcmpl = (flags & 2) != 0;
+    long long rx, ry; int rw, rl;
+    if (has_anchor) {                                                             // anchor_join(1 anchor) + anchor_widen, as k_sw_full_single
+      long long nw = it.ax + it.ay, sw = it.ax - it.ay, ne = sw + 2 * (it.awidth - 1), se = nw + 2 * (it.alen - 1);
+      if ((nw + sw) % 2 != 0) nw--;
+      rx = (nw + sw) / 2; ry = nw - rx;
+      if ((ne - sw) % 2 != 0) ne++;
+      rw = (int)((ne - sw) / 2 + 1);
+      if ((se - nw) % 2 != 0) se++;
+      rl = (int)((se - nw) / 2 + 1);
+      rx -= sc.anchor_width / 2; ry += sc.anchor_width / 2; rw += sc.anchor_width;
+    } else threshold_band(glen, rlen, sc.match, it.thresh, &rx, &ry, &rl, &rw);  // ref: sw-full-ls.c:179-192
+    FullOut fo = full_sw_wave<LOCAL>(db, glen, qr, rlen, sc, revcmpl, rx, ry, rl, rw, back, carry, lane);
+    __syncthreads();
+    if (LOCAL && has_anchor && fo.score != it.maxscore) {                         // ref: sw-full-ls.c:395-398 (per item: the waves diverge, a wave does not)
+      threshold_band(glen, rlen, sc.match, it.thresh, &rx, &ry, &rl, &rw);
+      fo = full_sw_wave<LOCAL>(db, glen, qr, rlen, sc, revcmpl, rx, ry, rl, rw, back, carry, lane);
+      __syncthreads();
+    }
+    if (lane == 0) {
+      uint8_t* ops = ops_all + it.ops_off; const int ops_cap = it.ops_cap;
+      int i = fo.max_i, j = fo.max_j, no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0;
+      if (fo.score > 0) {
+        int state = 0, fs = fo.e_nw;
+        if (fo.e_w > fs) { state = 2; fs = fo.e_w; }
+        if (fo.e_n > fs) state = 1;
+        while (i >= 0 && j >= 0) {
+          int bx_min, bx_max; band_range(rx, ry, rl, rw, glen, i, &bx_min, &bx_max);
+          if (j < bx_min || j > bx_max) break;                                    // outside the band: not this item's byte (see above)
+          const uint8_t bb = __hip_atomic_load(&back[(size_t)i * glen + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (!(bb & 0x80)) break;
+          if (LOCAL && ((bb >> (4 + state)) & 1)) break;
+          int nstate;
+          if (state == 1) { if (no < ops_cap) ops[no] = 'D'; no++; ndel++; rstart = i; i--; nstate = ((bb >> 2) & 1) ? 1 : 0; }
+          else if (state == 2) { if (no < ops_cap) ops[no] = 'I'; no++; nin++; gstart = j; j--; nstate = ((bb >> 3) & 1) ? 2 : 0; }
+          else { if (no < ops_cap) ops[no] = 'M'; no++; if (db[j] == qr[i]) nm++; else nmm++; rstart = i; gstart = j; i--; j--; nstate = (bb & 3); }
+          state = nstate;
+        }
+        const int nov = min(no, ops_cap);
+        for (int a = 0, b = nov - 1; a < b; a++, b--) { uint8_t tt = ops[a]; ops[a] = ops[b]; ops[b] = tt; }
+      }
+      GmFullOut o;
+      o.v[0] = fo.score; o.v[1] = rstart; o.v[2] = fo.max_i - rstart + 1; o.v[3] = gstart; o.v[4] = fo.max_j - gstart + 1;
+      o.v[5] = nm; o.v[6] = nmm; o.v[7] = nin; o.v[8] = ndel; o.v[9] = 0; o.v[10] = no; o.v[11] = 0;
+      out[it.idx] = o;
+    }
+  }
+}
+
+size_t gm_sw_full_batch_lds(int max_g, int max_r) { return ((max_r + 15) & ~15) + ((max_g + 15) & ~15) + (size_t)max_g * 12 + 64; }
+int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
+                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream) {
+  if (n == 0) return GM_OK;
+  const size_t lds = gm_sw_full_batch_lds(max_g, max_r);
+  if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("sw_full_ls batch: window of %d does not fit LDS", max_g); return GM_E_ARG; }
+  if (local) {
+    GM_HIP(gm_lds_at_least((const void*)k_sw_full_batch<true>, lds));
+    hipLaunchKernelGGL(k_sw_full_batch<true>, dim3(grid), dim3(GM_WAVE), lds, stream, sc, first, n, d_items, d_genome, d_reads, read_words, max_g, max_r, d_back, back_stride,
+                       d_out, d_ops);
+  } else {
+    GM_HIP(gm_lds_at_least((const void*)k_sw_full_batch<false>, lds));
+    hipLaunchKernelGGL(k_sw_full_batch<false>, dim3(grid), dim3(GM_WAVE), lds, stream, sc, first, n, d_items, d_genome, d_reads, read_words, max_g, max_r, d_back, back_stride,
+                       d_out, d_ops);
+  }
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
 // ---- launchers ---------------------------------------------------------------------------------
 int gm_launch_pass1(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                     int window_len, int window_overlap_abs, GmHit* d_hits, const uint16_t* d_perm, const uint32_t* d_hit_cnt, int hcap,
@@ -2324,6 +2427,131 @@ int gm_launch_sw_full_cs_single(const int* cs_params9, const uint32_t* d_genome_
   GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_single, lds));
   hipLaunchKernelGGL(k_sw_full_cs_single, dim3(1), dim3(GM_WAVE), lds, stream, P, d_genome_ls, goff, glen, d_read, rlen, initbp, thresh, ax, ay, alen, awidth,
                      revcmpl, d_back, d_out, d_ops, ops_cap, local, d_xrow);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// S2 batch in colour space: n independent sw_full_cs calls, grid-stride over the items, one wave per item at a time (k_sw_full_cs_single per item:
+// global mode by full_sw_cs_wave, local mode by one 16-lane group of full_sw_cs_g4).  The back-pointer scratch (three words a cell) belongs to the
+// wave and is reused by its items as in k_sw_full_batch.  The single call clears its scratch first, because the walk takes a cell outside the
+// band for "back == 0"; clearing max(glen x rlen) words per item is what a batch cannot afford, so the walk asks the band box instead (code_at
+// returns 0 outside it, as k_pass2_cs / k_pass2_cs_g4 do on their reused scratch): every cell inside the band is written by the current item
+// before the walk, and no word outside it is ever read.
+// ---------------------------------------------------------------------------------------------
+template <bool LOCAL>
+__global__ void __launch_bounds__(GM_WAVE)          // (one wave per SIMD: with a second one the four local-mode variants spill 100+ bytes a lane)
+k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ items, const uint32_t* __restrict__ genome_ls, const uint32_t* __restrict__ reads,
+                   int read_words, int max_g, int max_r, const int8_t* __restrict__ xrows, int xstride, uint32_t* __restrict__ back_pool, size_t back_words,
+                   GmFullOut* __restrict__ out, uint8_t* __restrict__ ops_all) {
+  extern __shared__ __align__(16) uint8_t sm[];
+  const int lane = threadIdx.x;
+  const int qstride = (max_r + 15) & ~15;
+  uint8_t* rc = sm;                                   // colours
+  uint8_t* qr4 = rc + qstride;                        // four translations
+  uint8_t* db = qr4 + 4 * qstride;
+  int* carry = (int*)(db + ((max_g + 15) & ~15));
+  uint32_t* back = back_pool + (size_t)blockIdx.x * back_words;
+  for (int k = blockIdx.x; k < n; k += gridDim.x) {
+    const GmFullItem it = items[first + k];
+    const int glen = __builtin_amdgcn_readfirstlane(it.glen), rlen = __builtin_amdgcn_readfirstlane(it.rlen), flags = __builtin_amdgcn_readfirstlane(it.flags);
+    const int ib = __builtin_amdgcn_readfirstlane(it.initbp);
+    const bool is_rna = (ib & GM_SEAM_RNA) != 0, revcmpl = (flags & 2) != 0;
+    const int initbp = ib & 0xff;
+    const int8_t* xrow = xrows ? xrows + (size_t)it.idx * xstride : nullptr;
+    __syncthreads();                                  // lane 0 may still read the previous item's db / qr4
+    load_read(reads + (size_t)it.idx * read_words, rlen, false, rc, lane);
+    load_window(genome_ls, (uint64_t)it.goff, glen, false, db, lane);
+    __syncthreads();
+    if (lane < 4) {                                   // ref: sw-full-cs.c:1182-1197
+      int letter = (lane + initbp) % 4;
+      for (int j = 0; j < rlen; j++) {
+        const int base = rc[j];
+        if (base == 15) { qr4[lane * qstride + j] = 15; letter = (lane + initbp) % 4; }
+        else { const int l2 = cs_cstols(letter, base, is_rna); qr4[lane * qstride + j] = (uint8_t)l2; letter = l2; }
+      }
+    }
+    __syncthreads();
+    long long nw = it.ax + it.ay, sw = it.ax - it.ay, ne = sw + 2 * (it.awidth - 1), se = nw + 2 * (it.alen - 1);      // anchor_join + anchor_widen, ref: anchors.c:9-61
+    if ((nw + sw) % 2 != 0) nw--;
+    long long rx = (nw + sw) / 2, ry = nw - rx;
+    if ((ne - sw) % 2 != 0) ne++;
+    int rw = (int)((ne - sw) / 2 + 1);
+    if ((se - nw) % 2 != 0) se++;
+    int rl = (int)((se - nw) / 2 + 1);
+    rx -= P.anchor_width / 2; ry += P.anchor_width / 2; rw += P.anchor_width;
+    CsBest fo;
+    if (LOCAL) {                                      // ref: sw-full-cs.c:199-203,315,439-552
+      const bool act = lane < 16;
+      if (revcmpl) fo = P.taboo > 0 ? full_sw_cs_g4<16, int, true, true, true>(db, glen, qr4, qstride, rlen, P, act, (int)rx, (int)ry, rl, rw, back, carry, lane, xrow)
+                                    : full_sw_cs_g4<16, int, true, false, true>(db, glen, qr4, qstride, rlen, P, act, (int)rx, (int)ry, rl, rw, back, carry, lane, xrow);
+      else fo = P.taboo > 0 ? full_sw_cs_g4<16, int, false, true, true>(db, glen, qr4, qstride, rlen, P, act, (int)rx, (int)ry, rl, rw, back, carry, lane, xrow)
+                            : full_sw_cs_g4<16, int, false, false, true>(db, glen, qr4, qstride, rlen, P, act, (int)rx, (int)ry, rl, rw, back, carry, lane, xrow);
+    } else fo = full_sw_cs_wave<true>(db, glen, qr4, qstride, rlen, P, revcmpl, rx, ry, rl, rw, back, carry, lane, xrow);
+    __syncthreads();
+    __threadfence();
+    if (lane == 0) {
+      GmFullOut o;
+      for (int x = 0; x < 12; x++) o.v[x] = 0;
+      if (fo.score >= 0 && fo.score >= it.thresh) {    // ref :1216; do_backtrace :633-937
+        uint8_t* ops = ops_all + it.ops_off; const int ops_cap = it.ops_cap;
+        auto code_at = [&](int ci, int cj, int word, int lay) -> int {
+          int x_min, x_max; band_range(rx, ry, rl, rw, glen, ci, &x_min, &x_max);
+          if (cj < x_min || cj > x_max) return 0;     // a cell outside the band keeps back == 0 in the reference; here the word may be an earlier item's
+          const uint32_t w = __hip_atomic_load(&back[((size_t)ci * glen + cj) * 3 + word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          return (int)((w >> (8 * lay)) & 0xFFu);
+        };
+        int i = fo.i, j = fo.j, kk = fo.k;
+        int from = code_at(i, j, 0, kk), fromscore = fo.e_nw;
+        if (fo.e_w > fromscore) { from = code_at(i, j, 2, kk); fromscore = fo.e_w; }
+        if (fo.e_n > fromscore) from = code_at(i, j, 1, kk);
+        int no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0, nx = 0;
+        while (i >= 0 && j >= 0 && from != 0) {
+          const int dir = from >> 2, lay = from & 3;
+          uint8_t bt;
+          if (dir == 1 || dir == 2) { ndel++; rstart = i--; bt = (uint8_t)(2 + kk); }
+          else if (dir == 3 || dir == 4) { nin++; gstart = j--; bt = 1; }
+          else {
+            const int qv = qr4[kk * qstride + i];
+            if (db[j] == qv || db[j] == 15 || qv == 15) nm++; else nmm++;
+            rstart = i--; gstart = j--; bt = (uint8_t)(6 + kk);
+          }
+          if (kk != lay) { bt |= 0x80; nx++; kk = lay; }
+          if (no < ops_cap) ops[no] = bt;
+          no++;
+          if (i < 0 || j < 0) break;                  // the virtual row / left sentinel: back == 0 in the reference
+          const int word = (dir == 1 || dir == 5) ? 1 : ((dir == 4 || dir == 7) ? 2 : 0);
+          from = code_at(i, j, word, kk);
+        }
+        if (kk != 0 && no > 0) { if (no - 1 < ops_cap) ops[no - 1] |= 0x80; nx++; }     // ref :929-932
+        const int nov = min(no, ops_cap);
+        for (int a2 = 0, b2 = nov - 1; a2 < b2; a2++, b2--) { const uint8_t tt = ops[a2]; ops[a2] = ops[b2]; ops[b2] = tt; }
+        o.v[0] = fo.score; o.v[1] = rstart; o.v[2] = fo.i - rstart + 1; o.v[3] = gstart; o.v[4] = fo.j - gstart + 1;
+        o.v[5] = nm; o.v[6] = nmm; o.v[7] = nin; o.v[8] = ndel; o.v[9] = nx; o.v[10] = no;
+      }
+      out[it.idx] = o;
+    }
+  }
+}
+
+size_t gm_sw_full_cs_batch_lds(int max_g, int max_r) { return 5 * (size_t)((max_r + 15) & ~15) + ((max_g + 15) & ~15) + (size_t)max_g * 48 + 64; }
+int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
+                               int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
+                               uint8_t* d_ops, int local, hipStream_t stream) {
+  if (n == 0) return GM_OK;
+  GmCsDev P; P.match = cs_params9[0]; P.mismatch = cs_params9[1]; P.xover = cs_params9[2]; P.a_go = cs_params9[3]; P.a_ge = cs_params9[4];
+  P.b_go = cs_params9[5]; P.b_ge = cs_params9[6]; P.anchor_width = cs_params9[7]; P.taboo = cs_params9[8];
+  const size_t lds = gm_sw_full_cs_batch_lds(max_g, max_r);
+  if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("sw_full_cs batch: window of %d does not fit LDS", max_g); return GM_E_ARG; }      // (the host entry refuses such items one by one before it gets here)
+  if (local) {
+    GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_batch<true>, lds));
+    hipLaunchKernelGGL(k_sw_full_cs_batch<true>, dim3(grid), dim3(GM_WAVE), lds, stream, P, first, n, d_items, d_genome_ls, d_reads, read_words, max_g, max_r, d_xrows, xstride,
+                       d_back, back_words, d_out, d_ops);
+  } else {
+    GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_batch<false>, lds));
+    hipLaunchKernelGGL(k_sw_full_cs_batch<false>, dim3(grid), dim3(GM_WAVE), lds, stream, P, first, n, d_items, d_genome_ls, d_reads, read_words, max_g, max_r, d_xrows, xstride,
+                       d_back, back_words, d_out, d_ops);
+  }
   GM_HIP(hipGetLastError());
   return GM_OK;
 }

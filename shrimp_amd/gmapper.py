@@ -107,6 +107,15 @@ class SwFullResults(C.Structure):   # struct gm_sw_full_results == the reference
                [("crossovers", C.c_int), ("dup", C.c_bool), ("in_use", C.c_bool)]
 
 
+class SwFullRec(C.Structure):       # gm_sw_full_rec_t: one alignment of gm_sw_full_ls_batch / gm_sw_full_cs_batch (checked against gm_abi_sizeof(4))
+    _fields_ = [(n, C.c_int) for n in ("score", "read_start", "rmapped", "gmapped", "matches", "mismatches", "insertions", "deletions", "crossovers", "status")] + \
+               [("genome_start", C.c_int64), ("ops_off", C.c_uint64), ("n_ops", C.c_uint32)]
+
+
+SW_FULL_REC_DTYPE = np.dtype(SwFullRec)      # the structured numpy view of an array of them
+ANCHOR_DTYPE = np.dtype(Anchor)
+
+
 # every entry point include/gmapper_hip.h declares
 EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", "gm_preprocess_read_text", "gm_map_pairs_cs_fastq", "gm_map_reads_file", "gm_merge_options_default", "gm_merge_sam", "gm_release_cache", "gm_map_pairs_cs", "gm_last_error", "gm_device_count", "gm_params_default", "gm_params_default_cs", "gm_index_build", "gm_index_build_fasta", "gm_index_n_contigs", "gm_index_contig", "gm_sam_header", "gm_index_build_timing", "gm_index_free", "gm_index_list_cutoff",
            "gm_index_save", "gm_index_load", "gm_index_bytes", "gm_index_n_slabs", "gm_index_has_buckets", "gm_index_get_list", "gm_index_device_array", "gm_index_meta", "gm_index_alloc_like",
@@ -114,6 +123,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "sw_gapless_setup", "sw_gapless", "sw_gapless_stats", "gm_sw_gapless_batch",
            "sw_full_ls_setup", "sw_full_ls", "sw_full_ls_cleanup", "sw_full_ls_stats",
            "sw_full_cs_setup", "sw_full_cs", "sw_full_cs_cleanup", "sw_full_cs_stats", "gm_sw_vector_batch_cs",
+           "gm_sw_full_ls_batch", "gm_sw_full_cs_batch", "gm_sw_full_batch_strings",
            "post_sw_setup", "post_sw", "post_sw_cleanup", "post_sw_stats",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
@@ -169,6 +179,12 @@ def lib():
     L.sw_full_cs.argtypes = [u32p, C.c_int, C.c_int, u32p, C.c_int, C.c_int, C.c_int, C.POINTER(SwFullResults), C.c_bool, C.c_bool, C.POINTER(Anchor), C.c_int, C.c_int, vp]
     L.sw_full_cs.restype = None
     L.gm_sw_vector_batch_cs.argtypes = [C.c_int, u32p, u32p, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int), u32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.gm_sw_full_ls_batch.argtypes = [C.c_int, u32p, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int), u32p, C.c_int, C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), vp,
+                                      C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.gm_sw_full_cs_batch.argtypes = [C.c_int, u32p, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int), u32p, C.c_int, C.POINTER(C.c_int), vp, vp, vp, C.POINTER(C.c_int), vp,
+                                      C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.gm_sw_full_batch_strings.argtypes = [C.c_int, vp, vp, C.c_uint64, u32p, C.c_uint64, u32p, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.gm_abi_sizeof.argtypes = [C.c_int]; L.gm_abi_sizeof.restype = C.c_int
     L.gm_session_create.argtypes = [C.POINTER(vp), vp, C.POINTER(Params), C.c_int]
     L.gm_session_free.argtypes = [vp]
     L.gm_map_reads.argtypes = [vp, C.c_int, C.c_int, u32p, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(MapStats)]
@@ -694,6 +710,81 @@ def sw_full_ls(genome_words, goff, glen, read_words, rlen, anchor, revcmpl=False
     qr = C.string_at(s.qralign).decode() if s.qralign else ""
     L.gm_free(s.dbalign); L.gm_free(s.qralign)
     return {n: getattr(s, n) for n, _ in SwFullResults._fields_[:9]}, db, qr
+
+
+def _anchor_array(anchors, n):
+    """(n, 4) rows of x, y, length, width (a row with length 0: no box) -> an array of struct gm_anchor"""
+    a = np.asarray(anchors, dtype=np.int64).reshape(n, 4)
+    out = np.zeros(n, dtype=ANCHOR_DTYPE)
+    out["x"] = a[:, 0]; out["y"] = a[:, 1]; out["length"] = a[:, 2]; out["width"] = a[:, 3]; out["weight"] = 1
+    return out
+
+
+def sw_full_batch_strings(colour_space, rec, ops, genome_words, read_words, initbp=0, is_rna=False, rlen=None):
+    """gm_sw_full_batch_strings (host only): (dbalign, qralign) of one record as the single seams return them; colour space without alignment: (None, None).
+    rlen: the read's length (default: all positions of read_words); the library refuses a record that points outside ops, the genome or the read."""
+    L = lib()
+    g = np.ascontiguousarray(genome_words, dtype=np.uint32); r = np.ascontiguousarray(read_words, dtype=np.uint32)
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    one = np.ascontiguousarray(np.asarray(rec, dtype=SW_FULL_REC_DTYPE).reshape(1))
+    db, qr = C.c_void_p(), C.c_void_p()
+    _check(L.gm_sw_full_batch_strings(1 if colour_space else 0, one.ctypes.data, o.ctypes.data if o.size else None, o.size, g.ctypes.data_as(C.POINTER(C.c_uint32)), g.size * 8,
+                                      r.ctypes.data_as(C.POINTER(C.c_uint32)), r.size * 8 if rlen is None else int(rlen), int(initbp), 1 if is_rna else 0, C.byref(db), C.byref(qr)), "gm_sw_full_batch_strings")
+    out = tuple(None if p.value is None else C.string_at(p.value).decode() for p in (db, qr))
+    L.gm_free(db); L.gm_free(qr)
+    return out
+
+
+def _sw_full_batch_finish(colour, recs, ops_p, ops_len, g, r, rl, initbp, is_rna):
+    L = lib()
+    ops = np.ctypeslib.as_array(C.cast(ops_p, C.POINTER(C.c_uint8)), shape=(ops_len.value,)).copy() if ops_len.value else np.zeros(0, dtype=np.uint8)
+    L.gm_free(ops_p)
+    def strings(i):
+        return sw_full_batch_strings(colour, recs[i], ops, g, r[i], 0 if initbp is None else int(initbp[i]), is_rna, rlen=int(rl[i]))
+    return recs, ops, strings
+
+
+def sw_full_ls_batch(genome_words, g_off, glen, reads_words, rlen, anchors=None, revcmpl=None, threshscore=None, maxscore=None, local_alignment=False):
+    """gm_sw_full_ls_batch: n sw_full_ls calls in one.  anchors: (n, 4) rows x, y, length, width (length 0: the threshold band for that item) or None (for all).
+    Returns (records: structured array of SW_FULL_REC_DTYPE, ops: uint8 buffer, strings: i -> (dbalign, qralign))."""
+    L = lib()
+    g = np.ascontiguousarray(genome_words, dtype=np.uint32); r = np.ascontiguousarray(reads_words, dtype=np.uint32)
+    if r.ndim != 2: raise GmError("sw_full_ls_batch: reads_words is (n, read_words)")
+    n = r.shape[0]
+    go = np.ascontiguousarray(g_off, dtype=np.int64); gn = np.ascontiguousarray(glen, dtype=np.int32); rl = np.ascontiguousarray(rlen, dtype=np.int32)
+    th = np.ascontiguousarray(threshscore if threshscore is not None else np.zeros(n), dtype=np.int32)
+    mx = None if maxscore is None else np.ascontiguousarray(maxscore, dtype=np.int32)
+    rv = None if revcmpl is None else np.ascontiguousarray(revcmpl, dtype=np.uint8)
+    an = None if anchors is None else _anchor_array(anchors, n)
+    if any(a is not None and a.shape[0] != n for a in (go, gn, rl, th, mx, rv)): raise GmError("sw_full_ls_batch: every per-item array has n entries")
+    recs = np.zeros(n, dtype=SW_FULL_REC_DTYPE); ops_p = C.c_void_p(); ops_len = C.c_uint64(0)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int)); dp = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    _check(L.gm_sw_full_ls_batch(n, g.ctypes.data_as(C.POINTER(C.c_uint32)), g.size, go.ctypes.data_as(C.POINTER(C.c_int64)), ip(gn), r.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                 r.shape[1], ip(rl), dp(an), dp(rv), ip(th), dp(mx), 1 if local_alignment else 0, dp(recs), C.byref(ops_p), C.byref(ops_len)), "gm_sw_full_ls_batch")
+    return _sw_full_batch_finish(False, recs, ops_p, ops_len, g, r, rl, None, False)
+
+
+def sw_full_cs_batch(genome_ls, g_off, glen, reads_words, rlen, initbp, anchors, revcmpl=None, threshscore=None, xover=None, is_rna=False, local_alignment=False):
+    """gm_sw_full_cs_batch: n sw_full_cs calls in one.  anchors: (n, 4) rows x, y, length, width; xover: None or (n, >= max rlen) per-position crossover scores.
+    Returns (records, ops, strings) as sw_full_ls_batch; an item the device path refuses has status < 0 (reason: gm_last_error)."""
+    L = lib()
+    g = np.ascontiguousarray(genome_ls, dtype=np.uint32); r = np.ascontiguousarray(reads_words, dtype=np.uint32)
+    if r.ndim != 2: raise GmError("sw_full_cs_batch: reads_words is (n, read_words)")
+    n = r.shape[0]
+    go = np.ascontiguousarray(g_off, dtype=np.int64); gn = np.ascontiguousarray(glen, dtype=np.int32); rl = np.ascontiguousarray(rlen, dtype=np.int32)
+    ib = np.ascontiguousarray(initbp, dtype=np.uint8)
+    th = np.ascontiguousarray(threshscore if threshscore is not None else np.zeros(n), dtype=np.int32)
+    rv = None if revcmpl is None else np.ascontiguousarray(revcmpl, dtype=np.uint8)
+    an = _anchor_array(anchors, n)
+    xs = None if xover is None else np.ascontiguousarray(xover, dtype=np.int32)
+    if xs is not None and (xs.ndim != 2 or xs.shape[0] != n): raise GmError("sw_full_cs_batch: xover is (n, row length)")
+    if any(a is not None and a.shape[0] != n for a in (go, gn, rl, th, ib, rv)): raise GmError("sw_full_cs_batch: every per-item array has n entries")
+    recs = np.zeros(n, dtype=SW_FULL_REC_DTYPE); ops_p = C.c_void_p(); ops_len = C.c_uint64(0)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int)); dp = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    _check(L.gm_sw_full_cs_batch(n, g.ctypes.data_as(C.POINTER(C.c_uint32)), g.size, go.ctypes.data_as(C.POINTER(C.c_int64)), ip(gn), r.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                 r.shape[1], ip(rl), dp(ib), dp(an), dp(rv), ip(th), dp(xs), 0 if xs is None else xs.shape[1], 1 if is_rna else 0,
+                                 1 if local_alignment else 0, dp(recs), C.byref(ops_p), C.byref(ops_len)), "gm_sw_full_cs_batch")
+    return _sw_full_batch_finish(True, recs, ops_p, ops_len, g, r, rl, ib, is_rna)
 
 
 # ---- colour space S1/S2/S3 at the kernel seams (the read pipeline is Session.map_reads_cs*) ----
