@@ -42,7 +42,7 @@ extern "C" {
 
 const char *gm_last_error(void);
 /* sizeof of the structs that cross the ABI, for bindings to check their mirrors against: which = 0 gm_params_t, 1 gm_pair_opts_t, 2 gm_map_stats_t, 3 gm_merge_options_t,
- * 4 gm_sw_full_rec_t (-1 for any other value) */
+ * 4 gm_sw_full_rec_t, 5 gm_post_rec_t (-1 for any other value) */
 int gm_abi_sizeof(int which);
 /* number of visible HIP devices (0 when none); never initialises more than the runtime */
 int gm_device_count(void);
@@ -270,6 +270,7 @@ void sw_full_cs_stats(uint64_t *invocs, uint64_t *cells, double *secs);   /* ref
  * the reference's operation order -- a host routine here as in the reference).  ref: common/sw-post.h:6-9, sw-post.c:364-758; called by
  * hit_run_post_sw (gmapper/mapping.c:1609-1625).  post_sw re-calls sfr->qralign in place, recounts matches / mismatches / crossovers,
  * mallocs sfr->qual (base qualities, PHRED+33) and fills sfr->posterior.  State is per calling thread.  Returns follow the reference (1).
+ * The batch form, gm_post_sw_batch, is declared behind the S2 batch entries whose records it takes.
  * ------------------------------------------------------------------------------------------- */
 int  post_sw_setup(int max_len, double pr_snp, double pr_xover, double pr_del_open, double pr_del_extend, double pr_ins_open, double pr_ins_extend,
                    bool use_read_qvs, bool use_sanger_qvs, int qual_vector_offset, int qual_delta, bool reset_stats);
@@ -315,6 +316,48 @@ int gm_sw_full_cs_batch(int n, const uint32_t *genome_ls, uint64_t genome_words,
                         gm_sw_full_rec_t *recs, uint8_t **ops, uint64_t *ops_len);
 int gm_sw_full_batch_strings(int colour_space, const gm_sw_full_rec_t *rec, const uint8_t *ops, uint64_t ops_len, const uint32_t *genome, uint64_t genome_len,
                              const uint32_t *read, int rlen, int initbp, int is_rna, char **dbalign, char **qralign);
+
+/* ---------------------------------------------------------------------------------------------
+ * S3, batch form: post_sw of n alignments of ONE gm_sw_full_cs_batch call, on this thread's post_sw_setup state (without it: GM_E_NOTSETUP, where the single seam
+ * aborts).  Pass 2 of a colour-space chunk is then two calls -- gm_sw_full_cs_batch, gm_post_sw_batch -- instead of 2 n.
+ * Input: recs / ops / ops_len as that call returned them, and the arrays it was given (the shared letter-space bitfield, the reads, rlen, initbp, is_rna).
+ *   quals   NULL, or n QV strings in the file's characters; used only when post_sw_setup got use_read_qvs (with its qual_vector_offset and qual_delta), exactly as
+ *           the single seam uses its `qual` argument.
+ * Output: post[i] for every item; *qralign_out: one buffer of ops_len bytes (gm_free), item i's re-called qralign -- exactly what post_sw leaves in sfr->qralign, upper
+ * and lower case, '-' in a column without a read position, not NUL-terminated -- at the place of its operations, [recs[i].ops_off, + n_ops); *quals_out / *quals_len:
+ * the items' sfr->qual strings (base qualities, PHRED+33) end to end (gm_free), item i's at [qual_off, + qual_len).  dbalign is untouched by post_sw: a caller who
+ * wants it still uses gm_sw_full_batch_strings.
+ * Items: recs[i].status < 0 comes back with the same status; score <= 0 (no alignment) is answered with status 0, qual_len 0, posterior 0.  A record that does not
+ * lie inside what the caller holds -- operations outside ops_len, an alignment that runs past the genome or the read, an operation byte that is none of the encoding,
+ * an alignment longer than post_sw_setup's max_len (or than 59 918 read positions, what one wave's column scratch holds), a QV string that is missing or shorter than
+ * qual_vector_offset + rlen[i] while QVs are in use -- is refused on the host with GM_E_ARG before anything is uploaded (the checks of gm_sw_full_batch_strings); the
+ * reason of the last refused item is in gm_last_error(), its neighbours are answered.  n <= 0: GM_OK, nothing is written.
+ * One call makes a fixed number of device allocations, copies and launches whatever n is: the kernel's column scratch (140 bytes a column) belongs to its thread slots, is
+ * sized by the longest alignment of a launch and capped at 512 MiB (fewer threads then); items of very different lengths go into at most three launches by length.
+ * Exactness: matches / mismatches / crossovers, the qralign slice and the qual slice are EQUAL to the single seam's for every item.  The device differs from the host
+ * routine in exp / log only (ocml against glibc); an item where those last bits could decide an output byte -- a letter call between two posteriors within 1e-9 of each
+ * other, a base quality within 1e-7 of its truncation boundary or at a cut-off -- is answered by the library's host routine instead and marked by_host = 1 (its posterior
+ * then carries the single seam's bits).  For by_host = 0 the posterior is within 1e-9 relative of the single seam's; the largest difference seen from the reference's over the
+ * 1 833 records of tests/golden/sw_kat_post.txt.gz on an MI355X: 5.4e-16 without QVs, 4.2e-16 with QVs (profiles/r07a_post_sw_batch_error.json).
+ * post_sw_stats counts an answered item with an alignment like a single call: invocs += 1, cells += 16 x read positions.
+ * gm_post_sw_batch_last_plan is a DIAGNOSTIC hook, not part of the stable surface (it may change or go with the launch planning; the tests use it to see that thread
+ * slots were reused): how the last call on this thread was laid out -- returns its number of launches (0: nothing reached the device) and, for launch `launch`, the
+ * items it took, its thread slots and the columns of scratch a slot had (the longest alignment of the launch).  items > threads: slots served several items in turn.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gm_post_rec {
+  double   posterior;                          /* what post_sw leaves in sfr->posterior */
+  int      matches, mismatches, crossovers;    /* recounted, as post_sw leaves them */
+  int      status;                             /* 0 answered; < 0 (GM_E_*): this item was refused */
+  int      by_host;                            /* 1: the host routine answered this item (see "Exactness") */
+  uint32_t qual_len;                           /* read positions in the alignment = strlen(sfr->qual) */
+  uint64_t qual_off;                           /* this item's base qualities: quals_out[qual_off .. qual_off + qual_len) */
+} gm_post_rec_t;
+int gm_post_sw_batch(int n, const gm_sw_full_rec_t *recs, const uint8_t *ops, uint64_t ops_len,
+                     const uint32_t *genome_ls, uint64_t genome_words,
+                     const uint32_t *reads, int read_words, const int *rlen, const uint8_t *initbp,
+                     const char *const *quals, int is_rna,
+                     gm_post_rec_t *post, char **qralign_out, char **quals_out, uint64_t *quals_len);
+int gm_post_sw_batch_last_plan(int launch, int *items, int *threads, int *columns);   /* diagnostic, see above */
 
 /* ---------------------------------------------------------------------------------------------
  * S4: the per-read pipeline.  Replaces handle_read() for unpaired letter-space reads

@@ -84,7 +84,7 @@ extern "C" void gm_params_default(gm_params_t* p) {
   p->trim_front = 0; p->trim_end = 0; p->trim_first = 1; p->trim_second = 1; p->trim_illumina = 0; p->min_avg_qv = 10; p->ignore_qvs = 0; p->no_qv_check = 0;      // ref: gmapper.h:63-67,75,81,104
 }
 extern "C" int gm_abi_sizeof(int which) {
-  switch (which) { case 0: return (int)sizeof(gm_params_t); case 1: return (int)sizeof(gm_pair_opts_t); case 2: return (int)sizeof(gm_map_stats_t); case 3: return (int)sizeof(gm_merge_options_t); case 4: return (int)sizeof(gm_sw_full_rec_t); }
+  switch (which) { case 0: return (int)sizeof(gm_params_t); case 1: return (int)sizeof(gm_pair_opts_t); case 2: return (int)sizeof(gm_map_stats_t); case 3: return (int)sizeof(gm_merge_options_t); case 4: return (int)sizeof(gm_sw_full_rec_t); case 5: return (int)sizeof(gm_post_rec_t); }
   return -1;
 }
 // compute_mapping_qualities (ref: gmapper.c:2258,2325-2328): off with --no-mapping-qualities and in local mode -- then MAPQ 255, no Z tags, no post_sw (mapping.c:1648)
@@ -2485,6 +2485,25 @@ extern "C" int gm_sw_full_cs_batch(int n, const uint32_t* genome_ls, uint64_t ge
   return sw_full_batch_impl(true, n, genome_ls, genome_words, g_off, glen, reads, read_words, rlen, initbp, anchors, revcmpl, threshscore, nullptr, crossover_scores,
                             xover_stride, is_rna, local_alignment, recs, ops, ops_len);
 }
+// What gm_sw_full_batch_strings and gm_post_sw_batch check of a batch record before anything is read through it: its operations lie inside the ops buffer, the
+// alignment inside the genome (genome_len positions) and the read (rlen positions), and in colour space every operation byte is of the encoding (low nibble 1..9).
+// Returns the reason, or null; *read_positions = the columns that hold a read position.
+static const char* swf_rec_check(bool colour_space, const gm_sw_full_rec_t* rec, const uint8_t* ops, uint64_t ops_len, uint64_t genome_len, int rlen, uint64_t* read_positions) {
+  if (rec->ops_off > ops_len || rec->n_ops > ops_len - rec->ops_off || rec->genome_start < 0 || rec->read_start < 0 || rlen < 0)
+    return "the record points outside the ops buffer or the bitfields";
+  const uint8_t* o = ops + rec->ops_off;
+  uint64_t adv_g = 0, adv_r = 0; bool coded = true;
+  for (uint32_t k = 0; k < rec->n_ops; k++) {
+    const int type = o[k] & 0x0f;
+    const bool ins = colour_space ? type == 1 : o[k] == 'I', del = colour_space ? (type >= 2 && type <= 5) : o[k] == 'D';
+    if (!del) adv_g++; if (!ins) adv_r++;
+    if (colour_space && (type < 1 || type > 9)) coded = false;
+  }
+  if ((uint64_t)rec->genome_start + adv_g > genome_len || (uint64_t)rec->read_start + adv_r > (uint64_t)rlen) return "the record's alignment runs past the genome or the read";
+  if (!coded) return "an operation byte that is none of the encoding";
+  if (read_positions) *read_positions = adv_r;
+  return nullptr;
+}
 // pretty_print of one batch item (ref: sw-full-ls.c:524-560, sw-full-cs.c:945-1060), as sw_full_ls / sw_full_cs above build their strings.  Host only.
 extern "C" int gm_sw_full_batch_strings(int colour_space, const gm_sw_full_rec_t* rec, const uint8_t* ops, uint64_t ops_len, const uint32_t* genome, uint64_t genome_len,
                                         const uint32_t* read, int rlen_in, int initbp, int is_rna, char** dbalign, char** qralign) {
@@ -2493,17 +2512,8 @@ extern "C" int gm_sw_full_batch_strings(int colour_space, const gm_sw_full_rec_t
   const bool aligned = rec->status == 0 && rec->score > 0;
   if (!aligned) { if (!colour_space) { *dbalign = strdup(""); *qralign = strdup(""); } return GM_OK; }
   if (!ops || !genome || !read || (colour_space && (initbp < 0 || initbp > 3))) { gm_set_error("gm_sw_full_batch_strings: a required argument is missing"); return GM_E_ARG; }
-  // a record that does not lie inside what the caller holds is refused before anything is read through it
-  uint64_t adv_g = 0, adv_r = 0;
-  if (rec->ops_off > ops_len || rec->n_ops > ops_len - rec->ops_off || rec->genome_start < 0 || rec->read_start < 0 || rlen_in < 0) {
-    gm_set_error("gm_sw_full_batch_strings: the record points outside the ops buffer or the bitfields"); return GM_E_ARG; }
+  if (const char* why = swf_rec_check(colour_space != 0, rec, ops, ops_len, genome_len, rlen_in, nullptr)) { gm_set_error("gm_sw_full_batch_strings: %s", why); return GM_E_ARG; }
   const uint8_t* o = ops + rec->ops_off;
-  for (uint32_t k = 0; k < rec->n_ops; k++) {
-    const bool ins = colour_space ? (o[k] & 0x0f) == 1 : o[k] == 'I', del = colour_space ? ((o[k] & 0x0f) >= 2 && (o[k] & 0x0f) <= 5) : o[k] == 'D';
-    if (!del) adv_g++; if (!ins) adv_r++;
-  }
-  if ((uint64_t)rec->genome_start + adv_g > genome_len || (uint64_t)rec->read_start + adv_r > (uint64_t)rlen_in) {
-    gm_set_error("gm_sw_full_batch_strings: the record's alignment runs past the genome or the read"); return GM_E_ARG; }
   std::string db, q;
   long long pj = rec->genome_start; int pi = rec->read_start;
   if (!colour_space) {
@@ -2532,7 +2542,6 @@ extern "C" int gm_sw_full_batch_strings(int colour_space, const gm_sw_full_rec_t
       if (type == 1) { db.push_back(LSTRANS[swf_nib(genome, pj++)]); q.push_back('-'); continue; }
       const bool del = type >= 2 && type <= 5;
       const int lay = del ? type - 2 : type - 6;
-      if (lay < 0 || lay > 3 || pi >= rlen) { gm_set_error("gm_sw_full_batch_strings: an operation byte that is none of the encoding"); return GM_E_ARG; }
       char c = LSTRANS[qr[lay][pi++]];
       if (xov) c = (char)tolower((int)c);
       if (del) { db.push_back('-'); q.push_back(c); }
@@ -2576,4 +2585,157 @@ extern "C" void post_sw(uint32_t* read, int initbp, char* qual, struct gm_sw_ful
   sfr->qual = (char*)malloc(h.qr.size() + 1);
   if (sfr->qual) { memcpy(sfr->qual, h.qual.data(), h.qual.size()); sfr->qual[h.qual.size()] = 0; }
   sfr->posterior = h.posterior;
+}
+
+
+// ---- S3 batch: gm_post_sw_batch -- post_sw of n records of a gm_sw_full_cs_batch call in one go (k_post_sw_batch, gm_post.hip) --------------------------------
+// A fixed number of device buffers, copies and launches whatever n is.  The column scratch (GM_POST_COL_BYTES a column) belongs to the thread slots of a launch and is
+// sized by the launch's longest alignment; when the slots the items would fill pass GM_POST_BUDGET the thread count is lowered to fit, and the items are sorted into at
+// most three launches by length (as swf_plan does by matrix size) so that one long alignment does not starve many short ones of threads.  A result the kernel flags
+// (a letter call or a base quality the last bits of exp / log could decide) is redone by cs_post_sw on the strings rebuilt from the record: by_host = 1.
+static const size_t GM_POST_BUDGET = (size_t)512 << 20;
+struct PostLaunch { int first = 0, count = 0, threads = 0, max_len = 0; };
+struct PostPlan { int n = 0; PostLaunch l[3]; };
+static thread_local PostPlan g_post_plan;
+static void post_plan(std::vector<GmPostItem>& items, std::vector<PostLaunch>& launches) {
+  launches.clear();
+  if (items.empty()) return;
+  int M = 0; for (const GmPostItem& it : items) M = std::max(M, it.len);
+  const size_t want = std::min<size_t>((items.size() + 63) & ~(size_t)63, (size_t)GM_POST_THREADS);
+  std::vector<int> bound;                                       // a class takes the items of at most this many columns that no earlier class took
+  if (want * (size_t)M * GM_POST_COL_BYTES > GM_POST_BUDGET) bound = {M / 64, M / 8, M}; else bound = {M};
+  std::vector<GmPostItem> sorted; sorted.reserve(items.size());
+  int lo = 0;
+  for (int b : bound) {
+    PostLaunch L; L.first = (int)sorted.size();
+    for (const GmPostItem& it : items) if (it.len > lo && it.len <= b) { sorted.push_back(it); L.max_len = std::max(L.max_len, it.len); }
+    lo = b;
+    L.count = (int)sorted.size() - L.first;
+    if (!L.count) continue;
+    const size_t fit = (GM_POST_BUDGET / ((size_t)L.max_len * GM_POST_COL_BYTES)) & ~(size_t)63;          // (>= 64: longer alignments were refused)
+    L.threads = (int)std::max<size_t>(64, std::min(std::min(want, ((size_t)L.count + 63) & ~(size_t)63), fit));
+    launches.push_back(L);
+  }
+  items.swap(sorted);
+}
+extern "C" int gm_post_sw_batch_last_plan(int launch, int* items, int* threads, int* columns) {
+  const PostPlan& P = g_post_plan;
+  if (launch >= 0 && launch < P.n) { if (items) *items = P.l[launch].count; if (threads) *threads = P.l[launch].threads; if (columns) *columns = P.l[launch].max_len; }
+  return P.n;
+}
+
+extern "C" int gm_post_sw_batch(int n, const gm_sw_full_rec_t* recs, const uint8_t* ops, uint64_t ops_len, const uint32_t* genome_ls, uint64_t genome_words,
+                                const uint32_t* reads, int read_words, const int* rlen, const uint8_t* initbp, const char* const* quals, int is_rna,
+                                gm_post_rec_t* post, char** qralign_out, char** quals_out, uint64_t* quals_len) {
+  if (!g_ps.init) { gm_set_error("gm_post_sw_batch called before post_sw_setup"); return GM_E_NOTSETUP; }
+  if (n <= 0) return GM_OK;
+  if (!recs || (!ops && ops_len) || !genome_ls || !reads || read_words < 1 || !rlen || !initbp || !post || !qralign_out || !quals_out || !quals_len) {
+    gm_set_error("gm_post_sw_batch: a required argument is missing"); return GM_E_ARG; }
+  *qralign_out = *quals_out = nullptr; *quals_len = 0;
+  SeamTimer tm(&g_ps.secs);
+  const bool use_qvs = g_ps.use_read_qvs; const int qoff = g_ps.K.qoff, qv_stride = read_words * 8;
+  // the longest alignment 64 thread slots can hold inside the budget
+  const uint64_t slot_max = GM_POST_BUDGET / (64 * GM_POST_COL_BYTES);
+  std::vector<GmPostItem> items; items.reserve(n);
+  std::vector<uint8_t> qv; if (use_qvs) qv.assign((size_t)n * qv_stride, 0);
+  uint64_t quals_total = 0; g_post_plan.n = 0;
+  for (int i = 0; i < n; i++) {
+    gm_post_rec_t& P = post[i]; memset(&P, 0, sizeof P);
+    const gm_sw_full_rec_t& R = recs[i];
+    if (R.status < 0) { P.status = R.status; continue; }
+    if (R.score <= 0) continue;                                           // no alignment: status 0, posterior 0, no base qualities
+    auto refuse = [&](const char* why) { P.status = GM_E_ARG; gm_set_error("gm_post_sw_batch: item %d refused: %s", i, why); };
+    if (rlen[i] < 1 || ((uint64_t)rlen[i] + 7) / 8 > (uint64_t)read_words || initbp[i] > 3) { refuse("read outside the bitfield, or initbp outside 0..3"); continue; }
+    uint64_t len = 0;
+    if (const char* why = swf_rec_check(true, &R, ops, ops_len, genome_words * 8, rlen[i], &len)) { refuse(why); continue; }
+    if ((int64_t)R.n_ops > (int64_t)g_ps.max_len) { refuse("an alignment longer than post_sw_setup's max_len"); continue; }
+    if (len > slot_max) { refuse("an alignment too long for the column scratch of one wave"); continue; }
+    if (use_qvs) {
+      const size_t need = (size_t)qoff + (size_t)rlen[i];
+      if (!quals || !quals[i] || strnlen(quals[i], need) < need) { refuse("a QV string is missing or shorter than the read"); continue; }
+      for (int j = 0; j < rlen[i]; j++)                                   // what the error-rate formula distinguishes (qv <= 0, qv >= 250, ref: util.h:285-293)
+        qv[(size_t)i * qv_stride + j] = (uint8_t)std::min(250, std::max(0, (int)quals[i][qoff + j] - g_ps.qual_delta));
+    }
+    GmPostItem it; memset(&it, 0, sizeof it);
+    it.ops_off = R.ops_off; it.n_ops = R.n_ops; it.genome_start = R.genome_start; it.read_start = R.read_start; it.rlen = rlen[i]; it.len = (int)len;
+    it.initbp = initbp[i]; it.idx = i; it.qual_off = quals_total;
+    P.qual_off = quals_total; P.qual_len = (uint32_t)len; quals_total += len;
+    items.push_back(it);
+  }
+  char* qa = (char*)calloc(ops_len ? ops_len : 1, 1); char* qo = (char*)malloc(quals_total ? quals_total : 1);
+  struct HostBufs { char *a, *b; ~HostBufs() { free(a); free(b); } } hb{qa, qo};
+  if (!qa || !qo) { gm_set_error("gm_post_sw_batch: out of memory"); return GM_E_NOMEM; }
+  std::vector<GmPostRes> res(items.size());
+  std::vector<PostLaunch> launches;
+  // an item without a read position never reaches the device: the host routine's early return answers it
+  std::vector<GmPostItem> dev; dev.reserve(items.size());
+  for (const GmPostItem& it : items) if (it.len > 0) dev.push_back(it);
+  post_plan(dev, launches);
+  if (!dev.empty()) {
+    if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
+    GmCsPostDev K; const CsPostConsts& c = g_ps.K;
+    K.let_m = c.let_m; K.let_x = c.let_x; K.col_m[0] = c.col_m[0]; K.col_m[1] = c.col_m[1]; K.col_x[0] = c.col_x[0]; K.col_x[1] = c.col_x[1];
+    K.pr_del_open = c.pr_del_open; K.pr_del_extend = c.pr_del_extend; K.pr_ins_open = c.pr_ins_open; K.pr_ins_extend = c.pr_ins_extend; K.qv = nullptr; K.qtab = nullptr; K.bq = nullptr;
+    size_t fw_bytes = 0, info_bytes = 0;
+    for (const PostLaunch& L : launches) { fw_bytes = std::max(fw_bytes, (size_t)L.threads * L.max_len * 17 * 8); info_bytes = std::max(info_bytes, (size_t)L.threads * L.max_len * 4); }
+    GmDevBufs bufs;
+    uint32_t *dg = nullptr, *dr = nullptr, *dinfo = nullptr; GmPostItem* di = nullptr; GmPostRes* dres = nullptr; uint8_t *dops = nullptr, *dqa = nullptr, *dqo = nullptr, *dqv = nullptr;
+    double *dfw = nullptr, *dqt = nullptr;
+    GM_HIP(bufs.get(&dg, (genome_words + 8) * 4)); GM_HIP(bufs.get(&dr, (size_t)n * read_words * 4 + 32)); GM_HIP(bufs.get(&di, dev.size() * sizeof(GmPostItem)));
+    GM_HIP(bufs.get(&dres, dev.size() * sizeof(GmPostRes))); GM_HIP(bufs.get(&dops, (size_t)ops_len + 16)); GM_HIP(bufs.get(&dqa, (size_t)ops_len + 16));
+    GM_HIP(bufs.get(&dqo, (size_t)quals_total + 16)); GM_HIP(bufs.get(&dfw, fw_bytes)); GM_HIP(bufs.get(&dinfo, info_bytes));
+    GM_HIP(hipMemcpyAsync(dg, genome_ls, genome_words * 4, hipMemcpyHostToDevice, 0));
+    GM_HIP(hipMemcpyAsync(dr, reads, (size_t)n * read_words * 4, hipMemcpyHostToDevice, 0));
+    GM_HIP(hipMemcpyAsync(di, dev.data(), dev.size() * sizeof(GmPostItem), hipMemcpyHostToDevice, 0));
+    GM_HIP(hipMemcpyAsync(dops, ops, (size_t)ops_len, hipMemcpyHostToDevice, 0));
+    GM_HIP(hipMemsetAsync(dqa, 0, (size_t)ops_len + 16, 0));                                   // (the slices of refused items and of those the host answers)
+    GM_HIP(hipMemsetAsync(dqo, 0, (size_t)quals_total + 16, 0));
+    std::vector<double> qt;
+    if (use_qvs) {
+      // the per-colour error rates of every QV the formula distinguishes, from the host's libm: the very doubles cs_post_sw computes (ref: sw-post.c:486-491)
+      qt.resize(2 * 251);
+      for (int q = 0; q <= 250; q++) {
+        double e = q <= 0 ? .99999999 : (q >= 250 ? 1E-25 : pow(10.0, -(double)q / 10.0));
+        if (!c.sanger) e /= (1 + e);
+        if (e > .75) e = .75;
+        qt[2 * q] = log(1 - e); qt[2 * q + 1] = log(e / 3.0);
+      }
+      GM_HIP(bufs.get(&dqv, qv.size() + 16)); GM_HIP(bufs.get(&dqt, qt.size() * 8));
+      GM_HIP(hipMemcpyAsync(dqv, qv.data(), qv.size(), hipMemcpyHostToDevice, 0));
+      GM_HIP(hipMemcpyAsync(dqt, qt.data(), qt.size() * 8, hipMemcpyHostToDevice, 0));
+      K.qv = dqv; K.qtab = dqt;
+    }
+    for (const PostLaunch& L : launches) {
+      const int rc = gm_launch_post_sw_batch(K, L.first, L.count, L.threads, di, dops, dg, dr, read_words, qv_stride, is_rna ? 1 : 0, dres, dqa, dqo, dfw, dinfo, 0);
+      if (rc != GM_OK) { (void)hipDeviceSynchronize(); gm_set_error("gm_post_sw_batch: the kernel launch failed"); return rc; }
+    }
+    res.resize(dev.size());
+    GM_HIP(hipMemcpyAsync(res.data(), dres, dev.size() * sizeof(GmPostRes), hipMemcpyDeviceToHost, 0));
+    if (ops_len) GM_HIP(hipMemcpyAsync(qa, dqa, (size_t)ops_len, hipMemcpyDeviceToHost, 0));
+    if (quals_total) GM_HIP(hipMemcpyAsync(qo, dqo, (size_t)quals_total, hipMemcpyDeviceToHost, 0));
+    GM_HIP(hipStreamSynchronize(0));
+    g_post_plan.n = (int)launches.size(); for (size_t k = 0; k < launches.size() && k < 3; k++) g_post_plan.l[k] = launches[k];
+  }
+  // the device's answers; then the items the host routine takes: flagged by the kernel, or without a read position
+  std::vector<uint8_t> by_dev((size_t)n, 0);
+  for (size_t k = 0; k < dev.size(); k++) {
+    if (res[k].valid != 1) continue;
+    gm_post_rec_t& P = post[dev[k].idx]; by_dev[dev[k].idx] = 1;
+    P.posterior = res[k].posterior; P.matches = res[k].cs_match; P.mismatches = res[k].cs_mismatch; P.crossovers = res[k].cs_xover;
+  }
+  for (const GmPostItem& it : items) {
+    g_ps.invocs++; g_ps.cells += 16 * (uint64_t)it.len;                                        // as one post_sw call counts (above)
+    if (by_dev[it.idx]) continue;
+    const int i = it.idx; gm_post_rec_t& P = post[i];
+    char *db = nullptr, *qr = nullptr;
+    const int rc = gm_sw_full_batch_strings(1, &recs[i], ops, ops_len, genome_ls, genome_words * 8, reads + (size_t)i * read_words, rlen[i], initbp[i], is_rna, &db, &qr);
+    if (rc != GM_OK || !db || !qr) { free(db); free(qr); P.status = rc != GM_OK ? rc : GM_E_ARG; P.qual_len = 0; continue; }
+    FHit h; h.db = db; h.qr = qr; free(db); free(qr);
+    cs_post_sw(g_ps.K, reads + (size_t)i * read_words, initbp[i], recs[i].read_start, h, use_qvs ? quals[i] : nullptr, g_ps.qual_delta, true);
+    P.posterior = h.posterior; P.matches = h.cs_match; P.mismatches = h.cs_mismatch; P.crossovers = h.cs_xover; P.by_host = 1;
+    memcpy(qa + it.ops_off, h.qr.data(), std::min<size_t>(h.qr.size(), it.n_ops));
+    memcpy(qo + it.qual_off, h.qual.data(), std::min<size_t>(h.qual.size(), (size_t)it.len));
+  }
+  *qralign_out = qa; *quals_out = qo; *quals_len = quals_total; hb.a = hb.b = nullptr;
+  return GM_OK;
 }

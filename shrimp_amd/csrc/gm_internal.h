@@ -169,6 +169,14 @@ struct GmPostRes { double posterior; int32_t cs_match, cs_mismatch, cs_xover, va
 #define GM_POST_THREADS 131072      // k_post_sw_cs: one thread per pass-2 result, a column scratch each (6.9 KB at 50 colours); 32 768 threads were half a wave per SIMD for a kernel that waits on its scratch: cfg4 5.62 -> 6.00 M reads/s (tools/post_threads_cfg4.sh)
 int gm_launch_post_sw_cs(const GmCsPostDev& K, const uint32_t* d_reads, const uint8_t* d_initbp, int read_len, int read_words, const GmFullRes* d_res, uint8_t* d_ops,
                          int ops_stride, const uint32_t* d_n_work, uint32_t res_cap, GmPostRes* d_post, double* d_fw, uint32_t* d_info, int threads, hipStream_t stream);
+// S3 batch (gm_post_sw_batch, k_post_sw_batch): one alignment of a gm_sw_full_cs_batch call.  The host fills an item only after it has checked the record against the caller's
+// buffers: ops[ops_off .. + n_ops), genome positions from genome_start, read positions read_start .. < rlen of read `idx`; len = read positions in the alignment (columns
+// of scratch the item takes), qual_off = where its base qualities go.  GmPostRes.valid: 1 answered, 2 the host routine decides.
+struct GmPostItem { unsigned long long ops_off, qual_off; long long genome_start; uint32_t n_ops; int read_start, rlen, len, initbp, idx; };
+static const size_t GM_POST_COL_BYTES = 17 * 8 + 4;       // scratch a column and thread slot: 16 forward values, the column's scale, the column word
+int gm_launch_post_sw_batch(const GmCsPostDev& K, int first, int n, int threads, const GmPostItem* d_items, const uint8_t* d_ops, const uint32_t* d_genome,
+                            const uint32_t* d_reads, int read_words, int qv_stride, int is_rna, GmPostRes* d_post, uint8_t* d_qralign, uint8_t* d_quals,
+                            double* d_fw, uint32_t* d_info, hipStream_t stream);
 int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs_params9, const uint32_t* d_reads, const uint8_t* d_initbp, int n_reads,
                        int read_len, int read_words, int window_len, const GmHit* d_hits, int hcap, const int32_t* d_sel, const uint32_t* d_work,
                        const uint32_t* d_n_work, GmFullRes* d_res, uint8_t* d_ops, int ops_stride, uint32_t* d_back, size_t back_words, int grid,

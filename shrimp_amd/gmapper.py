@@ -112,7 +112,13 @@ class SwFullRec(C.Structure):       # gm_sw_full_rec_t: one alignment of gm_sw_f
                [("genome_start", C.c_int64), ("ops_off", C.c_uint64), ("n_ops", C.c_uint32)]
 
 
+class PostRec(C.Structure):         # gm_post_rec_t: one answer of gm_post_sw_batch (checked against gm_abi_sizeof(5))
+    _fields_ = [("posterior", C.c_double), ("matches", C.c_int), ("mismatches", C.c_int), ("crossovers", C.c_int), ("status", C.c_int), ("by_host", C.c_int),
+                ("qual_len", C.c_uint32), ("qual_off", C.c_uint64)]
+
+
 SW_FULL_REC_DTYPE = np.dtype(SwFullRec)      # the structured numpy view of an array of them
+POST_REC_DTYPE = np.dtype(PostRec)
 ANCHOR_DTYPE = np.dtype(Anchor)
 
 
@@ -124,7 +130,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "sw_full_ls_setup", "sw_full_ls", "sw_full_ls_cleanup", "sw_full_ls_stats",
            "sw_full_cs_setup", "sw_full_cs", "sw_full_cs_cleanup", "sw_full_cs_stats", "gm_sw_vector_batch_cs",
            "gm_sw_full_ls_batch", "gm_sw_full_cs_batch", "gm_sw_full_batch_strings",
-           "post_sw_setup", "post_sw", "post_sw_cleanup", "post_sw_stats",
+           "post_sw_setup", "post_sw", "post_sw_cleanup", "post_sw_stats", "gm_post_sw_batch", "gm_post_sw_batch_last_plan",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
@@ -184,6 +190,11 @@ def lib():
     L.gm_sw_full_cs_batch.argtypes = [C.c_int, u32p, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int), u32p, C.c_int, C.POINTER(C.c_int), vp, vp, vp, C.POINTER(C.c_int), vp,
                                       C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.gm_sw_full_batch_strings.argtypes = [C.c_int, vp, vp, C.c_uint64, u32p, C.c_uint64, u32p, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.post_sw_setup.argtypes = [C.c_int] + [C.c_double] * 6 + [C.c_bool, C.c_bool, C.c_int, C.c_int, C.c_bool]
+    L.post_sw.argtypes = [u32p, C.c_int, C.c_char_p, C.POINTER(SwFullResults)]; L.post_sw.restype = None
+    L.gm_post_sw_batch.argtypes = [C.c_int, vp, vp, C.c_uint64, u32p, C.c_uint64, u32p, C.c_int, C.POINTER(C.c_int), vp, vp, C.c_int, vp, C.POINTER(vp), C.POINTER(vp),
+                                   C.POINTER(C.c_uint64)]
+    L.gm_post_sw_batch_last_plan.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.gm_abi_sizeof.argtypes = [C.c_int]; L.gm_abi_sizeof.restype = C.c_int
     L.gm_session_create.argtypes = [C.POINTER(vp), vp, C.POINTER(Params), C.c_int]
     L.gm_session_free.argtypes = [vp]
@@ -831,6 +842,61 @@ def sw_full_cs(genome_ls, goff, glen, read_words, rlen, initbp, thresh, anchor, 
     if s.qralign: L.gm_free(s.qralign)
     f = {n: getattr(s, n) for n in ("score", "read_start", "rmapped", "genome_start", "gmapped", "matches", "mismatches", "insertions", "deletions", "crossovers")}
     return f, db, qr
+
+
+def post_sw_setup(max_len, pr_snp, pr_xover, pr_del_open, pr_del_extend, pr_ins_open, pr_ins_extend, use_read_qvs=False, use_sanger_qvs=True, qual_vector_offset=0,
+                  qual_delta=33, reset_stats=True):
+    """post_sw_setup (ref: sw-post.c:364-441): this thread's state for post_sw and post_sw_batch.  Host only."""
+    lib().post_sw_setup(int(max_len), pr_snp, pr_xover, pr_del_open, pr_del_extend, pr_ins_open, pr_ins_extend, bool(use_read_qvs), bool(use_sanger_qvs), int(qual_vector_offset),
+                        int(qual_delta), bool(reset_stats))
+
+
+def post_sw(read_words, initbp, dbalign, qralign, read_start, qual=None):
+    """The single seam post_sw on a struct sw_full_results holding sw_full_cs's dbalign / qralign / read_start (host code, needs post_sw_setup; qual: the read's QV
+    string, used when the setup got use_read_qvs).  Returns dict(posterior, matches, mismatches, crossovers, qralign, qual) -- what post_sw leaves in the struct."""
+    L = lib()
+    r = np.ascontiguousarray(read_words, dtype=np.uint32)
+    b = lambda x: x if isinstance(x, bytes) else x.encode()
+    db = C.create_string_buffer(b(dbalign)); qr = C.create_string_buffer(b(qralign))
+    s = SwFullResults(); s.read_start = int(read_start); s.dbalign = C.addressof(db); s.qralign = C.addressof(qr)
+    L.post_sw(r.ctypes.data_as(C.POINTER(C.c_uint32)), int(initbp), None if qual is None else b(qual), C.byref(s))
+    q = C.string_at(s.qual).decode() if s.qual else ""
+    if s.qual: L.gm_free(s.qual)
+    return dict(posterior=s.posterior, matches=s.matches, mismatches=s.mismatches, crossovers=s.crossovers, qralign=qr.value.decode(), qual=q)
+
+
+def post_sw_batch(recs, ops, genome_ls, reads_words, rlen, initbp, quals=None, is_rna=False):
+    """gm_post_sw_batch: post_sw of every record of one sw_full_cs_batch call (recs, ops as it returned them; genome_ls, reads_words, rlen, initbp, is_rna as it was given
+    them) in one call.  quals: None or n QV strings (bytes).  Returns (post: structured array of POST_REC_DTYPE, qralign: i -> the re-called qralign of item i,
+    qual: i -> its base qualities), both strings as the single seam leaves them; an item that was refused has status < 0 (reason: gm_last_error)."""
+    L = lib()
+    rc_ = np.ascontiguousarray(recs, dtype=SW_FULL_REC_DTYPE); n = rc_.shape[0]
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    g = np.ascontiguousarray(genome_ls, dtype=np.uint32); r = np.ascontiguousarray(reads_words, dtype=np.uint32)
+    if r.ndim != 2 or r.shape[0] != n: raise GmError("post_sw_batch: reads_words is (n, read_words)")
+    rl = np.ascontiguousarray(rlen, dtype=np.int32); ib = np.ascontiguousarray(initbp, dtype=np.uint8)
+    if rl.shape[0] != n or ib.shape[0] != n or (quals is not None and len(quals) != n): raise GmError("post_sw_batch: every per-item array has n entries")
+    qp = None if quals is None else (C.c_char_p * max(n, 1))(*[None if q is None else (q if isinstance(q, bytes) else q.encode()) for q in quals])
+    post = np.zeros(n, dtype=POST_REC_DTYPE); qa_p, qo_p, qo_len = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+    dp = lambda a: None if a.size == 0 else a.ctypes.data
+    _check(L.gm_post_sw_batch(n, dp(rc_), dp(o), o.size, g.ctypes.data_as(C.POINTER(C.c_uint32)), g.size, r.ctypes.data_as(C.POINTER(C.c_uint32)), r.shape[1],
+                              rl.ctypes.data_as(C.POINTER(C.c_int)), dp(ib), qp, 1 if is_rna else 0, dp(post), C.byref(qa_p), C.byref(qo_p), C.byref(qo_len)), "gm_post_sw_batch")
+    qa = C.string_at(qa_p.value, o.size) if qa_p.value else b""
+    qo = C.string_at(qo_p.value, qo_len.value) if qo_p.value else b""
+    L.gm_free(qa_p); L.gm_free(qo_p)
+    def qralign(i):
+        return qa[int(rc_[i]["ops_off"]):int(rc_[i]["ops_off"]) + int(rc_[i]["n_ops"])].decode() if post[i]["status"] == 0 and rc_[i]["score"] > 0 else None
+    def qual(i):
+        return qo[int(post[i]["qual_off"]):int(post[i]["qual_off"]) + int(post[i]["qual_len"])].decode()
+    return post, qralign, qual
+
+
+def post_sw_batch_last_plan():
+    """gm_post_sw_batch_last_plan (a diagnostic hook for tests, not stable surface): [(items, thread slots, columns of scratch a slot)] of the launches of this thread's last post_sw_batch call"""
+    L = lib(); a, b, c = C.c_int(0), C.c_int(0), C.c_int(0); out = []
+    for k in range(L.gm_post_sw_batch_last_plan(-1, None, None, None)):
+        L.gm_post_sw_batch_last_plan(k, C.byref(a), C.byref(b), C.byref(c)); out.append((a.value, b.value, c.value))
+    return out
 
 
 def seam_stats(which):
