@@ -64,6 +64,18 @@ extern "C" int gm_debug_k5_stamps(unsigned long long* out) {
 #define K5_STAMP(i) do { } while (0)
 #endif
 
+// Tuning builds: how many read-strands k_lookup_v5 took, and how many of them it handed on -- [1] to the fall-back kernels, [2] to k_prune alone (the prune_only tail) -- so that a
+// test with small tables can tell whether its read-strands went through the exact stages at all.  gm_debug_k5_paths() reads and resets the three counts.
+#ifdef GM_TUNING
+__device__ unsigned long long k5_paths[3];
+extern "C" int gm_debug_k5_paths(unsigned long long* out) {
+  unsigned long long z[3] = {0, 0, 0};
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(k5_paths), sizeof z) != hipSuccess) return GM_E_NODEVICE;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(k5_paths), z, sizeof z) != hipSuccess) return GM_E_NODEVICE;
+  return GM_OK;
+}
+#endif
+
 struct K5Args {
   const uint32_t* reads; int n_reads, read_len, read_words, max_n_kmers, NL;
   int lsw, ltw;             // log2(words) of seen[] and twice[]

@@ -73,6 +73,30 @@ K5_KERNEL_HEAD {
     if ((old & m) == m) K5_LDS_OR(av & tmask4, m1);
   };
   auto has2 = [&](const uint32_t p) -> bool { return (*K5_LDS((p >> sh_a) & tmask4) >> ((p >> sh_b) & 31u)) & 1u; };
+  // The twice[] bit of region r as a FILTER for the neighbour-region look-ups of the exact stages (stage 2b, the prune_only tail): twice[] is written by pass A only and
+  // cleared at the very end of a read-strand, behind both, so it still holds pass A's answer there.  What a clear bit of region x proves:
+  //  (M) pass A marked x at most once.  A mark of x is a list entry inside x (main loop) or a strip entry inside x + 1 (strip loop).  The second mark of a region always finds
+  //      what the first one left in seen[] -- its one bit, or with BLOOM both of its bits; LDS atomics on one word are serialised, also within one instruction -- and sets the
+  //      region's twice[] bit.  Aliasing regions, the words a lane marks past its chunk and Bloom collisions only ever set more bits.
+  //  (B) x does not carry flag B in the region table of any round.  The table counts one mark of x per candidate inside x (first-slot CAS, probe_on) and one per candidate in the
+  //      strip of x + 1 (the mark-only k5_insert(r - 1, false), listed or inside probe_on).  Candidates are distinct list entries -- a strip entry is a candidate of the strip
+  //      loop only when its own region fails the main loop's test -- and pass A marked x for each of them on the same grounds, so the table's count is at most pass A's: <= 1.
+  //      A round of k_lookup_v5_rounds sees a subset of the candidates (its part and the halo), which lowers the count only.
+  //  (C) x holds no candidate of pass B's main loop (they pass has2 of their own region).  It may hold candidates of the strip loop -- entries in the strip of x whose region
+  //      BEFORE, x - 1, has its bit set; they sit in x's own slot with flags C / D / E and min / max.  So only with the bits of x AND x - 1 both clear is x free of flag C; a
+  //      slot of x may still exist then (mark-only, or a halo region), with flag A alone.
+  // Hence: a look-up that reads flag B only may answer "absent, tag 0" on a clear bit of x (2b's membership through the region before, the tail); one that reads flag C and
+  // min / max needs x and x - 1 clear (2b's prune look-up of the region BEFORE the candidate's).  The prune look-up of the region BEHIND, r + 1, gets no filter: its second bit
+  // is the candidate's own region r, which is set for every member that did not come in through the region before, and strip candidates in r + 1 are exactly what that look-up
+  // is for.  Region 0 has no strip candidates (the strip lists leave region 0 out); has2r(0 - 1) reads some other word of the table and can only let a look-up through.
+  // Every case where the flags could be there goes through the full probe sequence as before, so the tag words read, and with them the survivors, are the same bit for bit.
+  auto has2r = [&](const uint32_t r) -> bool {
+#ifdef K5_NO_TWICE_FILTER     // (diagnostic builds: the look-ups as before the filter)
+    return true;
+#else
+    return (*K5_LDS((r << 2) & tmask4) >> ((r >> lsw) & 31u)) & 1u;
+#endif
+  };
 
 #ifdef K5_STAMPS
   unsigned long long t_prev = __builtin_amdgcn_s_memtime();
@@ -577,9 +601,26 @@ K5_KERNEL_HEAD {
       K5_STAMP(10);
       if (!fallback) {
         const uint32_t ns = min(ctrl[C_NSTRIP], scap), nd = min(ctrl[C_NDEFER], dcap);
+#ifdef K5_1B_TWO_LOOPS     // (diagnostic builds: the two lists one after the other, as before)
         for (uint32_t j = tid; j < nd; j += nthr) probe_on(dlist[j]);
         for (uint32_t j = tid; j < ns; j += nthr)
           if (k5_insert(htag, hmask, hshift, elist[j], false) == 0xFFFFFFFFu) ctrl[C_OVERFLOW] = 1u;
+#else
+        // ONE index space, the strip marks behind the deferred candidates, and one probing loop for both kinds (a lane's kind is data: which flags it sets, where its
+        // sequence starts): the first threads no longer run a second probing loop behind their share of the first, the strip marks ride in the lanes behind the last deferred
+        // candidate.  The table's updates are single-shot atomics, their outcome does not depend on the order.
+        for (uint32_t j = tid; j < nd + ns; j += nthr) {
+          const bool own = j < nd;
+          const uint32_t v = *(own ? dlist + j : elist + (j - nd));      // candidate index / region number
+          const uint32_t p = candp[own ? v : 0u], r = own ? p >> rb : v, off = p & rmask;
+          const uint32_t h = k5_insert(htag, hmask, hshift, r, own, own);
+          if (h == 0xFFFFFFFFu) ctrl[C_OVERFLOW] = 1u;
+          else if (own) {
+            settle(v, h, off);
+            if (off < ovl && r > 0 && k5_insert(htag, hmask, hshift, r - 1u, false) == 0xFFFFFFFFu) ctrl[C_OVERFLOW] = 1u;
+          }
+        }
+#endif
       }
       __syncthreads();
       K5_STAMP(3);
@@ -595,6 +636,8 @@ K5_KERNEL_HEAD {
           const unsigned long long bm = __ballot(memb), bk = __ballot(keep);
           if (bm) {
             uint32_t base = 0;
+            // (C_NMEMB in front of the reservation the stores wait for: a member count kept per wave in a scalar and added once behind stage 2b was measured and dropped --
+            // stage 2a 5 977 against 6 029 ticks, as much as the build without it moved: profiles/r08a_k5_exact_stage_stamps.txt)
             if (lane == 0) { atomicAdd(&ctrl[C_NMEMB], (uint32_t)__popcll(bm)); if (bk) base = atomicAdd(&ctrl[C_NKEEP], (uint32_t)__popcll(bk)); }
             base = __builtin_amdgcn_readfirstlane(base);
             if (keep) {
@@ -682,12 +725,13 @@ K5_KERNEL_HEAD {
             uint32_t tlf = 0, trt = 0;
             memb = (town & K5_FB) != 0u;
             uint32_t hlf = 0xFFFFFFFFu; bool have_lf = false;
-            if (!memb && off < ovl && r > 0) { hlf = k5_find(htag, hmask, hshift, r - 1u, tlf); have_lf = true; memb = (tlf & K5_FB) != 0u; }
+            // (the filter: see has2r.  Flag B of the region before needs its own bit, flag C and min / max that bit and the one of the region before it)
+            if (!memb && off < ovl && r > 0) { hlf = k5_find_maybe(htag, hmask, hshift, r - 1u, has2r(r - 1u), tlf); have_lf = true; memb = (tlf & K5_FB) != 0u; }
             if (memb) {
               keep = true;
               if (a.prune) {
                 uint32_t hrt = 0xFFFFFFFFu; trt = 0;
-                if (off < edge) { if (!have_lf && r > 0) hlf = k5_find(htag, hmask, hshift, r - 1u, tlf); } else tlf = 0;
+                if (off < edge) { if (!have_lf && r > 0) hlf = k5_find_maybe(htag, hmask, hshift, r - 1u, has2r(r - 1u) | has2r(r - 2u), tlf); } else tlf = 0;
                 if (off + edge >= (1u << rb)) hrt = k5_find(htag, hmask, hshift, r + 1u, trt);
                 const uint32_t co = (town & K5_FE) ? 3u : ((town & K5_FD) ? 2u : 1u);
                 const uint32_t omin = 0x10000u - hmin[hown], omax = hmax[hown] - 1u;
@@ -735,7 +779,7 @@ K5_KERNEL_HEAD {
             p = (r << rb) | off;
             if ((int)(p >> ix.slab_bits) == sl || (sl == a.n_slabs - 1 && (int)(p >> ix.slab_bits) >= a.n_slabs)) {
               memb = (town & K5_FB) != 0u;
-              if (!memb && off < ovl && r > 0) { uint32_t tlf; k5_find(htag, hmask, hshift, r - 1u, tlf); memb = (tlf & K5_FB) != 0u; }
+              if (!memb && off < ovl && r > 0) { uint32_t tlf; k5_find_maybe(htag, hmask, hshift, r - 1u, has2r(r - 1u), tlf); memb = (tlf & K5_FB) != 0u; }
             }
           }
           const unsigned long long bm = __ballot(memb);
@@ -757,6 +801,9 @@ K5_KERNEL_HEAD {
     K5_STAMP(4);
 #ifdef K5_STAMPS
     if (tid == 0) { atomicAdd(&k5_stamps[6], (unsigned long long)nc); if (fallback) atomicAdd(&k5_stamps[7], 1ull); }
+#endif
+#ifdef GM_TUNING
+    if (tid == 0 && (fallback || prune_only)) atomicAdd(&k5_paths[fallback ? 1 : 2], 1ull);      // (the read-strands taken: once per workgroup, behind the loop)
 #endif
     if (tid == 0) {
       if (fallback) {                                          // candidates beyond the LDS tiers: the slab-sweep kernel redoes this read-strand
@@ -787,6 +834,9 @@ K5_KERNEL_HEAD {
     { uint4* t4 = (uint4*)smem; for (int w = tid; w < tab_q; w += nthr) t4[w] = make_uint4(0, 0, 0, 0); }
     K5_STAMP(5);
   }
+#ifdef GM_TUNING
+  if (tid == 0 && it > 0) atomicAdd(&k5_paths[0], (unsigned long long)it);
+#endif
   for (int d = GM_WAVE / 2; d > 0; d >>= 1) { my_lookups += __shfl_down(my_lookups, d); my_entries += __shfl_down(my_entries, d); }
   if (lane == 0) { GS_ADD(a.stats, GS_LOOKUPS, my_lookups); GS_ADD(a.stats, GS_ENTRIES, my_entries); }
 }

@@ -59,4 +59,19 @@ __device__ __forceinline__ uint32_t k5_find(const uint32_t* htag, uint32_t hmask
   tagword = 0u;
   return 0xFFFFFFFFu;
 }
+// The same for a caller that holds a filter answer `maybe` (k_lookup_v5: bits of twice[]): with `maybe` false region r, where it is in the table at all, carries none of the flags
+// the caller goes on to read, and "absent, tag 0" is returned without walking the probe sequence.  The first slot is read whatever the answer, so that its round trip and the
+// filter's own LDS read run side by side: a wave then pays the longest sequence among the lanes the filter lets through, and never a round trip more than k5_find.
+__device__ __forceinline__ uint32_t k5_find_maybe(const uint32_t* htag, uint32_t hmask, int hshift, uint32_t r, bool maybe, uint32_t& tagword) {
+  const uint32_t r1 = r + 1u;
+  uint32_t h = k5_hash(r1, hshift); const uint32_t step = k5_step(r1);
+  for (uint32_t n = 0; n <= hmask; n++) {
+    const uint32_t cur = htag[h];
+    if ((cur == 0u) | !maybe) break;
+    if ((cur >> 8) == r1) { tagword = cur; return h; }
+    h = (h + step) & hmask;
+  }
+  tagword = 0u;
+  return 0xFFFFFFFFu;
+}
 
