@@ -360,6 +360,59 @@ int gm_post_sw_batch(int n, const gm_sw_full_rec_t *recs, const uint8_t *ops, ui
 int gm_post_sw_batch_last_plan(int launch, int *items, int *threads, int *columns);   /* diagnostic, see above */
 
 /* ---------------------------------------------------------------------------------------------
+ * S1 - S3, batch forms on the resident index: the entries above with (genome, genome_words, g_off) replaced by (ix, cn[], gen_st[], g_off[]).  The kernels read
+ * the genome the index already holds on its device; no genome byte crosses the bus.  A window is addressed as the reference's call sites hold it (mapping.c:353-361,
+ * 1306-1319):
+ *   window i = glen[i] positions from offset g_off[i] of contig cn[i] on strand gen_st[i]
+ *              0: genome_contigs[cn];  1: genome_contigs_rc[cn], i.e. the reverse complement of the contig, the offset counted from ITS start
+ * Strand 1 of a contig is what the reference keeps in genome_contigs_rc[cn]: position p is complement_base(forward[clen - 1 - p], contig is RNA).  In colour space its
+ * colours are those of genome_cs_contigs_rc[cn]: the translation of that reverse complement, the first colour against 'T' (genome.c:1107-1118).  Nothing is stored in
+ * the index for it: windows of either strand are read from the forward arrays, by the routines the mapping pipeline reads them with.
+ * Device: an entry makes the index's device current for its own duration and sets the caller's current device back before it returns.
+ * State: each entry runs on the calling thread's setup state as its host-bitfield twin does -- sw_vector_setup (whose use_colours selects letter or colour space for
+ * gm_sw_vector_batch_ix), sw_gapless_setup, sw_full_ls_setup, sw_full_cs_setup, post_sw_setup; without it: GM_E_NOTSETUP.  The stats count as the twins count.  The
+ * work runs on the index's device (see above).
+ *   is_rna   -1: the index's own genome_is_rna, which is what gmapper passes (the flag of the LAST contig, genome.c:1063-1064); 0 / 1: that value, as the single seams
+ *            take it.  A contig's own flag always decides its reverse complement and its colour translation.
+ * Colour space: gm_sw_vector_batch_ix under use_colours, gm_sw_gapless_batch_ix with colour_space = 1 and gm_index_get_windows with colours = 1 need an index built
+ * with colour_space = 1; on a letter-space index they return GM_E_ARG with a message.  gm_sw_full_cs_batch_ix and gm_post_sw_batch_ix read letters only and work on
+ * either kind of index.  gm_sw_vector_batch_bounded_ix is letter space, as its twin.
+ * gm_sw_gapless_batch_ix scores against the WHOLE contig of that strand, as sw_gapless(genome, glen = contig length, ...) does; g_idx[i] is a position of that
+ * strand's contig.
+ * Records: recs[i].genome_start is counted from the start of the strand's contig, i.e. it includes g_off[i] -- the value the reference leaves in sfr->genome_start for
+ * that call.  gm_post_sw_batch_ix takes the records, ops and ops_len of ONE gm_sw_full_cs_batch_ix call together with the cn / gen_st it was given.
+ * Strings: gm_sw_full_batch_strings stays the one string builder.  A caller with its own genome_contigs[_rc][cn] passes that bitfield and the record as it is.  A
+ * caller without a host genome fetches the windows with gm_index_get_windows -- window i as a bitfield of its own at words + i * stride_words, position 0 in nibble 0,
+ * stride_words >= (glen[i] + 7) / 8; colours = 1: the colours of the strand's contig instead of its letters -- and passes that with a COPY of the record whose
+ * genome_start is less g_off[i].
+ * Refusals, all before anything is read through the arguments: cn outside the index, gen_st > 1, g_off < 0, glen < 1, g_off + glen beyond the contig.  The full and
+ * post forms refuse the ITEM (status = GM_E_ARG, score 0, the reason of the last one in gm_last_error(), its neighbours answered; the twins' other refusals apply
+ * too).  gm_index_get_windows, the vector forms and the gapless form have no per-item status: they fail the call with GM_E_ARG and name the item, as
+ * gm_sw_gapless_batch does.  n <= 0: GM_OK, nothing is written.  ix == NULL: GM_E_ARG, no device is touched.
+ * Cost: as for the twins, one call makes a fixed number of device allocations, copies and kernel launches whatever n is -- and here none of them is sized by the
+ * genome: what is uploaded is 16 bytes a window, the reads and the per-item scalars (figures: profiles/r08a_seam_ix_timing.json).
+ * ------------------------------------------------------------------------------------------- */
+int gm_index_genome_is_rna(const gm_index_t *ix);   /* 1 / 0: the index's genome_is_rna (what is_rna = -1 stands for); < 0: GM_E_* */
+int gm_index_get_windows(const gm_index_t *ix, int n, const int *cn, const uint8_t *gen_st, const int64_t *g_off, const int *glen,
+                         int colours, uint32_t *words, int stride_words);
+int gm_sw_vector_batch_ix(const gm_index_t *ix, int n, const int *cn, const uint8_t *gen_st, const int64_t *g_off, const int *glen,
+                          const uint32_t *reads, int read_words, const int *rlen, const int *initbp, int is_rna, int *scores);
+int gm_sw_vector_batch_bounded_ix(const gm_index_t *ix, int n, const int *cn, const uint8_t *gen_st, const int64_t *g_off, const int *glen,
+                          const uint32_t *reads, int read_words, const int *rlen, int threshold, int *scores, uint8_t *stopped);
+int gm_sw_gapless_batch_ix(const gm_index_t *ix, int n, const int *cn, const uint8_t *gen_st, int colour_space,
+                          const uint32_t *reads, int read_words, const int *rlen, const int *g_idx, const int *r_idx, const int *initbp, int is_rna, int *scores);
+int gm_sw_full_ls_batch_ix(const gm_index_t *ix, int n, const int *cn, const uint8_t *gen_st, const int64_t *g_off, const int *glen,
+                          const uint32_t *reads, int read_words, const int *rlen, const struct gm_anchor *anchors, const uint8_t *revcmpl,
+                          const int *threshscore, const int *maxscore, int local_alignment, gm_sw_full_rec_t *recs, uint8_t **ops, uint64_t *ops_len);
+int gm_sw_full_cs_batch_ix(const gm_index_t *ix, int n, const int *cn, const uint8_t *gen_st, const int64_t *g_off, const int *glen,
+                          const uint32_t *reads, int read_words, const int *rlen, const uint8_t *initbp, const struct gm_anchor *anchors, const uint8_t *revcmpl,
+                          const int *threshscore, const int *crossover_scores, int xover_stride, int is_rna, int local_alignment,
+                          gm_sw_full_rec_t *recs, uint8_t **ops, uint64_t *ops_len);
+int gm_post_sw_batch_ix(const gm_index_t *ix, int n, const int *cn, const uint8_t *gen_st, const gm_sw_full_rec_t *recs, const uint8_t *ops, uint64_t ops_len,
+                          const uint32_t *reads, int read_words, const int *rlen, const uint8_t *initbp, const char *const *quals, int is_rna,
+                          gm_post_rec_t *post, char **qralign_out, char **quals_out, uint64_t *quals_len);
+
+/* ---------------------------------------------------------------------------------------------
  * S4: the per-read pipeline.  Replaces handle_read() for unpaired letter-space reads
  * (ref: gmapper/mapping.c:1773-1868) and the read loop body around it (ref: gmapper/gmapper.c:436-560).
  * Input: n reads of one length, as 4-bit bitfields (read_words = (read_len+7)/8 words each), plus
@@ -534,6 +587,9 @@ int gm_merge_sam(const gm_merge_options_t *opts, const char *reads_text, size_t 
  * 12 x int64 per row: read st cn g_off w_len score_vector pct_score_vector matches ax ay alen awidth */
 int gm_debug_tophits(gm_session_t *s, int n_reads, int read_len, const uint32_t *reads_packed,
                      long long *rows, long cap, long *n_rows);
+/* the same in colour space: the reads' primer letters (A0 C1 G2 T3) go up with their colours; gm_debug_tophits takes none and leaves the session's primer buffer as it is */
+int gm_debug_tophits_cs(gm_session_t *s, int n_reads, int n_colours, const uint32_t *colours_packed, const uint8_t *initbp,
+                        long long *rows, long cap, long *n_rows);
 
 /* time of the dominant kernel (seed lookup) during the last gm_map_* call, from HIP events on the
  * session's own stream, and the algorithmic bytes it moved */

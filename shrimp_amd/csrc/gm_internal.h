@@ -172,11 +172,13 @@ int gm_launch_post_sw_cs(const GmCsPostDev& K, const uint32_t* d_reads, const ui
 // S3 batch (gm_post_sw_batch, k_post_sw_batch): one alignment of a gm_sw_full_cs_batch call.  The host fills an item only after it has checked the record against the caller's
 // buffers: ops[ops_off .. + n_ops), genome positions from genome_start, read positions read_start .. < rlen of read `idx`; len = read positions in the alignment (columns
 // of scratch the item takes), qual_off = where its base qualities go.  GmPostRes.valid: 1 answered, 2 the host routine decides.
-struct GmPostItem { unsigned long long ops_off, qual_off; long long genome_start; uint32_t n_ops; int read_start, rlen, len, initbp, idx; };
+// gbase / flags: where genome position p of the record lives in d_genome -- position gbase + p, or with flags & 1 (gm_post_sw_batch_ix, strand 1 of a contig: gbase is
+// then the contig's LAST forward base) the complement of position gbase - p, an RNA contig's (flags & 2) with U for A.  The host-bitfield entry passes 0 for both.
+struct GmPostItem { unsigned long long ops_off, qual_off; long long genome_start, gbase; uint32_t n_ops; int read_start, rlen, len, initbp, idx, flags; };
 static const size_t GM_POST_COL_BYTES = 17 * 8 + 4;       // scratch a column and thread slot: 16 forward values, the column's scale, the column word
 int gm_launch_post_sw_batch(const GmCsPostDev& K, int first, int n, int threads, const GmPostItem* d_items, const uint8_t* d_ops, const uint32_t* d_genome,
                             const uint32_t* d_reads, int read_words, int qv_stride, int is_rna, GmPostRes* d_post, uint8_t* d_qralign, uint8_t* d_quals,
-                            double* d_fw, uint32_t* d_info, hipStream_t stream);
+                            double* d_fw, uint32_t* d_info, hipStream_t stream, int ix = 0);      // ix: the items carry gbase / flags (gm_post_sw_batch_ix)
 int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs_params9, const uint32_t* d_reads, const uint8_t* d_initbp, int n_reads,
                        int read_len, int read_words, int window_len, const GmHit* d_hits, int hcap, const int32_t* d_sel, const uint32_t* d_work,
                        const uint32_t* d_n_work, GmFullRes* d_res, uint8_t* d_ops, int ops_stride, uint32_t* d_back, size_t back_words, int grid,
@@ -202,6 +204,17 @@ int gm_launch_pair_select(const GmScoreDev& sc, int n_pairs, int len1, int len2,
                           uint32_t* pairs, uint32_t* pair_cnt, hipStream_t stream);
 int gm_launch_mark_saved(uint8_t* d_saved, const uint32_t* d_list, int n, hipStream_t stream);
 
+// One window of an index-resident seam call (gm_*_ix): glen positions of contig cn whose lowest FORWARD base is contig position foff; rc: the window is read on strand 1
+// (the reverse complement of the contig), i.e. backwards and complemented.  The host has checked it against the contig (ix_window, gm_host.hip).
+struct GmWin { uint32_t foff; int glen, cn, rc; };
+int gm_launch_get_windows(const GmIndexDev& ix, int n, const GmWin* d_wins, int colours, uint32_t* d_words, int stride_words, hipStream_t stream);
+// d_initbp null: letter space (load_window); else colour space (load_window_cs: colours and first-colour row; ix.genome_is_rna = the call's is_rna)
+int gm_launch_sw_vector_batch_ix(const GmIndexDev& ix, const GmScoreDev& sc, int n, const GmWin* d_wins, const uint32_t* d_reads, int read_words, const int* d_rlen,
+                                 const int* d_initbp, int max_g, int max_r, int* d_scores, hipStream_t stream, int early_thr = 0, uint8_t* d_stopped = nullptr);
+// d_wins[i].glen is unused: the diagonal runs over the whole contig of the strand
+int gm_launch_sw_gapless_batch_ix(const GmIndexDev& ix, int n, int match, int mismatch, const GmWin* d_wins, int colour_space, const uint32_t* d_reads, int read_words,
+                                  const int* d_rlen, const int* d_gidx, const int* d_ridx, const int* d_initbp, int max_r, int* d_scores, hipStream_t stream);
+
 // S1 batch kernel on caller-provided bitfields
 int gm_launch_sw_vector_batch(const GmScoreDev& sc, int n, const uint32_t* d_genome, const long long* d_goff, const int* d_glen,
                               const uint32_t* d_reads, int read_words, const int* d_rlen, int max_g, int max_r, int* d_scores, hipStream_t stream,
@@ -224,7 +237,8 @@ int gm_launch_sw_full_cs_single(const int* cs_params9, const uint32_t* d_genome_
                                 int ops_cap, hipStream_t stream, int local = 0, const int8_t* d_xrow = nullptr);
 
 // S2 batch (gm_sw_full_ls_batch / gm_sw_full_cs_batch): one window as the batch kernels read it, and what they write back per window.
-// flags: 1 = anchor box given (else the threshold band), 2 = revcmpl; initbp: colour space only, the primer letter | GM_SEAM_RNA; idx: the caller's item
+// flags: 1 = anchor box given (else the threshold band), 2 = revcmpl, 4 = the window is read on strand 1 (backwards and complemented; goff is then the global position of
+// its lowest forward base), 8 = its contig is RNA (both 0 on caller bitfields); initbp: colour space only, the primer letter | GM_SEAM_RNA; idx: the caller's item
 // (row of reads[] and of the crossover rows, slot of out[]); ops_off / ops_cap: the item's segment of the device ops buffer.
 struct GmFullItem { long long goff, ax, ay; unsigned long long ops_off; int glen, rlen, alen, awidth, thresh, maxscore, flags, initbp, ops_cap, idx; };
 // v[0..10] = score read_start rmapped genome_start (window-relative) gmapped matches mismatches insertions deletions crossovers n_ops
@@ -234,7 +248,7 @@ size_t gm_sw_full_batch_lds(int max_g, int max_r);
 size_t gm_sw_full_cs_batch_lds(int max_g, int max_r);
 // items[first .. first + n) by `grid` waves; wave b owns back-pointer scratch d_back + b * back_stride (bytes; colour space: uint32 words)
 int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
-                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream);
+                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream, int ix = 0);
 int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
                                int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
-                               uint8_t* d_ops, int local, hipStream_t stream);
+                               uint8_t* d_ops, int local, hipStream_t stream, int ix = 0);      // ix: the items carry strand / RNA bits (gm_sw_full_cs_batch_ix)

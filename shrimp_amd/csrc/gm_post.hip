@@ -194,6 +194,7 @@ int gm_launch_post_sw_cs(const GmCsPostDev& K, const uint32_t* d_reads, const ui
 // values before it reads any, so nothing of the slot's earlier items is ever believed.
 // Out: GmPostRes per item (valid 1: answered; 2: the host routine decides, see k_post_fb), the re-called qralign characters at qralign[ops_off + t] ('-' where
 // the column holds no read position) and one base quality per read position at quals[qual_off ..).
+template <bool IX>      // IX: gm_post_sw_batch_ix -- genome positions through GmPostItem.gbase / flags (an instantiation of its own: the host-bitfield entry's code stays what it was)
 __global__ void __launch_bounds__(64)
 k_post_sw_batch(GmCsPostDev K, const GmPostItem* __restrict__ items, int first, int n_items, const uint8_t* __restrict__ ops, const uint32_t* __restrict__ genome,
                 const uint32_t* __restrict__ reads, int read_words, int qv_stride, int is_rna, GmPostRes* __restrict__ post, uint8_t* __restrict__ qralign,
@@ -240,7 +241,14 @@ k_post_sw_batch(GmCsPostDev K, const GmPostItem* __restrict__ items, int first, 
         const bool ins = type >= 2 && type <= 5;                                 // a read letter against a gap in the genome
         const int cc = colour(j);
         const int rl = (int)((translate(cc) >> (4 * (ins ? type - 2 : type - 6))) & 0xfu);
-        int d = 0; if (!ins) { d = (int)((genome[pj >> 3] >> ((pj & 7) * 4)) & 0xf); pj++; }
+        int d = 0;
+        if (!ins) {                                                 // (IX, strand 1: the complement of the forward letter, see GmPostItem)
+          const bool rcs = IX && (it.flags & 1);
+          const long long gp = !IX ? pj : (rcs ? it.gbase - pj : it.gbase + pj);
+          d = (int)((genome[gp >> 3] >> ((gp & 7) * 4)) & 0xf);
+          if (rcs) d = (int)((gm_cmpl_tab((it.flags & 2) != 0) >> (d * 4)) & 0xf);
+          pj++;
+        }
         const int let = ins ? -2 : (d < 4 ? d : -1);
         int col, which;
         if ((len == 0 && start_run == 15) || cc == 15) { col = 0; which = 1; } else { col = cc ^ (len == 0 ? start_run : 0); which = 0; }
@@ -288,10 +296,12 @@ k_post_sw_batch(GmCsPostDev K, const GmPostItem* __restrict__ items, int first, 
 
 int gm_launch_post_sw_batch(const GmCsPostDev& K, int first, int n, int threads, const GmPostItem* d_items, const uint8_t* d_ops, const uint32_t* d_genome,
                             const uint32_t* d_reads, int read_words, int qv_stride, int is_rna, GmPostRes* d_post, uint8_t* d_qralign, uint8_t* d_quals,
-                            double* d_fw, uint32_t* d_info, hipStream_t stream) {
+                            double* d_fw, uint32_t* d_info, hipStream_t stream, int ix) {
   if (n < 1 || threads < 64 || (threads & 63)) return GM_E_ARG;
-  hipLaunchKernelGGL(k_post_sw_batch, dim3(threads / 64), dim3(64), 0, stream, K, d_items, first, n, d_ops, d_genome, d_reads, read_words, qv_stride, is_rna, d_post,
-                     d_qralign, d_quals, d_fw, d_info);
+  if (ix) hipLaunchKernelGGL(k_post_sw_batch<true>, dim3(threads / 64), dim3(64), 0, stream, K, d_items, first, n, d_ops, d_genome, d_reads, read_words, qv_stride, is_rna, d_post,
+                             d_qralign, d_quals, d_fw, d_info);
+  else hipLaunchKernelGGL(k_post_sw_batch<false>, dim3(threads / 64), dim3(64), 0, stream, K, d_items, first, n, d_ops, d_genome, d_reads, read_words, qv_stride, is_rna, d_post,
+                          d_qralign, d_quals, d_fw, d_info);
   if (hipGetLastError() != hipSuccess) return GM_E_NODEVICE;
   return GM_OK;
 }

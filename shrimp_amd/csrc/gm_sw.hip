@@ -233,8 +233,10 @@ __device__ void load_read(const uint32_t* __restrict__ rw, int read_len, bool rc
 // sw_gapless (ref: common/sw-gapless.c:57-117) by one wave, letter space: the best ungapped segment on the contig diagonal through
 // (g_idx, r_idx).  The reference's running score with reset below zero is the maximum-subarray sum: max over r of
 // P[r] - min(0, P[j] for j < r) on the prefix sums P of the per-base scores -- two wave scans per 64 cells.
-__device__ int sw_gapless_wave(const uint32_t* __restrict__ genome, uint64_t cbase, long long clen, const uint8_t* qr, int rlen,
-                               long long g_idx, int r_idx, const GmScoreDev& sc, int lane) {
+// RC (the index-resident seam only): the contig is read on strand 1 -- position g is the complement (table cm) of forward position clen - 1 - g.
+template <bool RC>
+__device__ __forceinline__ int sw_gapless_wave_t(const uint32_t* __restrict__ genome, uint64_t cbase, long long clen, const uint8_t* qr, int rlen,
+                                                 long long g_idx, int r_idx, const GmScoreDev& sc, int lane, const uint64_t cm = 0) {
   long long g_left; int r_left;
   if (g_idx < r_idx) { g_left = 0; r_left = (int)(r_idx - g_idx); } else { g_left = g_idx - r_idx; r_left = 0; }
   const long long room = clen - g_left;
@@ -244,8 +246,9 @@ __device__ int sw_gapless_wave(const uint32_t* __restrict__ genome, uint64_t cba
     const int k = k0 + lane;
     int sv = 0;
     if (k < n) {
-      const uint64_t p = cbase + (uint64_t)g_left + (uint64_t)k;
-      const uint32_t gc = (genome[p >> 3] >> ((p & 7) * 4)) & 0xf;
+      const uint64_t p = RC ? cbase + (uint64_t)(clen - 1 - g_left - k) : cbase + (uint64_t)g_left + (uint64_t)k;
+      uint32_t gc = (genome[p >> 3] >> ((p & 7) * 4)) & 0xf;
+      if (RC) gc = (uint32_t)(cm >> (gc * 4)) & 0xf;
       sv = (gc == (uint32_t)qr[r_left + k]) ? sc.match : sc.mismatch;
     }
     int ps = sv;
@@ -261,6 +264,10 @@ __device__ int sw_gapless_wave(const uint32_t* __restrict__ genome, uint64_t cba
   }
   for (int d = 32; d > 0; d >>= 1) best = max(best, __shfl_xor(best, d));
   return best;
+}
+__device__ int sw_gapless_wave(const uint32_t* __restrict__ genome, uint64_t cbase, long long clen, const uint8_t* qr, int rlen,
+                               long long g_idx, int r_idx, const GmScoreDev& sc, int lane) {
+  return sw_gapless_wave_t<false>(genome, cbase, clen, qr, rlen, g_idx, r_idx, sc, lane);
 }
 
 // hash_genome_window % f1_window_cache_size (ref: common/util.h:224-245, common/hash.h:70-95, f1-wrapper.h:27)
@@ -1272,7 +1279,7 @@ int gm_launch_sw_full_single(const GmScoreDev& sc, const uint32_t* d_genome, lon
 // agent-scope atomic loads (no stale line of an earlier item in the vector cache); an item's stores precede its walk by a barrier, and the next
 // item's stores follow the walk in program order of the same wave.
 // ---------------------------------------------------------------------------------------------
-template <bool LOCAL>
+template <bool LOCAL, bool IX = false>      // IX: gm_sw_full_ls_batch_ix -- the strand / RNA bits of GmFullItem.flags are read (an instantiation of its own)
 __global__ void __launch_bounds__(GM_WAVE)
 k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ items, const uint32_t* __restrict__ genome, const uint32_t* __restrict__ reads,
                 int read_words, int max_g, int max_r, uint8_t* __restrict__ back_pool, size_t back_stride, GmFullOut* __restrict__ out, uint8_t* __restrict__ ops_all) {
@@ -1287,7 +1294,7 @@ k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ 
     const int glen = __builtin_amdgcn_readfirstlane(it.glen), rlen = __builtin_amdgcn_readfirstlane(it.rlen), flags = __builtin_amdgcn_readfirstlane(it.flags);
     __syncthreads();                                                              // lane 0 may still read the previous item's db / qr
     load_read(reads + (size_t)it.idx * read_words, rlen, false, qr, lane);
-    load_window(genome, (uint64_t)it.goff, glen, false, db, lane);
+    load_window(genome, (uint64_t)it.goff, glen, IX && (flags & 4) != 0, db, lane, IX && (flags & 8) != 0);
     __syncthreads();
     const bool has_anchor = (flags & 1) != 0, revcmpl = (flags & 2) != 0;
     long long rx, ry; int rw, rl;
@@ -1340,19 +1347,17 @@ k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ 
 
 size_t gm_sw_full_batch_lds(int max_g, int max_r) { return ((max_r + 15) & ~15) + ((max_g + 15) & ~15) + (size_t)max_g * 12 + 64; }
 int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
-                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream) {
+                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream, int ix) {
   if (n == 0) return GM_OK;
   const size_t lds = gm_sw_full_batch_lds(max_g, max_r);
   if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("sw_full_ls batch: window of %d does not fit LDS", max_g); return GM_E_ARG; }
-  if (local) {
-    GM_HIP(gm_lds_at_least((const void*)k_sw_full_batch<true>, lds));
-    hipLaunchKernelGGL(k_sw_full_batch<true>, dim3(grid), dim3(GM_WAVE), lds, stream, sc, first, n, d_items, d_genome, d_reads, read_words, max_g, max_r, d_back, back_stride,
-                       d_out, d_ops);
-  } else {
-    GM_HIP(gm_lds_at_least((const void*)k_sw_full_batch<false>, lds));
-    hipLaunchKernelGGL(k_sw_full_batch<false>, dim3(grid), dim3(GM_WAVE), lds, stream, sc, first, n, d_items, d_genome, d_reads, read_words, max_g, max_r, d_back, back_stride,
-                       d_out, d_ops);
-  }
+#define GM_SWF_LAUNCH(LOC, IX) do { \
+    GM_HIP(gm_lds_at_least((const void*)k_sw_full_batch<LOC, IX>, lds)); \
+    hipLaunchKernelGGL((k_sw_full_batch<LOC, IX>), dim3(grid), dim3(GM_WAVE), lds, stream, sc, first, n, d_items, d_genome, d_reads, read_words, max_g, max_r, d_back, back_stride, \
+                       d_out, d_ops); } while (0)
+  if (local) { if (ix) GM_SWF_LAUNCH(true, true); else GM_SWF_LAUNCH(true, false); }
+  else { if (ix) GM_SWF_LAUNCH(false, true); else GM_SWF_LAUNCH(false, false); }
+#undef GM_SWF_LAUNCH
   GM_HIP(hipGetLastError());
   return GM_OK;
 }
@@ -2439,8 +2444,8 @@ int gm_launch_sw_full_cs_single(const int* cs_params9, const uint32_t* d_genome_
 // returns 0 outside it, as k_pass2_cs / k_pass2_cs_g4 do on their reused scratch): every cell inside the band is written by the current item
 // before the walk, and no word outside it is ever read.
 // ---------------------------------------------------------------------------------------------
-template <bool LOCAL>
-__global__ void __launch_bounds__(GM_WAVE)          // (one wave per SIMD: with a second one the four local-mode variants spill 100+ bytes a lane)
+template <bool LOCAL, bool IX = false>                // IX: gm_sw_full_cs_batch_ix -- the strand / RNA bits of GmFullItem.flags are read (an instantiation of its own: the host-bitfield
+__global__ void __launch_bounds__(GM_WAVE)          // entry's code stays what it was).  (one wave per SIMD: with a second one the four local-mode variants spill 100+ bytes a lane)
 k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ items, const uint32_t* __restrict__ genome_ls, const uint32_t* __restrict__ reads,
                    int read_words, int max_g, int max_r, const int8_t* __restrict__ xrows, int xstride, uint32_t* __restrict__ back_pool, size_t back_words,
                    GmFullOut* __restrict__ out, uint8_t* __restrict__ ops_all) {
@@ -2461,7 +2466,7 @@ k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ i
     const int8_t* xrow = xrows ? xrows + (size_t)it.idx * xstride : nullptr;
     __syncthreads();                                  // lane 0 may still read the previous item's db / qr4
     load_read(reads + (size_t)it.idx * read_words, rlen, false, rc, lane);
-    load_window(genome_ls, (uint64_t)it.goff, glen, false, db, lane);
+    load_window(genome_ls, (uint64_t)it.goff, glen, IX && (flags & 4) != 0, db, lane, IX && (flags & 8) != 0);
     __syncthreads();
     if (lane < 4) {                                   // ref: sw-full-cs.c:1182-1197
       int letter = (lane + initbp) % 4;
@@ -2537,21 +2542,132 @@ k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ i
 size_t gm_sw_full_cs_batch_lds(int max_g, int max_r) { return 5 * (size_t)((max_r + 15) & ~15) + ((max_g + 15) & ~15) + (size_t)max_g * 48 + 64; }
 int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
                                int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
-                               uint8_t* d_ops, int local, hipStream_t stream) {
+                               uint8_t* d_ops, int local, hipStream_t stream, int ix) {
   if (n == 0) return GM_OK;
   GmCsDev P; P.match = cs_params9[0]; P.mismatch = cs_params9[1]; P.xover = cs_params9[2]; P.a_go = cs_params9[3]; P.a_ge = cs_params9[4];
   P.b_go = cs_params9[5]; P.b_ge = cs_params9[6]; P.anchor_width = cs_params9[7]; P.taboo = cs_params9[8];
   const size_t lds = gm_sw_full_cs_batch_lds(max_g, max_r);
   if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("sw_full_cs batch: window of %d does not fit LDS", max_g); return GM_E_ARG; }      // (the host entry refuses such items one by one before it gets here)
-  if (local) {
-    GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_batch<true>, lds));
-    hipLaunchKernelGGL(k_sw_full_cs_batch<true>, dim3(grid), dim3(GM_WAVE), lds, stream, P, first, n, d_items, d_genome_ls, d_reads, read_words, max_g, max_r, d_xrows, xstride,
-                       d_back, back_words, d_out, d_ops);
-  } else {
-    GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_batch<false>, lds));
-    hipLaunchKernelGGL(k_sw_full_cs_batch<false>, dim3(grid), dim3(GM_WAVE), lds, stream, P, first, n, d_items, d_genome_ls, d_reads, read_words, max_g, max_r, d_xrows, xstride,
-                       d_back, back_words, d_out, d_ops);
+#define GM_SWF_CS_LAUNCH(LOC, IX) do { \
+    GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_batch<LOC, IX>, lds)); \
+    hipLaunchKernelGGL((k_sw_full_cs_batch<LOC, IX>), dim3(grid), dim3(GM_WAVE), lds, stream, P, first, n, d_items, d_genome_ls, d_reads, read_words, max_g, max_r, d_xrows, xstride, \
+                       d_back, back_words, d_out, d_ops); } while (0)
+  if (local) { if (ix) GM_SWF_CS_LAUNCH(true, true); else GM_SWF_CS_LAUNCH(true, false); }
+  else { if (ix) GM_SWF_CS_LAUNCH(false, true); else GM_SWF_CS_LAUNCH(false, false); }
+#undef GM_SWF_CS_LAUNCH
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// =============================================================================================
+// Index-resident seams (gm_*_ix): the windows are read from the resident genome, addressed as the reference addresses them -- contig, strand, offset.  Strand 1 is the
+// reverse complement of the contig; nothing is stored for it: load_window / load_window_cs / sw_gapless_cs_wave read it from the forward arrays, as the pipeline does.
+// =============================================================================================
+#define GM_GETWIN_CHUNK 2048      // positions a wave unpacks, packs and writes at a time (a multiple of 8: every chunk starts a word of the output)
+// Window i as a bitfield of its own at words + i * stride_words, position 0 in nibble 0: letters, or (colours) the colour translation of the strand's contig.
+__global__ void __launch_bounds__(GM_WAVE)
+k_get_windows(GmIndexDev ix, int n, const GmWin* __restrict__ wins, int colours, uint32_t* __restrict__ words, int stride_words) {
+  __shared__ __align__(16) uint8_t db[GM_GETWIN_CHUNK];
+  __shared__ __align__(16) uint8_t db0[GM_GETWIN_CHUNK];
+  const int lane = threadIdx.x;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const GmWin w = wins[i];
+    const int glen = __builtin_amdgcn_readfirstlane(w.glen), cn = __builtin_amdgcn_readfirstlane(w.cn); const bool rc = __builtin_amdgcn_readfirstlane(w.rc) != 0;
+    const uint32_t foff = (uint32_t)__builtin_amdgcn_readfirstlane((int)w.foff);
+    uint32_t* dst = words + (size_t)i * stride_words;
+    for (int c0 = 0; c0 < glen; c0 += GM_GETWIN_CHUNK) {
+      const int len = min(GM_GETWIN_CHUNK, glen - c0);
+      // the chunk's lowest forward base: on strand 1 the window runs down from foff + glen - 1
+      const uint32_t f0 = rc ? foff + (uint32_t)(glen - c0 - len) : foff + (uint32_t)c0;
+      __syncthreads();
+      if (colours) load_window_cs(ix, cn, f0, len, rc, 0, db, db0, lane);
+      else load_window(ix.genome, (uint64_t)ix.contig_off[cn] + f0, len, rc, db, lane, ix.contig_rna && ix.contig_rna[cn]);
+      __syncthreads();
+      for (int k = lane; k < (len + 7) / 8; k += GM_WAVE) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int b = 0; b < 8; b++) if (k * 8 + b < len) v |= (uint32_t)(db[k * 8 + b] & 0xf) << (4 * b);
+        dst[c0 / 8 + k] = v;
+      }
+    }
   }
+}
+int gm_launch_get_windows(const GmIndexDev& ix, int n, const GmWin* d_wins, int colours, uint32_t* d_words, int stride_words, hipStream_t stream) {
+  if (n == 0) return GM_OK;
+  hipLaunchKernelGGL(k_get_windows, dim3(std::min(n, 256 * 16)), dim3(GM_WAVE), 0, stream, ix, n, d_wins, colours, d_words, stride_words);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// k_sw_vector_batch / k_sw_vector_batch_cs on windows of the index
+template <bool CS>
+__global__ void __launch_bounds__(GM_WAVE)
+k_sw_vector_batch_ix(GmIndexDev ix, GmScoreDev sc, int n, const GmWin* __restrict__ wins, const uint32_t* __restrict__ reads, int read_words, const int* __restrict__ rlen,
+                     const int* __restrict__ initbp, int max_g, int max_r, int* __restrict__ scores, int early_thr, uint8_t* __restrict__ stopped) {
+  extern __shared__ __align__(16) uint8_t sm[];
+  const int lane = threadIdx.x;
+  uint8_t* qr = sm;
+  uint8_t* db = sm + ((max_r + 15) & ~15);
+  uint8_t* db0 = db + ((max_g + 15) & ~15);
+  int16_t* carry = (int16_t*)(db0 + (CS ? ((max_g + 15) & ~15) : 0));
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const GmWin w = wins[i];
+    const int glen = __builtin_amdgcn_readfirstlane(w.glen), cn = __builtin_amdgcn_readfirstlane(w.cn), rl = __builtin_amdgcn_readfirstlane(rlen[i]);
+    const bool rc = __builtin_amdgcn_readfirstlane(w.rc) != 0;
+    __syncthreads();
+    load_read(reads + (size_t)i * read_words, rl, false, qr, lane);
+    if (CS) load_window_cs(ix, cn, w.foff, glen, rc, initbp[i] & 0xff, db, db0, lane);
+    else load_window(ix.genome, (uint64_t)ix.contig_off[cn] + w.foff, glen, rc, db, lane, ix.contig_rna && ix.contig_rna[cn]);
+    __syncthreads();
+    bool cut = false;
+    int s;
+    if (CS) s = sw_vector_wave_t<true>(db, db0, glen, qr, rl, sc, carry, lane);
+    else s = early_thr > 0 ? sw_vector_wave_t<false>(db, nullptr, glen, qr, rl, sc, carry, lane, early_thr, &cut) : sw_vector_wave(db, glen, qr, rl, sc, carry, lane);
+    if (lane == 0) { scores[i] = s; if (stopped) stopped[i] = cut ? 1 : 0; }
+  }
+}
+int gm_launch_sw_vector_batch_ix(const GmIndexDev& ix, const GmScoreDev& sc, int n, const GmWin* d_wins, const uint32_t* d_reads, int read_words, const int* d_rlen,
+                                 const int* d_initbp, int max_g, int max_r, int* d_scores, hipStream_t stream, int early_thr, uint8_t* d_stopped) {
+  if (n == 0) return GM_OK;
+  const size_t lds = ((max_r + 15) & ~15) + (d_initbp ? 2 : 1) * ((max_g + 15) & ~15) + (size_t)max_g * 4 + 64;      // as the host-bitfield launchers size it
+  const int grid = std::min(n, 256 * 16);
+  if (d_initbp) hipLaunchKernelGGL(k_sw_vector_batch_ix<true>, dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, n, d_wins, d_reads, read_words, d_rlen, d_initbp, max_g, max_r,
+                                   d_scores, 0, nullptr);
+  else hipLaunchKernelGGL(k_sw_vector_batch_ix<false>, dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, n, d_wins, d_reads, read_words, d_rlen, d_initbp, max_g, max_r,
+                          d_scores, early_thr, d_stopped);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// k_sw_gapless_batch on the whole contig of a strand: letter space by sw_gapless_wave_t, colour space by the pipeline's -U routine
+__global__ void __launch_bounds__(GM_WAVE)
+k_sw_gapless_batch_ix(GmIndexDev ix, int n, int match, int mismatch, const GmWin* __restrict__ wins, int colour_space, const uint32_t* __restrict__ reads, int read_words,
+                      const int* __restrict__ rlen, const int* __restrict__ g_idx, const int* __restrict__ r_idx, const int* __restrict__ initbp, int* __restrict__ scores) {
+  extern __shared__ __align__(16) uint8_t gl_smem[];
+  uint8_t* qr = gl_smem;
+  const int lane = threadIdx.x;
+  GmScoreDev sc; sc.match = match; sc.mismatch = mismatch;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const int cn = __builtin_amdgcn_readfirstlane(wins[i].cn), rl = __builtin_amdgcn_readfirstlane(rlen[i]); const bool rc = __builtin_amdgcn_readfirstlane(wins[i].rc) != 0;
+    __syncthreads();
+    load_read(reads + (size_t)i * read_words, rl, false, qr, lane);
+    __syncthreads();
+    int best;
+    if (colour_space) best = sw_gapless_cs_wave(ix, cn, rc, qr, rl, (long long)g_idx[i], r_idx[i], initbp[i] & 0xff, sc, lane);
+    else {
+      const uint64_t cbase = ix.contig_off[cn]; const long long clen = (long long)ix.contig_off[cn + 1] - (long long)cbase;
+      best = rc ? sw_gapless_wave_t<true>(ix.genome, cbase, clen, qr, rl, (long long)g_idx[i], r_idx[i], sc, lane, gm_cmpl_tab(ix.contig_rna && ix.contig_rna[cn]))
+                : sw_gapless_wave(ix.genome, cbase, clen, qr, rl, (long long)g_idx[i], r_idx[i], sc, lane);
+    }
+    if (lane == 0) scores[i] = best;
+  }
+}
+int gm_launch_sw_gapless_batch_ix(const GmIndexDev& ix, int n, int match, int mismatch, const GmWin* d_wins, int colour_space, const uint32_t* d_reads, int read_words,
+                                  const int* d_rlen, const int* d_gidx, const int* d_ridx, const int* d_initbp, int max_r, int* d_scores, hipStream_t stream) {
+  if (n == 0) return GM_OK;
+  const size_t lds = ((size_t)max_r + 15) & ~(size_t)15;
+  hipLaunchKernelGGL(k_sw_gapless_batch_ix, dim3(std::min(n, 256 * 16)), dim3(GM_WAVE), lds, stream, ix, n, match, mismatch, d_wins, colour_space, d_reads, read_words, d_rlen,
+                     d_gidx, d_ridx, d_initbp, d_scores);
   GM_HIP(hipGetLastError());
   return GM_OK;
 }

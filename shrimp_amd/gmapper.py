@@ -131,7 +131,9 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "sw_full_cs_setup", "sw_full_cs", "sw_full_cs_cleanup", "sw_full_cs_stats", "gm_sw_vector_batch_cs",
            "gm_sw_full_ls_batch", "gm_sw_full_cs_batch", "gm_sw_full_batch_strings",
            "post_sw_setup", "post_sw", "post_sw_cleanup", "post_sw_stats", "gm_post_sw_batch", "gm_post_sw_batch_last_plan",
-           "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits",
+           "gm_index_genome_is_rna", "gm_index_get_windows", "gm_sw_vector_batch_ix", "gm_sw_vector_batch_bounded_ix", "gm_sw_gapless_batch_ix", "gm_sw_full_ls_batch_ix", "gm_sw_full_cs_batch_ix",
+           "gm_post_sw_batch_ix",
+           "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits", "gm_debug_tophits_cs",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
 
@@ -195,6 +197,16 @@ def lib():
     L.gm_post_sw_batch.argtypes = [C.c_int, vp, vp, C.c_uint64, u32p, C.c_uint64, u32p, C.c_int, C.POINTER(C.c_int), vp, vp, C.c_int, vp, C.POINTER(vp), C.POINTER(vp),
                                    C.POINTER(C.c_uint64)]
     L.gm_post_sw_batch_last_plan.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    ipt, i64p, u8p = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    win = [vp, C.c_int, ipt, u8p, i64p, ipt]      # ix, n, cn, gen_st, g_off, glen
+    L.gm_index_genome_is_rna.argtypes = [vp]
+    L.gm_index_get_windows.argtypes = win + [C.c_int, u32p, C.c_int]
+    L.gm_sw_vector_batch_ix.argtypes = win + [u32p, C.c_int, ipt, ipt, C.c_int, ipt]
+    L.gm_sw_vector_batch_bounded_ix.argtypes = win + [u32p, C.c_int, ipt, C.c_int, ipt, u8p]
+    L.gm_sw_gapless_batch_ix.argtypes = [vp, C.c_int, ipt, u8p, C.c_int, u32p, C.c_int, ipt, ipt, ipt, ipt, C.c_int, ipt]
+    L.gm_sw_full_ls_batch_ix.argtypes = win + [u32p, C.c_int, ipt, vp, vp, ipt, vp, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.gm_sw_full_cs_batch_ix.argtypes = win + [u32p, C.c_int, ipt, vp, vp, vp, ipt, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.gm_post_sw_batch_ix.argtypes = [vp, C.c_int, ipt, u8p, vp, vp, C.c_uint64, u32p, C.c_int, ipt, vp, vp, C.c_int, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.gm_abi_sizeof.argtypes = [C.c_int]; L.gm_abi_sizeof.restype = C.c_int
     L.gm_session_create.argtypes = [C.POINTER(vp), vp, C.POINTER(Params), C.c_int]
     L.gm_session_free.argtypes = [vp]
@@ -218,6 +230,7 @@ def lib():
     L.gm_map_pairs_cs.argtypes = [vp, C.c_int, C.c_int, u32p, C.POINTER(C.c_uint8), C.c_int, u32p, C.POINTER(C.c_uint8), C.c_char_p, C.c_char_p, C.POINTER(PairOpts),
                                   C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(MapStats)]
     L.gm_debug_tophits.argtypes = [vp, C.c_int, C.c_int, u32p, C.POINTER(C.c_longlong), C.c_long, C.POINTER(C.c_long)]
+    L.gm_debug_tophits_cs.argtypes = [vp, C.c_int, C.c_int, u32p, C.POINTER(C.c_uint8), C.POINTER(C.c_longlong), C.c_long, C.POINTER(C.c_long)]
     L.gm_last_lookup_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     _lib = L
     return L
@@ -358,6 +371,145 @@ class Index:
         self.h = C.c_void_p(); self.device = device; self.params = default_params()
         _check(lib().gm_index_alloc_like(C.byref(self.h), device, meta, len(meta)), "gm_index_alloc_like")
         return self
+
+    # ---- the batch seams on the resident genome (gm_*_ix): window i = glen[i] positions from offset g_off[i] of contig cn[i] on strand gen_st[i] ----
+    def contig_lengths(self) -> np.ndarray:
+        return np.array([ln for _, ln in self.contigs()], dtype=np.int64)
+
+    @staticmethod
+    def strand_offset(clen, g_off, glen):
+        """the offset of a window on the other strand of its contig: forward offset <-> offset on the reverse-complement contig (its own inverse)"""
+        return np.asarray(clen, dtype=np.int64) - np.asarray(g_off, dtype=np.int64) - np.asarray(glen, dtype=np.int64)
+
+    @staticmethod
+    def _win(cn, gen_st, g_off=None, glen=None):
+        c = np.ascontiguousarray(cn, dtype=np.int32); n = c.shape[0]
+        st = np.ascontiguousarray(gen_st, dtype=np.uint8)
+        go = None if g_off is None else np.ascontiguousarray(g_off, dtype=np.int64); gn = None if glen is None else np.ascontiguousarray(glen, dtype=np.int32)
+        if any(a is not None and a.shape != (n,) for a in (st, go, gn)): raise GmError("cn, gen_st, g_off, glen have n entries each")
+        ipt, i64p, u8p = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+        args = [c.ctypes.data_as(ipt), st.ctypes.data_as(u8p)]
+        if go is not None: args += [go.ctypes.data_as(i64p), gn.ctypes.data_as(ipt)]
+        return n, args, (c, st, go, gn)
+
+    @staticmethod
+    def _reads(reads_words, n):
+        r = np.ascontiguousarray(reads_words, dtype=np.uint32)
+        if r.ndim != 2 or r.shape[0] != n: raise GmError("reads_words is (n, read_words)")
+        return r
+
+    def get_windows(self, cn, gen_st, g_off, glen, colours=False) -> np.ndarray:
+        """gm_index_get_windows: (n, stride) uint32 -- window i as a bitfield of its own (position 0 in nibble 0): letters, or the colour translation of the strand's contig"""
+        n, wargs, keep = self._win(cn, gen_st, g_off, glen)
+        stride = max(1, (int(keep[3].max()) + 7) // 8) if n else 1
+        out = np.zeros((n, stride), dtype=np.uint32)
+        _check(lib().gm_index_get_windows(self.h, n, *wargs, 1 if colours else 0, out.ctypes.data_as(C.POINTER(C.c_uint32)), stride), "gm_index_get_windows")
+        return out
+
+    def sw_vector_batch(self, cn, gen_st, g_off, glen, reads_words, rlen, initbp=None, is_rna=-1) -> np.ndarray:
+        """gm_sw_vector_batch_ix (letter or colour space as sw_vector_setup's use_colours chose; colour space: initbp per read)"""
+        n, wargs, keep = self._win(cn, gen_st, g_off, glen)
+        r = self._reads(reads_words, n); rl = np.ascontiguousarray(rlen, dtype=np.int32)
+        ib = None if initbp is None else np.ascontiguousarray(initbp, dtype=np.int32)
+        out = np.zeros(n, dtype=np.int32); ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+        _check(lib().gm_sw_vector_batch_ix(self.h, n, *wargs, r.ctypes.data_as(C.POINTER(C.c_uint32)), r.shape[1], ip(rl), ip(ib), int(is_rna), ip(out)), "gm_sw_vector_batch_ix")
+        return out
+
+    def sw_vector_batch_bounded(self, cn, gen_st, g_off, glen, reads_words, rlen, threshold: int):
+        """gm_sw_vector_batch_bounded_ix: (scores, stopped) as the module-level sw_vector_batch_bounded"""
+        n, wargs, keep = self._win(cn, gen_st, g_off, glen)
+        r = self._reads(reads_words, n); rl = np.ascontiguousarray(rlen, dtype=np.int32)
+        out = np.zeros(n, dtype=np.int32); stopped = np.zeros(n, dtype=np.uint8); ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        _check(lib().gm_sw_vector_batch_bounded_ix(self.h, n, *wargs, r.ctypes.data_as(C.POINTER(C.c_uint32)), r.shape[1], ip(rl), int(threshold), ip(out),
+                                                   stopped.ctypes.data_as(C.POINTER(C.c_uint8))), "gm_sw_vector_batch_bounded_ix")
+        return out, stopped
+
+    def sw_gapless_batch(self, cn, gen_st, reads_words, rlen, g_idx, r_idx, initbp=None, colour_space=False, is_rna=-1) -> np.ndarray:
+        """gm_sw_gapless_batch_ix: the ungapped filter against the whole contig of the strand; g_idx is a position of that strand's contig"""
+        n, wargs, keep = self._win(cn, gen_st)
+        r = self._reads(reads_words, n)
+        rl, gi, ri = (np.ascontiguousarray(a, dtype=np.int32) for a in (rlen, g_idx, r_idx))
+        ib = None if initbp is None else np.ascontiguousarray(initbp, dtype=np.int32)
+        out = np.zeros(n, dtype=np.int32); ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+        _check(lib().gm_sw_gapless_batch_ix(self.h, n, *wargs, 1 if colour_space else 0, r.ctypes.data_as(C.POINTER(C.c_uint32)), r.shape[1], ip(rl), ip(gi), ip(ri), ip(ib),
+                                            int(is_rna), ip(out)), "gm_sw_gapless_batch_ix")
+        return out
+
+    def _full_finish(self, colour, recs, ops_p, ops_len, keep, r, rl, initbp, is_rna):
+        ops = np.ctypeslib.as_array(C.cast(ops_p, C.POINTER(C.c_uint8)), shape=(ops_len.value,)).copy() if ops_len.value else np.zeros(0, dtype=np.uint8)
+        lib().gm_free(ops_p)
+        c, st, go, gn = keep
+        wins = {}
+        def strings(i):      # item i's window fetched from the index (one small call; strings.prefetch() fetches those of all items in one), the record moved onto it
+            w = wins["all"][i] if "all" in wins else self.get_windows(c[i:i + 1], st[i:i + 1], go[i:i + 1], gn[i:i + 1])[0]
+            rna = (colour and self.genome_is_rna()) if is_rna < 0 else bool(is_rna)
+            rec = recs[i].copy(); rec["genome_start"] -= go[i]
+            return sw_full_batch_strings(colour, rec, ops, w, r[i], 0 if initbp is None else int(initbp[i]), rna, rlen=int(rl[i]))
+        def prefetch():
+            ok = recs["status"] == 0                                     # (a refused item may have no window to fetch)
+            if "all" not in wins and ok.any():
+                got = self.get_windows(c[ok], st[ok], go[ok], gn[ok]); full = np.zeros((len(recs), got.shape[1]), dtype=np.uint32); full[ok] = got; wins["all"] = full
+        strings.prefetch = prefetch
+        return recs, ops, strings
+
+    def genome_is_rna(self) -> bool:
+        """gm_index_genome_is_rna: the flag of the last contig, what is_rna = -1 stands for in the _ix entries"""
+        rc = lib().gm_index_genome_is_rna(self.h)
+        if rc < 0: _check(rc, "gm_index_genome_is_rna")
+        return bool(rc)
+
+    def sw_full_ls_batch(self, cn, gen_st, g_off, glen, reads_words, rlen, anchors=None, revcmpl=None, threshscore=None, maxscore=None, local_alignment=False):
+        """gm_sw_full_ls_batch_ix: (records, ops, strings) as the module-level sw_full_ls_batch; genome_start is counted on the strand's contig.  strings(i) fetches
+        item i's window with one gm_index_get_windows call; a caller who wants the strings of many items calls strings.prefetch() first (one call for all windows)."""
+        n, wargs, keep = self._win(cn, gen_st, g_off, glen)
+        r = self._reads(reads_words, n); rl = np.ascontiguousarray(rlen, dtype=np.int32)
+        th = np.ascontiguousarray(threshscore if threshscore is not None else np.zeros(n), dtype=np.int32)
+        mx = None if maxscore is None else np.ascontiguousarray(maxscore, dtype=np.int32)
+        rv = None if revcmpl is None else np.ascontiguousarray(revcmpl, dtype=np.uint8)
+        an = None if anchors is None else _anchor_array(anchors, n)
+        recs = np.zeros(n, dtype=SW_FULL_REC_DTYPE); ops_p = C.c_void_p(); ops_len = C.c_uint64(0)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int)); dp = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        _check(lib().gm_sw_full_ls_batch_ix(self.h, n, *wargs, r.ctypes.data_as(C.POINTER(C.c_uint32)), r.shape[1], ip(rl), dp(an), dp(rv), ip(th), dp(mx),
+                                            1 if local_alignment else 0, dp(recs), C.byref(ops_p), C.byref(ops_len)), "gm_sw_full_ls_batch_ix")
+        return self._full_finish(False, recs, ops_p, ops_len, keep, r, rl, None, 0)
+
+    def sw_full_cs_batch(self, cn, gen_st, g_off, glen, reads_words, rlen, initbp, anchors, revcmpl=None, threshscore=None, xover=None, is_rna=-1, local_alignment=False):
+        """gm_sw_full_cs_batch_ix: (records, ops, strings) as the module-level sw_full_cs_batch"""
+        n, wargs, keep = self._win(cn, gen_st, g_off, glen)
+        r = self._reads(reads_words, n); rl = np.ascontiguousarray(rlen, dtype=np.int32)
+        ib = np.ascontiguousarray(initbp, dtype=np.uint8)
+        th = np.ascontiguousarray(threshscore if threshscore is not None else np.zeros(n), dtype=np.int32)
+        rv = None if revcmpl is None else np.ascontiguousarray(revcmpl, dtype=np.uint8)
+        an = _anchor_array(anchors, n)
+        xs = None if xover is None else np.ascontiguousarray(xover, dtype=np.int32)
+        if xs is not None and (xs.ndim != 2 or xs.shape[0] != n): raise GmError("sw_full_cs_batch: xover is (n, row length)")
+        recs = np.zeros(n, dtype=SW_FULL_REC_DTYPE); ops_p = C.c_void_p(); ops_len = C.c_uint64(0)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int)); dp = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        _check(lib().gm_sw_full_cs_batch_ix(self.h, n, *wargs, r.ctypes.data_as(C.POINTER(C.c_uint32)), r.shape[1], ip(rl), dp(ib), dp(an), dp(rv), ip(th), dp(xs),
+                                            0 if xs is None else xs.shape[1], int(is_rna), 1 if local_alignment else 0, dp(recs), C.byref(ops_p), C.byref(ops_len)),
+               "gm_sw_full_cs_batch_ix")
+        return self._full_finish(True, recs, ops_p, ops_len, keep, r, rl, ib, int(is_rna))
+
+    def post_sw_batch(self, cn, gen_st, recs, ops, reads_words, rlen, initbp, quals=None, is_rna=-1):
+        """gm_post_sw_batch_ix: (post, qralign, qual) as the module-level post_sw_batch, on the records of Index.sw_full_cs_batch"""
+        n, wargs, keep = self._win(cn, gen_st)
+        rc_ = np.ascontiguousarray(recs, dtype=SW_FULL_REC_DTYPE); o = np.ascontiguousarray(ops, dtype=np.uint8)
+        r = self._reads(reads_words, n)
+        rl = np.ascontiguousarray(rlen, dtype=np.int32); ib = np.ascontiguousarray(initbp, dtype=np.uint8)
+        if rc_.shape[0] != n or rl.shape[0] != n or ib.shape[0] != n or (quals is not None and len(quals) != n): raise GmError("post_sw_batch: every per-item array has n entries")
+        qp = None if quals is None else (C.c_char_p * max(n, 1))(*[None if q is None else (q if isinstance(q, bytes) else q.encode()) for q in quals])
+        post = np.zeros(n, dtype=POST_REC_DTYPE); qa_p, qo_p, qo_len = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        dp = lambda a: None if a.size == 0 else a.ctypes.data
+        _check(lib().gm_post_sw_batch_ix(self.h, n, *wargs, dp(rc_), dp(o), o.size, r.ctypes.data_as(C.POINTER(C.c_uint32)), r.shape[1], rl.ctypes.data_as(C.POINTER(C.c_int)),
+                                         dp(ib), qp, int(is_rna), dp(post), C.byref(qa_p), C.byref(qo_p), C.byref(qo_len)), "gm_post_sw_batch_ix")
+        qa = C.string_at(qa_p.value, o.size) if qa_p.value else b""
+        qo = C.string_at(qo_p.value, qo_len.value) if qo_p.value else b""
+        lib().gm_free(qa_p); lib().gm_free(qo_p)
+        def qralign(i):
+            return qa[int(rc_[i]["ops_off"]):int(rc_[i]["ops_off"]) + int(rc_[i]["n_ops"])].decode() if post[i]["status"] == 0 and rc_[i]["score"] > 0 else None
+        def qual(i):
+            return qo[int(post[i]["qual_off"]):int(post[i]["qual_off"]) + int(post[i]["qual_len"])].decode()
+        return post, qralign, qual
 
     def close(self):
         if getattr(self, "h", None):
@@ -611,12 +763,19 @@ class Session:
         self.stats = st.as_dict()
         return out
 
-    def tophits(self, reads_codes: np.ndarray) -> np.ndarray:
+    def tophits(self, reads_codes: np.ndarray, initbp=None) -> np.ndarray:
+        """initbp (colour space): the reads' primer letters, one per row of colours (gm_debug_tophits_cs)"""
         from .synth import pack_reads
         reads_codes = np.ascontiguousarray(reads_codes, dtype=np.uint8)
         n, Lr = reads_codes.shape
         packed = np.ascontiguousarray(pack_reads(reads_codes))
         rows = np.zeros((n * 30, 12), dtype=np.int64); nr = C.c_long()
+        if initbp is not None:
+            ib = np.ascontiguousarray(initbp, dtype=np.uint8)
+            if ib.shape != (n,): raise GmError("tophits: one primer letter per read")
+            _check(lib().gm_debug_tophits_cs(self.h, n, Lr, packed.ctypes.data_as(C.POINTER(C.c_uint32)), ib.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             rows.ctypes.data_as(C.POINTER(C.c_longlong)), n * 30, C.byref(nr)), "gm_debug_tophits_cs")
+            return rows[:nr.value]
         _check(lib().gm_debug_tophits(self.h, n, Lr, packed.ctypes.data_as(C.POINTER(C.c_uint32)),
                                       rows.ctypes.data_as(C.POINTER(C.c_longlong)), n * 30, C.byref(nr)), "gm_debug_tophits")
         return rows[:nr.value]
