@@ -360,6 +360,46 @@ int gm_post_sw_batch(int n, const gm_sw_full_rec_t *recs, const uint8_t *ops, ui
 int gm_post_sw_batch_last_plan(int launch, int *items, int *threads, int *columns);   /* diagnostic, see above */
 
 /* ---------------------------------------------------------------------------------------------
+ * The text of a batch's alignments: dbalign / qralign, the CIGAR and the edit string of every record of ONE gm_sw_full_ls_batch / gm_sw_full_cs_batch call, made on
+ * the device in one call (one wave an alignment).  What hit_output needs of an alignment then comes from one more call a chunk instead of a host loop an item.
+ * Input: recs / ops / ops_len as the batch call returned them and the arrays it was given (colour space: the shared LETTER-space bitfield, the colour reads, initbp).
+ *   what        GM_TEXT_* bits, at least one; outputs of a kind not asked for may be NULL and are left alone
+ *   qralign_in  NULL, or gm_post_sw_batch's qralign_out for these records (ops_len bytes): item i's slice of it stands in place of the qralign rebuilt from the
+ *               operations (post_sw re-calls letters and moves no gap; a slice whose gaps are not the operations' is refused).  reads / initbp are then not read.
+ *   reverse     NULL (none) or n flags: item i is printed as a mapping to the reverse strand
+ *   clip_char   'S' or 'H'
+ * Output, every buffer released with gm_free:
+ *   GM_TEXT_ALIGN  *dbalign_out / *qralign_out, ops_len bytes each: item i's strings at the place of its operations, [recs[i].ops_off, + n_ops), no NUL -- the layout
+ *                  of gm_post_sw_batch's qralign_out -- byte for byte what gm_sw_full_batch_strings returns (colour space: the four letter translations, lower case on
+ *                  a crossover, the genome's letter for an unknown read letter); bytes outside every item's slice are 0.  Never reversed.
+ *   GM_TEXT_CIGAR  *cigar_out with cigar_off[n + 1]: item i's CIGAR at [cigar_off[i], cigar_off[i + 1]), tight, no separators -- make_cigar (ref: gmapper/output.c:15-64)
+ *                  on those strings: runs of columns, a gap in qralign 'D', a gap in dbalign 'I', anything else 'M', as <decimal length><op>; a leading clip of
+ *                  recs[i].read_start and a trailing clip of rlen[i] - read_start - (read positions in the alignment), each only when > 0, with clip_char.
+ *                  reverse[i]: the runs in reverse order (reverse_cigar, ref: :67-80).
+ *   GM_TEXT_EDIT   *edit_out with edit_off[n + 1], likewise: alignment_edit_string (ref: common/output.c:60-121; the ZE:Z tag) on the item's final dbalign / qralign;
+ *                  reverse[i]: passed through reverse_alignment_edit_string (ref: gmapper/output.c:83-122) -- digit runs whole, parentheses swapped, A C G T
+ *                  complemented, any other character unchanged.
+ * Items: status[i] = recs[i].status where that is < 0, and 0 for score <= 0, both with empty slices.  A record that does not lie inside what the caller holds -- the
+ * checks of gm_sw_full_batch_strings -- or whose initbp is > 3 is refused on the host with status[i] = GM_E_ARG before anything is uploaded; the reason of the last
+ * one is in gm_last_error(), its neighbours are answered.  A missing required argument, what == 0 or bits beyond 7: the call fails with GM_E_ARG.  n <= 0: GM_OK,
+ * nothing is written.  No setup state is needed and no score is read.
+ * Cost: a fixed number of device allocations, copies and launches whatever n is -- a sizing launch, one copy of the n lengths whose exclusive scan on the host gives the
+ * offsets, a writing launch.  The genome bitfield is uploaded once a call, as by the twins.
+ * ------------------------------------------------------------------------------------------- */
+#define GM_TEXT_ALIGN 1   /* dbalign + qralign */
+#define GM_TEXT_CIGAR 2
+#define GM_TEXT_EDIT  4
+int gm_sw_full_batch_text(int colour_space, int what, int n,
+                          const gm_sw_full_rec_t *recs, const uint8_t *ops, uint64_t ops_len,
+                          const uint32_t *genome, uint64_t genome_words,
+                          const uint32_t *reads, int read_words, const int *rlen, const uint8_t *initbp, int is_rna,
+                          const char *qralign_in, const uint8_t *reverse, int clip_char,
+                          int *status,
+                          char **dbalign_out, char **qralign_out,
+                          char **cigar_out, uint64_t *cigar_off,
+                          char **edit_out, uint64_t *edit_off);
+
+/* ---------------------------------------------------------------------------------------------
  * S1 - S3, batch forms on the resident index: the entries above with (genome, genome_words, g_off) replaced by (ix, cn[], gen_st[], g_off[]).  The kernels read
  * the genome the index already holds on its device; no genome byte crosses the bus.  A window is addressed as the reference's call sites hold it (mapping.c:353-361,
  * 1306-1319):
@@ -411,6 +451,18 @@ int gm_sw_full_cs_batch_ix(const gm_index_t *ix, int n, const int *cn, const uin
 int gm_post_sw_batch_ix(const gm_index_t *ix, int n, const int *cn, const uint8_t *gen_st, const gm_sw_full_rec_t *recs, const uint8_t *ops, uint64_t ops_len,
                           const uint32_t *reads, int read_words, const int *rlen, const uint8_t *initbp, const char *const *quals, int is_rna,
                           gm_post_rec_t *post, char **qralign_out, char **quals_out, uint64_t *quals_len);
+/* gm_sw_full_batch_text on the records of ONE gm_sw_full_*_batch_ix call with the cn / gen_st it was given (genome_start counted on the strand's contig): the genome
+ * letters come from the resident forward arrays (strand 1 backwards and complemented, an RNA contig with U for A), so a caller without a host genome gets its strings,
+ * CIGARs and edit strings without fetching a window.  It reads letters only and works on either kind of index; the contig and strand of a record are checked as
+ * gm_post_sw_batch_ix checks them (per item); nothing sized by the genome is uploaded. */
+int gm_sw_full_batch_text_ix(const gm_index_t *ix, int colour_space, int what, int n, const int *cn, const uint8_t *gen_st,
+                          const gm_sw_full_rec_t *recs, const uint8_t *ops, uint64_t ops_len,
+                          const uint32_t *reads, int read_words, const int *rlen, const uint8_t *initbp, int is_rna,
+                          const char *qralign_in, const uint8_t *reverse, int clip_char,
+                          int *status,
+                          char **dbalign_out, char **qralign_out,
+                          char **cigar_out, uint64_t *cigar_off,
+                          char **edit_out, uint64_t *edit_off);
 
 /* ---------------------------------------------------------------------------------------------
  * S4: the per-read pipeline.  Replaces handle_read() for unpaired letter-space reads

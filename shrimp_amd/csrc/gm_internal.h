@@ -252,3 +252,16 @@ int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, co
 int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
                                int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
                                uint8_t* d_ops, int local, hipStream_t stream, int ix = 0);      // ix: the items carry strand / RNA bits (gm_sw_full_cs_batch_ix)
+
+// Text of the alignments of an S2 batch call (gm_sw_full_batch_text[_ix], k_sw_text in gm_text.hip): one accepted record.  The host has checked it (swf_rec_check):
+// ops[ops_off .. + n_ops), the genome positions from genome_start and the read positions read_start .. of read `idx` lie inside what was uploaded; tail = the read
+// positions behind the alignment (the trailing clip).  gbase: as GmPostItem's; flags: 1 = strand 1 of a contig, 2 = its contig is RNA (both 0 on caller
+// bitfields), 4 = the item is printed as a reverse-strand mapping (CIGAR runs reversed, edit string through reverse_alignment_edit_string).
+struct GmTextItem { unsigned long long ops_off; long long genome_start, gbase; uint32_t n_ops; int read_start, tail, initbp, idx, flags; };
+#define GM_TEXT_MAX_GRID 16384      // waves of one launch (grid-stride over the items): 64 a CU
+// write = 0: the sizing launch -- d_lens[2 k] / [2 k + 1] = bytes of item k's CIGAR / edit string; write = 1: the bytes, at d_offs[2 k] / [2 k + 1] of d_cigar / d_edit
+// (d_lens as the sizing launch left it), dbalign / qralign at the place of the operations in d_db / d_qr.  what: GM_TEXT_* bits; buffers of kinds not asked for may be
+// null, d_genome / d_reads too when neither strings nor the edit string are; d_qin: null, or the qralign to use in place of the one rebuilt from the operations.
+int gm_launch_sw_text(int n_items, const GmTextItem* d_items, int colour, int what, int write, const uint8_t* d_ops, const uint32_t* d_genome, const uint32_t* d_reads,
+                      int read_words, int is_rna, const uint8_t* d_qin, int clip_char, uint32_t* d_lens, const unsigned long long* d_offs, uint8_t* d_db, uint8_t* d_qr,
+                      uint8_t* d_cigar, uint8_t* d_edit, hipStream_t stream, int ix = 0);      // ix: the items carry gbase / flags (gm_sw_full_batch_text_ix)

@@ -132,7 +132,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_sw_full_ls_batch", "gm_sw_full_cs_batch", "gm_sw_full_batch_strings",
            "post_sw_setup", "post_sw", "post_sw_cleanup", "post_sw_stats", "gm_post_sw_batch", "gm_post_sw_batch_last_plan",
            "gm_index_genome_is_rna", "gm_index_get_windows", "gm_sw_vector_batch_ix", "gm_sw_vector_batch_bounded_ix", "gm_sw_gapless_batch_ix", "gm_sw_full_ls_batch_ix", "gm_sw_full_cs_batch_ix",
-           "gm_post_sw_batch_ix",
+           "gm_post_sw_batch_ix", "gm_sw_full_batch_text", "gm_sw_full_batch_text_ix",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits", "gm_debug_tophits_cs",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
@@ -207,6 +207,10 @@ def lib():
     L.gm_sw_full_ls_batch_ix.argtypes = win + [u32p, C.c_int, ipt, vp, vp, ipt, vp, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.gm_sw_full_cs_batch_ix.argtypes = win + [u32p, C.c_int, ipt, vp, vp, vp, ipt, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.gm_post_sw_batch_ix.argtypes = [vp, C.c_int, ipt, u8p, vp, vp, C.c_uint64, u32p, C.c_int, ipt, vp, vp, C.c_int, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
+    text = [vp, vp, C.c_uint64]                                                              # recs, ops, ops_len
+    text_tail = [u32p, C.c_int, ipt, vp, C.c_int, vp, vp, C.c_int, ipt, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.gm_sw_full_batch_text.argtypes = [C.c_int, C.c_int, C.c_int] + text + [u32p, C.c_uint64] + text_tail
+    L.gm_sw_full_batch_text_ix.argtypes = [vp, C.c_int, C.c_int, C.c_int, ipt, u8p] + text + text_tail
     L.gm_abi_sizeof.argtypes = [C.c_int]; L.gm_abi_sizeof.restype = C.c_int
     L.gm_session_create.argtypes = [C.POINTER(vp), vp, C.POINTER(Params), C.c_int]
     L.gm_session_free.argtypes = [vp]
@@ -510,6 +514,15 @@ class Index:
         def qual(i):
             return qo[int(post[i]["qual_off"]):int(post[i]["qual_off"]) + int(post[i]["qual_len"])].decode()
         return post, qralign, qual
+
+    def sw_full_batch_text(self, cn, gen_st, recs, ops, reads_words, rlen, initbp=None, is_rna=-1, qralign=None, reverse=None, clip="S", what=("align", "cigar", "edit"),
+                           colour_space=None):
+        """gm_sw_full_batch_text_ix: (status, dbalign, qralign, cigar, edit) as the module-level sw_full_batch_text, on the records of Index.sw_full_ls_batch /
+        sw_full_cs_batch with the cn / gen_st they were given.  colour_space: default -- colour space iff initbp is given."""
+        n, wargs, keep = self._win(cn, gen_st)
+        colour = (initbp is not None) if colour_space is None else bool(colour_space)
+        return _batch_text(lambda *a: lib().gm_sw_full_batch_text_ix(self.h, *a[:3], *wargs, *a[3:]), "gm_sw_full_batch_text_ix", colour, n, recs, ops, [],
+                           reads_words, rlen, initbp, int(is_rna), qralign, reverse, clip, what)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1048,6 +1061,60 @@ def post_sw_batch(recs, ops, genome_ls, reads_words, rlen, initbp, quals=None, i
     def qual(i):
         return qo[int(post[i]["qual_off"]):int(post[i]["qual_off"]) + int(post[i]["qual_len"])].decode()
     return post, qralign, qual
+
+
+TEXT_KINDS = {"align": 1, "cigar": 2, "edit": 4}      # GM_TEXT_ALIGN / GM_TEXT_CIGAR / GM_TEXT_EDIT
+
+
+def _batch_text(call, name, colour, n, recs, ops, genome_args, reads_words, rlen, initbp, is_rna, qralign, reverse, clip, what):
+    rc_ = np.ascontiguousarray(recs, dtype=SW_FULL_REC_DTYPE); o = np.ascontiguousarray(ops, dtype=np.uint8)
+    bits = 0
+    for k in ([what] if isinstance(what, str) else what): bits |= TEXT_KINDS[k]
+    r = None if reads_words is None else np.ascontiguousarray(reads_words, dtype=np.uint32)
+    if r is not None and (r.ndim != 2 or r.shape[0] != n): raise GmError("sw_full_batch_text: reads_words is (n, read_words)")
+    rl = np.ascontiguousarray(rlen, dtype=np.int32)
+    ib = None if initbp is None else np.ascontiguousarray(initbp, dtype=np.uint8)
+    rv = None if reverse is None else np.ascontiguousarray(reverse, dtype=np.uint8)
+    if rc_.shape[0] != n or any(a is not None and a.shape[0] != n for a in (rl, ib, rv)): raise GmError("sw_full_batch_text: every per-item array has n entries")
+    qin = None
+    if qralign is not None:
+        qin = bytes(qralign)
+        if len(qin) != o.size: raise GmError("sw_full_batch_text: qralign holds ops_len bytes (post_sw_batch's buffer)")
+    status = np.zeros(n, dtype=np.int32)
+    db_p, qr_p, cg_p, ed_p = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    coff = np.zeros(n + 1, dtype=np.uint64); eoff = np.zeros(n + 1, dtype=np.uint64)
+    dp = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    u64p = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+    _check(call(1 if colour else 0, bits, n, dp(rc_), dp(o), o.size, *genome_args, None if r is None else r.ctypes.data_as(C.POINTER(C.c_uint32)), 1 if r is None else r.shape[1],
+                rl.ctypes.data_as(C.POINTER(C.c_int)), dp(ib), is_rna, qin, dp(rv), ord(clip), status.ctypes.data_as(C.POINTER(C.c_int)),
+                C.byref(db_p), C.byref(qr_p), C.byref(cg_p), u64p(coff), C.byref(ed_p), u64p(eoff)), name)
+    def take(p, size):
+        b = C.string_at(p.value, size) if p.value and size else b""
+        lib().gm_free(p)
+        return b
+    db, qr = take(db_p, o.size), take(qr_p, o.size)
+    cg, ed = take(cg_p, int(coff[n])), take(ed_p, int(eoff[n]))
+    answered = lambda i: status[i] == 0 and rc_[i]["score"] > 0
+    def by_ops(buf): return lambda i: buf[int(rc_[i]["ops_off"]):int(rc_[i]["ops_off"]) + int(rc_[i]["n_ops"])] if answered(i) else b""
+    def by_off(buf, off): return lambda i: buf[int(off[i]):int(off[i + 1])]
+    fd, fq = (by_ops(db), by_ops(qr)) if bits & 1 else (None, None)
+    fc = by_off(cg, coff) if bits & 2 else None
+    fe = by_off(ed, eoff) if bits & 4 else None
+    for f, buf, off in ((fd, db, None), (fq, qr, None), (fc, cg, coff), (fe, ed, eoff)):
+        if f is not None: f.buffer = buf; f.offsets = off                      # the whole buffer and (CIGAR, edit string) its n + 1 offsets
+    return status, fd, fq, fc, fe
+
+
+def sw_full_batch_text(colour_space, recs, ops, genome_words, reads_words, rlen, initbp=None, is_rna=False, qralign=None, reverse=None, clip="S", what=("align", "cigar", "edit")):
+    """gm_sw_full_batch_text: the text of every record of one sw_full_ls_batch / sw_full_cs_batch call (recs, ops as it returned them; genome_words, reads_words, rlen,
+    initbp, is_rna as it was given them) in one call.  qralign: None or post_sw_batch's whole qralign buffer (ops.size bytes), used in place of the rebuilt one;
+    reverse: None or n flags (the item is printed as a reverse-strand mapping); clip: "S" or "H"; what: kinds out of "align", "cigar", "edit".
+    Returns (status, dbalign, qralign, cigar, edit): status is an int32 array (< 0: the item was refused, reason: gm_last_error), the others are i -> bytes for the
+    kinds asked for (empty for an item without alignment) and None otherwise; each carries the whole buffer as .buffer and, CIGAR and edit string, .offsets."""
+    g = np.ascontiguousarray(genome_words, dtype=np.uint32)
+    n = np.asarray(recs).shape[0]
+    return _batch_text(lib().gm_sw_full_batch_text, "gm_sw_full_batch_text", colour_space, n, recs, ops, [g.ctypes.data_as(C.POINTER(C.c_uint32)), g.size],
+                       reads_words, rlen, initbp, 1 if is_rna else 0, qralign, reverse, clip, what)
 
 
 def post_sw_batch_last_plan():
