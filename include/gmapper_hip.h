@@ -643,6 +643,42 @@ int gm_debug_tophits(gm_session_t *s, int n_reads, int read_len, const uint32_t 
 int gm_debug_tophits_cs(gm_session_t *s, int n_reads, int n_colours, const uint32_t *colours_packed, const uint8_t *initbp,
                         long long *rows, long cap, long *n_rows);
 
+/* The candidate windows of a read batch: every window read_get_hit_list_per_strand (ref: mapping.c:1025-1229) yields for each read on each strand, as the list stands
+ * before pass 1 touches it -- seed lookup, region counts, anchor merge and collapse, window generation on the device, under the session's parameters
+ * (seeds, -H, list cutoff, match_mode 1 / 2, region bits / overlap, window length, window-generation threshold, -F / -C, -U).  This is the front of a pipeline a
+ * caller composes from the gm_*_ix seams: nothing else of it has to run on the CPU.
+ *   Windows of read r, strand st: wins[off[2 r + st] .. off[2 r + st + 1]), in the reference's list order, ascending (cn, g_off).  Windows of one read-strand with
+ *   equal (cn, g_off) come in no particular order (the reference keeps those in anchor order; pass 1 cannot tell them apart).
+ *   off: 2 * n_reads + 1 entries, the caller's.  *wins: one buffer of *n_wins records, released with gm_free; NULL when *n_wins == 0.
+ *   Letter space: initbp must be NULL.  Colour space: read_len is the number of colours and initbp (one primer letter code 0..3 per read) is required; the argument
+ *   checks are those of gm_map_reads / gm_map_reads_cs (GM_E_ARG, GM_E_RANGE).  n_reads <= 0: GM_OK, off[0] = 0, *wins = NULL.
+ *   n_reads may exceed the session's sub-batch size: the sub-batches run one after the other and their windows are appended.  The call takes its turn on the device
+ *   like a mapping call and leaves the session ready for any other call.
+ *   stats (or NULL): reads, lookups, list_entries, list_bytes, survivors, anchors, windows (== *n_wins), survivors_pruned, exact_order_reads, retries, ms_lookup,
+ *   ms_anchors; every other field 0.
+ *   Unpaired sessions only: a session has no pair mode of its own (pairing is an argument of gm_map_pairs*), so there is no paired form of this call, and the
+ *   mate-pair region counts of the paired option sets (-p) never apply here.
+ * How a window feeds the _ix seams (cn, gen_st, g_off, glen), with contig_len the length of contig cn:
+ *   read strand 0: (cn, 0, g_off, w_len) with the read as given;
+ *   read strand 1: (cn, 1, contig_len - g_off - w_len, w_len) with the read as given -- what reverse_hit (ref: mapping.c:254-263) makes of the hit, and what the
+ *                  reference scores for ZV and, in colour space, in pass 1.  In letter space the window may equally be taken as (cn, 0, g_off, w_len) with the
+ *                  reverse complement of the read (the reference's pass 1).
+ *   The anchor box is relative to the window as the list holds it (before reverse_hit): a caller that turns a hit onto strand 1 of the contig reverses the box
+ *   itself, as anchor_reverse (ref: anchors.h:30-34) does. */
+typedef struct gm_read_window {      /* 12 x 32 bits = 48 bytes, no padding */
+  int32_t  read;                     /* index of the read in this call */
+  int32_t  st;                       /* read strand: 0 the read as given, 1 its reverse complement (read_hit.st) */
+  int32_t  cn;
+  uint32_t g_off;                    /* window start on the FORWARD contig (g_off_pos_strand; == g_off before reverse_hit) */
+  int32_t  w_len;
+  int32_t  score_window_gen, matches;
+  int32_t  ax, ay, alen, awidth;     /* anchor box relative to the window, as read_get_hit_list_per_strand leaves it (before reverse_hit) */
+  int32_t  reserved;                 /* 0 */
+} gm_read_window_t;
+int gm_read_window_size(void);       /* sizeof(gm_read_window_t), for the Python mirror */
+int gm_read_windows(gm_session_t *s, int n_reads, int read_len, const uint32_t *reads_packed, const uint8_t *initbp,
+                    gm_read_window_t **wins, uint64_t *n_wins, uint64_t *off, gm_map_stats_t *stats);
+
 /* time of the dominant kernel (seed lookup) during the last gm_map_* call, from HIP events on the
  * session's own stream, and the algorithmic bytes it moved */
 int gm_last_lookup_timing(gm_session_t *s, double *ms, uint64_t *alg_bytes, int *launches);

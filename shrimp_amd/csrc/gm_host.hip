@@ -2043,6 +2043,8 @@ extern "C" int gm_debug_tophits_cs(gm_session_t* s, int n_reads, int n_colours, 
   return debug_tophits_impl(s, n_reads, n_colours, colours_packed, initbp, rows, cap, n_rows);
 }
 
+#include "gm_host_windows.inc"
+
 // ---- S1: vector SW on caller bitfields ----------------------------------------------------------
 struct SwVecState { bool init = false, colours = false; GmScoreDev sc; int dblen = 0, qrlen = 0; uint64_t invocs = 0, cells = 0; double secs = 0; };
 static thread_local SwVecState g_sv;

@@ -138,6 +138,12 @@ int gm_launch_anchors_heavy(const GmIndexDev& ix, const GmScoreDev& sc, int n_re
                             uint64_t* d_keys_in, uint64_t* d_keys_sorted, uint32_t* d_aux, uint32_t* d_nxt, uint32_t* d_ord,
                             GmHit* d_hits, uint16_t* d_perm, uint32_t* d_hit_cnt, int hcap, unsigned long long* d_stats, hipStream_t stream);
 
+// Export of K2's windows (gm_read_windows, gm_windows.hip).  gm_launch_win_scan: d_off[0 .. n_rs] = exclusive scan of min(d_hit_cnt[rs], hcap), d_off[n_rs] = their
+// sum (one launch).  gm_launch_win_scatter: window j of the `total` = d_off[n_rs] windows, read through d_perm, becomes d_out[j] with read = read_base + rs / 2.
+int gm_launch_win_scan(const uint32_t* d_hit_cnt, int n_rs, int hcap, unsigned long long* d_off, hipStream_t stream);
+int gm_launch_win_scatter(const GmHit* d_hits, const uint16_t* d_perm, const unsigned long long* d_off, int n_rs, int hcap, unsigned long long total, int read_base,
+                          gm_read_window_t* d_out, hipStream_t stream);
+
 // K3 pass 1 (vector SW + overlap rule), one wave per read-strand
 int gm_launch_pass1(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                     int window_len, int window_overlap_abs, GmHit* d_hits, const uint16_t* d_perm, const uint32_t* d_hit_cnt, int hcap,

@@ -117,9 +117,15 @@ class PostRec(C.Structure):         # gm_post_rec_t: one answer of gm_post_sw_ba
                 ("qual_len", C.c_uint32), ("qual_off", C.c_uint64)]
 
 
+class ReadWindow(C.Structure):      # gm_read_window_t: one candidate window of gm_read_windows (checked against gm_read_window_size())
+    _fields_ = [("read", C.c_int32), ("st", C.c_int32), ("cn", C.c_int32), ("g_off", C.c_uint32), ("w_len", C.c_int32), ("score_window_gen", C.c_int32), ("matches", C.c_int32),
+                ("ax", C.c_int32), ("ay", C.c_int32), ("alen", C.c_int32), ("awidth", C.c_int32), ("reserved", C.c_int32)]
+
+
 SW_FULL_REC_DTYPE = np.dtype(SwFullRec)      # the structured numpy view of an array of them
 POST_REC_DTYPE = np.dtype(PostRec)
 ANCHOR_DTYPE = np.dtype(Anchor)
+READ_WINDOW_DTYPE = np.dtype(ReadWindow)
 
 
 # every entry point include/gmapper_hip.h declares
@@ -134,6 +140,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_index_genome_is_rna", "gm_index_get_windows", "gm_sw_vector_batch_ix", "gm_sw_vector_batch_bounded_ix", "gm_sw_gapless_batch_ix", "gm_sw_full_ls_batch_ix", "gm_sw_full_cs_batch_ix",
            "gm_post_sw_batch_ix", "gm_sw_full_batch_text", "gm_sw_full_batch_text_ix",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits", "gm_debug_tophits_cs",
+           "gm_read_windows", "gm_read_window_size",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
 
@@ -236,6 +243,10 @@ def lib():
     L.gm_debug_tophits.argtypes = [vp, C.c_int, C.c_int, u32p, C.POINTER(C.c_longlong), C.c_long, C.POINTER(C.c_long)]
     L.gm_debug_tophits_cs.argtypes = [vp, C.c_int, C.c_int, u32p, C.POINTER(C.c_uint8), C.POINTER(C.c_longlong), C.c_long, C.POINTER(C.c_long)]
     L.gm_last_lookup_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.gm_read_window_size.argtypes = []; L.gm_read_window_size.restype = C.c_int
+    L.gm_read_windows.argtypes = [vp, C.c_int, C.c_int, u32p, u8p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MapStats)]
+    if L.gm_read_window_size() != READ_WINDOW_DTYPE.itemsize:
+        raise GmError("gm_read_window_t is %d bytes in the library, %d in READ_WINDOW_DTYPE" % (L.gm_read_window_size(), READ_WINDOW_DTYPE.itemsize))
     _lib = L
     return L
 
@@ -792,6 +803,30 @@ class Session:
         _check(lib().gm_debug_tophits(self.h, n, Lr, packed.ctypes.data_as(C.POINTER(C.c_uint32)),
                                       rows.ctypes.data_as(C.POINTER(C.c_longlong)), n * 30, C.byref(nr)), "gm_debug_tophits")
         return rows[:nr.value]
+
+    def read_windows(self, reads_codes: np.ndarray, initbp=None):
+        """The candidate windows of every read on both strands, before pass 1 (gm_read_windows): -> (wins, off).  wins: structured array of READ_WINDOW_DTYPE;
+        off: uint64[2 n + 1], the windows of read r on strand st are wins[off[2 r + st]:off[2 r + st + 1]], ascending (cn, g_off).  As an `_ix` window: strand 0 is
+        (cn, 0, g_off, w_len), strand 1 is (cn, 1, Index.strand_offset(contig_len, g_off, w_len), w_len), both with the read as given.
+        initbp (colour space): the reads' primer letters, one per row of colours.  The stage counters of the call are left in self.stats."""
+        from .synth import pack_reads
+        reads_codes = np.ascontiguousarray(reads_codes, dtype=np.uint8)
+        if reads_codes.ndim != 2: raise GmError("read_windows: reads_codes is [n, L]")
+        n, Lr = reads_codes.shape
+        packed = np.ascontiguousarray(pack_reads(reads_codes), dtype=np.uint32) if n else np.zeros(1, dtype=np.uint32)
+        ib = None
+        if initbp is not None:
+            ib = np.ascontiguousarray(initbp, dtype=np.uint8)
+            if ib.shape != (n,): raise GmError("read_windows: one primer letter per read")
+        L = lib(); out = C.c_void_p(); nw = C.c_uint64(0); st = MapStats()
+        off = np.zeros(2 * n + 1, dtype=np.uint64)
+        _check(L.gm_read_windows(self.h, n, Lr, packed.ctypes.data_as(C.POINTER(C.c_uint32)), None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                 C.byref(out), C.byref(nw), off.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(st)), "gm_read_windows")
+        wins = np.zeros(nw.value, dtype=READ_WINDOW_DTYPE)
+        if nw.value: C.memmove(wins.ctypes.data, out, nw.value * READ_WINDOW_DTYPE.itemsize)
+        if out.value: L.gm_free(out)
+        self.stats = st.as_dict()
+        return wins, off
 
     def lookup_timing(self):
         ms = C.c_double(); b = C.c_uint64(); n = C.c_int()
