@@ -679,6 +679,81 @@ int gm_read_window_size(void);       /* sizeof(gm_read_window_t), for the Python
 int gm_read_windows(gm_session_t *s, int n_reads, int read_len, const uint32_t *reads_packed, const uint8_t *initbp,
                     gm_read_window_t **wins, uint64_t *n_wins, uint64_t *off, gm_map_stats_t *stats);
 
+/* The two selections of a read batch, so that a chunk is a chain of batch calls on arrays with nothing per read on the CPU in between:
+ *   gm_read_windows -> gm_sw_vector_batch_ix (-U: gm_sw_gapless_batch_ix) -> gm_select_pass1 -> gm_sw_full_ls_batch_ix (colour space: gm_sw_full_cs_batch_ix, then
+ *   gm_post_sw_batch_ix) -> gm_select_pass2 -> gm_sw_full_batch_text_ix.
+ * Both take their rules from the session's gm_params_t, read neither the genome nor the reads, make a fixed number of device allocations, copies and launches whatever
+ * n is, take their turn on the device like gm_read_windows and leave the session ready for any other call.  Unpaired sessions only (see gm_read_windows); the mapping
+ * entries do not use them and print what they printed.
+ *
+ * gm_select_pass1: read_pass1_per_strand's overlap rule and threshold and read_get_vector_hits' ext-heap (ref: mapping.c:1261-1339, 1376-1411, heap.h:226-327; SURVEY
+ * A10 / A13) on the windows of gm_read_windows and their scores.
+ *   wins, n_wins, off[2 n_reads + 1]   exactly as gm_read_windows returned them;  scores[n_wins]: the vector (under -U: gapless) score of each window as pass 1
+ *   takes it -- letter space: (cn, 0, g_off, w_len) against the read, for a strand-1 window against the read's reverse complement (mapping.c:1321-1328); colour space:
+ *   the address the gm_read_windows block gives (strand 1: the reverse-complement contig), against the read as given (:1297-1319).  Scoring a letter-space strand-1
+ *   window on the reverse-complement contig against the read as given is NOT the same call: the vector filter is not mirror-symmetric (2 of the 5 586 windows of
+ *   tests/golden/stress_60bp score 25 points apart), and the reference's top hits are those of the first form;  read_len: the reads' length (colour space: the colours).
+ *   Per read, strand 0 then strand 1, windows in list order: a window with matches < match_mode is passed over; a window on the contig of the last PASSING window of
+ *   its read-strand with g_off + (uint)abs_or_pct(window_overlap, W) <= that window's g_off + W is skipped and counts from then on with score 0 -- W the session's
+ *   (uint16_t)abs_or_pct(window_len, read_len), not the window's clamped w_len; score_max = min(read_len, w_len) * match; pct = (1000 * 100 * score) / score_max; the
+ *   last passing window advances only where score >= (int)abs_or_pct(sw_vect_threshold, score_max).  A window enters the heap when score >= that threshold and
+ *   (fewer than num_tmp_outputs are in it, or its key > the heap's minimum: a strict >); the key is pct, or the score for an absolute threshold.
+ *   Output: *hits, one buffer of *n_hits records (gm_free; NULL when there are none), read r's at [hit_off[r], hit_off[r + 1]) in the heap's ARRAY order, which is the
+ *   input order of pass 2 and of its stable sorts; hit_off: n_reads + 1 entries, the caller's.  A hit of strand 1 has been turned as reverse_hit turns it (gen_st = 1,
+ *   g_off = contig_len - g_off - w_len, the anchor box through anchor_reverse); strand 0 keeps gen_st = 0: (cn, gen_st, g_off, w_len), the box and the read as given
+ *   are what gm_sw_full_ls_batch_ix / gm_sw_full_cs_batch_ix take, nothing is left for the caller to turn.  win: the record's window in wins.
+ *   NOT emulated: the f1 cache (hash_filter_calls).  The seam takes the scores it is given, so the result is the reference's under -Z; with the cache on the two differ
+ *   only where two windows of one read-strand share a cache slot and differ in score.
+ *   Refusals: num_tmp_outputs > 64: GM_E_RANGE (the mapping entries select at most 64 and say nothing; a seam must not); 2^31 windows or more: GM_E_RANGE.  Offsets
+ *   that do not ascend from 0, off[2 n_reads] != n_wins, a window whose read / st contradicts its slot, cn outside the index, w_len < 1, a window that ends beyond
+ *   its contig, read_len < 1: GM_E_ARG, before anything is uploaded.  n_reads <= 0: GM_OK, hit_off[0] = 0, *hits = NULL. */
+typedef struct gm_pass1_hit {        /* 16 x 32 bits = 64 bytes, no padding */
+  int32_t  read, st;                 /* as the window's: st is the READ strand the seeds matched on */
+  int32_t  win;                      /* index of the window in wins */
+  int32_t  cn, gen_st;               /* gen_st = st: the hit lies on strand gen_st of the contig, the read as given */
+  uint32_t g_off;                    /* on strand gen_st of the contig */
+  int32_t  w_len;
+  int32_t  score_vector, pct_score_vector;      /* after the overlap rule: 0 for a skipped window */
+  int32_t  score_max, matches, score_window_gen;
+  int32_t  ax, ay, alen, awidth;     /* the anchor box, on the turned window for strand 1 */
+} gm_pass1_hit_t;
+int gm_pass1_hit_size(void);         /* sizeof(gm_pass1_hit_t), for the Python mirror */
+int gm_select_pass1(gm_session_t *s, int n_reads, int read_len, const gm_read_window_t *wins, uint64_t n_wins, const uint64_t *off, const int *scores,
+                    gm_pass1_hit_t **hits, uint64_t *n_hits, uint64_t *hit_off);
+
+/* gm_select_pass2: read_pass2's selection and compute_unpaired_mqv (ref: mapping.c:1628-1750, read_remove_duplicate_hits :1552-1600, hit_run_post_sw :1609-1625,
+ * output.c:777-793, 975-984) on the records of ONE full batch call over the hits of gm_select_pass1, in that order.
+ *   hit_off[n_reads + 1], hits[n_hits]   as gm_select_pass1 returned them (read, cn, gen_st and score_max are read);  recs[n_hits]: the records of the full call;
+ *   post[n_hits]: colour space with mapping qualities on (neither local_alignment nor no_mapping_qualities): the answers of gm_post_sw_batch(_ix), required; else NULL.
+ *   Per read: score_full = the record's score (a refused record counts as 0); with mapping qualities on and score_full > 0 the posterior (letter space:
+ *   pow(2, (score - rmapped (2 alpha + beta)) / alpha); colour space: post's) and score_full = max(0, (int)rint(alpha log(posterior) / log 2 + rmapped (2 alpha +
+ *   beta))); pct = (1000 * 100 * score_full) / score_max; kept where score_full >= abs_or_pct(sw_full_threshold, score_max) as doubles.  Two duplicate removals: a
+ *   stable sort by (cn, gen_st, genome_start), every equal run collapsed to its FIRST maximum key (pct, or score_full for an absolute threshold), then the same by
+ *   (cn, gen_st, -genome_start - rmapped + deletions - insertions).  A stable sort by descending key, the cut to num_outputs, strata (the leading run of equal
+ *   score_full), max_alignments (more than that many leaves none).  With mapping qualities on: z1 = the sum of the posteriors, z0 = the posterior, mqv =
+ *   qv_from_pr_corr(z0 / z1) and 0 below 4, single_best_mapping keeps the first mapping of the highest mqv; otherwise mqv = 255 and posterior = z0 = z1 = 0.
+ *   The doubles go through the host's libm, as in the mapping entries (the same functions); the sorts and removals run on the device, a wave a read.
+ *   Output: *maps, one buffer of *n_maps records (gm_free; NULL when there are none), read r's at [map_off[r], map_off[r + 1]) in the reference's output order;
+ *   map_off: n_reads + 1 entries, the caller's.  hit: the mapping's index in hits / recs; score_full is the SAM AS, mqv the MAPQ, z0 / z1 the Z0 / Z1 tags' values.
+ *   flags bit 0, the rounding guard: the mapping is a colour-space one whose post[hit].by_host == 0 (a device posterior, exact to 1e-9 relative but not to the bit),
+ *   and a value that this read's AS, MAPQ, Z0 or Z1 is rounded from lies within 1e-7 of its rounding boundary.  Recipe: redo the posterior of every hit of such a
+ *   read with the single post_sw seam, put the values into a copy of post with by_host = 1, and call again for those reads; the mapping entries do the same inside.
+ *   (A read none of whose hits comes out has no record to carry the bit; its device posteriors decided nothing that is printed.)
+ *   Refusals (GM_E_ARG, before anything is uploaded): offsets that do not ascend from 0, more than 64 hits of one read, a hit whose read is not its slot's, cn
+ *   outside the index, gen_st > 1, score_max < 1, post missing where it is required.  n_reads <= 0: GM_OK, map_off[0] = 0, *maps = NULL. */
+typedef struct gm_mapping {          /* 6 x 32 bits + 3 doubles = 48 bytes, no padding */
+  int32_t  read;
+  int32_t  hit;                      /* index into hits / recs */
+  int32_t  score_full;               /* AS */
+  int32_t  pct_score_full;
+  int32_t  mqv;                      /* MAPQ */
+  int32_t  flags;                    /* bit 0: rounding guard, see above */
+  double   posterior, z0, z1;
+} gm_mapping_t;
+int gm_mapping_size(void);           /* sizeof(gm_mapping_t), for the Python mirror */
+int gm_select_pass2(gm_session_t *s, int n_reads, const uint64_t *hit_off, const gm_pass1_hit_t *hits, const gm_sw_full_rec_t *recs, const gm_post_rec_t *post,
+                    gm_mapping_t **maps, uint64_t *n_maps, uint64_t *map_off);
+
 /* time of the dominant kernel (seed lookup) during the last gm_map_* call, from HIP events on the
  * session's own stream, and the algorithmic bytes it moved */
 int gm_last_lookup_timing(gm_session_t *s, double *ms, uint64_t *alg_bytes, int *launches);

@@ -771,6 +771,23 @@ static int qv_from_pr_corr(double pr_corr) {   // ref: common/util.h:267-283
 }
 static int double_to_neglog(double x) { return (int)((double)1000 * -log(x)); }   // ref: common/util.h:297-301
 
+// The double expressions of hit_run_post_sw and compute_unpaired_mqv (ref: mapping.c:1609-1625, output.c:777-793), shared by the finalisation of the mapping entries
+// and by gm_select_pass2: one text, so both round through the host's libm alike.
+static inline double gm_ls_posterior(double a, double b, int score, int rmapped) { return pow(2.0, ((double)score - (double)rmapped * (2.0 * a + b)) / a); }
+static inline double gm_post_score_x(double a, double b, double posterior, int rmapped) { return a * log(posterior) / log(2.0) + (double)rmapped * (2.0 * a + b); }   // what rint() turns into AS
+static inline int gm_post_score(double a, double b, double posterior, int rmapped) { return (int)rint(gm_post_score_x(a, b, posterior, rmapped)); }
+static inline double gm_full_threshold(const gm_params_t& P, int score_max) { return P.sw_full_threshold < 0 ? -P.sw_full_threshold : score_max * (P.sw_full_threshold / 100.0); }   // ref: mapping.c:1661
+static inline int gm_unpaired_mqv(double posterior, double z1) { const int q = qv_from_pr_corr(posterior / z1); return q < 4 ? 0 : q; }
+// the rounding guard's distance tests (see Finalizer::guard_tol)
+static inline bool gm_near_rint(double x, double tol) { const double f = x - floor(x); return fabs(f - 0.5) < tol; }              // rint(): boundary at the half integers
+static inline bool gm_near_trunc(double x, double tol) { return fabs(x - rint(x)) < tol; }                                          // (int): boundary at the integers
+static inline bool gm_near_qv(double pr_corr, double tol) {                                                                         // qv_from_pr_corr, ref: common/util.h:267-283
+  const double pr_err = 1 - pr_corr;
+  if (fabs(pr_err - .99999999) < tol * 1e-2 || (pr_err > 0 && fabs(pr_err / 1E-25 - 1.0) < tol)) return true;
+  if (pr_err > .99999999 || pr_err < 1E-25) return false;
+  return gm_near_trunc(-10.0 * log(pr_err) / log(10.0), tol);
+}
+
 static int cmp_gen_start(const FHit* a, const FHit* b) {   // ref: mapping.c:1485-1494
   if (a->r->cn != b->r->cn) return (int)a->r->cn - (int)b->r->cn;
   if (a->r->gen_st != b->r->gen_st) return a->r->gen_st - b->r->gen_st;
@@ -1112,21 +1129,16 @@ struct Finalizer {
   // (with its two cut-offs) and for the Z tags -- checks the distance to the boundary; within guard_tol (1e-7, five orders above the difference) the read's device
   // results are redone by the host routine (same libm as the reference), so the bytes never hang on the device's last bits.
   double guard_tol = 1e-7; std::atomic<uint64_t>* redo_ctr = nullptr;
-  bool near_rint(double x) const { const double f = x - floor(x); return fabs(f - 0.5) < guard_tol; }              // rint(): boundary at the half integers
-  bool near_trunc(double x) const { return fabs(x - rint(x)) < guard_tol; }                                          // (int): boundary at the integers
-  bool near_qv(double pr_corr) const {                                                                               // qv_from_pr_corr, ref: common/util.h:267-283
-    const double pr_err = 1 - pr_corr;
-    if (fabs(pr_err - .99999999) < guard_tol * 1e-2 || (pr_err > 0 && fabs(pr_err / 1E-25 - 1.0) < guard_tol)) return true;
-    if (pr_err > .99999999 || pr_err < 1E-25) return false;
-    return near_trunc(-10.0 * log(pr_err) / log(10.0));
-  }
+  bool near_rint(double x) const { return gm_near_rint(x, guard_tol); }
+  bool near_trunc(double x) const { return gm_near_trunc(x, guard_tol); }
+  bool near_qv(double pr_corr) const { return gm_near_qv(pr_corr, guard_tol); }
   void redo_on_host(FHit& h) const {                    // sw_full_cs's own strings, then the host's post_sw (ref: sw-post.c:636-758), then the posterior score
     const GmFullRes* r = h.r;
     cs_alignment_strings(h.ops, h.ops + ops_half, std::min(r->n_ops, ops_half), h.db, h.qr);
     cs_post_sw(csk, reads + (size_t)r->read_idx * read_words, (int)initbp[r->read_idx], r->read_start, h, qual_ptr ? qual_ptr[r->read_idx] : nullptr, qual_delta);
     h.dev_post = false;
     const double a = s->score_alpha, b = s->score_beta;
-    int ps = (int)rint(a * log(h.posterior) / log(2.0) + (double)r->rmapped * (2.0 * a + b));
+    int ps = gm_post_score(a, b, h.posterior, r->rmapped);
     if (ps < 0) ps = 0;
     h.score_full = ps; h.pct_score_full = (1000 * 100 * ps) / r->score_max;
     h.pass2_key = s->P.sw_full_threshold < 0 ? h.score_full : (int)h.pct_score_full;
@@ -1150,7 +1162,7 @@ struct Finalizer {
             size_t nq = 0; for (char c : h.qr) nq += c != '-';
             h.qual.assign((const char*)bq_base + (size_t)(r - res_base) * read_len, std::min(nq, (size_t)read_len));
           }
-          if (near_rint(a * log(h.posterior) / log(2.0) + (double)r->rmapped * (2.0 * a + b))) { redo_on_host(h); return; }      // AS at a rounding boundary
+          if (near_rint(gm_post_score_x(a, b, h.posterior, r->rmapped))) { redo_on_host(h); return; }      // AS at a rounding boundary
         } else {
         cs_alignment_strings(h.ops, h.ops + ops_half, std::min(r->n_ops, ops_half), h.db, h.qr);
         cs_post_sw(csk, reads + (size_t)r->read_idx * read_words, (int)initbp[r->read_idx], r->read_start, h,
@@ -1166,12 +1178,12 @@ struct Finalizer {
         Memo& m = memo[((unsigned)r->score * 31u + (unsigned)r->rmapped) & 255u];
         if (m.score != r->score || m.rmapped != r->rmapped || m.a != a || m.b != b) {
           m.score = r->score; m.rmapped = r->rmapped; m.a = a; m.b = b;
-          m.post = pow(2.0, ((double)r->score - (double)r->rmapped * (2.0 * a + b)) / a);
-          m.ps = (int)rint(a * log(m.post) / log(2.0) + (double)r->rmapped * (2.0 * a + b));
+          m.post = gm_ls_posterior(a, b, r->score, r->rmapped);
+          m.ps = gm_post_score(a, b, m.post, r->rmapped);
         }
         h.posterior = m.post; ps = m.ps;
       } else
-      ps = (int)rint(a * log(h.posterior) / log(2.0) + (double)r->rmapped * (2.0 * a + b));
+      ps = gm_post_score(a, b, h.posterior, r->rmapped);
       if (ps < 0) ps = 0;
       h.score_full = ps; h.pct_score_full = (1000 * 100 * ps) / r->score_max;
     }
@@ -1189,7 +1201,7 @@ struct Finalizer {
     fh.resize(n);
     for (int i = 0; i < n; i++) {
       FHit& h = fh[i]; post_sw(h, &res[i], ops);
-      const double thr = P.sw_full_threshold < 0 ? -P.sw_full_threshold : h.r->score_max * (P.sw_full_threshold / 100.0);
+      const double thr = gm_full_threshold(P, h.r->score_max);
       if (h.score_full >= thr) p2.push_back(&h);                                   // ref: mapping.c:1661 (double compare)
     }
     GM_HP(0);
@@ -1242,7 +1254,7 @@ struct Finalizer {
       for (int pass = 0; pass < 2; pass++) {
         double z1 = 0.0;
         for (auto* h : p2) z1 += h->posterior;
-        for (auto* h : p2) { h->z0 = h->posterior; h->z1 = z1; h->mqv = qv_from_pr_corr(h->posterior / z1); if (h->mqv < 4) h->mqv = 0; }
+        for (auto* h : p2) { h->z0 = h->posterior; h->z1 = z1; h->mqv = gm_unpaired_mqv(h->posterior, z1); }
         // rounding guard (see post_sw above): MAPQ and the Z0 / Z1 tags of this read's records, when any posterior came from the device
         bool dev = false, near = false;
         for (auto* h : p2) dev = dev || h->dev_post;
@@ -2044,6 +2056,7 @@ extern "C" int gm_debug_tophits_cs(gm_session_t* s, int n_reads, int n_colours, 
 }
 
 #include "gm_host_windows.inc"
+#include "gm_host_select.inc"
 
 // ---- S1: vector SW on caller bitfields ----------------------------------------------------------
 struct SwVecState { bool init = false, colours = false; GmScoreDev sc; int dblen = 0, qrlen = 0; uint64_t invocs = 0, cells = 0; double secs = 0; };

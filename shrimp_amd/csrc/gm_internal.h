@@ -144,6 +144,20 @@ int gm_launch_win_scan(const uint32_t* d_hit_cnt, int n_rs, int hcap, unsigned l
 int gm_launch_win_scatter(const GmHit* d_hits, const uint16_t* d_perm, const unsigned long long* d_off, int n_rs, int hcap, unsigned long long total, int read_base,
                           gm_read_window_t* d_out, hipStream_t stream);
 
+// The selection seams (gm_select_pass1 / gm_select_pass2, gm_select.hip); GM_SEL_MAX below bounds K and the items of a read.
+//   gm_launch_sel_pass1: a wave a read over wins[off[2 r] .. off[2 r + 2]) with their scores: overlap rule, threshold and the ext-heap; d_sel_id / d_sel_score[r * K ..]
+//                        = window index and score after the rule of the d_sel_cnt[r] selected windows, in heap array order.
+//   gm_launch_sel_emit:  the selected windows as records at d_hit_off[r] + slot, strand 1 turned by reverse_hit.
+//   gm_launch_sel_pass2: a wave a read over items[hit_off[r] .. hit_off[r + 1]) (at most 64): d_order[hit_off[r] + k] = the item (0-based within the read) that is
+//                        the k-th final mapping, d_cnt[r] = their number.
+struct GmSel2Item { int32_t grp, start, endkey, key, score_full, keep; };      // grp = cn * 2 + gen_st; keep: the host's threshold compare
+int gm_launch_sel_pass1(const GmScoreDev& sc, int n_reads, int read_len, int K, int window_len, int overlap_abs, const gm_read_window_t* d_wins,
+                        const unsigned long long* d_off, const int* d_scores, int32_t* d_sel_id, int32_t* d_sel_score, uint32_t* d_sel_cnt, hipStream_t stream);
+int gm_launch_sel_emit(const GmScoreDev& sc, int n_reads, int read_len, int K, const gm_read_window_t* d_wins, const uint32_t* d_contig_off, const int32_t* d_sel_id,
+                       const int32_t* d_sel_score, const uint32_t* d_sel_cnt, const unsigned long long* d_hit_off, gm_pass1_hit_t* d_out, hipStream_t stream);
+int gm_launch_sel_pass2(int n_reads, int num_outputs, int strata, int max_alignments, const unsigned long long* d_hit_off, const GmSel2Item* d_items,
+                        int32_t* d_order, uint32_t* d_cnt, hipStream_t stream);
+
 // K3 pass 1 (vector SW + overlap rule), one wave per read-strand
 int gm_launch_pass1(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                     int window_len, int window_overlap_abs, GmHit* d_hits, const uint16_t* d_perm, const uint32_t* d_hit_cnt, int hcap,

@@ -122,10 +122,23 @@ class ReadWindow(C.Structure):      # gm_read_window_t: one candidate window of 
                 ("ax", C.c_int32), ("ay", C.c_int32), ("alen", C.c_int32), ("awidth", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Pass1Hit(C.Structure):        # gm_pass1_hit_t: one selected hit of gm_select_pass1 (checked against gm_pass1_hit_size())
+    _fields_ = [("read", C.c_int32), ("st", C.c_int32), ("win", C.c_int32), ("cn", C.c_int32), ("gen_st", C.c_int32), ("g_off", C.c_uint32), ("w_len", C.c_int32),
+                ("score_vector", C.c_int32), ("pct_score_vector", C.c_int32), ("score_max", C.c_int32), ("matches", C.c_int32), ("score_window_gen", C.c_int32),
+                ("ax", C.c_int32), ("ay", C.c_int32), ("alen", C.c_int32), ("awidth", C.c_int32)]
+
+
+class Mapping(C.Structure):         # gm_mapping_t: one final mapping of gm_select_pass2 (checked against gm_mapping_size())
+    _fields_ = [("read", C.c_int32), ("hit", C.c_int32), ("score_full", C.c_int32), ("pct_score_full", C.c_int32), ("mqv", C.c_int32), ("flags", C.c_int32),
+                ("posterior", C.c_double), ("z0", C.c_double), ("z1", C.c_double)]
+
+
 SW_FULL_REC_DTYPE = np.dtype(SwFullRec)      # the structured numpy view of an array of them
 POST_REC_DTYPE = np.dtype(PostRec)
 ANCHOR_DTYPE = np.dtype(Anchor)
 READ_WINDOW_DTYPE = np.dtype(ReadWindow)
+PASS1_HIT_DTYPE = np.dtype(Pass1Hit)
+MAPPING_DTYPE = np.dtype(Mapping)
 
 
 # every entry point include/gmapper_hip.h declares
@@ -140,7 +153,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_index_genome_is_rna", "gm_index_get_windows", "gm_sw_vector_batch_ix", "gm_sw_vector_batch_bounded_ix", "gm_sw_gapless_batch_ix", "gm_sw_full_ls_batch_ix", "gm_sw_full_cs_batch_ix",
            "gm_post_sw_batch_ix", "gm_sw_full_batch_text", "gm_sw_full_batch_text_ix",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits", "gm_debug_tophits_cs",
-           "gm_read_windows", "gm_read_window_size",
+           "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
 
@@ -247,6 +260,14 @@ def lib():
     L.gm_read_windows.argtypes = [vp, C.c_int, C.c_int, u32p, u8p, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MapStats)]
     if L.gm_read_window_size() != READ_WINDOW_DTYPE.itemsize:
         raise GmError("gm_read_window_t is %d bytes in the library, %d in READ_WINDOW_DTYPE" % (L.gm_read_window_size(), READ_WINDOW_DTYPE.itemsize))
+    u64p = C.POINTER(C.c_uint64)
+    L.gm_pass1_hit_size.argtypes = []; L.gm_pass1_hit_size.restype = C.c_int
+    L.gm_mapping_size.argtypes = []; L.gm_mapping_size.restype = C.c_int
+    L.gm_select_pass1.argtypes = [vp, C.c_int, C.c_int, vp, C.c_uint64, u64p, ipt, C.POINTER(vp), u64p, u64p]
+    L.gm_select_pass2.argtypes = [vp, C.c_int, u64p, vp, vp, vp, C.POINTER(vp), u64p, u64p]
+    for fn, dt, what in ((L.gm_pass1_hit_size, PASS1_HIT_DTYPE, "gm_pass1_hit_t"), (L.gm_mapping_size, MAPPING_DTYPE, "gm_mapping_t")):
+        if fn() != dt.itemsize:
+            raise GmError("%s is %d bytes in the library, %d in its numpy dtype" % (what, fn(), dt.itemsize))
     _lib = L
     return L
 
@@ -524,6 +545,7 @@ class Index:
             return qa[int(rc_[i]["ops_off"]):int(rc_[i]["ops_off"]) + int(rc_[i]["n_ops"])].decode() if post[i]["status"] == 0 and rc_[i]["score"] > 0 else None
         def qual(i):
             return qo[int(post[i]["qual_off"]):int(post[i]["qual_off"]) + int(post[i]["qual_len"])].decode()
+        qralign.buffer = qa                                                  # the whole buffer (ops.size bytes): what sw_full_batch_text takes as qralign
         return post, qralign, qual
 
     def sw_full_batch_text(self, cn, gen_st, recs, ops, reads_words, rlen, initbp=None, is_rna=-1, qralign=None, reverse=None, clip="S", what=("align", "cigar", "edit"),
@@ -825,8 +847,52 @@ class Session:
         wins = np.zeros(nw.value, dtype=READ_WINDOW_DTYPE)
         if nw.value: C.memmove(wins.ctypes.data, out, nw.value * READ_WINDOW_DTYPE.itemsize)
         if out.value: L.gm_free(out)
-        self.stats = st.as_dict()
+        self.stats = st.as_dict(); self._windows_read_len = Lr
         return wins, off
+
+    def select_pass1(self, wins, off, scores, read_len=None):
+        """Pass 1's selection (gm_select_pass1) over the windows of read_windows and their vector scores: -> (hits, hit_off).  hits: structured array of
+        PASS1_HIT_DTYPE, read r's at hits[hit_off[r]:hit_off[r + 1]] in the heap's array order, strand-1 hits already turned by reverse_hit: (cn, gen_st, g_off, w_len)
+        and the box (ax, ay, alen, awidth) go to Index.sw_full_ls_batch / sw_full_cs_batch as they are.  read_len: the reads' length (colours in colour space);
+        None: that of this session's last read_windows call."""
+        if read_len is None: read_len = getattr(self, "_windows_read_len", None)
+        if read_len is None: raise GmError("select_pass1: read_len is needed (no read_windows call on this session yet)")
+        wins = np.ascontiguousarray(wins, dtype=READ_WINDOW_DTYPE); off = np.ascontiguousarray(off, dtype=np.uint64)
+        scores = np.ascontiguousarray(scores, dtype=np.int32)
+        if off.ndim != 1 or len(off) < 1 or len(off) % 2 != 1: raise GmError("select_pass1: off has 2 n + 1 entries")
+        if scores.shape != (len(wins),): raise GmError("select_pass1: one score per window")
+        n = (len(off) - 1) // 2
+        L = lib(); out = C.c_void_p(); nh = C.c_uint64(0)
+        hit_off = np.zeros(n + 1, dtype=np.uint64)
+        _check(L.gm_select_pass1(self.h, n, int(read_len), wins.ctypes.data_as(C.c_void_p), len(wins), off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                 scores.ctypes.data_as(C.POINTER(C.c_int)), C.byref(out), C.byref(nh), hit_off.ctypes.data_as(C.POINTER(C.c_uint64))), "gm_select_pass1")
+        hits = np.zeros(nh.value, dtype=PASS1_HIT_DTYPE)
+        if nh.value: C.memmove(hits.ctypes.data, out, nh.value * PASS1_HIT_DTYPE.itemsize)
+        if out.value: L.gm_free(out)
+        return hits, hit_off
+
+    def select_pass2(self, hits, hit_off, recs, post=None):
+        """Pass 2's selection and the mapping qualities (gm_select_pass2) over the records of ONE full batch call on the hits of select_pass1: -> (maps, map_off).
+        maps: structured array of MAPPING_DTYPE in the reference's output order, read r's at maps[map_off[r]:map_off[r + 1]]; post: the POST_REC_DTYPE answers of
+        post_sw_batch, required in colour space with mapping qualities on.  flags bit 0: see include/gmapper_hip.h."""
+        hits = np.ascontiguousarray(hits, dtype=PASS1_HIT_DTYPE); hit_off = np.ascontiguousarray(hit_off, dtype=np.uint64)
+        recs = np.ascontiguousarray(recs, dtype=SW_FULL_REC_DTYPE)
+        if hit_off.ndim != 1 or len(hit_off) < 1: raise GmError("select_pass2: hit_off has n + 1 entries")
+        if len(recs) != len(hits): raise GmError("select_pass2: one record per hit")
+        if post is not None:
+            post = np.ascontiguousarray(post, dtype=POST_REC_DTYPE)
+            if len(post) != len(hits): raise GmError("select_pass2: one post record per hit")
+        n = len(hit_off) - 1
+        if int(hit_off[-1]) != len(hits): raise GmError("select_pass2: hit_off ends at %d, there are %d hits" % (int(hit_off[-1]), len(hits)))
+        L = lib(); out = C.c_void_p(); nm = C.c_uint64(0)
+        map_off = np.zeros(n + 1, dtype=np.uint64)
+        _check(L.gm_select_pass2(self.h, n, hit_off.ctypes.data_as(C.POINTER(C.c_uint64)), hits.ctypes.data_as(C.c_void_p), recs.ctypes.data_as(C.c_void_p),
+                                 None if post is None else post.ctypes.data_as(C.c_void_p), C.byref(out), C.byref(nm), map_off.ctypes.data_as(C.POINTER(C.c_uint64))),
+               "gm_select_pass2")
+        maps = np.zeros(nm.value, dtype=MAPPING_DTYPE)
+        if nm.value: C.memmove(maps.ctypes.data, out, nm.value * MAPPING_DTYPE.itemsize)
+        if out.value: L.gm_free(out)
+        return maps, map_off
 
     def lookup_timing(self):
         ms = C.c_double(); b = C.c_uint64(); n = C.c_int()
@@ -1095,6 +1161,7 @@ def post_sw_batch(recs, ops, genome_ls, reads_words, rlen, initbp, quals=None, i
         return qa[int(rc_[i]["ops_off"]):int(rc_[i]["ops_off"]) + int(rc_[i]["n_ops"])].decode() if post[i]["status"] == 0 and rc_[i]["score"] > 0 else None
     def qual(i):
         return qo[int(post[i]["qual_off"]):int(post[i]["qual_off"]) + int(post[i]["qual_len"])].decode()
+    qralign.buffer = qa                                                  # the whole buffer (ops.size bytes): what sw_full_batch_text takes as qralign
     return post, qralign, qual
 
 
