@@ -754,6 +754,73 @@ int gm_mapping_size(void);           /* sizeof(gm_mapping_t), for the Python mir
 int gm_select_pass2(gm_session_t *s, int n_reads, const uint64_t *hit_off, const gm_pass1_hit_t *hits, const gm_sw_full_rec_t *recs, const gm_post_rec_t *post,
                     gm_mapping_t **maps, uint64_t *n_maps, uint64_t *map_off);
 
+/* gm_sam_records: the last link of the chain -- the SAM text of a chunk's mappings, made on the device (a wave a record) from the arrays the seams above return.  After
+ * it a chunk goes from packed reads to the reference's bytes through batch calls only.  The rules are hit_output's for an unpaired read (ref: gmapper/output.c:227-774),
+ * under the session's gm_params_t; the mapping entries do not use this entry and print what they printed.
+ *   reads       n_reads, read_len, reads_packed, initbp as the mapping entries take them (colour space: read_len colours, initbp required; letter space: initbp NULL).
+ *   names       '\n' separated, or NULL: r<index>, the names gm_map_reads gives.  seqs: NULL, or the reads' text lines as gm_map_reads_text takes them (read_len
+ *               letters; colour space: the primer letter and read_len colours).  quals / qual_delta: NULL, or '\n' separated QV strings of read_len characters and
+ *               the file's offset.
+ *   hits, recs  n_hits of each: gm_select_pass1's hits and the records of the ONE full batch call over them.  score_vector: ZV of every hit, or NULL:
+ *               hits[i].score_vector (letter space prints pass 2's second vector score there, mapping.c:386-396: pass that).
+ *   post, post_quals, post_quals_len   colour space with mapping qualities on: the answers of gm_post_sw_batch(_ix) and its quals_out; else NULL.
+ *   qralign, ops_len   colour space: gm_post_sw_batch's qralign_out, or the text call's where there is no post_sw; hit i's slice is [recs[i].ops_off, + n_ops).
+ *   cigar, cigar_off / edit, edit_off   gm_sw_full_batch_text[_ix] over ALL n_hits records with reverse[i] = hits[i].gen_st and clip_char 'S' (letter space) / 'H'
+ *               (colour space): n_hits + 1 offsets each.  edit / edit_off are required iff extra_sam_fields.
+ *   maps, map_off, n_maps   gm_select_pass2's: read r's mappings at [map_off[r], map_off[r + 1]).
+ * Output: *sam (gm_free; NULL when nothing is printed), *sam_len bytes: the text gm_map_reads* would append for these reads, in input order; read r's records are the
+ * bytes [read_off[r], read_off[r + 1]) (read_off: n_reads + 1 entries, the caller's).  A read with mappings gets one record per mapping, in maps order; a read without
+ * gets the unaligned record when sam_unaligned is set and nothing otherwise.
+ * Mapped record: QNAME, FLAG 0 / 16 (gen_st), RNAME, POS, MAPQ = mqv, CIGAR (the slice as given), "*\t0\t0", SEQ, QUAL, then the tags.
+ *   POS         forward strand: genome_start + 1; strand 1: (contig_len - genome_start) - (rmapped - 1 - deletions + insertions) (output.c:626-634); the low 32 bits,
+ *               printed unsigned.
+ *   SEQ, QUAL   letter space: every base from its code (A C G T, anything else N); strand 1: the read reversed and complemented.  With seqs, the positions the
+ *               alignment clips (outside [read_start, read_start + rmapped)) print the file's letter through seq_from_text (output.c:326-351), on strand 1 its
+ *               complement, a '.' staying '.'.  QUAL: '*', or the QV characters re-based to PHRED + 33 (+ 33 - qual_delta) and reversed with the read.
+ *               colour space: SEQ = the non-gap characters of the hit's qralign slice, upper-cased, anything outside A C G T N an N; strand 1: reversed and
+ *               complemented.  QUAL = the hit's post_quals slice, reversed on strand 1; '*' without quals, without post / post_quals, or for an empty slice.
+ *   tags        AS:i = score_full; Z0:i / Z1:i, only with mapping qualities on and not all_contigs: (int)(1000 * -log(z)) of the mapping's z0 / z1 -- computed on the
+ *               HOST by the function the mapping entries print them with (the host's log, one per mapping) and uploaded as integers: the kernel has no double
+ *               arithmetic; NM:i = mismatches + deletions + insertions (colour space: post's mismatches where post is given).  Colour space, then: CQ:Z (the QV
+ *               line; only with quals), CS:Z (the seqs line verbatim; without seqs the primer letter and the colours, '.' for a code above 3), CM:i = crossovers
+ *               (post's where given), XX:Z = the qralign slice.
+ *   tail        RG:Z (read_group, when set); with extra_sam_fields ZM:i ZR:i ZV:i ZH:i ZE:Z = hits[].matches, hits[].score_window_gen, score_vector, recs[].score, the
+ *               edit slice; then '\n'.
+ * Unaligned record: QNAME "\t4\t*\t0\t0\t*\t*\t0\t0\t", then letter space: SEQ (the codes' letters A C G T U M R W S Y K V H D B N, or with seqs the file's letters
+ *   through seq_from_text), a tab and QUAL (the QV line verbatim, or '*'); colour space: "*\t*\tCQ:Z:" the QV line or '*', "\tCS:Z:" as above; then the tail without
+ *   the extra fields.
+ * Scope: unpaired sessions (see gm_read_windows); sam_r2 is a paired option and is ignored; output_format 0 only: --shrimp-format / --pretty return GM_E_ARG.
+ * Refusals (GM_E_ARG, on the host before anything is uploaded, the item named in gm_last_error()): a missing required array; map_off not ascending from 0 or not ending
+ * at n_maps; a mapping whose read is not its slot's; hit outside n_hits; a hit whose cn is outside the index or whose gen_st is above 1; a record with status < 0 or
+ * score <= 0 that a mapping points to; a cigar, edit, qralign or post_quals slice outside its buffer (cigar / edit: offsets that descend or pass the last one); names,
+ * seqs or quals with fewer lines than reads, or a seqs / quals line of the wrong length; a qralign slice whose read positions are not the record's rmapped, or with
+ * its clip run past read_len.  n_reads <= 0: GM_OK, read_off[0] = 0, *sam = NULL.  The session is usable after every refusal.
+ * Cost: a fixed number of device allocations, copies and launches whatever the sizes -- the caller's buffers go up as they are beside one 112-byte line a record, a
+ * sizing launch, the scan of gm_read_windows, a writing launch, one copy of the offsets and one of the text.  The call takes its turn on the device like
+ * gm_select_pass2 and leaves the session ready for any other call. */
+typedef struct gm_sam_input {
+  /* the reads, as the mapping entries take them */
+  int n_reads, read_len;                 /* colour space: number of colours */
+  const uint32_t *reads_packed;          /* n_reads * ((read_len + 7) / 8) words */
+  const uint8_t  *initbp;                /* colour space: required; letter space: NULL */
+  const char *names;                     /* '\n' separated, or NULL: the names gm_map_reads gives when it gets NULL */
+  const char *seqs;                      /* NULL, or the reads' text lines as gm_map_reads_text takes them */
+  const char *quals; int qual_delta;     /* NULL, or '\n' separated QV strings and the file's offset */
+  /* the chain's arrays */
+  uint64_t n_hits;
+  const gm_pass1_hit_t   *hits;          /* gm_select_pass1 */
+  const gm_sw_full_rec_t *recs;          /* the ONE full batch call over those hits */
+  const int              *score_vector;  /* ZV per hit; NULL: hits[i].score_vector (letter space: pass 2's second vector score, mapping.c:386-396) */
+  const gm_post_rec_t    *post;          /* colour space with mapping qualities on, else NULL */
+  const char *post_quals; uint64_t post_quals_len;   /* gm_post_sw_batch's quals_out, or NULL */
+  const char *qralign; uint64_t ops_len; /* colour space: post's qralign_out (or the text call's, where there is no post_sw); letter space: NULL */
+  const char *cigar; const uint64_t *cigar_off;      /* gm_sw_full_batch_text[_ix] over all n_hits, reverse[i] = gen_st, clip 'S' letter / 'H' colour */
+  const char *edit;  const uint64_t *edit_off;       /* required iff extra_sam_fields */
+  uint64_t n_maps; const gm_mapping_t *maps; const uint64_t *map_off;   /* gm_select_pass2, n_reads + 1 offsets */
+} gm_sam_input_t;
+int gm_sam_input_size(void);             /* sizeof(gm_sam_input_t), for the Python mirror */
+int gm_sam_records(gm_session_t *s, const gm_sam_input_t *in, char **sam, size_t *sam_len, uint64_t *read_off /* n_reads + 1, caller's */);
+
 /* time of the dominant kernel (seed lookup) during the last gm_map_* call, from HIP events on the
  * session's own stream, and the algorithmic bytes it moved */
 int gm_last_lookup_timing(gm_session_t *s, double *ms, uint64_t *alg_bytes, int *launches);

@@ -2057,6 +2057,7 @@ extern "C" int gm_debug_tophits_cs(gm_session_t* s, int n_reads, int n_colours, 
 
 #include "gm_host_windows.inc"
 #include "gm_host_select.inc"
+#include "gm_host_sam.inc"
 
 // ---- S1: vector SW on caller bitfields ----------------------------------------------------------
 struct SwVecState { bool init = false, colours = false; GmScoreDev sc; int dblen = 0, qrlen = 0; uint64_t invocs = 0, cells = 0; double secs = 0; };

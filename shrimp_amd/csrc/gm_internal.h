@@ -285,3 +285,25 @@ struct GmTextItem { unsigned long long ops_off; long long genome_start, gbase; u
 int gm_launch_sw_text(int n_items, const GmTextItem* d_items, int colour, int what, int write, const uint8_t* d_ops, const uint32_t* d_genome, const uint32_t* d_reads,
                       int read_words, int is_rna, const uint8_t* d_qin, int clip_char, uint32_t* d_lens, const unsigned long long* d_offs, uint8_t* d_db, uint8_t* d_qr,
                       uint8_t* d_cigar, uint8_t* d_edit, hipStream_t stream, int ix = 0);      // ix: the items carry gbase / flags (gm_sw_full_batch_text_ix)
+
+// Text kernels (gm_text.hip, gm_sam.hip): eight characters as one 64-bit table, and the decimal digits of a 32-bit value.
+constexpr uint64_t pack8(const char* s) { uint64_t v = 0; for (int i = 0; i < 8; i++) v |= (uint64_t)(uint8_t)s[i] << (8 * i); return v; }
+__device__ __forceinline__ int ndig(uint32_t v) {
+  return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
+}
+
+// The SAM text of a chunk's mappings (gm_sam_records, k_sam_records in gm_sam.hip): one output record -- a mapping, or (cn < 0) the unaligned record of a read.  The host
+// has checked it (gm_host_sam.inc): read < n_reads, cn inside the index, every slice inside its uploaded buffer; every integer the record prints is here, Z0 / Z1 through
+// the host's log.  flags: 1 = the mapping is on strand 1; keep_lo / keep_hi: letter space, the read positions of the alignment (outside them a read that came as text
+// prints the file's letter); pq_len == 0: QUAL of a colour-space record is '*'.
+struct GmSamRec { unsigned long long cigar_off, edit_off, qr_off, pq_off; uint32_t cigar_len, edit_len, qr_len, pq_len, pos; int32_t read, cn, flags, mqv, as, z0, z1, nm, cm,
+                  zm, zr, zv, zh, keep_lo, keep_hi; };
+// names: null (the records are named r<read>), or the caller's text with name_off[r] the start of read r's name and name_off[r + 1] - 1 its end; seqs / quals: null, or
+// one line a read of read_len (colour space, seqs: read_len + 1) characters and a separator; cnames / cname_off: the contig names end to end with n_contigs + 1
+// offsets, the read group (rg_len bytes) behind them at cname_off[n_contigs]; dq: what re-bases a QV character to PHRED + 33; ztags: Z0 / Z1 are printed; extra: ZM ZR ZV
+// ZH ZE are.  lens: the sizing launch's output, one length a record; offs / out: the writing launch's, record k at out + offs[k].
+struct GmSamArgs { const GmSamRec* recs; int n_recs, colour, read_len, read_words, n_contigs, rg_len, dq, ztags, extra;
+                   const uint32_t* reads; const uint8_t* initbp; const uint8_t* names; const unsigned long long* name_off; const uint8_t* seqs; const uint8_t* quals;
+                   const uint8_t* cigar; const uint8_t* edit; const uint8_t* qralign; const uint8_t* post_quals; const uint8_t* cnames; const uint32_t* cname_off;
+                   uint32_t* lens; const unsigned long long* offs; uint8_t* out; };
+int gm_launch_sam_records(const GmSamArgs& args, int write, hipStream_t stream);      // write = 0: the sizing launch; 1: the bytes

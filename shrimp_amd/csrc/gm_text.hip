@@ -28,15 +28,11 @@
 
 namespace {
 
-constexpr uint64_t pack8(const char* s) { uint64_t v = 0; for (int i = 0; i < 8; i++) v |= (uint64_t)(uint8_t)s[i] << (8 * i); return v; }
 __device__ __forceinline__ int ls_char(int code) {             // base_translate, ref: common/fasta.c:689-690
   constexpr uint64_t lo = pack8("ACGTUMRW"), hi = pack8("SYKVHDBN");
   return (int)(((code & 8) ? hi : lo) >> (8 * (code & 7))) & 0xff;
 }
 __device__ __forceinline__ int nib(const uint32_t* __restrict__ b, long long i) { return (int)((b[i >> 3] >> ((i & 7) * 4)) & 0xf); }
-__device__ __forceinline__ int ndig(uint32_t v) {
-  return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
-}
 __device__ __forceinline__ void put_num(uint8_t* at, uint32_t v, int nd) { for (int k = nd - 1; k >= 0; k--) { at[k] = (uint8_t)('0' + v % 10u); v /= 10u; } }
 __device__ __forceinline__ int top_bit(unsigned long long m) { return 63 - __clzll((long long)m); }      // m != 0
 __device__ __forceinline__ int wave_excl_scan(int v, int lane, int* total) {

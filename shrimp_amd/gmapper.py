@@ -133,6 +133,14 @@ class Mapping(C.Structure):         # gm_mapping_t: one final mapping of gm_sele
                 ("posterior", C.c_double), ("z0", C.c_double), ("z1", C.c_double)]
 
 
+class SAM_INPUT(C.Structure):       # gm_sam_input_t: what gm_sam_records takes (checked against gm_sam_input_size())
+    _fields_ = [("n_reads", C.c_int), ("read_len", C.c_int), ("reads_packed", C.c_void_p), ("initbp", C.c_void_p), ("names", C.c_char_p), ("seqs", C.c_char_p),
+                ("quals", C.c_char_p), ("qual_delta", C.c_int), ("n_hits", C.c_uint64), ("hits", C.c_void_p), ("recs", C.c_void_p), ("score_vector", C.c_void_p),
+                ("post", C.c_void_p), ("post_quals", C.c_char_p), ("post_quals_len", C.c_uint64), ("qralign", C.c_char_p), ("ops_len", C.c_uint64),
+                ("cigar", C.c_char_p), ("cigar_off", C.c_void_p), ("edit", C.c_char_p), ("edit_off", C.c_void_p), ("n_maps", C.c_uint64), ("maps", C.c_void_p),
+                ("map_off", C.c_void_p)]
+
+
 SW_FULL_REC_DTYPE = np.dtype(SwFullRec)      # the structured numpy view of an array of them
 POST_REC_DTYPE = np.dtype(PostRec)
 ANCHOR_DTYPE = np.dtype(Anchor)
@@ -153,7 +161,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_index_genome_is_rna", "gm_index_get_windows", "gm_sw_vector_batch_ix", "gm_sw_vector_batch_bounded_ix", "gm_sw_gapless_batch_ix", "gm_sw_full_ls_batch_ix", "gm_sw_full_cs_batch_ix",
            "gm_post_sw_batch_ix", "gm_sw_full_batch_text", "gm_sw_full_batch_text_ix",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits", "gm_debug_tophits_cs",
-           "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size",
+           "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size", "gm_sam_records", "gm_sam_input_size",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
 
@@ -268,6 +276,10 @@ def lib():
     for fn, dt, what in ((L.gm_pass1_hit_size, PASS1_HIT_DTYPE, "gm_pass1_hit_t"), (L.gm_mapping_size, MAPPING_DTYPE, "gm_mapping_t")):
         if fn() != dt.itemsize:
             raise GmError("%s is %d bytes in the library, %d in its numpy dtype" % (what, fn(), dt.itemsize))
+    L.gm_sam_input_size.argtypes = []; L.gm_sam_input_size.restype = C.c_int
+    L.gm_sam_records.argtypes = [vp, C.POINTER(SAM_INPUT), C.POINTER(vp), C.POINTER(C.c_size_t), u64p]
+    if L.gm_sam_input_size() != C.sizeof(SAM_INPUT):
+        raise GmError("gm_sam_input_t is %d bytes in the library, %d in SAM_INPUT" % (L.gm_sam_input_size(), C.sizeof(SAM_INPUT)))
     _lib = L
     return L
 
@@ -546,6 +558,7 @@ class Index:
         def qual(i):
             return qo[int(post[i]["qual_off"]):int(post[i]["qual_off"]) + int(post[i]["qual_len"])].decode()
         qralign.buffer = qa                                                  # the whole buffer (ops.size bytes): what sw_full_batch_text takes as qralign
+        qual.buffer = qo                                                     # ... and the base qualities end to end: what sam_records takes as post_quals
         return post, qralign, qual
 
     def sw_full_batch_text(self, cn, gen_st, recs, ops, reads_words, rlen, initbp=None, is_rna=-1, qralign=None, reverse=None, clip="S", what=("align", "cigar", "edit"),
@@ -894,6 +907,59 @@ class Session:
         if out.value: L.gm_free(out)
         return maps, map_off
 
+    def sam_records(self, reads_codes, hits, recs, maps, map_off, cigar, *, initbp=None, names=None, seqs=None, quals=None, qual_delta=33, score_vector=None, post=None,
+                    post_quals=None, qralign=None, edit=None):
+        """The SAM text of a chunk's mappings (gm_sam_records): -> (bytes, read_off), read r's records at bytes[read_off[r]:read_off[r + 1]].
+        reads_codes: [n, L] uint8 codes (colour space: the colours, with initbp); hits / recs / maps / map_off: select_pass1's hits, the records of the ONE full batch
+        call over them, select_pass2's answer; cigar / edit: what Index.sw_full_batch_text returned for ALL hits (reverse = gen_st; clip "S" letter / "H" colour), or a
+        (buffer, offsets) pair; qralign / post_quals: what post_sw_batch returned (the text call's qralign where there is no post_sw), or the whole buffers; names /
+        seqs / quals: None or one bytes a read; score_vector: ZV of every hit (None: hits["score_vector"]).  The rules: include/gmapper_hip.h."""
+        from .synth import pack_reads
+        reads_codes = np.ascontiguousarray(reads_codes, dtype=np.uint8)
+        if reads_codes.ndim != 2: raise GmError("sam_records: reads_codes is (n, read_len)")
+        n, Lr = reads_codes.shape
+        packed = np.ascontiguousarray(pack_reads(reads_codes), dtype=np.uint32) if n and Lr else np.zeros((n, 1), dtype=np.uint32)
+        hits = np.ascontiguousarray(hits, dtype=PASS1_HIT_DTYPE); recs = np.ascontiguousarray(recs, dtype=SW_FULL_REC_DTYPE)
+        maps = np.ascontiguousarray(maps, dtype=MAPPING_DTYPE); map_off = np.ascontiguousarray(map_off, dtype=np.uint64)
+        if len(recs) != len(hits): raise GmError("sam_records: one record per hit")
+        if len(map_off) != n + 1: raise GmError("sam_records: map_off has n + 1 entries")
+        keep = []
+        def arr(a, dtype, what):
+            if a is None: return None
+            a = np.ascontiguousarray(a, dtype=dtype); keep.append(a)
+            if len(a) != len(hits): raise GmError("sam_records: one %s per hit" % what)
+            return a.ctypes.data
+        def lines(x):
+            if x is None: return None
+            return x if isinstance(x, bytes) else b"\n".join(t if isinstance(t, bytes) else t.encode() for t in x)
+        def whole(x):                                                        # a buffer, or the accessor a batch call returned
+            if x is None: return None
+            b = getattr(x, "buffer", x)
+            return b if isinstance(b, bytes) else bytes(b)
+        def text(x, what):                                                   # (buffer, n_hits + 1 offsets)
+            if x is None: return None, None
+            b, off = (x.buffer, x.offsets) if hasattr(x, "buffer") else x
+            off = np.ascontiguousarray(off, dtype=np.uint64); keep.append(off)
+            if len(off) != len(hits) + 1: raise GmError("sam_records: %s has n_hits + 1 offsets" % what)
+            return (b if isinstance(b, bytes) else bytes(b)), off.ctypes.data
+        ib = None if initbp is None else np.ascontiguousarray(initbp, dtype=np.uint8)
+        if ib is not None and len(ib) != n: raise GmError("sam_records: one primer letter per read")
+        I = SAM_INPUT(); I.n_reads, I.read_len = n, Lr
+        I.reads_packed = packed.ctypes.data; I.initbp = None if ib is None else ib.ctypes.data
+        I.names, I.seqs, I.quals, I.qual_delta = lines(names), lines(seqs), lines(quals), int(qual_delta)
+        I.n_hits = len(hits); I.hits = hits.ctypes.data if len(hits) else None; I.recs = recs.ctypes.data if len(hits) else None
+        I.score_vector = arr(score_vector, np.int32, "vector score"); I.post = arr(post, POST_REC_DTYPE, "post record")
+        pq = whole(post_quals); I.post_quals = pq; I.post_quals_len = 0 if pq is None else len(pq)
+        qa = whole(qralign); I.qralign = qa; I.ops_len = 0 if qa is None else len(qa)
+        I.cigar, I.cigar_off = text(cigar, "cigar"); I.edit, I.edit_off = text(edit, "edit")
+        I.n_maps = len(maps); I.maps = maps.ctypes.data if len(maps) else None; I.map_off = map_off.ctypes.data
+        L = lib(); out = C.c_void_p(); sl = C.c_size_t(0)
+        read_off = np.zeros(n + 1, dtype=np.uint64)
+        _check(L.gm_sam_records(self.h, C.byref(I), C.byref(out), C.byref(sl), read_off.ctypes.data_as(C.POINTER(C.c_uint64))), "gm_sam_records")
+        sam = C.string_at(out, sl.value) if out.value else b""
+        if out.value: L.gm_free(out)
+        return sam, read_off
+
     def lookup_timing(self):
         ms = C.c_double(); b = C.c_uint64(); n = C.c_int()
         lib().gm_last_lookup_timing(self.h, C.byref(ms), C.byref(b), C.byref(n))
@@ -1162,6 +1228,7 @@ def post_sw_batch(recs, ops, genome_ls, reads_words, rlen, initbp, quals=None, i
     def qual(i):
         return qo[int(post[i]["qual_off"]):int(post[i]["qual_off"]) + int(post[i]["qual_len"])].decode()
     qralign.buffer = qa                                                  # the whole buffer (ops.size bytes): what sw_full_batch_text takes as qralign
+    qual.buffer = qo                                                     # ... and the base qualities end to end: what Session.sam_records takes as post_quals
     return post, qralign, qual
 
 
