@@ -26,6 +26,7 @@
 #include <zlib.h>
 #include "gm_common.h"
 #include "gm_internal.h"
+#include "gm_devmem.h"
 
 // ---- errors -----------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -1406,10 +1407,10 @@ static int run_heavy_tier(gm_session* s, DevSet& D, const GmIndexDev& dv, int n,
   off[n_heavy] = tot;
   if (tot >= (1ull << 32)) { gm_set_error("heavy tier: %llu keys in one sub-batch", (unsigned long long)tot); return GM_E_OVERFLOW; }
   uint32_t *d_list = nullptr, *d_segn = nullptr, *d_b32 = nullptr, *d_e32 = nullptr, *d_aux = nullptr, *d_nxt = nullptr, *d_ord = nullptr;
-  uint64_t *d_off = nullptr, *d_kin = nullptr, *d_ks = nullptr;
-  GM_HIP(hipMalloc(&d_list, (size_t)n_heavy * 4)); GM_HIP(hipMalloc(&d_segn, (size_t)n_heavy * 4)); GM_HIP(hipMalloc(&d_b32, (size_t)n_heavy * 4)); GM_HIP(hipMalloc(&d_e32, (size_t)n_heavy * 4));
-  GM_HIP(hipMalloc(&d_off, (size_t)(n_heavy + 1) * 8));
-  GM_HIP(hipMalloc(&d_kin, tot * 8)); GM_HIP(hipMalloc(&d_ks, tot * 8)); GM_HIP(hipMalloc(&d_aux, tot * 4)); GM_HIP(hipMalloc(&d_nxt, tot * 4)); GM_HIP(hipMalloc(&d_ord, tot * 4));
+  uint64_t *d_off = nullptr, *d_kin = nullptr, *d_ks = nullptr; GmDevMem mem;      // (mem's scope ends behind the synchronise below)
+  GM_HIP(mem.get(&d_list, (size_t)n_heavy * 4)); GM_HIP(mem.get(&d_segn, (size_t)n_heavy * 4)); GM_HIP(mem.get(&d_b32, (size_t)n_heavy * 4)); GM_HIP(mem.get(&d_e32, (size_t)n_heavy * 4));
+  GM_HIP(mem.get(&d_off, (size_t)(n_heavy + 1) * 8));
+  GM_HIP(mem.get(&d_kin, tot * 8)); GM_HIP(mem.get(&d_ks, tot * 8)); GM_HIP(mem.get(&d_aux, tot * 4)); GM_HIP(mem.get(&d_nxt, tot * 4)); GM_HIP(mem.get(&d_ord, tot * 4));
   GM_HIP(hipMemcpyAsync(d_list, list.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice, q));
   GM_HIP(hipMemcpyAsync(d_segn, segn.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice, q));
   GM_HIP(hipMemcpyAsync(d_b32, b32.data(), (size_t)n_heavy * 4, hipMemcpyHostToDevice, q));
@@ -1420,9 +1421,7 @@ static int run_heavy_tier(gm_session* s, DevSet& D, const GmIndexDev& dv, int n,
   if (rc == GM_OK)
     rc = gm_launch_anchors_heavy(dv, *sc, n, read_len, W, n_heavy, d_list, d_off, d_segn, d_b32, d_e32, tot, d_kin, d_ks, d_aux, d_nxt, d_ord,
                                  D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, d_stats, q);
-  GM_HIP(hipStreamSynchronize(q));
-  (void)hipFree(d_list); (void)hipFree(d_segn); (void)hipFree(d_b32); (void)hipFree(d_e32); (void)hipFree(d_off);
-  (void)hipFree(d_kin); (void)hipFree(d_ks); (void)hipFree(d_aux); (void)hipFree(d_nxt); (void)hipFree(d_ord);
+  GM_HIP(hipStreamSynchronize(q));      // (also behind a launch that failed)
   return rc;
 }
 
@@ -2058,1080 +2057,6 @@ extern "C" int gm_debug_tophits_cs(gm_session_t* s, int n_reads, int n_colours, 
 #include "gm_host_windows.inc"
 #include "gm_host_select.inc"
 #include "gm_host_sam.inc"
-
-// ---- S1: vector SW on caller bitfields ----------------------------------------------------------
-struct SwVecState { bool init = false, colours = false; GmScoreDev sc; int dblen = 0, qrlen = 0; uint64_t invocs = 0, cells = 0; double secs = 0; };
-static thread_local SwVecState g_sv;
-
-extern "C" int sw_vector_setup(int dblen, int qrlen, int a_gap_open, int a_gap_ext, int b_gap_open, int b_gap_ext,
-                               int match, int mismatch, int use_colours, bool reset_stats) {
-  if (match * qrlen >= 32768) { gm_set_error("match * qrlen >= 32768 (ref: sw-vector.c:393-398)"); return GM_E_RANGE; }
-  if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
-  gm_params_t P; gm_params_default(&P);
-  P.match_score = match; P.mismatch_score = mismatch; P.a_gap_open_score = a_gap_open; P.a_gap_extend_score = a_gap_ext;
-  P.b_gap_open_score = b_gap_open; P.b_gap_extend_score = b_gap_ext;
-  g_sv.sc = make_score(P); g_sv.dblen = dblen; g_sv.qrlen = qrlen; g_sv.init = true; g_sv.colours = use_colours != 0;
-  if (reset_stats) { g_sv.invocs = g_sv.cells = 0; g_sv.secs = 0; }
-  return 0;
-}
-extern "C" int sw_vector_cleanup(void) { g_sv.init = false; return 0; }
-extern "C" void sw_vector_stats(uint64_t* invocs, uint64_t* cells, double* secs) {
-  if (invocs) *invocs = g_sv.invocs; if (cells) *cells = g_sv.cells; if (secs) *secs = g_sv.secs;
-}
-
-static int sw_vector_batch_impl(int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen,
-                                const uint32_t* reads, int read_words, const int* rlen, int* scores, int early_thr, uint8_t* stopped) {
-  if (!g_sv.init) { gm_set_error("sw_vector called before sw_vector_setup"); return GM_E_NOTSETUP; }
-  if (n <= 0) return GM_OK;
-  int max_g = 0, max_r = 0;
-  for (int i = 0; i < n; i++) { max_g = std::max(max_g, glen[i]); max_r = std::max(max_r, rlen[i]); if (glen[i] < 1 || rlen[i] < 1) return GM_E_ARG; }
-  if (max_g > g_sv.dblen || max_r > g_sv.qrlen) { gm_set_error("window/read longer than sw_vector_setup sizes"); return GM_E_ARG; }
-  uint32_t *dg = nullptr, *dr = nullptr; long long* dgo = nullptr; int *dgl = nullptr, *drl = nullptr, *ds = nullptr;
-  GM_HIP(hipMalloc(&dg, (genome_words + 8) * 4)); GM_HIP(hipMalloc(&dr, (size_t)n * read_words * 4 + 32));
-  GM_HIP(hipMalloc(&dgo, (size_t)n * 8)); GM_HIP(hipMalloc(&dgl, (size_t)n * 4)); GM_HIP(hipMalloc(&drl, (size_t)n * 4)); GM_HIP(hipMalloc(&ds, (size_t)n * 4));
-  GM_HIP(hipMemset(dg, 0, (genome_words + 8) * 4));
-  GM_HIP(hipMemcpy(dg, genome, genome_words * 4, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(dr, reads, (size_t)n * read_words * 4, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(dgo, g_off, (size_t)n * 8, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(dgl, glen, (size_t)n * 4, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(drl, rlen, (size_t)n * 4, hipMemcpyHostToDevice));
-  uint8_t* dst = nullptr;
-  if (stopped) GM_HIP(hipMalloc(&dst, (size_t)n));
-  // (the early stop needs a scheme in which a cell gains at most `match` and gaps cost: otherwise every window runs to its end)
-  const GmScoreDev& sv = g_sv.sc;
-  if (!(sv.match > 0 && sv.mismatch <= sv.match && sv.a_go >= 0 && sv.a_ge >= 0 && sv.b_go >= 0 && sv.b_ge >= 0 && sv.match * (2 * 128 + 2) < 32000)) early_thr = 0;
-  int rc = gm_launch_sw_vector_batch(g_sv.sc, n, dg, dgo, dgl, dr, read_words, drl, max_g, max_r, ds, 0, early_thr, dst);
-  if (rc == GM_OK) {
-    GM_HIP(hipDeviceSynchronize()); GM_HIP(hipMemcpy(scores, ds, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (stopped) GM_HIP(hipMemcpy(stopped, dst, (size_t)n, hipMemcpyDeviceToHost));
-  }
-  (void)hipFree(dg); (void)hipFree(dr); (void)hipFree(dgo); (void)hipFree(dgl); (void)hipFree(drl); (void)hipFree(ds); if (dst) (void)hipFree(dst);
-  for (int i = 0; i < n; i++) { g_sv.invocs++; g_sv.cells += (uint64_t)glen[i] * rlen[i]; }
-  return rc;
-}
-extern "C" int gm_sw_vector_batch(int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen,
-                                  const uint32_t* reads, int read_words, const int* rlen, int* scores) {
-  return sw_vector_batch_impl(n, genome, genome_words, g_off, glen, reads, read_words, rlen, scores, 0, nullptr);
-}
-extern "C" int gm_sw_vector_batch_bounded(int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen,
-                                          const uint32_t* reads, int read_words, const int* rlen, int threshold, int* scores, uint8_t* stopped) {
-  if (threshold <= 0 || !stopped) { gm_set_error("gm_sw_vector_batch_bounded: threshold > 0 and a stopped[] array are required"); return GM_E_ARG; }
-  return sw_vector_batch_impl(n, genome, genome_words, g_off, glen, reads, read_words, rlen, scores, threshold, stopped);
-}
-
-extern "C" int sw_vector(uint32_t* genome, int goff, int glen, uint32_t* read, int rlen, uint32_t* genome_ls, int initbp, bool is_rna) {
-  if (!g_sv.init) abort();   // ref: sw-vector.c:462-463
-  // is_rna only matters to the colour-space first-colour row (lstocs(genome_ls[j], initbp, is_rna), ref: sw-vector.c:129,289): it rides in bit 8 of the primer word
-  if (is_rna && genome_ls) initbp |= GM_SEAM_RNA;
-  int64_t go = goff; int score = 0;
-  const uint64_t gw = ((uint64_t)goff + glen + 7) / 8;
-  if (g_sv.colours) {        // colour space: genome = colours, genome_ls = letters of the same contig (ref: sw-vector.c:476-479)
-    if (!genome_ls) { gm_set_error("sw_vector: colour space needs genome_ls"); return GM_E_ARG; }
-    int rc = gm_sw_vector_batch_cs(1, genome, genome_ls, gw, &go, &glen, read, (rlen + 7) / 8, &rlen, &initbp, &score);
-    return rc == GM_OK ? score : rc;
-  }
-  int rc = gm_sw_vector_batch(1, genome, gw, &go, &glen, read, (rlen + 7) / 8, &rlen, &score);
-  return rc == GM_OK ? score : rc;
-}
-
-// ---- S1, ungapped: sw_gapless on caller bitfields (ref: common/sw-gapless.h:11-14, sw-gapless.c:29-117) -----------------------------
-// What f1_setup / f1_run call when gapless_sw is set (ref: f1-wrapper.h:66-68,122-125).  State per calling thread, like the reference's threadprivate statics.
-struct SwGaplessState { bool init = false; int match = 0, mismatch = 0; uint64_t invocs = 0, cells = 0, ticks = 0; };
-static thread_local SwGaplessState g_sg;
-extern "C" int sw_gapless_setup(int match, int mismatch, bool reset_stats) {
-  if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
-  g_sg.match = match; g_sg.mismatch = mismatch; g_sg.init = true;
-  if (reset_stats) g_sg.invocs = g_sg.cells = g_sg.ticks = 0;
-  return 0;
-}
-extern "C" void sw_gapless_stats(uint64_t* invocs, uint64_t* cells, uint64_t* ticks) {      // (ticks: nanoseconds spent inside sw_gapless on this thread; the reference counts rdtsc ticks)
-  if (invocs) *invocs = g_sg.invocs; if (cells) *cells = g_sg.cells; if (ticks) *ticks = g_sg.ticks;
-}
-// n independent calls; call i's genome bitfield starts at word genome_woff[i] of `genome` (and of `genome_ls`, colour space only: then `genome` holds colours,
-// `genome_ls` the letters of the same contig and initbp[i] the read's primer letter) and holds glen[i] positions
-// device buffers released when the holder goes out of scope
-struct GmDevBufs { std::vector<void*> p; ~GmDevBufs() { for (void* q : p) if (q) (void)hipFree(q); }
-                   template <class T> hipError_t get(T** out, size_t bytes) { void* q = nullptr; const hipError_t e = hipMalloc(&q, bytes); if (e == hipSuccess) { p.push_back(q); *out = (T*)q; } return e; } };
-extern "C" int gm_sw_gapless_batch(int n, const uint32_t* genome, const uint32_t* genome_ls, uint64_t genome_words, const int64_t* genome_woff, const int* glen,
-                                   const uint32_t* reads, int read_words, const int* rlen, const int* g_idx, const int* r_idx, const int* initbp, int* scores) {
-  if (!g_sg.init) { gm_set_error("sw_gapless called before sw_gapless_setup"); return GM_E_NOTSETUP; }
-  if (n <= 0) return GM_OK;
-  if (genome_ls && !initbp) { gm_set_error("gm_sw_gapless_batch: colour space needs initbp"); return GM_E_ARG; }
-  int max_r = 0;
-  for (int i = 0; i < n; i++) {
-    if (glen[i] < 1 || rlen[i] < 1 || g_idx[i] < 0 || r_idx[i] < 0 || g_idx[i] >= glen[i] || r_idx[i] >= rlen[i] || genome_woff[i] < 0 ||
-        (uint64_t)genome_woff[i] + ((uint64_t)glen[i] + 7) / 8 > genome_words || (rlen[i] + 7) / 8 > read_words) { gm_set_error("gm_sw_gapless_batch: call %d out of range", i); return GM_E_ARG; }
-    max_r = std::max(max_r, rlen[i]);
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  GmDevBufs bufs;      // (owns every device buffer below: a failing call in the middle returns without leaking the ones allocated before it)
-  uint32_t *dg = nullptr, *dgl = nullptr, *dr = nullptr; long long* dwo = nullptr; int *dn = nullptr, *drl = nullptr, *dgi = nullptr, *dri = nullptr, *dib = nullptr, *ds = nullptr;
-  GM_HIP(bufs.get(&dg, (genome_words + 8) * 4)); GM_HIP(hipMemset(dg, 0, (genome_words + 8) * 4)); GM_HIP(hipMemcpy(dg, genome, genome_words * 4, hipMemcpyHostToDevice));
-  if (genome_ls) { GM_HIP(bufs.get(&dgl, (genome_words + 8) * 4)); GM_HIP(hipMemset(dgl, 0, (genome_words + 8) * 4)); GM_HIP(hipMemcpy(dgl, genome_ls, genome_words * 4, hipMemcpyHostToDevice)); }
-  GM_HIP(bufs.get(&dr, (size_t)n * read_words * 4 + 32)); GM_HIP(hipMemcpy(dr, reads, (size_t)n * read_words * 4, hipMemcpyHostToDevice));
-  GM_HIP(bufs.get(&dwo, (size_t)n * 8)); GM_HIP(hipMemcpy(dwo, genome_woff, (size_t)n * 8, hipMemcpyHostToDevice));
-  int** const dst[5] = {&dn, &drl, &dgi, &dri, &dib}; const int* const src[5] = {glen, rlen, g_idx, r_idx, initbp};
-  for (int k = 0; k < 5; k++) { if (!src[k]) continue; GM_HIP(bufs.get(dst[k], (size_t)n * 4)); GM_HIP(hipMemcpy(*dst[k], src[k], (size_t)n * 4, hipMemcpyHostToDevice)); }
-  GM_HIP(bufs.get(&ds, (size_t)n * 4));
-  int rc = gm_launch_sw_gapless_batch(n, g_sg.match, g_sg.mismatch, dg, dgl, dwo, dn, dr, read_words, drl, dgi, dri, dib, max_r, ds, 0);
-  if (rc == GM_OK) { GM_HIP(hipDeviceSynchronize()); GM_HIP(hipMemcpy(scores, ds, (size_t)n * 4, hipMemcpyDeviceToHost)); }
-  if (rc == GM_OK) {                                                                             // (a failed launch scored nothing: it does not count)
-    for (int i = 0; i < n; i++) { g_sg.invocs++; g_sg.cells += (uint64_t)rlen[i]; }              // ref: sw-gapless.c:111 (cells += rlen)
-    g_sg.ticks += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return rc;
-}
-extern "C" int sw_gapless(uint32_t* genome, int glen, uint32_t* read, int rlen, int g_idx, int r_idx, uint32_t* genome_ls, int init_bp, bool is_rna) {
-  if (!g_sg.init) abort();   // ref: sw-gapless.c:66-67
-  if (is_rna && genome_ls) init_bp |= GM_SEAM_RNA;      // lstocs(letter, init_bp, is_rna), ref: sw-gapless.c:84
-  int64_t wo = 0; int score = 0;
-  int rc = gm_sw_gapless_batch(1, genome, genome_ls, ((uint64_t)glen + 7) / 8, &wo, &glen, read, (rlen + 7) / 8, &rlen, &g_idx, &r_idx, genome_ls ? &init_bp : nullptr, &score);
-  return rc == GM_OK ? score : rc;
-}
-
-// ---- S2: full SW on caller bitfields ------------------------------------------------------------
-struct SwFullState { bool init = false; GmScoreDev sc; int dblen = 0, qrlen = 0; uint64_t invocs = 0, cells = 0; double secs = 0; };
-static thread_local SwFullState g_sf;
-static const char LSTRANS[17] = "ACGTUMRWSYKVHDBN";   // base_translate, ref: common/fasta.c:689-690
-
-extern "C" int sw_full_ls_setup(int dblen, int qrlen, int a_gap_open, int a_gap_ext, int b_gap_open, int b_gap_ext,
-                                int match, int mismatch, bool reset_stats, int anchor_width) {
-  if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
-  gm_params_t P; gm_params_default(&P);
-  P.match_score = match; P.mismatch_score = mismatch; P.a_gap_open_score = a_gap_open; P.a_gap_extend_score = a_gap_ext;
-  P.b_gap_open_score = b_gap_open; P.b_gap_extend_score = b_gap_ext; P.anchor_width = anchor_width;
-  g_sf.sc = make_score(P); g_sf.dblen = dblen; g_sf.qrlen = qrlen; g_sf.init = true;
-  if (reset_stats) { g_sf.invocs = g_sf.cells = 0; g_sf.secs = 0; }
-  return 0;
-}
-extern "C" int sw_full_ls_cleanup(void) { g_sf.init = false; return 0; }
-// invocations, cells (window x read, the upper bound of the band the reference counts, ref: sw-full-ls.c:237) and seconds spent inside sw_full_ls on this thread
-extern "C" void sw_full_ls_stats(uint64_t* invocs, uint64_t* cells, double* secs) {
-  if (invocs) *invocs = g_sf.invocs; if (cells) *cells = g_sf.cells; if (secs) *secs = g_sf.secs;
-}
-struct SeamTimer { double* acc; std::chrono::steady_clock::time_point t0; explicit SeamTimer(double* a) : acc(a), t0(std::chrono::steady_clock::now()) {}
-                   ~SeamTimer() { *acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } };
-
-extern "C" void sw_full_ls(uint32_t* genome, int goff, int glen, uint32_t* read, int rlen, int threshscore, int maxscore,
-                           struct gm_sw_full_results* sfr, bool revcmpl, struct gm_anchor* anchors, int anchors_cnt, int local_alignment) {
-  if (!g_sf.init) abort();   // ref: sw-full-ls.c:649-650
-  SeamTimer tm(&g_sf.secs); g_sf.invocs++; g_sf.cells += (uint64_t)std::max(glen, 0) * (uint64_t)std::max(rlen, 0);
-  if ((anchors != nullptr && anchors_cnt != 1) || glen > g_sf.dblen || rlen > g_sf.qrlen || glen < 1 || rlen < 1) {
-    gm_set_error("sw_full_ls: one anchor box (gmapper's call, ref: mapping.c:391-394) or none (the threshold band) is implemented");
-    sfr->score = 0; sfr->dbalign = strdup(""); sfr->qralign = strdup(""); return;
-  }
-  const uint64_t gw = ((uint64_t)goff + glen + 7) / 8 + 8; const int rwords = (rlen + 7) / 8 + 1;
-  const int ops_cap = glen + rlen + 8;
-  uint32_t *dg = nullptr, *dr = nullptr; uint8_t *dback = nullptr, *dops = nullptr; int* dout = nullptr;
-  bool ok = hipMalloc(&dg, gw * 4) == hipSuccess && hipMalloc(&dr, (size_t)rwords * 4) == hipSuccess &&
-            hipMalloc(&dback, (size_t)glen * rlen + 256) == hipSuccess && hipMalloc(&dops, ops_cap) == hipSuccess && hipMalloc(&dout, 16 * 4) == hipSuccess;
-  int out[16] = {0}; std::vector<uint8_t> ops(ops_cap);
-  if (ok) {
-    ok = hipMemset(dg, 0, gw * 4) == hipSuccess && hipMemcpy(dg, genome, (gw - 8) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(dr, read, (size_t)(rwords - 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         gm_launch_sw_full_single(g_sf.sc, dg, goff, glen, dr, rlen, anchors ? anchors[0].x : 0, anchors ? anchors[0].y : 0, anchors ? anchors[0].length : 1,
-                                  anchors ? anchors[0].width : 1, revcmpl ? 1 : 0, dback, dout, dops, ops_cap, 0, anchors ? 1 : 0, threshscore, maxscore,
-                                  local_alignment ? 1 : 0) == GM_OK &&
-         hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, sizeof out, hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(ops.data(), dops, ops_cap, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  (void)hipFree(dg); (void)hipFree(dr); (void)hipFree(dback); (void)hipFree(dops); (void)hipFree(dout);
-  if (!ok) { gm_set_error("sw_full_ls: HIP failure"); sfr->score = 0; sfr->dbalign = strdup(""); sfr->qralign = strdup(""); return; }
-  sfr->score = out[0];
-  std::string db, qr;
-  if (out[0] > 0) {
-    sfr->read_start = out[1]; sfr->rmapped = out[2]; sfr->genome_start = out[3]; sfr->gmapped = out[4];
-    sfr->matches += out[5]; sfr->mismatches += out[6]; sfr->insertions += out[7]; sfr->deletions += out[8];
-    int pi = out[1], pj = out[3];   // pretty_print, ref: sw-full-ls.c:524-560 (genome_start already includes goff)
-    auto nib = [](const uint32_t* b, long long i) { return (int)((b[i / 8] >> (4 * (i % 8))) & 0xf); };
-    for (int k = 0; k < out[9]; k++) {
-      if (ops[k] == 'D') { db.push_back('-'); qr.push_back(LSTRANS[nib(read, pi++)]); }
-      else if (ops[k] == 'I') { db.push_back(LSTRANS[nib(genome, pj++)]); qr.push_back('-'); }
-      else { db.push_back(LSTRANS[nib(genome, pj++)]); qr.push_back(LSTRANS[nib(read, pi++)]); }
-    }
-  } else {   // the reference backtraces stale scratch here; every caller discards it (score 0 < threshold)
-    sfr->rmapped = 1; sfr->gmapped = 1; sfr->genome_start = goff;
-  }
-  sfr->dbalign = strdup(db.c_str()); sfr->qralign = strdup(qr.c_str());
-}
-
-extern "C" int gm_sw_vector_batch_cs(int n, const uint32_t* genome_cs, const uint32_t* genome_ls, uint64_t genome_words, const int64_t* g_off,
-                                     const int* glen, const uint32_t* reads, int read_words, const int* rlen, const int* initbp, int* scores) {
-  if (!g_sv.init) { gm_set_error("sw_vector called before sw_vector_setup"); return GM_E_NOTSETUP; }
-  if (n <= 0) return GM_OK;
-  int max_g = 0, max_r = 0;
-  for (int i = 0; i < n; i++) { max_g = std::max(max_g, glen[i]); max_r = std::max(max_r, rlen[i]); if (glen[i] < 1 || rlen[i] < 1 || initbp[i] < 0 || (initbp[i] & ~GM_SEAM_RNA) > 3) return GM_E_ARG; }
-  if (max_g > g_sv.dblen || max_r > g_sv.qrlen) { gm_set_error("window/read longer than sw_vector_setup sizes"); return GM_E_ARG; }
-  uint32_t *dgc = nullptr, *dgl = nullptr, *dr = nullptr; long long* dgo = nullptr; int *dgn = nullptr, *drl = nullptr, *dib = nullptr, *ds = nullptr;
-  GM_HIP(hipMalloc(&dgc, (genome_words + 8) * 4)); GM_HIP(hipMalloc(&dgl, (genome_words + 8) * 4)); GM_HIP(hipMalloc(&dr, (size_t)n * read_words * 4 + 32));
-  GM_HIP(hipMalloc(&dgo, (size_t)n * 8)); GM_HIP(hipMalloc(&dgn, (size_t)n * 4)); GM_HIP(hipMalloc(&drl, (size_t)n * 4)); GM_HIP(hipMalloc(&dib, (size_t)n * 4)); GM_HIP(hipMalloc(&ds, (size_t)n * 4));
-  GM_HIP(hipMemset(dgc, 0, (genome_words + 8) * 4)); GM_HIP(hipMemset(dgl, 0, (genome_words + 8) * 4));
-  GM_HIP(hipMemcpy(dgc, genome_cs, genome_words * 4, hipMemcpyHostToDevice)); GM_HIP(hipMemcpy(dgl, genome_ls, genome_words * 4, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(dr, reads, (size_t)n * read_words * 4, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(dgo, g_off, (size_t)n * 8, hipMemcpyHostToDevice)); GM_HIP(hipMemcpy(dgn, glen, (size_t)n * 4, hipMemcpyHostToDevice));
-  GM_HIP(hipMemcpy(drl, rlen, (size_t)n * 4, hipMemcpyHostToDevice)); GM_HIP(hipMemcpy(dib, initbp, (size_t)n * 4, hipMemcpyHostToDevice));
-  int rc = gm_launch_sw_vector_batch_cs(g_sv.sc, n, dgc, dgl, dgo, dgn, dr, read_words, drl, dib, max_g, max_r, ds, 0);
-  if (rc == GM_OK) { GM_HIP(hipDeviceSynchronize()); GM_HIP(hipMemcpy(scores, ds, (size_t)n * 4, hipMemcpyDeviceToHost)); }
-  (void)hipFree(dgc); (void)hipFree(dgl); (void)hipFree(dr); (void)hipFree(dgo); (void)hipFree(dgn); (void)hipFree(drl); (void)hipFree(dib); (void)hipFree(ds);
-  for (int i = 0; i < n; i++) { g_sv.invocs++; g_sv.cells += (uint64_t)glen[i] * rlen[i]; }
-  return rc;
-}
-
-// ---- S2 in colour space: sw_full_cs on caller bitfields (ref: common/sw-full-cs.c:1084-1236) --------------
-struct SwFullCsState { bool init = false; int p[9]; int dblen = 0, qrlen = 0; uint64_t invocs = 0, cells = 0; double secs = 0; };
-static thread_local SwFullCsState g_sc;
-extern "C" int sw_full_cs_setup(int dblen, int qrlen, int a_gap_open, int a_gap_ext, int b_gap_open, int b_gap_ext,
-                                int match, int mismatch, int global_xover_penalty, bool reset_stats, int anchor_width, int indel_taboo_len) {
-  if (reset_stats) { g_sc.invocs = g_sc.cells = 0; g_sc.secs = 0; }
-  if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
-  const int p[9] = {match, mismatch, global_xover_penalty, -a_gap_open, -a_gap_ext, -b_gap_open, -b_gap_ext, anchor_width, indel_taboo_len};
-  memcpy(g_sc.p, p, sizeof p); g_sc.dblen = dblen; g_sc.qrlen = qrlen; g_sc.init = true;
-  return 0;
-}
-extern "C" int sw_full_cs_cleanup(void) { g_sc.init = false; return 0; }
-extern "C" void sw_full_cs_stats(uint64_t* invocs, uint64_t* cells, double* secs) {   // ref: sw-full-cs.c:1127-1140 (cells: window x read x 4 layers here)
-  if (invocs) *invocs = g_sc.invocs; if (cells) *cells = g_sc.cells; if (secs) *secs = g_sc.secs;
-}
-
-extern "C" void sw_full_cs(uint32_t* genome_ls, int goff, int glen, uint32_t* read, int rlen, int initbp, int threshscore,
-                           struct gm_sw_full_results* sfr, bool revcmpl, bool is_rna, struct gm_anchor* anchors, int anchors_cnt,
-                           int local_alignment, int* crossover_score) {
-  if (!g_sc.init) abort();   // ref: sw-full-cs.c:1155-1156
-  SeamTimer tm(&g_sc.secs); g_sc.invocs++; g_sc.cells += 4ull * (uint64_t)std::max(glen, 0) * (uint64_t)std::max(rlen, 0);
-  // A refusal must not read as "no alignment" (score 0 is what a window below the threshold returns): the reason goes to stderr as well as to gm_last_error().
-  auto fail = [&](const char* why) { gm_set_error("sw_full_cs: %s", why); fprintf(stderr, "gmapper_hip: sw_full_cs refused: %s\n", why); sfr->score = 0; sfr->dbalign = nullptr; sfr->qralign = nullptr; };
-  if (anchors == nullptr || anchors_cnt != 1 || glen > g_sc.dblen || rlen > g_sc.qrlen || glen < 1 || rlen < 1 ||
-      initbp < 0 || initbp > 3 || g_sc.p[7] < 0) {
-    fail("only one anchor box (gmapper's call, ref: mapping.c:375-379) is implemented"); return;
-  }
-  // crossover_score: one score per read position (from the QVs, ref: gmapper.c:532-544 -- clamped there to [2 * global, -1]); the kernels keep a row of them in 8 bits
-  std::vector<int8_t> xrow;
-  if (crossover_score) {
-    xrow.resize((size_t)rlen + 16, 0);
-    for (int i = 0; i < rlen; i++) {
-      if (crossover_score[i] < -128 || crossover_score[i] > 127) { fail("a per-position crossover score outside [-128, 127] (the device keeps them in 8 bits)"); return; }
-      xrow[i] = (int8_t)crossover_score[i];
-    }
-  }
-  const uint64_t gw = ((uint64_t)goff + glen + 7) / 8 + 8; const int rwords = (rlen + 7) / 8 + 1;
-  const int ops_cap = glen + rlen + 8;
-  const size_t back_bytes = ((size_t)glen * rlen * 3 + 64) * 4;
-  uint32_t *dg = nullptr, *dr = nullptr, *dback = nullptr; uint8_t* dops = nullptr; int* dout = nullptr; int8_t* dx = nullptr;
-  bool ok = hipMalloc(&dg, gw * 4) == hipSuccess && hipMalloc(&dr, (size_t)rwords * 4) == hipSuccess && hipMalloc(&dback, back_bytes) == hipSuccess &&
-            hipMalloc(&dops, ops_cap) == hipSuccess && hipMalloc(&dout, 16 * 4) == hipSuccess && (xrow.empty() || hipMalloc(&dx, xrow.size()) == hipSuccess);
-  int out[16] = {0}; std::vector<uint8_t> ops(ops_cap);
-  if (ok) {
-    ok = hipMemset(dg, 0, gw * 4) == hipSuccess && hipMemcpy(dg, genome_ls, (gw - 8) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemset(dr, 0, (size_t)rwords * 4) == hipSuccess && hipMemcpy(dr, read, (size_t)(rwords - 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         (!dx || hipMemcpy(dx, xrow.data(), xrow.size(), hipMemcpyHostToDevice) == hipSuccess) &&
-         hipMemset(dback, 0, back_bytes) == hipSuccess &&                                     // out-of-band cells: back == 0 (ref: init_cell)
-         gm_launch_sw_full_cs_single(g_sc.p, dg, goff, glen, dr, rlen, initbp | (is_rna ? GM_SEAM_RNA : 0), threshscore, anchors[0].x, anchors[0].y, anchors[0].length, anchors[0].width,
-                                     revcmpl ? 1 : 0, dback, dout, dops, ops_cap, 0, local_alignment ? 1 : 0, dx) == GM_OK &&
-         hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, 12 * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(ops.data(), dops, ops_cap, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  (void)hipFree(dg); (void)hipFree(dr); (void)hipFree(dback); (void)hipFree(dops); (void)hipFree(dout); (void)hipFree(dx);
-  if (!ok) { fail("HIP failure"); return; }
-  sfr->score = out[0];
-  if (out[0] <= 0) { sfr->score = 0; sfr->dbalign = nullptr; sfr->qralign = nullptr; return; }          // below threshold: no strings (ref :1224-1226)
-  sfr->read_start = out[1]; sfr->rmapped = out[2]; sfr->genome_start = out[3]; sfr->gmapped = out[4];
-  sfr->matches += out[5]; sfr->mismatches += out[6]; sfr->insertions += out[7]; sfr->deletions += out[8]; sfr->crossovers += out[9];
-  // pretty_print, ref :945-1060: the four translations of the colour read, lower case on crossovers, N in the read shows the genome letter
-  auto nib = [](const uint32_t* b, long long i) { return (int)((b[i / 8] >> (4 * (i % 8))) & 0xf); };
-  std::vector<uint8_t> qr[4];
-  for (int k = 0; k < 4; k++) {
-    qr[k].resize(rlen); int letter = (k + initbp) % 4;
-    for (int j = 0; j < rlen; j++) {
-      const int base = nib(read, j);
-      if (base == 15) { qr[k][j] = 15; letter = (k + initbp) % 4; }
-      else {                                                   // cstols(letter, base, is_rna), ref: util.h:157-180
-        const int lt = (is_rna && letter == 4) ? 3 : letter;
-        int l2 = (lt % 2 == 0) ? ((4 + lt + base) % 4) : ((4 + lt - base) % 4); if (is_rna && l2 == 3) l2 = 4;
-        qr[k][j] = (uint8_t)((letter == 15 || base > 3) ? 15 : l2); letter = qr[k][j];
-      }
-    }
-  }
-  std::string db, q;
-  int pi = out[1], pj = out[3];
-  for (int t = 0; t < std::min(out[10], ops_cap); t++) {
-    const int type = ops[t] & 0x0f; const bool xov = (ops[t] & 0x80) != 0;
-    if (type == 1) { db.push_back(LSTRANS[nib(genome_ls, pj++)]); q.push_back('-'); continue; }
-    const bool del = type >= 2 && type <= 5;
-    const int lay = del ? type - 2 : type - 6;
-    char c = LSTRANS[qr[lay][pi++]];
-    if (xov) c = (char)tolower((int)c);
-    if (del) { db.push_back('-'); q.push_back(c); }
-    else { const char d = LSTRANS[nib(genome_ls, pj++)]; if (c == 'n' || c == 'N') c = xov ? (char)tolower((int)d) : d; db.push_back(d); q.push_back(c); }
-  }
-  sfr->dbalign = strdup(db.c_str()); sfr->qralign = strdup(q.c_str());
-}
-
-// ---- S2 batch: gm_sw_full_ls_batch / gm_sw_full_cs_batch -----------------------------------------------------------------------------
-// One call = a fixed number of device buffers (genome, reads, items, results, ops, back-pointer scratch, crossover rows), copies and launches.  The scratch is
-// grid x (largest glen x rlen of the launch), never the sum over the items; when that passes GM_SWF_BACK_BUDGET with the grid the items would fill, the items are
-// sorted into at most three launches by matrix size (so that a few large windows do not starve the many small ones of waves) that share the one scratch.
-static const size_t GM_SWF_BACK_BUDGET = (size_t)512 << 20;
-static const int GM_SWF_MAX_GRID = 2048;
-struct SwfLaunch { int first = 0, count = 0, grid = 0, max_g = 0, max_r = 0; size_t stride = 0; };
-// items (accepted ones only) are reordered by class; unit = scratch bytes a cell; *pool = bytes of the shared scratch
-static void swf_plan(std::vector<GmFullItem>& items, size_t unit, std::vector<SwfLaunch>& launches, size_t* pool) {
-  launches.clear(); *pool = 0;
-  if (items.empty()) return;
-  auto cells = [](const GmFullItem& it) { return (size_t)it.glen * (size_t)it.rlen; };
-  size_t M = 0; for (const GmFullItem& it : items) M = std::max(M, cells(it));
-  int want = (int)std::min<size_t>(items.size(), (size_t)GM_SWF_MAX_GRID);
-  if (gm_tune("GM_SWF_SLOTS") && atoi(gm_tune("GM_SWF_SLOTS")) > 0) want = std::min(want, atoi(gm_tune("GM_SWF_SLOTS")));      // (tuning build: few slots, i.e. many items of all shapes through each)
-  std::vector<size_t> bound;                                  // a class takes the items of at most this many cells that no earlier class took
-  if ((size_t)want * (M * unit + 256) > GM_SWF_BACK_BUDGET) { bound = {M / 64, M / 8, M}; } else bound = {M};
-  std::vector<GmFullItem> sorted; sorted.reserve(items.size());
-  size_t lo = 0;
-  for (size_t b : bound) {
-    SwfLaunch L; L.first = (int)sorted.size(); size_t mc = 0;
-    for (const GmFullItem& it : items) { const size_t c = cells(it); if (c > lo && c <= b) { sorted.push_back(it); mc = std::max(mc, c); L.max_g = std::max(L.max_g, it.glen); L.max_r = std::max(L.max_r, it.rlen); } }
-    lo = b;
-    L.count = (int)sorted.size() - L.first;
-    if (!L.count) continue;
-    L.stride = (mc * unit + 256 + 15) & ~(size_t)15;
-    L.grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(want, L.count), GM_SWF_BACK_BUDGET / L.stride));
-    *pool = std::max(*pool, (size_t)L.grid * L.stride);
-    launches.push_back(L);
-  }
-  items.swap(sorted);
-}
-static inline int swf_nib(const uint32_t* b, long long i) { return (int)((b[i / 8] >> (4 * (i % 8))) & 0xf); }
-
-
-// ---- index-resident seams: one window as the reference addresses it ------------------------------------------------------------------------------------------
-// Checks (cn, gen_st, g_off, glen) against the index before anything is read through it and turns it into the forward coordinates the kernels take.  whole_contig
-// (the gapless seam, the post form's contig bounds): g_off and glen are not looked at, the window is the whole contig of the strand.  Returns the reason of a
-// refusal, or null.
-static const char* ix_window(const gm_index* ix, int cn, int gen_st, int64_t g_off, int glen, GmWin* w, bool whole_contig = false) {
-  if (cn < 0 || cn >= ix->n_contigs) return "cn outside the index's contigs";
-  if (gen_st > 1) return "gen_st is neither 0 nor 1";
-  const int64_t clen = (int64_t)ix->contig_off[cn + 1] - (int64_t)ix->contig_off[cn];
-  if (whole_contig) { g_off = 0; glen = (int)std::min<int64_t>(clen, INT_MAX); }
-  if (g_off < 0) return "g_off < 0";
-  if (glen < 1) return "glen < 1";
-  if (g_off > clen || (int64_t)glen > clen - g_off) return "the window runs past the end of the contig";
-  w->cn = cn; w->rc = gen_st ? 1 : 0; w->glen = glen; w->foff = (uint32_t)(gen_st ? clen - g_off - glen : g_off);
-  return nullptr;
-}
-// What every _ix entry does first: the index's device (the caller's current device is set back when the scope ends), its RNA flags (once per index, under
-// gm_index_derive_rna's lock), the view the kernels take with the call's is_rna (-1: the index's own)
-struct IxScope {
-  int prev = -1; GmIndexDev view;
-  int enter(const gm_index_t* ix, int is_rna) {
-    GM_HIP(hipGetDevice(&prev));
-    GM_HIP(hipSetDevice(ix->device));
-    { const int rc = gm_index_derive_rna(const_cast<gm_index*>(ix), nullptr); if (rc) return rc; }
-    view = ix->dev_view();
-    view.genome_is_rna = is_rna < 0 ? ix->genome_is_rna : (is_rna ? 1 : 0);
-    return GM_OK;
-  }
-  ~IxScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// shared body: colour = gm_sw_full_cs_batch; ix: the _ix forms -- window i is (cn, gen_st, g_off, glen) of the resident genome, nothing of it is uploaded
-static int sw_full_batch_impl(bool colour, int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen, const uint32_t* reads, int read_words,
-                              const int* rlen, const uint8_t* initbp, const struct gm_anchor* anchors, const uint8_t* revcmpl, const int* threshscore, const int* maxscore,
-                              const int* xover, int xover_stride, int is_rna, int local, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len,
-                              const gm_index_t* ix = nullptr, const int* cn = nullptr, const uint8_t* gen_st = nullptr) {
-  const char* who = ix ? (colour ? "gm_sw_full_cs_batch_ix" : "gm_sw_full_ls_batch_ix") : (colour ? "gm_sw_full_cs_batch" : "gm_sw_full_ls_batch");
-  if (ops) *ops = nullptr; if (ops_len) *ops_len = 0;
-  if (colour ? !g_sc.init : !g_sf.init) { gm_set_error("%s called before sw_full_%s_setup", who, colour ? "cs" : "ls"); return GM_E_NOTSETUP; }
-  if (n <= 0) return GM_OK;
-  if ((ix ? (!cn || !gen_st) : !genome) || !g_off || !glen || !reads || !rlen || !threshscore || !recs || !ops || !ops_len || read_words < 1 || (colour && !initbp) ||
-      (xover && xover_stride < 1) || (!colour && local && !maxscore)) { gm_set_error("%s: a required argument is missing", who); return GM_E_ARG; }
-  SeamTimer tm(colour ? &g_sc.secs : &g_sf.secs);
-  IxScope scope;
-  if (ix) { const int rc = scope.enter(ix, is_rna); if (rc) return rc; is_rna = scope.view.genome_is_rna; }
-  auto win_of = [&](int i, GmWin* w) -> const char* { return ix_window(ix, cn[i], gen_st[i], g_off[i], glen[i], w); };      // (index forms only)
-  const int dblen = colour ? g_sc.dblen : g_sf.dblen, qrlen = colour ? g_sc.qrlen : g_sf.qrlen;
-  std::vector<GmFullItem> items; items.reserve(n);
-  std::vector<int8_t> xrows;
-  const int xstride = xover ? ((xover_stride + 15) & ~15) : 0;
-  if (xover) xrows.assign((size_t)n * xstride, 0);
-  unsigned long long ops_total = 0;
-  // LDS is laid out for the longest read and the longest window of a launch, which may belong to different items: an item is admitted when its window fits beside the
-  // longest read of the call that is otherwise in order (so whatever the launch classes turn out to be, each fits)
-  auto in_order = [&](int i) { return glen[i] >= 1 && rlen[i] >= 1 && g_off[i] >= 0 && (ix ? [&] { GmWin w; return !win_of(i, &w); }() : (uint64_t)g_off[i] + (uint64_t)glen[i] <= genome_words * 8) &&
-                                      ((uint64_t)rlen[i] + 7) / 8 <= (uint64_t)read_words && glen[i] <= dblen && rlen[i] <= qrlen; };
-  int call_max_r = 1;
-  for (int i = 0; i < n; i++) if (in_order(i)) call_max_r = std::max(call_max_r, rlen[i]);
-  for (int i = 0; i < n; i++) {
-    gm_sw_full_rec_t& R = recs[i]; memset(&R, 0, sizeof R);
-    auto refuse = [&](int code, const char* why) { R.status = code; gm_set_error("%s: item %d refused: %s", who, i, why); };
-    GmWin win;                                                                        // this item's window on the index
-    if (ix) { if (const char* why = win_of(i, &win)) { refuse(GM_E_ARG, why); continue; } }
-    if (glen[i] < 1 || rlen[i] < 1 || g_off[i] < 0 || (!ix && (uint64_t)g_off[i] + (uint64_t)glen[i] > genome_words * 8) || ((uint64_t)rlen[i] + 7) / 8 > (uint64_t)read_words) {
-      refuse(GM_E_ARG, "window or read outside the bitfields"); continue; }
-    if (glen[i] > dblen || rlen[i] > qrlen) { refuse(GM_E_ARG, "window / read longer than the setup sizes"); continue; }
-    const bool has_anchor = anchors && anchors[i].length > 0;
-    if (colour) {
-      if (!has_anchor || g_sc.p[7] < 0) { refuse(GM_E_ARG, "colour space needs one anchor box (gmapper's call, ref: mapping.c:375-379)"); continue; }
-      if (initbp[i] > 3) { refuse(GM_E_ARG, "initbp outside 0..3"); continue; }
-      if (gm_sw_full_cs_batch_lds(glen[i], call_max_r) > GM_SWF_LDS_LIMIT) { refuse(GM_E_ARG, "the window does not fit LDS (48 bytes a column) beside the call's longest read"); continue; }
-      if (xover) {
-        if (xover_stride < rlen[i]) { refuse(GM_E_ARG, "xover_stride shorter than the read"); continue; }
-        bool ok = true;
-        for (int k = 0; k < rlen[i]; k++) { const int v = xover[(size_t)i * xover_stride + k]; if (v < -128 || v > 127) { ok = false; break; } xrows[(size_t)i * xstride + k] = (int8_t)v; }
-        if (!ok) { refuse(GM_E_RANGE, "a per-position crossover score outside [-128, 127] (the device keeps them in 8 bits)"); continue; }
-      }
-    } else if (gm_sw_full_batch_lds(glen[i], call_max_r) > GM_SWF_LDS_LIMIT) { refuse(GM_E_ARG, "the window does not fit LDS beside the call's longest read"); continue; }
-    GmFullItem it; memset(&it, 0, sizeof it);
-    it.goff = g_off[i]; it.glen = glen[i]; it.rlen = rlen[i];
-    if (has_anchor) { it.ax = anchors[i].x; it.ay = anchors[i].y; it.alen = anchors[i].length; it.awidth = anchors[i].width; } else { it.alen = it.awidth = 1; }
-    it.thresh = threshscore[i]; it.maxscore = maxscore ? maxscore[i] : 0;
-    it.flags = (has_anchor ? 1 : 0) | ((revcmpl && revcmpl[i]) ? 2 : 0);
-    if (ix) {
-      it.goff = (long long)ix->contig_off[win.cn] + (long long)win.foff;
-      it.flags |= (win.rc ? 4 : 0) | ((ix->rna_ready && ix->contig_rna[win.cn]) ? 8 : 0);
-    }
-    it.initbp = colour ? ((int)initbp[i] | (is_rna ? GM_SEAM_RNA : 0)) : 0;
-    it.ops_cap = glen[i] + rlen[i] + 8; it.ops_off = ops_total; it.idx = i;           // exclusive scan of the caps, in item order
-    ops_total += (unsigned long long)it.ops_cap;
-    items.push_back(it);
-  }
-  if (items.empty()) return GM_OK;
-  std::vector<SwfLaunch> launches; size_t pool = 0;
-  swf_plan(items, colour ? 12 : 1, launches, &pool);
-  GmDevBufs bufs;
-  uint32_t *dg = nullptr, *dr = nullptr; GmFullItem* di = nullptr; GmFullOut* dout = nullptr; uint8_t *dops = nullptr, *dback = nullptr; int8_t* dx = nullptr;
-  if (ix) dg = ix->d_genome; else GM_HIP(bufs.get(&dg, (genome_words + 8) * 4));
-  GM_HIP(bufs.get(&dr, (size_t)n * read_words * 4 + 32)); GM_HIP(bufs.get(&di, items.size() * sizeof(GmFullItem)));
-  GM_HIP(bufs.get(&dout, (size_t)n * sizeof(GmFullOut))); GM_HIP(bufs.get(&dops, (size_t)ops_total + 16)); GM_HIP(bufs.get(&dback, pool));
-  if (xover) GM_HIP(bufs.get(&dx, xrows.size() + 16));
-  if (!ix) {
-    GM_HIP(hipMemsetAsync(dg + genome_words, 0, 8 * 4, 0));
-    GM_HIP(hipMemcpyAsync(dg, genome, genome_words * 4, hipMemcpyHostToDevice, 0));
-  }
-  GM_HIP(hipMemcpyAsync(dr, reads, (size_t)n * read_words * 4, hipMemcpyHostToDevice, 0));
-  GM_HIP(hipMemcpyAsync(di, items.data(), items.size() * sizeof(GmFullItem), hipMemcpyHostToDevice, 0));
-  if (xover) GM_HIP(hipMemcpyAsync(dx, xrows.data(), xrows.size(), hipMemcpyHostToDevice, 0));
-  for (const SwfLaunch& L : launches) {
-    const int rc = colour ? gm_launch_sw_full_cs_batch(g_sc.p, L.first, L.count, L.grid, di, dg, dr, read_words, L.max_g, L.max_r, dx, xstride, (uint32_t*)dback, L.stride / 4, dout,
-                                                       dops, local ? 1 : 0, 0, ix ? 1 : 0)
-                          : gm_launch_sw_full_batch(g_sf.sc, L.first, L.count, L.grid, di, dg, dr, read_words, L.max_g, L.max_r, dback, L.stride, dout, dops, local ? 1 : 0, 0, ix ? 1 : 0);
-    if (rc != GM_OK) { (void)hipDeviceSynchronize(); return rc; }
-  }
-  std::vector<GmFullOut> out(n); std::vector<uint8_t> hops((size_t)ops_total);
-  GM_HIP(hipMemcpyAsync(hops.data(), dops, (size_t)ops_total, hipMemcpyDeviceToHost, 0));
-  GM_HIP(hipMemcpyAsync(out.data(), dout, (size_t)n * sizeof(GmFullOut), hipMemcpyDeviceToHost, 0));
-  GM_HIP(hipStreamSynchronize(0));
-  for (const GmFullItem& it : items) {                                               // (the items that ran: a refused item, or a call that failed before here, scored nothing)
-    if (colour) { g_sc.invocs++; g_sc.cells += 4ull * (uint64_t)it.glen * (uint64_t)it.rlen; }
-    else { g_sf.invocs++; g_sf.cells += (uint64_t)it.glen * (uint64_t)it.rlen; }
-  }
-  // the used lengths, compacted in item order
-  std::sort(items.begin(), items.end(), [](const GmFullItem& a, const GmFullItem& b) { return a.idx < b.idx; });
-  uint64_t used = 0;
-  for (const GmFullItem& it : items) { const int* v = out[it.idx].v; if (v[0] > 0) used += (uint64_t)std::min(v[10], it.ops_cap); }
-  uint8_t* obuf = (uint8_t*)malloc(used ? used : 1);
-  if (!obuf) { gm_set_error("%s: out of memory", who); return GM_E_NOMEM; }
-  uint64_t at = 0;
-  for (const GmFullItem& it : items) {
-    const int* v = out[it.idx].v; gm_sw_full_rec_t& R = recs[it.idx];
-    R.score = v[0];
-    if (v[0] > 0) {
-      R.read_start = v[1]; R.rmapped = v[2]; R.genome_start = g_off[it.idx] + v[3]; R.gmapped = v[4];      // (g_off: the caller's -- on the index, counted on the strand's contig)
-      R.matches = v[5]; R.mismatches = v[6]; R.insertions = v[7]; R.deletions = v[8]; R.crossovers = v[9];
-      R.n_ops = (uint32_t)std::min(v[10], it.ops_cap); R.ops_off = at;
-      memcpy(obuf + at, hops.data() + it.ops_off, R.n_ops); at += R.n_ops;
-    } else if (!colour) { R.score = v[0] < 0 ? 0 : v[0]; R.rmapped = 1; R.gmapped = 1; R.genome_start = g_off[it.idx]; R.ops_off = at; }      // as sw_full_ls leaves a window without alignment
-    else { R.score = 0; R.ops_off = at; }
-  }
-  *ops = obuf; *ops_len = used;
-  return GM_OK;
-}
-extern "C" int gm_sw_full_ls_batch(int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen, const uint32_t* reads, int read_words,
-                                   const int* rlen, const struct gm_anchor* anchors, const uint8_t* revcmpl, const int* threshscore, const int* maxscore,
-                                   int local_alignment, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len) {
-  return sw_full_batch_impl(false, n, genome, genome_words, g_off, glen, reads, read_words, rlen, nullptr, anchors, revcmpl, threshscore, maxscore, nullptr, 0, 0,
-                            local_alignment, recs, ops, ops_len);
-}
-extern "C" int gm_sw_full_cs_batch(int n, const uint32_t* genome_ls, uint64_t genome_words, const int64_t* g_off, const int* glen, const uint32_t* reads, int read_words,
-                                   const int* rlen, const uint8_t* initbp, const struct gm_anchor* anchors, const uint8_t* revcmpl, const int* threshscore,
-                                   const int* crossover_scores, int xover_stride, int is_rna, int local_alignment, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len) {
-  return sw_full_batch_impl(true, n, genome_ls, genome_words, g_off, glen, reads, read_words, rlen, initbp, anchors, revcmpl, threshscore, nullptr, crossover_scores,
-                            xover_stride, is_rna, local_alignment, recs, ops, ops_len);
-}
-// What gm_sw_full_batch_strings and gm_post_sw_batch check of a batch record before anything is read through it: its operations lie inside the ops buffer, the
-// alignment inside the genome (genome_len positions) and the read (rlen positions), and in colour space every operation byte is of the encoding (low nibble 1..9).
-// Returns the reason, or null; *read_positions = the columns that hold a read position.
-static const char* swf_rec_check(bool colour_space, const gm_sw_full_rec_t* rec, const uint8_t* ops, uint64_t ops_len, uint64_t genome_len, int rlen, uint64_t* read_positions) {
-  if (rec->ops_off > ops_len || rec->n_ops > ops_len - rec->ops_off || rec->genome_start < 0 || rec->read_start < 0 || rlen < 0)
-    return "the record points outside the ops buffer or the bitfields";
-  const uint8_t* o = ops + rec->ops_off;
-  uint64_t adv_g = 0, adv_r = 0; bool coded = true;
-  for (uint32_t k = 0; k < rec->n_ops; k++) {
-    const int type = o[k] & 0x0f;
-    const bool ins = colour_space ? type == 1 : o[k] == 'I', del = colour_space ? (type >= 2 && type <= 5) : o[k] == 'D';
-    if (!del) adv_g++; if (!ins) adv_r++;
-    if (colour_space && (type < 1 || type > 9)) coded = false;
-  }
-  if ((uint64_t)rec->genome_start + adv_g > genome_len || (uint64_t)rec->read_start + adv_r > (uint64_t)rlen) return "the record's alignment runs past the genome or the read";
-  if (!coded) return "an operation byte that is none of the encoding";
-  if (read_positions) *read_positions = adv_r;
-  return nullptr;
-}
-// pretty_print of one batch item (ref: sw-full-ls.c:524-560, sw-full-cs.c:945-1060), as sw_full_ls / sw_full_cs above build their strings.  Host only.
-extern "C" int gm_sw_full_batch_strings(int colour_space, const gm_sw_full_rec_t* rec, const uint8_t* ops, uint64_t ops_len, const uint32_t* genome, uint64_t genome_len,
-                                        const uint32_t* read, int rlen_in, int initbp, int is_rna, char** dbalign, char** qralign) {
-  if (!rec || !dbalign || !qralign) { gm_set_error("gm_sw_full_batch_strings: a required argument is missing"); return GM_E_ARG; }
-  *dbalign = *qralign = nullptr;
-  const bool aligned = rec->status == 0 && rec->score > 0;
-  if (!aligned) { if (!colour_space) { *dbalign = strdup(""); *qralign = strdup(""); } return GM_OK; }
-  if (!ops || !genome || !read || (colour_space && (initbp < 0 || initbp > 3))) { gm_set_error("gm_sw_full_batch_strings: a required argument is missing"); return GM_E_ARG; }
-  if (const char* why = swf_rec_check(colour_space != 0, rec, ops, ops_len, genome_len, rlen_in, nullptr)) { gm_set_error("gm_sw_full_batch_strings: %s", why); return GM_E_ARG; }
-  const uint8_t* o = ops + rec->ops_off;
-  std::string db, q;
-  long long pj = rec->genome_start; int pi = rec->read_start;
-  if (!colour_space) {
-    for (uint32_t k = 0; k < rec->n_ops; k++) {
-      if (o[k] == 'D') { db.push_back('-'); q.push_back(LSTRANS[swf_nib(read, pi++)]); }
-      else if (o[k] == 'I') { db.push_back(LSTRANS[swf_nib(genome, pj++)]); q.push_back('-'); }
-      else { db.push_back(LSTRANS[swf_nib(genome, pj++)]); q.push_back(LSTRANS[swf_nib(read, pi++)]); }
-    }
-  } else {
-    const int rlen = rlen_in;
-    std::vector<uint8_t> qr[4];
-    for (int k = 0; k < 4; k++) {
-      qr[k].resize(rlen); int letter = (k + initbp) % 4;
-      for (int j = 0; j < rlen; j++) {
-        const int base = swf_nib(read, j);
-        if (base == 15) { qr[k][j] = 15; letter = (k + initbp) % 4; }
-        else {                                                   // cstols(letter, base, is_rna), ref: util.h:157-180
-          const int lt = (is_rna && letter == 4) ? 3 : letter;
-          int l2 = (lt % 2 == 0) ? ((4 + lt + base) % 4) : ((4 + lt - base) % 4); if (is_rna && l2 == 3) l2 = 4;
-          qr[k][j] = (uint8_t)((letter == 15 || base > 3) ? 15 : l2); letter = qr[k][j];
-        }
-      }
-    }
-    for (uint32_t t = 0; t < rec->n_ops; t++) {
-      const int type = o[t] & 0x0f; const bool xov = (o[t] & 0x80) != 0;
-      if (type == 1) { db.push_back(LSTRANS[swf_nib(genome, pj++)]); q.push_back('-'); continue; }
-      const bool del = type >= 2 && type <= 5;
-      const int lay = del ? type - 2 : type - 6;
-      char c = LSTRANS[qr[lay][pi++]];
-      if (xov) c = (char)tolower((int)c);
-      if (del) { db.push_back('-'); q.push_back(c); }
-      else { const char d = LSTRANS[swf_nib(genome, pj++)]; if (c == 'n' || c == 'N') c = xov ? (char)tolower((int)d) : d; db.push_back(d); q.push_back(c); }
-    }
-  }
-  *dbalign = strdup(db.c_str()); *qralign = strdup(q.c_str());
-  return GM_OK;
-}
-
-
-// ---- S3: post_sw on a caller's sw_full_results (ref: common/sw-post.c:364-758, sw-post.h:6-9) ------------------------------------------
-// The colour-space posterior of one alignment, host doubles through libm in the reference's operation order (cs_post_sw above, the routine the
-// read pipeline uses).  State per calling thread, like the reference's threadprivate statics.
-struct PostSwState { bool init = false; CsPostConsts K; bool use_read_qvs = false; int qual_delta = 33, max_len = 0; uint64_t invocs = 0, cells = 0; double secs = 0; };
-static thread_local PostSwState g_ps;
-extern "C" int post_sw_setup(int max_len, double pr_snp, double pr_xover, double pr_del_open, double pr_del_extend, double pr_ins_open, double pr_ins_extend,
-                             bool use_read_qvs, bool use_sanger_qvs, int qual_vector_offset, int qual_delta, bool reset_stats) {
-  g_ps.K = cs_post_consts_from(pr_snp, pr_xover, pr_del_open, pr_del_extend, pr_ins_open, pr_ins_extend, use_sanger_qvs, use_read_qvs ? qual_vector_offset : 0);
-  g_ps.use_read_qvs = use_read_qvs; g_ps.qual_delta = qual_delta; g_ps.max_len = max_len; g_ps.init = true;
-  if (reset_stats) { g_ps.invocs = g_ps.cells = 0; g_ps.secs = 0; }
-  return 1;                                                  // the reference returns 1 (sw-post.c:441)
-}
-extern "C" int post_sw_cleanup(void) { g_ps.init = false; return 1; }
-extern "C" int post_sw_stats(uint64_t* invocs, uint64_t* cells, double* secs) {
-  if (invocs) *invocs = g_ps.invocs; if (cells) *cells = g_ps.cells; if (secs) *secs = g_ps.secs;
-  return 1;
-}
-// read: the colour read as the reference's 4-bit bitfield; qual: its QV string (used when post_sw_setup got use_read_qvs); sfr: the result of
-// sw_full_cs -- qralign is re-called in place, matches / mismatches / crossovers are recounted, qual (malloc) and posterior are filled.
-extern "C" void post_sw(uint32_t* read, int initbp, char* qual, struct gm_sw_full_results* sfr) {
-  if (!g_ps.init) abort();                                   // ref: sw-post.c:657-658
-  if (!sfr || !sfr->dbalign || !sfr->qralign) abort();
-  SeamTimer tm(&g_ps.secs); g_ps.invocs++;
-  FHit h; h.db = sfr->dbalign; h.qr = sfr->qralign;
-  cs_post_sw(g_ps.K, read, initbp, sfr->read_start, h, g_ps.use_read_qvs ? qual : nullptr, g_ps.qual_delta, true);
-  size_t len = 0; for (char c : h.qr) len += c != '-';
-  g_ps.cells += 16 * (uint64_t)len;
-  memcpy(sfr->qralign, h.qr.data(), h.qr.size());
-  sfr->matches = h.cs_match; sfr->mismatches = h.cs_mismatch; sfr->crossovers = h.cs_xover;
-  sfr->qual = (char*)malloc(h.qr.size() + 1);
-  if (sfr->qual) { memcpy(sfr->qual, h.qual.data(), h.qual.size()); sfr->qual[h.qual.size()] = 0; }
-  sfr->posterior = h.posterior;
-}
-
-
-// ---- S3 batch: gm_post_sw_batch -- post_sw of n records of a gm_sw_full_cs_batch call in one go (k_post_sw_batch, gm_post.hip) --------------------------------
-// A fixed number of device buffers, copies and launches whatever n is.  The column scratch (GM_POST_COL_BYTES a column) belongs to the thread slots of a launch and is
-// sized by the launch's longest alignment; when the slots the items would fill pass GM_POST_BUDGET the thread count is lowered to fit, and the items are sorted into at
-// most three launches by length (as swf_plan does by matrix size) so that one long alignment does not starve many short ones of threads.  A result the kernel flags
-// (a letter call or a base quality the last bits of exp / log could decide) is redone by cs_post_sw on the strings rebuilt from the record: by_host = 1.
-static const size_t GM_POST_BUDGET = (size_t)512 << 20;
-struct PostLaunch { int first = 0, count = 0, threads = 0, max_len = 0; };
-struct PostPlan { int n = 0; PostLaunch l[3]; };
-static thread_local PostPlan g_post_plan;
-static void post_plan(std::vector<GmPostItem>& items, std::vector<PostLaunch>& launches) {
-  launches.clear();
-  if (items.empty()) return;
-  int M = 0; for (const GmPostItem& it : items) M = std::max(M, it.len);
-  const size_t want = std::min<size_t>((items.size() + 63) & ~(size_t)63, (size_t)GM_POST_THREADS);
-  std::vector<int> bound;                                       // a class takes the items of at most this many columns that no earlier class took
-  if (want * (size_t)M * GM_POST_COL_BYTES > GM_POST_BUDGET) bound = {M / 64, M / 8, M}; else bound = {M};
-  std::vector<GmPostItem> sorted; sorted.reserve(items.size());
-  int lo = 0;
-  for (int b : bound) {
-    PostLaunch L; L.first = (int)sorted.size();
-    for (const GmPostItem& it : items) if (it.len > lo && it.len <= b) { sorted.push_back(it); L.max_len = std::max(L.max_len, it.len); }
-    lo = b;
-    L.count = (int)sorted.size() - L.first;
-    if (!L.count) continue;
-    const size_t fit = (GM_POST_BUDGET / ((size_t)L.max_len * GM_POST_COL_BYTES)) & ~(size_t)63;          // (>= 64: longer alignments were refused)
-    L.threads = (int)std::max<size_t>(64, std::min(std::min(want, ((size_t)L.count + 63) & ~(size_t)63), fit));
-    launches.push_back(L);
-  }
-  items.swap(sorted);
-}
-extern "C" int gm_post_sw_batch_last_plan(int launch, int* items, int* threads, int* columns) {
-  const PostPlan& P = g_post_plan;
-  if (launch >= 0 && launch < P.n) { if (items) *items = P.l[launch].count; if (threads) *threads = P.l[launch].threads; if (columns) *columns = P.l[launch].max_len; }
-  return P.n;
-}
-
-extern "C" int gm_index_get_windows(const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, const int64_t* g_off, const int* glen,
-                                    int colours, uint32_t* words, int stride_words);
-// shared body; ix: gm_post_sw_batch_ix -- record i lies on strand gen_st[i] of contig cn[i] of the resident genome (genome_start counted on that strand's contig)
-static int post_sw_batch_impl(int n, const gm_sw_full_rec_t* recs, const uint8_t* ops, uint64_t ops_len, const uint32_t* genome_ls, uint64_t genome_words,
-                              const uint32_t* reads, int read_words, const int* rlen, const uint8_t* initbp, const char* const* quals, int is_rna,
-                              gm_post_rec_t* post, char** qralign_out, char** quals_out, uint64_t* quals_len,
-                              const gm_index_t* ix = nullptr, const int* cn = nullptr, const uint8_t* gen_st = nullptr) {
-  const char* who = ix ? "gm_post_sw_batch_ix" : "gm_post_sw_batch";
-  if (!g_ps.init) { gm_set_error("%s called before post_sw_setup", who); return GM_E_NOTSETUP; }
-  if (n <= 0) return GM_OK;
-  if (!recs || (!ops && ops_len) || (ix ? (!cn || !gen_st) : !genome_ls) || !reads || read_words < 1 || !rlen || !initbp || !post || !qralign_out || !quals_out || !quals_len) {
-    gm_set_error("%s: a required argument is missing", who); return GM_E_ARG; }
-  *qralign_out = *quals_out = nullptr; *quals_len = 0;
-  SeamTimer tm(&g_ps.secs);
-  IxScope scope;
-  if (ix) { const int rc = scope.enter(ix, is_rna); if (rc) return rc; is_rna = scope.view.genome_is_rna; }
-  const bool use_qvs = g_ps.use_read_qvs; const int qoff = g_ps.K.qoff, qv_stride = read_words * 8;
-  // the longest alignment 64 thread slots can hold inside the budget
-  const uint64_t slot_max = GM_POST_BUDGET / (64 * GM_POST_COL_BYTES);
-  std::vector<GmPostItem> items; items.reserve(n);
-  std::vector<uint8_t> qv; if (use_qvs) qv.assign((size_t)n * qv_stride, 0);
-  uint64_t quals_total = 0; g_post_plan.n = 0;
-  for (int i = 0; i < n; i++) {
-    gm_post_rec_t& P = post[i]; memset(&P, 0, sizeof P);
-    const gm_sw_full_rec_t& R = recs[i];
-    if (R.status < 0) { P.status = R.status; continue; }
-    if (R.score <= 0) continue;                                           // no alignment: status 0, posterior 0, no base qualities
-    auto refuse = [&](const char* why) { P.status = GM_E_ARG; gm_set_error("%s: item %d refused: %s", who, i, why); };
-    uint64_t genome_len = genome_words * 8; GmWin win;
-    if (ix) {
-      if (const char* why = ix_window(ix, cn[i], gen_st[i], 0, 0, &win, true)) { refuse(why); continue; }
-      genome_len = (uint64_t)ix->contig_off[win.cn + 1] - (uint64_t)ix->contig_off[win.cn];
-    }
-    if (rlen[i] < 1 || ((uint64_t)rlen[i] + 7) / 8 > (uint64_t)read_words || initbp[i] > 3) { refuse("read outside the bitfield, or initbp outside 0..3"); continue; }
-    uint64_t len = 0;
-    if (const char* why = swf_rec_check(true, &R, ops, ops_len, genome_len, rlen[i], &len)) { refuse(why); continue; }
-    if ((int64_t)R.n_ops > (int64_t)g_ps.max_len) { refuse("an alignment longer than post_sw_setup's max_len"); continue; }
-    if (len > slot_max) { refuse("an alignment too long for the column scratch of one wave"); continue; }
-    if (use_qvs) {
-      const size_t need = (size_t)qoff + (size_t)rlen[i];
-      if (!quals || !quals[i] || strnlen(quals[i], need) < need) { refuse("a QV string is missing or shorter than the read"); continue; }
-      for (int j = 0; j < rlen[i]; j++)                                   // what the error-rate formula distinguishes (qv <= 0, qv >= 250, ref: util.h:285-293)
-        qv[(size_t)i * qv_stride + j] = (uint8_t)std::min(250, std::max(0, (int)quals[i][qoff + j] - g_ps.qual_delta));
-    }
-    GmPostItem it; memset(&it, 0, sizeof it);
-    it.ops_off = R.ops_off; it.n_ops = R.n_ops; it.genome_start = R.genome_start; it.read_start = R.read_start; it.rlen = rlen[i]; it.len = (int)len;
-    it.initbp = initbp[i]; it.idx = i; it.qual_off = quals_total;
-    if (ix) {
-      it.gbase = (long long)ix->contig_off[win.cn] + (win.rc ? (long long)genome_len - 1 : 0);
-      it.flags = (win.rc ? 1 : 0) | ((ix->rna_ready && ix->contig_rna[win.cn]) ? 2 : 0);
-    }
-    P.qual_off = quals_total; P.qual_len = (uint32_t)len; quals_total += len;
-    items.push_back(it);
-  }
-  char* qa = (char*)calloc(ops_len ? ops_len : 1, 1); char* qo = (char*)malloc(quals_total ? quals_total : 1);
-  struct HostBufs { char *a, *b; ~HostBufs() { free(a); free(b); } } hb{qa, qo};
-  if (!qa || !qo) { gm_set_error("%s: out of memory", who); return GM_E_NOMEM; }
-  std::vector<GmPostRes> res(items.size());
-  std::vector<PostLaunch> launches;
-  // an item without a read position never reaches the device: the host routine's early return answers it
-  std::vector<GmPostItem> dev; dev.reserve(items.size());
-  for (const GmPostItem& it : items) if (it.len > 0) dev.push_back(it);
-  post_plan(dev, launches);
-  if (!dev.empty()) {
-    if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
-    GmCsPostDev K; const CsPostConsts& c = g_ps.K;
-    K.let_m = c.let_m; K.let_x = c.let_x; K.col_m[0] = c.col_m[0]; K.col_m[1] = c.col_m[1]; K.col_x[0] = c.col_x[0]; K.col_x[1] = c.col_x[1];
-    K.pr_del_open = c.pr_del_open; K.pr_del_extend = c.pr_del_extend; K.pr_ins_open = c.pr_ins_open; K.pr_ins_extend = c.pr_ins_extend; K.qv = nullptr; K.qtab = nullptr; K.bq = nullptr;
-    size_t fw_bytes = 0, info_bytes = 0;
-    for (const PostLaunch& L : launches) { fw_bytes = std::max(fw_bytes, (size_t)L.threads * L.max_len * 17 * 8); info_bytes = std::max(info_bytes, (size_t)L.threads * L.max_len * 4); }
-    GmDevBufs bufs;
-    uint32_t *dg = nullptr, *dr = nullptr, *dinfo = nullptr; GmPostItem* di = nullptr; GmPostRes* dres = nullptr; uint8_t *dops = nullptr, *dqa = nullptr, *dqo = nullptr, *dqv = nullptr;
-    double *dfw = nullptr, *dqt = nullptr;
-    if (ix) dg = ix->d_genome; else GM_HIP(bufs.get(&dg, (genome_words + 8) * 4));
-    GM_HIP(bufs.get(&dr, (size_t)n * read_words * 4 + 32)); GM_HIP(bufs.get(&di, dev.size() * sizeof(GmPostItem)));
-    GM_HIP(bufs.get(&dres, dev.size() * sizeof(GmPostRes))); GM_HIP(bufs.get(&dops, (size_t)ops_len + 16)); GM_HIP(bufs.get(&dqa, (size_t)ops_len + 16));
-    GM_HIP(bufs.get(&dqo, (size_t)quals_total + 16)); GM_HIP(bufs.get(&dfw, fw_bytes)); GM_HIP(bufs.get(&dinfo, info_bytes));
-    if (!ix) GM_HIP(hipMemcpyAsync(dg, genome_ls, genome_words * 4, hipMemcpyHostToDevice, 0));
-    GM_HIP(hipMemcpyAsync(dr, reads, (size_t)n * read_words * 4, hipMemcpyHostToDevice, 0));
-    GM_HIP(hipMemcpyAsync(di, dev.data(), dev.size() * sizeof(GmPostItem), hipMemcpyHostToDevice, 0));
-    GM_HIP(hipMemcpyAsync(dops, ops, (size_t)ops_len, hipMemcpyHostToDevice, 0));
-    GM_HIP(hipMemsetAsync(dqa, 0, (size_t)ops_len + 16, 0));                                   // (the slices of refused items and of those the host answers)
-    GM_HIP(hipMemsetAsync(dqo, 0, (size_t)quals_total + 16, 0));
-    std::vector<double> qt;
-    if (use_qvs) {
-      // the per-colour error rates of every QV the formula distinguishes, from the host's libm: the very doubles cs_post_sw computes (ref: sw-post.c:486-491)
-      qt.resize(2 * 251);
-      for (int q = 0; q <= 250; q++) {
-        double e = q <= 0 ? .99999999 : (q >= 250 ? 1E-25 : pow(10.0, -(double)q / 10.0));
-        if (!c.sanger) e /= (1 + e);
-        if (e > .75) e = .75;
-        qt[2 * q] = log(1 - e); qt[2 * q + 1] = log(e / 3.0);
-      }
-      GM_HIP(bufs.get(&dqv, qv.size() + 16)); GM_HIP(bufs.get(&dqt, qt.size() * 8));
-      GM_HIP(hipMemcpyAsync(dqv, qv.data(), qv.size(), hipMemcpyHostToDevice, 0));
-      GM_HIP(hipMemcpyAsync(dqt, qt.data(), qt.size() * 8, hipMemcpyHostToDevice, 0));
-      K.qv = dqv; K.qtab = dqt;
-    }
-    for (const PostLaunch& L : launches) {
-      const int rc = gm_launch_post_sw_batch(K, L.first, L.count, L.threads, di, dops, dg, dr, read_words, qv_stride, is_rna ? 1 : 0, dres, dqa, dqo, dfw, dinfo, 0, ix ? 1 : 0);
-      if (rc != GM_OK) { (void)hipDeviceSynchronize(); gm_set_error("%s: the kernel launch failed", who); return rc; }
-    }
-    res.resize(dev.size());
-    GM_HIP(hipMemcpyAsync(res.data(), dres, dev.size() * sizeof(GmPostRes), hipMemcpyDeviceToHost, 0));
-    if (ops_len) GM_HIP(hipMemcpyAsync(qa, dqa, (size_t)ops_len, hipMemcpyDeviceToHost, 0));
-    if (quals_total) GM_HIP(hipMemcpyAsync(qo, dqo, (size_t)quals_total, hipMemcpyDeviceToHost, 0));
-    GM_HIP(hipStreamSynchronize(0));
-    g_post_plan.n = (int)launches.size(); for (size_t k = 0; k < launches.size() && k < 3; k++) g_post_plan.l[k] = launches[k];
-  }
-  // the device's answers; then the items the host routine takes: flagged by the kernel, or without a read position
-  std::vector<uint8_t> by_dev((size_t)n, 0);
-  for (size_t k = 0; k < dev.size(); k++) {
-    if (res[k].valid != 1) continue;
-    gm_post_rec_t& P = post[dev[k].idx]; by_dev[dev[k].idx] = 1;
-    P.posterior = res[k].posterior; P.matches = res[k].cs_match; P.mismatches = res[k].cs_mismatch; P.crossovers = res[k].cs_xover;
-  }
-  // on the index, the host routine's items get the genome stretch of their alignment in one more call (gm_index_get_windows), each as a bitfield of its own
-  std::vector<uint32_t> hw; std::vector<int> hslot((size_t)n, -1); int hstride = 0;
-  if (ix) {
-    std::vector<int> hcn, hlen; std::vector<uint8_t> hst; std::vector<int64_t> hoff;
-    for (const GmPostItem& it : items) {
-      if (by_dev[it.idx]) continue;
-      int adv_g = 0; for (uint32_t k = 0; k < it.n_ops; k++) { const int type = ops[it.ops_off + k] & 0x0f; if (!(type >= 2 && type <= 5)) adv_g++; }
-      if (adv_g < 1) continue;
-      hslot[it.idx] = (int)hcn.size(); hcn.push_back(cn[it.idx]); hst.push_back(gen_st[it.idx]); hoff.push_back(it.genome_start); hlen.push_back(adv_g);
-      hstride = std::max(hstride, (adv_g + 7) / 8);
-    }
-    if (!hcn.empty()) {
-      hw.assign((size_t)hcn.size() * hstride, 0);
-      const int rc = gm_index_get_windows(ix, (int)hcn.size(), hcn.data(), hst.data(), hoff.data(), hlen.data(), 0, hw.data(), hstride);
-      if (rc != GM_OK) return rc;
-    }
-  }
-  for (const GmPostItem& it : items) {
-    g_ps.invocs++; g_ps.cells += 16 * (uint64_t)it.len;                                        // as one post_sw call counts (above)
-    if (by_dev[it.idx]) continue;
-    const int i = it.idx; gm_post_rec_t& P = post[i];
-    char *db = nullptr, *qr = nullptr;
-    gm_sw_full_rec_t rloc = recs[i]; const uint32_t* hg = genome_ls; uint64_t hg_len = genome_words * 8;
-    static const uint32_t no_genome[1] = {0};
-    if (ix) {                                                                                  // the record against its own stretch: genome_start 0
-      rloc.genome_start = 0;
-      if (hslot[i] >= 0) { hg = hw.data() + (size_t)hslot[i] * hstride; hg_len = (uint64_t)hstride * 8; } else { hg = no_genome; hg_len = 0; }
-    }
-    const int rc = gm_sw_full_batch_strings(1, &rloc, ops, ops_len, hg, hg_len, reads + (size_t)i * read_words, rlen[i], initbp[i], is_rna, &db, &qr);
-    if (rc != GM_OK || !db || !qr) { free(db); free(qr); P.status = rc != GM_OK ? rc : GM_E_ARG; P.qual_len = 0; continue; }
-    FHit h; h.db = db; h.qr = qr; free(db); free(qr);
-    cs_post_sw(g_ps.K, reads + (size_t)i * read_words, initbp[i], rloc.read_start, h, use_qvs ? quals[i] : nullptr, g_ps.qual_delta, true);
-    P.posterior = h.posterior; P.matches = h.cs_match; P.mismatches = h.cs_mismatch; P.crossovers = h.cs_xover; P.by_host = 1;
-    memcpy(qa + it.ops_off, h.qr.data(), std::min<size_t>(h.qr.size(), it.n_ops));
-    memcpy(qo + it.qual_off, h.qual.data(), std::min<size_t>(h.qual.size(), (size_t)it.len));
-  }
-  *qralign_out = qa; *quals_out = qo; *quals_len = quals_total; hb.a = hb.b = nullptr;
-  return GM_OK;
-}
-extern "C" int gm_post_sw_batch(int n, const gm_sw_full_rec_t* recs, const uint8_t* ops, uint64_t ops_len, const uint32_t* genome_ls, uint64_t genome_words,
-                                const uint32_t* reads, int read_words, const int* rlen, const uint8_t* initbp, const char* const* quals, int is_rna,
-                                gm_post_rec_t* post, char** qralign_out, char** quals_out, uint64_t* quals_len) {
-  return post_sw_batch_impl(n, recs, ops, ops_len, genome_ls, genome_words, reads, read_words, rlen, initbp, quals, is_rna, post, qralign_out, quals_out, quals_len);
-}
-
-// ---- the batch seams on the resident index (gm_*_ix) ----------------------------------------------------------------------------------------------------------
-// The twins of the batch entries above with (genome, genome_words, g_off) replaced by (ix, cn[], gen_st[], g_off[]): the kernels read ix->d_genome / d_genome_cs, so a
-// call uploads the window descriptors, the reads and the per-item scalars -- a fixed number of buffers, copies and launches, none of them sized by the genome.
-#define GM_IX_NULL(who) do { if (!ix) { gm_set_error(who ": ix is NULL"); return GM_E_ARG; } } while (0)
-// the windows of a call without per-item status: the first bad one fails the call
-static int ix_windows(const gm_index_t* ix, const char* who, int n, const int* cn, const uint8_t* gen_st, const int64_t* g_off, const int* glen, std::vector<GmWin>& w) {
-  w.resize(n);
-  const bool whole = !g_off || !glen;      // (the gapless form passes neither: the whole contig of the strand)
-  for (int i = 0; i < n; i++)
-    if (const char* why = ix_window(ix, cn[i], gen_st[i], whole ? 0 : g_off[i], whole ? 0 : glen[i], &w[i], whole)) { gm_set_error("%s: item %d: %s", who, i, why); return GM_E_ARG; }
-  return GM_OK;
-}
-template <class T> static int ix_upload(GmDevBufs& bufs, T** d, const T* h, size_t count) {
-  GM_HIP(bufs.get(d, count * sizeof(T) + 32)); GM_HIP(hipMemcpyAsync(*d, h, count * sizeof(T), hipMemcpyHostToDevice, 0));
-  return GM_OK;
-}
-#define GM_IX_UP(d, h, count) do { const int rc_ = ix_upload(bufs, &(d), (h), (size_t)(count)); if (rc_) return rc_; } while (0)
-
-extern "C" int gm_index_genome_is_rna(const gm_index_t* ix) {
-  GM_IX_NULL("gm_index_genome_is_rna");
-  IxScope scope; { const int rc = scope.enter(ix, -1); if (rc) return rc; }
-  return ix->genome_is_rna ? 1 : 0;
-}
-
-extern "C" int gm_index_get_windows(const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, const int64_t* g_off, const int* glen,
-                                    int colours, uint32_t* words, int stride_words) {
-  GM_IX_NULL("gm_index_get_windows");
-  if (n <= 0) return GM_OK;
-  if (!cn || !gen_st || !g_off || !glen || !words || stride_words < 1) { gm_set_error("gm_index_get_windows: a required argument is missing"); return GM_E_ARG; }
-  if (colours && !ix->d_genome_cs) { gm_set_error("gm_index_get_windows: colours need an index built with colour_space = 1"); return GM_E_ARG; }
-  std::vector<GmWin> w;
-  { const int rc = ix_windows(ix, "gm_index_get_windows", n, cn, gen_st, g_off, glen, w); if (rc) return rc; }
-  for (int i = 0; i < n; i++) if ((glen[i] + 7) / 8 > stride_words) { gm_set_error("gm_index_get_windows: item %d: the window does not fit stride_words", i); return GM_E_ARG; }
-  IxScope scope; { const int rc = scope.enter(ix, -1); if (rc) return rc; }
-  const GmIndexDev& view = scope.view;
-  GmDevBufs bufs; GmWin* dw = nullptr; uint32_t* dout = nullptr;
-  GM_IX_UP(dw, w.data(), n);
-  GM_HIP(bufs.get(&dout, (size_t)n * stride_words * 4)); GM_HIP(hipMemsetAsync(dout, 0, (size_t)n * stride_words * 4, 0));
-  { const int rc = gm_launch_get_windows(view, n, dw, colours ? 1 : 0, dout, stride_words, 0); if (rc) { (void)hipDeviceSynchronize(); return rc; } }
-  GM_HIP(hipMemcpyAsync(words, dout, (size_t)n * stride_words * 4, hipMemcpyDeviceToHost, 0));
-  GM_HIP(hipStreamSynchronize(0));
-  return GM_OK;
-}
-
-static int sw_vector_batch_ix_impl(const char* who, const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, const int64_t* g_off, const int* glen,
-                                   const uint32_t* reads, int read_words, const int* rlen, const int* initbp, int is_rna, int* scores, int early_thr, uint8_t* stopped) {
-  if (!g_sv.init) { gm_set_error("%s called before sw_vector_setup", who); return GM_E_NOTSETUP; }
-  if (n <= 0) return GM_OK;
-  const bool cs = g_sv.colours;
-  if (!cn || !gen_st || !g_off || !glen || !reads || !rlen || !scores || read_words < 1 || (cs && !initbp)) { gm_set_error("%s: a required argument is missing", who); return GM_E_ARG; }
-  if (cs && !ix->d_genome_cs) { gm_set_error("%s: sw_vector_setup chose colour space, the index was built without colour_space", who); return GM_E_ARG; }
-  if (cs && stopped) { gm_set_error("%s: the bounded form is letter space only", who); return GM_E_ARG; }
-  std::vector<GmWin> w;
-  { const int rc = ix_windows(ix, who, n, cn, gen_st, g_off, glen, w); if (rc) return rc; }
-  int max_g = 0, max_r = 0;
-  for (int i = 0; i < n; i++) {
-    if (rlen[i] < 1 || (rlen[i] + 7) / 8 > read_words || (cs && (initbp[i] < 0 || initbp[i] > 3))) { gm_set_error("%s: item %d: read outside its bitfield, or initbp outside 0..3", who, i); return GM_E_ARG; }
-    if (glen[i] > g_sv.dblen || rlen[i] > g_sv.qrlen) { gm_set_error("%s: item %d: window / read longer than the sw_vector_setup sizes", who, i); return GM_E_ARG; }
-    max_g = std::max(max_g, glen[i]); max_r = std::max(max_r, rlen[i]);
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  IxScope scope; { const int rc = scope.enter(ix, is_rna); if (rc) return rc; }
-  const GmIndexDev& view = scope.view;
-  GmDevBufs bufs; GmWin* dw = nullptr; uint32_t* dr = nullptr; int *drl = nullptr, *dib = nullptr, *ds = nullptr; uint8_t* dst = nullptr;
-  GM_IX_UP(dw, w.data(), n); GM_IX_UP(dr, reads, (size_t)n * read_words); GM_IX_UP(drl, rlen, n);
-  if (cs) GM_IX_UP(dib, initbp, n);
-  GM_HIP(bufs.get(&ds, (size_t)n * 4));
-  if (stopped) GM_HIP(bufs.get(&dst, (size_t)n));
-  const GmScoreDev& sv = g_sv.sc;      // (the early stop's conditions: see sw_vector_batch_impl)
-  if (!(sv.match > 0 && sv.mismatch <= sv.match && sv.a_go >= 0 && sv.a_ge >= 0 && sv.b_go >= 0 && sv.b_ge >= 0 && sv.match * (2 * 128 + 2) < 32000)) early_thr = 0;
-  const int rc = gm_launch_sw_vector_batch_ix(view, g_sv.sc, n, dw, dr, read_words, drl, dib, max_g, max_r, ds, 0, early_thr, dst);
-  if (rc != GM_OK) { (void)hipDeviceSynchronize(); return rc; }
-  GM_HIP(hipMemcpyAsync(scores, ds, (size_t)n * 4, hipMemcpyDeviceToHost, 0));
-  if (stopped) GM_HIP(hipMemcpyAsync(stopped, dst, (size_t)n, hipMemcpyDeviceToHost, 0));
-  GM_HIP(hipStreamSynchronize(0));
-  for (int i = 0; i < n; i++) { g_sv.invocs++; g_sv.cells += (uint64_t)glen[i] * rlen[i]; }
-  g_sv.secs += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return GM_OK;
-}
-extern "C" int gm_sw_vector_batch_ix(const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, const int64_t* g_off, const int* glen,
-                                     const uint32_t* reads, int read_words, const int* rlen, const int* initbp, int is_rna, int* scores) {
-  GM_IX_NULL("gm_sw_vector_batch_ix");
-  return sw_vector_batch_ix_impl("gm_sw_vector_batch_ix", ix, n, cn, gen_st, g_off, glen, reads, read_words, rlen, initbp, is_rna, scores, 0, nullptr);
-}
-extern "C" int gm_sw_vector_batch_bounded_ix(const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, const int64_t* g_off, const int* glen,
-                                             const uint32_t* reads, int read_words, const int* rlen, int threshold, int* scores, uint8_t* stopped) {
-  GM_IX_NULL("gm_sw_vector_batch_bounded_ix");
-  if (threshold <= 0 || !stopped) { gm_set_error("gm_sw_vector_batch_bounded_ix: threshold > 0 and a stopped[] array are required"); return GM_E_ARG; }
-  return sw_vector_batch_ix_impl("gm_sw_vector_batch_bounded_ix", ix, n, cn, gen_st, g_off, glen, reads, read_words, rlen, nullptr, 0, scores, threshold, stopped);
-}
-
-extern "C" int gm_sw_gapless_batch_ix(const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, int colour_space,
-                                      const uint32_t* reads, int read_words, const int* rlen, const int* g_idx, const int* r_idx, const int* initbp, int is_rna, int* scores) {
-  GM_IX_NULL("gm_sw_gapless_batch_ix");
-  if (!g_sg.init) { gm_set_error("gm_sw_gapless_batch_ix called before sw_gapless_setup"); return GM_E_NOTSETUP; }
-  if (n <= 0) return GM_OK;
-  if (!cn || !gen_st || !reads || !rlen || !g_idx || !r_idx || !scores || read_words < 1 || (colour_space && !initbp)) {
-    gm_set_error("gm_sw_gapless_batch_ix: a required argument is missing"); return GM_E_ARG; }
-  if (colour_space && !ix->d_genome_cs) { gm_set_error("gm_sw_gapless_batch_ix: colour_space = 1 needs an index built with colour_space = 1"); return GM_E_ARG; }
-  std::vector<GmWin> w;
-  { const int rc = ix_windows(ix, "gm_sw_gapless_batch_ix", n, cn, gen_st, nullptr, nullptr, w); if (rc) return rc; }
-  int max_r = 0;
-  for (int i = 0; i < n; i++) {
-    const int64_t clen = (int64_t)ix->contig_off[cn[i] + 1] - (int64_t)ix->contig_off[cn[i]];
-    if (rlen[i] < 1 || g_idx[i] < 0 || r_idx[i] < 0 || (int64_t)g_idx[i] >= clen || r_idx[i] >= rlen[i] || (rlen[i] + 7) / 8 > read_words ||
-        (colour_space && (initbp[i] < 0 || initbp[i] > 3))) { gm_set_error("gm_sw_gapless_batch_ix: item %d out of range", i); return GM_E_ARG; }
-    max_r = std::max(max_r, rlen[i]);
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  IxScope scope; { const int rc = scope.enter(ix, is_rna); if (rc) return rc; }
-  const GmIndexDev& view = scope.view;
-  GmDevBufs bufs; GmWin* dw = nullptr; uint32_t* dr = nullptr; int *drl = nullptr, *dgi = nullptr, *dri = nullptr, *dib = nullptr, *ds = nullptr;
-  GM_IX_UP(dw, w.data(), n); GM_IX_UP(dr, reads, (size_t)n * read_words); GM_IX_UP(drl, rlen, n); GM_IX_UP(dgi, g_idx, n); GM_IX_UP(dri, r_idx, n);
-  if (colour_space) GM_IX_UP(dib, initbp, n);
-  GM_HIP(bufs.get(&ds, (size_t)n * 4));
-  const int rc = gm_launch_sw_gapless_batch_ix(view, n, g_sg.match, g_sg.mismatch, dw, colour_space ? 1 : 0, dr, read_words, drl, dgi, dri, dib, max_r, ds, 0);
-  if (rc != GM_OK) { (void)hipDeviceSynchronize(); return rc; }
-  GM_HIP(hipMemcpyAsync(scores, ds, (size_t)n * 4, hipMemcpyDeviceToHost, 0));
-  GM_HIP(hipStreamSynchronize(0));
-  for (int i = 0; i < n; i++) { g_sg.invocs++; g_sg.cells += (uint64_t)rlen[i]; }
-  g_sg.ticks += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  return GM_OK;
-}
-
-extern "C" int gm_sw_full_ls_batch_ix(const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, const int64_t* g_off, const int* glen,
-                                      const uint32_t* reads, int read_words, const int* rlen, const struct gm_anchor* anchors, const uint8_t* revcmpl,
-                                      const int* threshscore, const int* maxscore, int local_alignment, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len) {
-  GM_IX_NULL("gm_sw_full_ls_batch_ix");
-  return sw_full_batch_impl(false, n, nullptr, 0, g_off, glen, reads, read_words, rlen, nullptr, anchors, revcmpl, threshscore, maxscore, nullptr, 0, 0,
-                            local_alignment, recs, ops, ops_len, ix, cn, gen_st);
-}
-extern "C" int gm_sw_full_cs_batch_ix(const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, const int64_t* g_off, const int* glen,
-                                      const uint32_t* reads, int read_words, const int* rlen, const uint8_t* initbp, const struct gm_anchor* anchors, const uint8_t* revcmpl,
-                                      const int* threshscore, const int* crossover_scores, int xover_stride, int is_rna, int local_alignment,
-                                      gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len) {
-  GM_IX_NULL("gm_sw_full_cs_batch_ix");
-  return sw_full_batch_impl(true, n, nullptr, 0, g_off, glen, reads, read_words, rlen, initbp, anchors, revcmpl, threshscore, nullptr, crossover_scores,
-                            xover_stride, is_rna, local_alignment, recs, ops, ops_len, ix, cn, gen_st);
-}
-extern "C" int gm_post_sw_batch_ix(const gm_index_t* ix, int n, const int* cn, const uint8_t* gen_st, const gm_sw_full_rec_t* recs, const uint8_t* ops, uint64_t ops_len,
-                                   const uint32_t* reads, int read_words, const int* rlen, const uint8_t* initbp, const char* const* quals, int is_rna,
-                                   gm_post_rec_t* post, char** qralign_out, char** quals_out, uint64_t* quals_len) {
-  GM_IX_NULL("gm_post_sw_batch_ix");
-  return post_sw_batch_impl(n, recs, ops, ops_len, nullptr, 0, reads, read_words, rlen, initbp, quals, is_rna, post, qralign_out, quals_out, quals_len, ix, cn, gen_st);
-}
-
-// ---- the text of a batch's alignments: gm_sw_full_batch_text[_ix] (k_sw_text, gm_text.hip) ----------------------------------------------------------------------
-// dbalign / qralign as gm_sw_full_batch_strings builds them, the CIGAR and the edit string of every record of one gm_sw_full_*_batch[_ix] call, in one call: a fixed
-// number of device buffers, copies and launches whatever n is.  A record is checked here, on the host, before anything is uploaded; the sizing launch leaves the
-// CIGAR / edit-string lengths of the accepted ones, their exclusive scan in item order gives the tight offsets the writing launch stores at.
-static int sw_full_batch_text_impl(int colour, int what, int n, const gm_sw_full_rec_t* recs, const uint8_t* ops, uint64_t ops_len, const uint32_t* genome, uint64_t genome_words,
-                                   const uint32_t* reads, int read_words, const int* rlen, const uint8_t* initbp, int is_rna, const char* qralign_in, const uint8_t* reverse,
-                                   int clip_char, int* status, char** dbalign_out, char** qralign_out, char** cigar_out, uint64_t* cigar_off, char** edit_out, uint64_t* edit_off,
-                                   const gm_index_t* ix = nullptr, const int* cn = nullptr, const uint8_t* gen_st = nullptr) {
-  const char* who = ix ? "gm_sw_full_batch_text_ix" : "gm_sw_full_batch_text";
-  if (what <= 0 || (what & ~(GM_TEXT_ALIGN | GM_TEXT_CIGAR | GM_TEXT_EDIT))) { gm_set_error("%s: what is none of GM_TEXT_ALIGN | GM_TEXT_CIGAR | GM_TEXT_EDIT", who); return GM_E_ARG; }
-  if (n <= 0) return GM_OK;
-  const bool want_al = what & GM_TEXT_ALIGN, want_cig = what & GM_TEXT_CIGAR, want_ed = what & GM_TEXT_EDIT, strings = want_al || want_ed;
-  if (!recs || (!ops && ops_len) || (ix ? (!cn || !gen_st) : !genome) || !rlen || !status || (strings && !qralign_in && (!reads || read_words < 1)) ||
-      (colour && strings && !qralign_in && !initbp) || (want_al && (!dbalign_out || !qralign_out)) || (want_cig && (!cigar_out || !cigar_off)) || (want_ed && (!edit_out || !edit_off))) {
-    gm_set_error("%s: a required argument is missing", who); return GM_E_ARG; }
-  if (want_cig && clip_char != 'S' && clip_char != 'H') { gm_set_error("%s: clip_char is neither 'S' nor 'H'", who); return GM_E_ARG; }
-  IxScope scope;
-  if (ix) { const int rc = scope.enter(ix, is_rna); if (rc) return rc; is_rna = scope.view.genome_is_rna; }
-  const bool translate = colour && strings && !qralign_in, use_reads = strings && !qralign_in;
-  std::vector<GmTextItem> items; items.reserve(n);
-  for (int i = 0; i < n; i++) {
-    const gm_sw_full_rec_t& R = recs[i];
-    status[i] = 0;
-    if (R.status < 0) { status[i] = R.status; continue; }
-    if (R.score <= 0) continue;                                           // no alignment: status 0, empty slices
-    auto refuse = [&](const char* why) { status[i] = GM_E_ARG; gm_set_error("%s: item %d refused: %s", who, i, why); };
-    uint64_t genome_len = genome_words * 8; GmWin win;
-    if (ix) {
-      if (const char* why = ix_window(ix, cn[i], gen_st[i], 0, 0, &win, true)) { refuse(why); continue; }
-      genome_len = (uint64_t)ix->contig_off[win.cn + 1] - (uint64_t)ix->contig_off[win.cn];
-    }
-    if (use_reads && (rlen[i] < 0 || ((uint64_t)rlen[i] + 7) / 8 > (uint64_t)read_words)) { refuse("read outside the bitfield"); continue; }
-    if (colour && initbp && initbp[i] > 3) { refuse("initbp outside 0..3"); continue; }
-    uint64_t adv_r = 0;
-    if (const char* why = swf_rec_check(colour != 0, &R, ops, ops_len, genome_len, rlen[i], &adv_r)) { refuse(why); continue; }
-    if (R.n_ops > (1u << 27)) { refuse("an alignment of more than 2^27 columns"); continue; }
-    if (qralign_in && strings) {                                          // its gaps are the operations' (post_sw re-calls letters, it moves no gap)
-      const uint8_t* o = ops + R.ops_off; const char* q = qralign_in + R.ops_off; bool same = true;
-      for (uint32_t k = 0; k < R.n_ops && same; k++) same = (q[k] == '-') == (colour ? (o[k] & 0x0f) == 1 : o[k] == 'I');
-      if (!same) { refuse("qralign_in has a gap where the operations have none, or none where they have one"); continue; }
-    }
-    GmTextItem it; memset(&it, 0, sizeof it);
-    it.ops_off = R.ops_off; it.n_ops = R.n_ops; it.genome_start = R.genome_start; it.read_start = R.read_start; it.tail = (int)((int64_t)rlen[i] - R.read_start - (int64_t)adv_r);
-    it.initbp = translate ? initbp[i] : 0; it.idx = i; it.flags = (reverse && reverse[i]) ? 4 : 0;
-    if (ix) {
-      it.gbase = (long long)ix->contig_off[win.cn] + (win.rc ? (long long)genome_len - 1 : 0);
-      it.flags |= (win.rc ? 1 : 0) | ((ix->rna_ready && ix->contig_rna[win.cn]) ? 2 : 0);
-    }
-    items.push_back(it);
-  }
-  const size_t m = items.size();
-  std::vector<uint64_t> coff, eoff;                                       // n + 1 each, in item order
-  if (want_cig) coff.assign((size_t)n + 1, 0);
-  if (want_ed) eoff.assign((size_t)n + 1, 0);
-  struct HostBufs { char* p[4] = {nullptr, nullptr, nullptr, nullptr}; ~HostBufs() { for (char* q : p) free(q); } } hb;      // dbalign, qralign, cigar, edit
-  if (want_al) { hb.p[0] = (char*)calloc(ops_len ? ops_len : 1, 1); hb.p[1] = (char*)calloc(ops_len ? ops_len : 1, 1); if (!hb.p[0] || !hb.p[1]) { gm_set_error("%s: out of memory", who); return GM_E_NOMEM; } }
-  uint64_t cig_total = 0, edit_total = 0;
-  if (m) {
-    if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
-    GmDevBufs bufs;
-    uint32_t *dg = nullptr, *dr = nullptr, *dlens = nullptr; GmTextItem* di = nullptr; unsigned long long* doffs = nullptr;
-    uint8_t *dops = nullptr, *dqin = nullptr, *ddb = nullptr, *dqr = nullptr, *dcig = nullptr, *ded = nullptr;
-    if (strings) {
-      if (ix) dg = ix->d_genome;
-      else {
-        GM_HIP(bufs.get(&dg, (genome_words + 8) * 4));
-        GM_HIP(hipMemsetAsync(dg + genome_words, 0, 8 * 4, 0));
-        GM_HIP(hipMemcpyAsync(dg, genome, genome_words * 4, hipMemcpyHostToDevice, 0));
-      }
-      if (use_reads) { GM_HIP(bufs.get(&dr, (size_t)n * read_words * 4 + 32)); GM_HIP(hipMemcpyAsync(dr, reads, (size_t)n * read_words * 4, hipMemcpyHostToDevice, 0)); }
-      else { GM_HIP(bufs.get(&dqin, (size_t)ops_len + 16)); GM_HIP(hipMemcpyAsync(dqin, qralign_in, (size_t)ops_len, hipMemcpyHostToDevice, 0)); }
-    }
-    GM_HIP(bufs.get(&di, m * sizeof(GmTextItem))); GM_HIP(hipMemcpyAsync(di, items.data(), m * sizeof(GmTextItem), hipMemcpyHostToDevice, 0));
-    GM_HIP(bufs.get(&dops, (size_t)ops_len + 16)); GM_HIP(hipMemcpyAsync(dops, ops, (size_t)ops_len, hipMemcpyHostToDevice, 0));
-    GM_HIP(bufs.get(&dlens, m * 2 * sizeof(uint32_t))); GM_HIP(bufs.get(&doffs, m * 2 * sizeof(unsigned long long)));
-    std::vector<unsigned long long> offs(m * 2, 0);
-    if (want_cig || want_ed) {
-      int rc = gm_launch_sw_text((int)m, di, colour ? 1 : 0, what, 0, dops, dg, dr, read_words, is_rna ? 1 : 0, dqin, clip_char, dlens, doffs, nullptr, nullptr, nullptr, nullptr, 0, ix ? 1 : 0);
-      if (rc != GM_OK) { (void)hipDeviceSynchronize(); gm_set_error("%s: the kernel launch failed", who); return rc; }
-      std::vector<uint32_t> lens(m * 2);
-      GM_HIP(hipMemcpyAsync(lens.data(), dlens, m * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, 0));
-      GM_HIP(hipStreamSynchronize(0));
-      // the exclusive scan in item order (items[] is in item order: refused items and those without alignment take no bytes)
-      size_t k = 0;
-      for (int i = 0; i < n; i++) {
-        if (want_cig) coff[i] = cig_total;
-        if (want_ed) eoff[i] = edit_total;
-        if (k < m && items[k].idx == i) { offs[2 * k] = cig_total; offs[2 * k + 1] = edit_total; cig_total += lens[2 * k]; edit_total += lens[2 * k + 1]; k++; }
-      }
-      if (want_cig) coff[n] = cig_total;
-      if (want_ed) eoff[n] = edit_total;
-      GM_HIP(hipMemcpyAsync(doffs, offs.data(), m * 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, 0));
-    }
-    if (want_al) {
-      GM_HIP(bufs.get(&ddb, (size_t)ops_len + 16)); GM_HIP(bufs.get(&dqr, (size_t)ops_len + 16));
-      GM_HIP(hipMemsetAsync(ddb, 0, (size_t)ops_len + 16, 0)); GM_HIP(hipMemsetAsync(dqr, 0, (size_t)ops_len + 16, 0));
-    }
-    if (want_cig) GM_HIP(bufs.get(&dcig, (size_t)cig_total + 16));
-    if (want_ed) GM_HIP(bufs.get(&ded, (size_t)edit_total + 16));
-    int rc = gm_launch_sw_text((int)m, di, colour ? 1 : 0, what, 1, dops, dg, dr, read_words, is_rna ? 1 : 0, dqin, clip_char, dlens, doffs, ddb, dqr, dcig, ded, 0, ix ? 1 : 0);
-    if (rc != GM_OK) { (void)hipDeviceSynchronize(); gm_set_error("%s: the kernel launch failed", who); return rc; }
-    if (want_cig) { hb.p[2] = (char*)malloc(cig_total ? cig_total : 1); if (!hb.p[2]) { (void)hipDeviceSynchronize(); gm_set_error("%s: out of memory", who); return GM_E_NOMEM; } }
-    if (want_ed) { hb.p[3] = (char*)malloc(edit_total ? edit_total : 1); if (!hb.p[3]) { (void)hipDeviceSynchronize(); gm_set_error("%s: out of memory", who); return GM_E_NOMEM; } }
-    if (want_al && ops_len) {
-      GM_HIP(hipMemcpyAsync(hb.p[0], ddb, (size_t)ops_len, hipMemcpyDeviceToHost, 0));
-      GM_HIP(hipMemcpyAsync(hb.p[1], dqr, (size_t)ops_len, hipMemcpyDeviceToHost, 0));
-    }
-    if (want_cig && cig_total) GM_HIP(hipMemcpyAsync(hb.p[2], dcig, (size_t)cig_total, hipMemcpyDeviceToHost, 0));
-    if (want_ed && edit_total) GM_HIP(hipMemcpyAsync(hb.p[3], ded, (size_t)edit_total, hipMemcpyDeviceToHost, 0));
-    GM_HIP(hipStreamSynchronize(0));
-  } else {
-    if (want_cig) hb.p[2] = (char*)malloc(1);
-    if (want_ed) hb.p[3] = (char*)malloc(1);
-    if ((want_cig && !hb.p[2]) || (want_ed && !hb.p[3])) { gm_set_error("%s: out of memory", who); return GM_E_NOMEM; }
-  }
-  if (want_al) { *dbalign_out = hb.p[0]; *qralign_out = hb.p[1]; hb.p[0] = hb.p[1] = nullptr; }
-  if (want_cig) { *cigar_out = hb.p[2]; hb.p[2] = nullptr; memcpy(cigar_off, coff.data(), ((size_t)n + 1) * sizeof(uint64_t)); }
-  if (want_ed) { *edit_out = hb.p[3]; hb.p[3] = nullptr; memcpy(edit_off, eoff.data(), ((size_t)n + 1) * sizeof(uint64_t)); }
-  return GM_OK;
-}
-extern "C" int gm_sw_full_batch_text(int colour_space, int what, int n, const gm_sw_full_rec_t* recs, const uint8_t* ops, uint64_t ops_len, const uint32_t* genome, uint64_t genome_words,
-                                     const uint32_t* reads, int read_words, const int* rlen, const uint8_t* initbp, int is_rna, const char* qralign_in, const uint8_t* reverse,
-                                     int clip_char, int* status, char** dbalign_out, char** qralign_out, char** cigar_out, uint64_t* cigar_off, char** edit_out, uint64_t* edit_off) {
-  return sw_full_batch_text_impl(colour_space, what, n, recs, ops, ops_len, genome, genome_words, reads, read_words, rlen, initbp, is_rna ? 1 : 0, qralign_in, reverse, clip_char, status,
-                                 dbalign_out, qralign_out, cigar_out, cigar_off, edit_out, edit_off);
-}
-extern "C" int gm_sw_full_batch_text_ix(const gm_index_t* ix, int colour_space, int what, int n, const int* cn, const uint8_t* gen_st, const gm_sw_full_rec_t* recs, const uint8_t* ops,
-                                        uint64_t ops_len, const uint32_t* reads, int read_words, const int* rlen, const uint8_t* initbp, int is_rna, const char* qralign_in,
-                                        const uint8_t* reverse, int clip_char, int* status, char** dbalign_out, char** qralign_out, char** cigar_out, uint64_t* cigar_off,
-                                        char** edit_out, uint64_t* edit_off) {
-  GM_IX_NULL("gm_sw_full_batch_text_ix");
-  return sw_full_batch_text_impl(colour_space, what, n, recs, ops, ops_len, nullptr, 0, reads, read_words, rlen, initbp, is_rna, qralign_in, reverse, clip_char, status,
-                                 dbalign_out, qralign_out, cigar_out, cigar_off, edit_out, edit_off, ix, cn, gen_st);
-}
+#include "gm_host_seams.inc"
+#include "gm_host_seams_ix.inc"
+#include "gm_host_text.inc"

@@ -6,10 +6,6 @@
 // offsets and the text come back.  Every buffer is sized by the call's arrays: a fixed number of allocations, copies and launches.
 
 namespace {
-struct SamBufs {                     // device and host memory of one gm_sam_records call
-  void* d[16] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; void* h = nullptr;
-  ~SamBufs() { for (void* p : d) if (p) (void)hipFree(p); free(h); }
-};
 // n lines of `want` characters each, '\n' between them (one behind the last is allowed): the bytes to upload, or 0 with the error set
 size_t sam_fixed_lines(const char* text, int n, size_t want, const char* what) {
   const char* p = text;
@@ -132,49 +128,38 @@ extern "C" int gm_sam_records(gm_session_t* s, const gm_sam_input_t* in, char** 
   GmDevTurn dev_turn(s);     // (admitted like the mapping entries)
   GM_HIP(hipSetDevice(ix->device));
   hipStream_t q = s->stream;
-  SamBufs B;
-  enum { RECS, READS, INITBP, NAMES, NAME_OFF, SEQS, QUALS, CIGAR, EDIT, QRALIGN, POSTQ, CNAMES, CNAME_OFF, LENS, OFFS, OUT };
-  auto up = [&](int slot, const void* src, size_t bytes) -> hipError_t {      // (an absent array stays a null pointer on the device)
-    if (!src || !bytes) return hipSuccess;
-    hipError_t e = hipMalloc(&B.d[slot], bytes); if (e != hipSuccess) return e;
-    return hipMemcpyAsync(B.d[slot], src, bytes, hipMemcpyHostToDevice, q);
-  };
-  GM_HIP(up(RECS, recs.data(), (size_t)n_recs * sizeof(GmSamRec)));
-  GM_HIP(up(READS, in->reads_packed, (size_t)n * read_words * 4));
-  GM_HIP(up(INITBP, in->initbp, (size_t)n));
-  GM_HIP(up(NAMES, in->names, std::max<size_t>(names_bytes, 1)));
-  GM_HIP(up(NAME_OFF, name_off.data(), name_off.size() * 8));
-  GM_HIP(up(SEQS, in->seqs, seqs_bytes));
-  GM_HIP(up(QUALS, in->quals, quals_bytes));
-  GM_HIP(up(CIGAR, in->cigar, cigar_bytes));
-  GM_HIP(up(EDIT, in->edit, edit_bytes));
-  GM_HIP(up(QRALIGN, cs ? in->qralign : nullptr, (size_t)ops_hi));
-  GM_HIP(up(POSTQ, in->post_quals, pq_bytes));
-  GM_HIP(up(CNAMES, cnames.data(), std::max<size_t>(cnames.size(), 1)));
-  GM_HIP(up(CNAME_OFF, cname_off.data(), cname_off.size() * 4));
-  GM_HIP(hipMalloc(&B.d[LENS], (size_t)n_recs * 4));
-  GM_HIP(hipMalloc(&B.d[OFFS], ((size_t)n_recs + 1) * 8));
-  GmSamArgs A;
-  A.recs = (const GmSamRec*)B.d[RECS]; A.n_recs = (int)n_recs; A.colour = cs ? 1 : 0; A.read_len = L; A.read_words = read_words; A.n_contigs = ix->n_contigs;
+  GmDevMem mem;
+  GmSamArgs A = {};                    // (an absent array stays a null pointer on the device: up() leaves it as it is here)
+  A.n_recs = (int)n_recs; A.colour = cs ? 1 : 0; A.read_len = L; A.read_words = read_words; A.n_contigs = ix->n_contigs;
   A.rg_len = (int)rg_len; A.dq = 33 - in->qual_delta; A.ztags = mqv_on && !P.all_contigs ? 1 : 0; A.extra = extra ? 1 : 0;
-  A.reads = (const uint32_t*)B.d[READS]; A.initbp = (const uint8_t*)B.d[INITBP]; A.names = (const uint8_t*)B.d[NAMES]; A.name_off = (const unsigned long long*)B.d[NAME_OFF];
-  A.seqs = (const uint8_t*)B.d[SEQS]; A.quals = (const uint8_t*)B.d[QUALS]; A.cigar = (const uint8_t*)B.d[CIGAR]; A.edit = (const uint8_t*)B.d[EDIT];
-  A.qralign = (const uint8_t*)B.d[QRALIGN]; A.post_quals = (const uint8_t*)B.d[POSTQ]; A.cnames = (const uint8_t*)B.d[CNAMES]; A.cname_off = (const uint32_t*)B.d[CNAME_OFF];
-  A.lens = (uint32_t*)B.d[LENS]; A.offs = (const unsigned long long*)B.d[OFFS]; A.out = nullptr;
+  GM_HIP(mem.up(&A.recs, recs.data(), (size_t)n_recs, q));
+  GM_HIP(mem.up(&A.reads, in->reads_packed, (size_t)n * read_words, q));
+  GM_HIP(mem.up(&A.initbp, in->initbp, (size_t)n, q));
+  GM_HIP(mem.up(&A.names, in->names, std::max<size_t>(names_bytes, 1), q));
+  GM_HIP(mem.up(&A.name_off, name_off.data(), name_off.size(), q));
+  GM_HIP(mem.up(&A.seqs, in->seqs, seqs_bytes, q));
+  GM_HIP(mem.up(&A.quals, in->quals, quals_bytes, q));
+  GM_HIP(mem.up(&A.cigar, in->cigar, cigar_bytes, q));
+  GM_HIP(mem.up(&A.edit, in->edit, edit_bytes, q));
+  GM_HIP(mem.up(&A.qralign, cs ? in->qralign : nullptr, (size_t)ops_hi, q));
+  GM_HIP(mem.up(&A.post_quals, in->post_quals, pq_bytes, q));
+  GM_HIP(mem.up(&A.cnames, cnames.data(), std::max<size_t>(cnames.size(), 1), q));
+  GM_HIP(mem.up(&A.cname_off, cname_off.data(), cname_off.size(), q));
+  GM_HIP(mem.get(&A.lens, (size_t)n_recs * 4));
+  unsigned long long* d_offs = nullptr; GM_HIP(mem.get(&d_offs, ((size_t)n_recs + 1) * 8)); A.offs = d_offs;
   int rc = gm_launch_sam_records(A, 0, q); if (rc) return rc;
-  rc = gm_launch_win_scan((const uint32_t*)B.d[LENS], (int)n_recs, 0x7fffffff, (unsigned long long*)B.d[OFFS], q); if (rc) return rc;
-  GM_HIP(hipMemcpyAsync(offs.data(), B.d[OFFS], offs.size() * 8, hipMemcpyDeviceToHost, q));
+  rc = gm_launch_win_scan(A.lens, (int)n_recs, 0x7fffffff, d_offs, q); if (rc) return rc;
+  GM_HIP(hipMemcpyAsync(offs.data(), d_offs, offs.size() * 8, hipMemcpyDeviceToHost, q));
   GM_HIP(hipStreamSynchronize(q));
   const unsigned long long total = offs[(size_t)n_recs];
-  B.h = malloc((size_t)total + 1);
-  if (!B.h) { gm_set_error("gm_sam_records: out of memory at %llu bytes of text", total); return GM_E_NOMEM; }
-  GM_HIP(hipMalloc(&B.d[OUT], (size_t)total));
-  A.out = (uint8_t*)B.d[OUT];
+  char* text = mem.host((size_t)total + 1);
+  if (!text) { gm_set_error("gm_sam_records: out of memory at %llu bytes of text", total); return GM_E_NOMEM; }
+  GM_HIP(mem.get(&A.out, (size_t)total));
   rc = gm_launch_sam_records(A, 1, q); if (rc) return rc;
-  GM_HIP(hipMemcpyAsync(B.h, B.d[OUT], (size_t)total, hipMemcpyDeviceToHost, q));
+  GM_HIP(hipMemcpyAsync(text, A.out, (size_t)total, hipMemcpyDeviceToHost, q));
   GM_HIP(hipStreamSynchronize(q));
-  ((char*)B.h)[total] = 0;
+  text[total] = 0;
   for (int r = 0; r <= n; r++) read_off[r] = offs[(size_t)first[r]];
-  *sam = (char*)B.h; B.h = nullptr; *sam_len = (size_t)total;
+  *sam = mem.give(text); *sam_len = (size_t)total;
   return GM_OK;
 }

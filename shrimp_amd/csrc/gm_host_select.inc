@@ -6,13 +6,6 @@
 // entries uses), 24 bytes an item go up, k_sel_pass2 leaves the order of every read's final mappings, and the host adds z0 / z1 / mqv in that order.
 // Every buffer is sized by the call's n: a fixed number of allocations, copies and launches.
 
-namespace {
-struct SelBufs {                     // device and host memory of one selection call
-  void* d[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; void* h = nullptr;
-  ~SelBufs() { for (void* p : d) if (p) (void)hipFree(p); free(h); }
-};
-}  // namespace
-
 extern "C" int gm_pass1_hit_size(void) { return (int)sizeof(gm_pass1_hit_t); }
 extern "C" int gm_mapping_size(void) { return (int)sizeof(gm_mapping_t); }
 
@@ -44,40 +37,35 @@ extern "C" int gm_select_pass1(gm_session_t* s, int n_reads, int read_len, const
   hipStream_t q = s->stream;
   const int W = window_len_of(s->P, read_len);
   const int overlap_abs = (int)(unsigned int)(s->P.window_overlap < 0 ? -s->P.window_overlap : W * (s->P.window_overlap / 100.0));   // ref: mapping.c:1289
-  SelBufs B;
-  enum { WINS, OFF, SCORES, SEL_ID, SEL_SCORE, SEL_CNT, HIT_OFF, OUT };
+  GmDevMem mem;
+  gm_read_window_t* d_wins = nullptr; unsigned long long *d_off = nullptr, *d_hit_off = nullptr; int* d_scores = nullptr; int32_t *d_sel_id = nullptr, *d_sel_score = nullptr;
+  uint32_t* d_sel_cnt = nullptr; gm_pass1_hit_t *d_out = nullptr, *h_out = nullptr;
   const size_t nw = std::max<uint64_t>(n_wins, 1), slots = (size_t)n_reads * K;
-  GM_HIP(hipMalloc(&B.d[WINS], nw * sizeof(gm_read_window_t)));
-  GM_HIP(hipMalloc(&B.d[OFF], ((size_t)2 * n_reads + 1) * 8));
-  GM_HIP(hipMalloc(&B.d[SCORES], nw * 4));
-  GM_HIP(hipMalloc(&B.d[SEL_ID], slots * 4));
-  GM_HIP(hipMalloc(&B.d[SEL_SCORE], slots * 4));
-  GM_HIP(hipMalloc(&B.d[SEL_CNT], (size_t)n_reads * 4));
-  GM_HIP(hipMalloc(&B.d[HIT_OFF], ((size_t)n_reads + 1) * 8));
+  GM_HIP(mem.get(&d_wins, nw * sizeof(gm_read_window_t))); GM_HIP(mem.get(&d_off, ((size_t)2 * n_reads + 1) * 8)); GM_HIP(mem.get(&d_scores, nw * 4));
+  GM_HIP(mem.get(&d_sel_id, slots * 4)); GM_HIP(mem.get(&d_sel_score, slots * 4));
+  GM_HIP(mem.get(&d_sel_cnt, (size_t)n_reads * 4)); GM_HIP(mem.get(&d_hit_off, ((size_t)n_reads + 1) * 8));
   if (n_wins) {
-    GM_HIP(hipMemcpyAsync(B.d[WINS], wins, n_wins * sizeof(gm_read_window_t), hipMemcpyHostToDevice, q));
-    GM_HIP(hipMemcpyAsync(B.d[SCORES], scores, n_wins * 4, hipMemcpyHostToDevice, q));
+    GM_HIP(hipMemcpyAsync(d_wins, wins, n_wins * sizeof(gm_read_window_t), hipMemcpyHostToDevice, q));
+    GM_HIP(hipMemcpyAsync(d_scores, scores, n_wins * 4, hipMemcpyHostToDevice, q));
   }
-  GM_HIP(hipMemcpyAsync(B.d[OFF], off, ((size_t)2 * n_reads + 1) * 8, hipMemcpyHostToDevice, q));
-  int rc = gm_launch_sel_pass1(s->sc, n_reads, read_len, K, W, overlap_abs, (const gm_read_window_t*)B.d[WINS], (const unsigned long long*)B.d[OFF], (const int*)B.d[SCORES],
-                               (int32_t*)B.d[SEL_ID], (int32_t*)B.d[SEL_SCORE], (uint32_t*)B.d[SEL_CNT], q);
+  GM_HIP(hipMemcpyAsync(d_off, off, ((size_t)2 * n_reads + 1) * 8, hipMemcpyHostToDevice, q));
+  int rc = gm_launch_sel_pass1(s->sc, n_reads, read_len, K, W, overlap_abs, d_wins, d_off, d_scores, d_sel_id, d_sel_score, d_sel_cnt, q);
   if (rc) return rc;
-  rc = gm_launch_win_scan((const uint32_t*)B.d[SEL_CNT], n_reads, GM_SEL_MAX, (unsigned long long*)B.d[HIT_OFF], q); if (rc) return rc;
+  rc = gm_launch_win_scan(d_sel_cnt, n_reads, GM_SEL_MAX, d_hit_off, q); if (rc) return rc;
   static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "offsets are copied as they are");
-  GM_HIP(hipMemcpyAsync(hit_off, B.d[HIT_OFF], ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, q));
+  GM_HIP(hipMemcpyAsync(hit_off, d_hit_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, q));
   GM_HIP(hipStreamSynchronize(q));
   const uint64_t total = hit_off[n_reads];
   if (total > (uint64_t)slots) { gm_set_error("gm_select_pass1: %llu hits in %zu slots", (unsigned long long)total, slots); hit_off[0] = 0; return GM_E_OVERFLOW; }
   if (total == 0) return GM_OK;
-  GM_HIP(hipMalloc(&B.d[OUT], (size_t)total * sizeof(gm_pass1_hit_t)));
-  B.h = malloc((size_t)total * sizeof(gm_pass1_hit_t));
-  if (!B.h) { gm_set_error("gm_select_pass1: out of memory at %llu hits", (unsigned long long)total); return GM_E_NOMEM; }
-  rc = gm_launch_sel_emit(s->sc, n_reads, read_len, K, (const gm_read_window_t*)B.d[WINS], ix->d_contig_off, (const int32_t*)B.d[SEL_ID], (const int32_t*)B.d[SEL_SCORE],
-                          (const uint32_t*)B.d[SEL_CNT], (const unsigned long long*)B.d[HIT_OFF], (gm_pass1_hit_t*)B.d[OUT], q);
+  GM_HIP(mem.get(&d_out, (size_t)total * sizeof(gm_pass1_hit_t)));
+  h_out = mem.host<gm_pass1_hit_t>((size_t)total * sizeof(gm_pass1_hit_t));
+  if (!h_out) { gm_set_error("gm_select_pass1: out of memory at %llu hits", (unsigned long long)total); return GM_E_NOMEM; }
+  rc = gm_launch_sel_emit(s->sc, n_reads, read_len, K, d_wins, ix->d_contig_off, d_sel_id, d_sel_score, d_sel_cnt, d_hit_off, d_out, q);
   if (rc) return rc;
-  GM_HIP(hipMemcpyAsync(B.h, B.d[OUT], (size_t)total * sizeof(gm_pass1_hit_t), hipMemcpyDeviceToHost, q));
+  GM_HIP(hipMemcpyAsync(h_out, d_out, (size_t)total * sizeof(gm_pass1_hit_t), hipMemcpyDeviceToHost, q));
   GM_HIP(hipStreamSynchronize(q));
-  *hits = (gm_pass1_hit_t*)B.h; B.h = nullptr; *n_hits = total;
+  *hits = mem.give(h_out); *n_hits = total;
   return GM_OK;
 }
 
@@ -135,19 +123,16 @@ extern "C" int gm_select_pass2(gm_session_t* s, int n_reads, const uint64_t* hit
     GmDevTurn dev_turn(s);     // (admitted like the mapping entries)
     GM_HIP(hipSetDevice(ix->device));
     hipStream_t q = s->stream;
-    SelBufs B;
-    enum { OFF, ITEMS, ORDER, CNT };
-    GM_HIP(hipMalloc(&B.d[OFF], ((size_t)n_reads + 1) * 8));
-    GM_HIP(hipMalloc(&B.d[ITEMS], (size_t)nh * sizeof(GmSel2Item)));
-    GM_HIP(hipMalloc(&B.d[ORDER], (size_t)nh * 4));
-    GM_HIP(hipMalloc(&B.d[CNT], (size_t)n_reads * 4));
-    GM_HIP(hipMemcpyAsync(B.d[OFF], hit_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, q));
-    GM_HIP(hipMemcpyAsync(B.d[ITEMS], items.data(), (size_t)nh * sizeof(GmSel2Item), hipMemcpyHostToDevice, q));
-    int rc = gm_launch_sel_pass2(n_reads, P.num_outputs, P.strata ? 1 : 0, P.max_alignments, (const unsigned long long*)B.d[OFF], (const GmSel2Item*)B.d[ITEMS],
-                                 (int32_t*)B.d[ORDER], (uint32_t*)B.d[CNT], q);
+    GmDevMem mem;
+    unsigned long long* d_off = nullptr; GmSel2Item* d_items = nullptr; int32_t* d_order = nullptr; uint32_t* d_cnt = nullptr;
+    GM_HIP(mem.up(&d_off, hit_off, (size_t)n_reads + 1, q));
+    GM_HIP(mem.up(&d_items, items.data(), (size_t)nh, q));
+    GM_HIP(mem.get(&d_order, (size_t)nh * 4));
+    GM_HIP(mem.get(&d_cnt, (size_t)n_reads * 4));
+    int rc = gm_launch_sel_pass2(n_reads, P.num_outputs, P.strata ? 1 : 0, P.max_alignments, d_off, d_items, d_order, d_cnt, q);
     if (rc) return rc;
-    GM_HIP(hipMemcpyAsync(order.data(), B.d[ORDER], (size_t)nh * 4, hipMemcpyDeviceToHost, q));
-    GM_HIP(hipMemcpyAsync(cnt.data(), B.d[CNT], (size_t)n_reads * 4, hipMemcpyDeviceToHost, q));
+    GM_HIP(hipMemcpyAsync(order.data(), d_order, (size_t)nh * 4, hipMemcpyDeviceToHost, q));
+    GM_HIP(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n_reads * 4, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
   }
   uint64_t total = 0;

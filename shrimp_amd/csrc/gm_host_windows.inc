@@ -5,15 +5,6 @@
 // scanned and the windows exported (gm_windows.hip).  What crosses the bus: the counters, the scan's total (8 bytes), the 2 n + 1 offsets and the tight records --
 // nothing is sized by hcap.
 
-namespace {
-struct WinBufs {                     // what one gm_read_windows call owns until it hands the records over
-  unsigned long long* d_off = nullptr; size_t off_cap = 0;
-  gm_read_window_t* d_out = nullptr; size_t out_cap = 0;
-  gm_read_window_t* h = nullptr; size_t h_cap = 0;
-  ~WinBufs() { if (d_off) (void)hipFree(d_off); if (d_out) (void)hipFree(d_out); free(h); }
-};
-}  // namespace
-
 extern "C" int gm_read_window_size(void) { return (int)sizeof(gm_read_window_t); }
 
 extern "C" int gm_read_windows(gm_session_t* s, int n_reads, int read_len, const uint32_t* reads_packed, const uint8_t* initbp,
@@ -37,7 +28,8 @@ extern "C" int gm_read_windows(gm_session_t* s, int n_reads, int read_len, const
   const int W = window_len_of(s->P, read_len);
   hipStream_t q = s->stream;
   unsigned long long* d_stats = s->d_pstats[0];
-  WinBufs B;
+  GmDevMem mem;                        // the offsets, the records on the device and the records of the call so far on the host, each grown on demand
+  unsigned long long* d_off = nullptr; gm_read_window_t *d_out = nullptr, *h = nullptr; size_t off_cap = 0, out_cap = 0, h_cap = 0;
   std::vector<unsigned long long> hraw((size_t)GS_STRIPES * GS_STRIDE), hoff;
   uint64_t total = 0;
   int base = 0;
@@ -66,30 +58,28 @@ extern "C" int gm_read_windows(gm_session_t* s, int n_reads, int read_len, const
       continue;
     }
     const int n_rs = 2 * n;
-    if ((size_t)n_rs + 1 > B.off_cap) {
-      if (B.d_off) { (void)hipFree(B.d_off); B.d_off = nullptr; }
-      B.off_cap = (size_t)2 * std::max(n, D.eff_batch) + 1;
-      GM_HIP(hipMalloc(&B.d_off, B.off_cap * 8));
+    if ((size_t)n_rs + 1 > off_cap) {
+      mem.drop(d_off); off_cap = (size_t)2 * std::max(n, D.eff_batch) + 1;
+      GM_HIP(mem.get(&d_off, off_cap * 8));
     }
-    rc = gm_launch_win_scan(D.d_hit_cnt, n_rs, D.hcap, B.d_off, q); if (rc) return rc;
+    rc = gm_launch_win_scan(D.d_hit_cnt, n_rs, D.hcap, d_off, q); if (rc) return rc;
     unsigned long long t = 0;
-    GM_HIP(hipMemcpyAsync(&t, B.d_off + n_rs, 8, hipMemcpyDeviceToHost, q));
+    GM_HIP(hipMemcpyAsync(&t, d_off + n_rs, 8, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
-    if (t > B.out_cap) {
-      if (B.d_out) { (void)hipFree(B.d_out); B.d_out = nullptr; }
-      B.out_cap = (size_t)t;
-      GM_HIP(hipMalloc(&B.d_out, B.out_cap * sizeof(gm_read_window_t)));
+    if (t > out_cap) {
+      mem.drop(d_out); out_cap = (size_t)t;
+      GM_HIP(mem.get(&d_out, out_cap * sizeof(gm_read_window_t)));
     }
-    if (total + t > B.h_cap) {
-      const size_t cap = std::max<size_t>((size_t)(total + t), B.h_cap + B.h_cap / 2);
-      gm_read_window_t* p = (gm_read_window_t*)realloc(B.h, cap * sizeof(gm_read_window_t));
+    if (total + t > h_cap) {
+      const size_t cap = std::max<size_t>((size_t)(total + t), h_cap + h_cap / 2);
+      gm_read_window_t* p = mem.host(cap * sizeof(gm_read_window_t), false, h);
       if (!p) { gm_set_error("gm_read_windows: out of memory at %zu windows", cap); return GM_E_NOMEM; }
-      B.h = p; B.h_cap = cap;
+      h = p; h_cap = cap;
     }
-    rc = gm_launch_win_scatter(D.d_hits, D.d_perm, B.d_off, n_rs, D.hcap, t, base, B.d_out, q); if (rc) return rc;
+    rc = gm_launch_win_scatter(D.d_hits, D.d_perm, d_off, n_rs, D.hcap, t, base, d_out, q); if (rc) return rc;
     hoff.resize((size_t)n_rs + 1);
-    if (t) GM_HIP(hipMemcpyAsync(B.h + total, B.d_out, (size_t)t * sizeof(gm_read_window_t), hipMemcpyDeviceToHost, q));
-    GM_HIP(hipMemcpyAsync(hoff.data(), B.d_off, hoff.size() * 8, hipMemcpyDeviceToHost, q));
+    if (t) GM_HIP(hipMemcpyAsync(h + total, d_out, (size_t)t * sizeof(gm_read_window_t), hipMemcpyDeviceToHost, q));
+    GM_HIP(hipMemcpyAsync(hoff.data(), d_off, hoff.size() * 8, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
     for (int i = 0; i <= n_rs; i++) off[(size_t)2 * base + i] = total + hoff[i];
     total += t;
@@ -102,7 +92,7 @@ extern "C" int gm_read_windows(gm_session_t* s, int n_reads, int read_len, const
     }
     base += n;
   }
-  if (total) { *wins = B.h; B.h = nullptr; }
+  if (total) *wins = mem.give(h);
   *n_wins = total;
   return GM_OK;
 }
