@@ -17,6 +17,7 @@
 #include <memory>
 #include <thread>
 #include <mutex>
+#include <optional>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -493,8 +494,8 @@ static int gm_usable_cores() {
   }();
   return cached;
 }
-static int gm_host_threads() {
-  int n = (int)std::min<unsigned>(32, std::max(1u, std::thread::hardware_concurrency()));
+static int gm_host_threads(int cap) {                         // (cap: 32 for the unpaired jobs and the parallel loops, 16 for the paired stages; the environment is read on every call)
+  int n = (int)std::min<unsigned>((unsigned)cap, std::max(1u, std::thread::hardware_concurrency()));
   if (const char* e = getenv("GM_HOST_THREADS")) n = std::max(1, atoi(e));
   (void)&gm_usable_cores;
   return n;
@@ -544,7 +545,7 @@ static void gm_text_pool_drop() { gm_text_pool().drop(); }
 // fn(begin, end) over [0, n) in pieces of `grain`, on the host threads
 template <class F> static void gm_parallel_for(size_t n, size_t grain, F fn) {
   const size_t pieces = (n + grain - 1) / std::max<size_t>(1, grain);
-  const int nt = (int)std::min<size_t>((size_t)gm_host_threads(), pieces);
+  const int nt = (int)std::min<size_t>((size_t)gm_host_threads(32), pieces);
   if (nt <= 1) { if (n) fn((size_t)0, n); return; }
   std::atomic<size_t> next(0);
   gm_run_on_threads(nt, [&]() { for (;;) { const size_t c = next.fetch_add(1); if (c >= pieces) break; fn(c * grain, std::min(n, (c + 1) * grain)); } });
@@ -1499,6 +1500,14 @@ static int pipeline_front(gm_session* s, int k, int n, int read_len) {
   return GM_OK;
 }
 
+// the folded device counters of one sub-batch (hs[GS_N]) into the call's statistics: unpaired and paired mode alike
+static void add_device_stats(gm_map_stats_t* st, const unsigned long long* hs) {
+  st->lookups += hs[GS_LOOKUPS]; st->list_entries += hs[GS_ENTRIES]; st->list_bytes += 12ull * hs[GS_LOOKUPS] + 4ull * hs[GS_ENTRIES];
+  st->survivors += hs[GS_SURVIVORS]; st->anchors += hs[GS_ANCHORS]; st->windows += hs[GS_WINDOWS];
+  st->vec_calls += hs[GS_VEC_CALLS]; st->vec_cells += hs[GS_VEC_CELLS]; st->vec_bypassed += hs[GS_VEC_BYPASSED];
+  st->full_calls += hs[GS_FULL_CALLS]; st->full_cells += hs[GS_FULL_CELLS]; st->exact_order_reads += hs[GS_EXACT_ORDER]; st->survivors_pruned += hs[GS_PRUNED];
+}
+
 // Back, stream B: heavy tier if any (stream A, rare), pass 1, selection, pass 2, results to the host slot.  Returns 1 when a capacity grew
 // (the buffers of set k were re-allocated: the caller re-submits the sub-batch from the front).
 static int pipeline_back(gm_session* s, int k, HostSlot& H, int n, int read_len, gm_map_stats_t* st, float* lookup_ms, bool next_front_queued = false,
@@ -1616,10 +1625,7 @@ static int pipeline_back(gm_session* s, int k, HostSlot& H, int n, int read_len,
     GM_HIP(hipEventElapsedTime(&ms[4], s->pev[k][5], s->pev[k][7]));
     *lookup_ms = ms[0];
     if (st) {
-      st->lookups += hs[GS_LOOKUPS]; st->list_entries += hs[GS_ENTRIES]; st->list_bytes += 12ull * hs[GS_LOOKUPS] + 4ull * hs[GS_ENTRIES];
-      st->survivors += hs[GS_SURVIVORS]; st->anchors += hs[GS_ANCHORS]; st->windows += hs[GS_WINDOWS];
-      st->vec_calls += hs[GS_VEC_CALLS]; st->vec_cells += hs[GS_VEC_CELLS]; st->vec_bypassed += hs[GS_VEC_BYPASSED];
-      st->full_calls += hs[GS_FULL_CALLS]; st->full_cells += hs[GS_FULL_CELLS]; st->exact_order_reads += hs[GS_EXACT_ORDER]; st->survivors_pruned += hs[GS_PRUNED];
+      add_device_stats(st, hs);
       st->ms_lookup += ms[0]; st->ms_anchors += ms[1]; st->ms_pass1 += ms[2]; st->ms_select += ms[3]; st->ms_pass2 += ms[4];
     }
     s->last_lookup_bytes += 12ull * hs[GS_LOOKUPS] + 4ull * hs[GS_ENTRIES];
@@ -1652,13 +1658,51 @@ struct GmDevTurn {
   GmDevTurn(const GmDevTurn&) = delete; GmDevTurn& operator=(const GmDevTurn&) = delete;
 };
 
+// ---- per-call set-up that map_impl and map_pairs_impl (gm_host_pairs.inc) share ----
+static const char* line_end(const char* p) { const char* e = strchr(p, '\n'); return e ? e : p + strlen(p); }
+// The first n lines of a text block: ptr gets each line's start, len (or null) its length.  want >= 0: every line has that many characters, or the call fails with the
+// caller's message -- bad_len_fmt takes the line's number, its length and want, in that order
+static int split_lines(const char* text, int n, std::vector<const char*>& ptr, std::vector<int>* len, int want = -1, const char* bad_len_fmt = nullptr) {
+  for (int i = 0; i < n; i++) {
+    const char* p = text; const char* e = line_end(p);
+    if (want >= 0 && (int)(e - p) != want) { gm_set_error(bad_len_fmt, i, (int)(e - p), want); return GM_E_ARG; }
+    ptr.push_back(p); if (len) len->push_back((int)(e - p)); text = *e ? e + 1 : e;
+  }
+  return GM_OK;
+}
+// per-position crossover scores of n colour-space reads from their QUAL strings (ref: gmapper.c:532-544); qv (or null): also the clamped quality values
+static void xover_from_quals(const gm_session* s, const char* const* quals, int n, int read_len, int qual_delta, int8_t* xover, uint8_t* qv_out) {
+  for (int i = 0; i < n; i++) {
+    const char* q = quals[i];
+    for (int j = 0; j < read_len; j++) {
+      const int qv = (int)q[j] - qual_delta;
+      if (qv_out) qv_out[(size_t)i * read_len + j] = (uint8_t)std::min(250, std::max(0, qv));   // what post_sw's error-rate formula distinguishes (qv <= 0, qv >= 250, ref: util.h:285-293)
+      const double pe = qv <= 0 ? .99999999 : (qv >= 250 ? 1E-25 : pow(10.0, -(double)qv / 10.0));   // pr_err_from_qv, ref: util.h:285-293
+      int cx = (int)(s->score_alpha * log(pe / 3.0) / log(2.0));
+      if (cx > -1) cx = -1; else if (cx < 2 * s->P.crossover_score) cx = 2 * s->P.crossover_score;
+      xover[(size_t)i * read_len + j] = (int8_t)cx;
+    }
+  }
+}
+// the SHRiMP / pretty formats and the ZE:Z edit string print genome letters: one download per session
+static int ensure_host_genome(gm_session* s) {
+  if (!(s->P.output_format || s->P.extra_sam_fields) || !s->h_genome.empty()) return GM_OK;
+  s->h_genome.resize(s->ix->genome_words);
+  GM_HIP(hipMemcpy(s->h_genome.data(), s->ix->d_genome, s->ix->genome_words * 4, hipMemcpyDeviceToHost));
+  return GM_OK;
+}
+static int check_read_len(const gm_session* s, int read_len) {
+  if (read_len > s->P.longest_read_len || read_len >= 32768 / std::max(1, s->P.match_score)) { gm_set_error("read length %d out of range (ref: sw-vector.c:393-398)", read_len); return GM_E_RANGE; }
+  return GM_OK;
+}
+
 static int map_impl(gm_session* s, int n_reads, int read_len, const uint32_t* reads_host, const void* reads_dev,
                     const char* names, int emit_sam, char** sam, size_t* sam_len, gm_map_stats_t* stats, const uint8_t* initbp_host = nullptr,
                     const char* quals = nullptr, int qual_delta = 33, const char* seq_text = nullptr, uint32_t* per_read_bytes = nullptr) {
   if (!s || n_reads < 0 || read_len < 1) { gm_set_error("gm_map_reads: bad arguments"); return GM_E_ARG; }
   if ((s->P.colour_space != 0) != (initbp_host != nullptr)) {
     gm_set_error(s->P.colour_space ? "colour-space session: use gm_map_reads_cs (colours + primer letters)" : "gm_map_reads_cs needs a colour-space session"); return GM_E_ARG; }
-  if (read_len > s->P.longest_read_len || read_len >= 32768 / std::max(1, s->P.match_score)) { gm_set_error("read length %d out of range (ref: sw-vector.c:393-398)", read_len); return GM_E_RANGE; }
+  if (int rc = check_read_len(s, read_len)) return rc;
   const double tl_in = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
   GmDevTurn dev_turn(s);
   const double tl_turn = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -1667,38 +1711,19 @@ static int map_impl(gm_session* s, int n_reads, int read_len, const uint32_t* re
   if (stats) memset(stats, 0, sizeof *stats);
   if (D.cur_len != read_len || (D.caps_pair_mode != 0 && D.caps_pair_mode != 4)) { choose_caps(s, D, read_len); D.caps_pair_mode = 0; int rc = alloc_buffers(s, D, read_len); if (rc) return rc; }
   const int read_words = (read_len + 7) / 8;
-  if ((s->P.output_format || s->P.extra_sam_fields) && s->h_genome.empty()) {    // the SHRiMP / pretty formats and the ZE:Z edit string print genome letters: one download per session
-    s->h_genome.resize(s->ix->genome_words);
-    GM_HIP(hipMemcpy(s->h_genome.data(), s->ix->d_genome, s->ix->genome_words * 4, hipMemcpyDeviceToHost));
-  }
+  if (int rc = ensure_host_genome(s)) return rc;
   s->last_lookup_ms = 0; s->last_lookup_bytes = 0; s->last_lookup_launches = 0;
   // names
   std::vector<const char*> nptr; std::vector<int> nlen;
   std::vector<const char*> qptr; std::vector<int8_t> xbuf; std::vector<uint8_t> qvbuf; std::vector<const char*> sptr;
-  if (seq_text && gm_fixed_lines(seq_text, (size_t)n_reads, (size_t)(read_len + (s->P.colour_space ? 1 : 0)))) {     // (the usual case: no search for the line ends)
-    const size_t stride = (size_t)(read_len + (s->P.colour_space ? 1 : 0)) + 1; sptr.resize(n_reads);
-    for (int i = 0; i < n_reads; i++) sptr[i] = seq_text + (size_t)i * stride;
-  } else
-  if (seq_text) {                                            // one line per read: read_len letters, or primer + read_len colours
-    const char* p = seq_text; const int want = read_len + (s->P.colour_space ? 1 : 0);
-    for (int i = 0; i < n_reads; i++) {
-      const char* e = strchr(p, '\n'); if (!e) e = p + strlen(p);
-      if ((int)(e - p) != want) { gm_set_error("read %d: %d characters, expected %d", i, (int)(e - p), want); return GM_E_ARG; }
-      sptr.push_back(p); p = *e ? e + 1 : e;
-    }
-  }
-  if (quals && gm_fixed_lines(quals, (size_t)n_reads, (size_t)read_len)) {
-    qptr.resize(n_reads); for (int i = 0; i < n_reads; i++) qptr[i] = quals + (size_t)i * ((size_t)read_len + 1);
-  } else
-  if (quals) {
-    const char* p = quals;
-    for (int i = 0; i < n_reads; i++) {
-      const char* e = strchr(p, '\n'); if (!e) e = p + strlen(p);
-      if ((int)(e - p) != read_len) { gm_set_error("read %d: QUAL string of %d characters for %d bases", i, (int)(e - p), read_len); return GM_E_ARG; }
-      qptr.push_back(p); p = *e ? e + 1 : e;
-    }
-  }
-  if (names) { const char* p = names; for (int i = 0; i < n_reads; i++) { const char* e = strchr(p, '\n'); if (!e) e = p + strlen(p); nptr.push_back(p); nlen.push_back((int)(e - p)); p = *e ? e + 1 : e; } }
+  auto lines_of = [&](const char* text, int want, std::vector<const char*>& ptr, const char* bad_len_fmt) -> int {      // one line of `want` characters per read
+    if (!gm_fixed_lines(text, (size_t)n_reads, (size_t)want)) return split_lines(text, n_reads, ptr, nullptr, want, bad_len_fmt);
+    ptr.resize(n_reads); for (int i = 0; i < n_reads; i++) ptr[i] = text + (size_t)i * ((size_t)want + 1);      // (the usual case: no search for the line ends)
+    return GM_OK;
+  };
+  if (seq_text) { if (int rc = lines_of(seq_text, read_len + (s->P.colour_space ? 1 : 0), sptr, "read %d: %d characters, expected %d")) return rc; }   // letters, or primer + colours
+  if (quals) { if (int rc = lines_of(quals, read_len, qptr, "read %d: QUAL string of %d characters for %d bases")) return rc; }
+  if (names) split_lines(names, n_reads, nptr, &nlen);
   // Sub-batches are pipelined: while the GPU works on sub-batch i+1, host threads finish sub-batch i
   // (pass-2 selection, MAPQ, SAM text).  Output stays in input order.
   struct Job {
@@ -1709,8 +1734,7 @@ static int map_impl(gm_session* s, int n_reads, int read_len, const uint32_t* re
     std::thread th;
   };
   std::vector<std::unique_ptr<Job>> jobs;
-  int nthreads = (int)std::min<unsigned>(32, std::max(1u, std::thread::hardware_concurrency()));   // a multi-rank job divides the cores itself: GM_HOST_THREADS (bench.py: cores / ranks of this node)
-  if (const char* e = getenv("GM_HOST_THREADS")) nthreads = std::max(1, atoi(e));
+  const int nthreads = gm_host_threads(32);                  // a multi-rank job divides the cores itself: GM_HOST_THREADS (bench.py: cores / ranks of this node)
   const int ops_stride = D.ops_stride;
   // The SAM text is assembled as the jobs finish, in input order (each job appends after its predecessor), so that the copy -- and the
   // first touch of the output pages -- overlaps the device work instead of following it.
@@ -1803,17 +1827,7 @@ static int map_impl(gm_session* s, int n_reads, int read_len, const uint32_t* re
     S.xover_on = false;
     if (initbp_host && quals) {                              // per-position crossover scores from the QVs, ref: gmapper.c:532-544
       xbuf.resize((size_t)n * read_len); qvbuf.resize((size_t)n * read_len);
-      for (int i = 0; i < n; i++) {
-        const char* q = qptr[base + i];
-        for (int j = 0; j < read_len; j++) {
-          const int qv = (int)q[j] - qual_delta;
-          qvbuf[(size_t)i * read_len + j] = (uint8_t)std::min(250, std::max(0, qv));   // what post_sw's error-rate formula distinguishes (qv <= 0, qv >= 250, ref: util.h:285-293)
-          const double pe = qv <= 0 ? .99999999 : (qv >= 250 ? 1E-25 : pow(10.0, -(double)qv / 10.0));   // pr_err_from_qv, ref: util.h:285-293
-          int cx = (int)(s->score_alpha * log(pe / 3.0) / log(2.0));
-          if (cx > -1) cx = -1; else if (cx < 2 * s->P.crossover_score) cx = 2 * s->P.crossover_score;
-          xbuf[(size_t)i * read_len + j] = (int8_t)cx;
-        }
-      }
+      xover_from_quals(s, qptr.data() + base, n, read_len, qual_delta, xbuf.data(), qvbuf.data());
       GM_HIP(hipMemcpyAsync(S.d_xover, xbuf.data(), xbuf.size(), hipMemcpyHostToDevice, c));
       GM_HIP(hipMemcpyAsync(S.d_qv, qvbuf.data(), qvbuf.size(), hipMemcpyHostToDevice, c));
       GM_HIP(hipStreamSynchronize(c));                      // xbuf is reused by the next sub-batch
@@ -1990,7 +2004,7 @@ extern "C" int gm_map_reads_text(gm_session_t* s, int n_reads, int read_len, con
   } else {
   const char* p = seqs;
   for (int i = 0; i < n_reads; i++) {
-    const char* e = strchr(p, '\n'); if (!e) e = p + strlen(p);
+    const char* e = line_end(p);
     if ((int)(e - p) != line) { gm_set_error("read %d: %d characters, expected %d", i, (int)(e - p), line); return GM_E_ARG; }
     int b = 0; const int rc = gm_sequence_to_bitfield(cs, p, line, packed.data() + (size_t)i * rwords, &b); if (rc) return rc;
     if (cs) ibp[i] = (uint8_t)b;

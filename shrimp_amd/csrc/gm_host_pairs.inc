@@ -331,73 +331,81 @@ static int stage_windows_async(gm_session* s, DevSet& D, const GmIndexDev& dv, i
   return GM_OK;
 }
 
-static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* m1, int len2, const uint32_t* m2,
-                          const char* names1, const char* names2, const gm_pair_opts_t* opts, char** sam, size_t* sam_len, gm_map_stats_t* stats,
-                          const char* quals1 = nullptr, const char* quals2 = nullptr, int qual_delta = 33,
-                          const uint8_t* initbp1 = nullptr, const uint8_t* initbp2 = nullptr, uint32_t* per_pair_bytes = nullptr) {
-  if (!s || n_pairs < 0 || len1 < 1 || len2 < 1 || (n_pairs > 0 && (!m1 || !m2))) { gm_set_error("gm_map_pairs: bad arguments"); return GM_E_ARG; }
-  GmDevTurn dev_turn(s);
-  GM_HIP(hipSetDevice(s->ix->device));
-  if ((s->P.output_format || s->P.extra_sam_fields) && s->h_genome.empty()) {      // the SHRiMP / pretty formats and the ZE:Z edit string print genome letters: one download per session
-    s->h_genome.resize(s->ix->genome_words);
-    GM_HIP(hipMemcpy(s->h_genome.data(), s->ix->d_genome, s->ix->genome_words * 4, hipMemcpyDeviceToHost));
+namespace {                                                    // (the call's own types: nothing of them is exported)
+// -C / -F do not apply in paired mode (ref: gmapper.c:2448-2451)
+struct BothStrands { gm_session* s; int v; explicit BothStrands(gm_session* s_) : s(s_), v(s_->sc.skip_strands) { s->sc.skip_strands = 0; } ~BothStrands() { s->sc.skip_strands = v; } };
+// One gm_map_pairs call: what init() settles before the first sub-batch and nothing changes after it (the output thread reads it beside the calling thread).
+struct PairCall {
+  gm_session* s = nullptr; const gm_index* ix = nullptr; gm_pair_opts_t O; int pmode = 4, n_pairs = 0; bool mp_counts = false, cs = false, timing = false;
+  std::optional<BothStrands> both_strands;
+  int len[2], rwords[2], W[2], ovl[2], in_st[2]; const uint32_t* mates[2]; const uint8_t* initbp_in[2];
+  GmIndexDev dv, dvm[2];                                       // dvm: the view each mate's kernels get (see init)
+  hipStream_t qa = nullptr, q = nullptr;                       // the front's stream; the stream of everything after the front
+  int dmin[2], dmax[2], dmin2[2], dmax2[2];                    // insert ranges as window-offset deltas, from the first mate and from the second
+  GmScoreDev scp, scr, sc_half; int cs9[9];                    // score sets: the paired pass 1, the rescue's pass 1, the paired pass 2; sw_full_cs_setup's arguments
+  PairCtx C;
+  std::vector<const char*> nptr[2], qptr[2]; std::vector<int> nlen[2]; bool named = false, quals = false; int qual_delta = 33;   // name and QUAL line of every mate
+  int nthreads = 1; DevSet* PS[2][2]; bool overlap = false; uint32_t* per_pair_bytes = nullptr; gm_map_stats_t* stats = nullptr;
+  void parallel_chunks(int nchunks, const std::function<void(int)>& fn) const {
+    std::atomic<int> next(0);
+    auto worker = [&]() { for (;;) { int c = next.fetch_add(1); if (c >= nchunks) break; fn(c); } };
+    gm_run_on_threads(std::min(nthreads, nchunks), worker);
   }
-  const bool cs = s->P.colour_space != 0;
-  const uint8_t* initbp_in[2] = {initbp1, initbp2};
-  if (cs && n_pairs > 0 && (!initbp1 || !initbp2)) { gm_set_error("gm_map_pairs_cs: no primer letters"); return GM_E_ARG; }
-  gm_pair_opts_t O; if (opts) O = *opts; else gm_pair_opts_default(&O);
-  if (O.pair_mode < GM_PAIR_OPP_IN || O.pair_mode > GM_PAIR_COL_BW) { gm_set_error("gm_map_pairs: pair_mode %d", O.pair_mode); return GM_E_ARG; }
-  // half_paired = 0 (--no-half-paired): each mate's list entries are filtered by the other mate's region counts (k_mp_filter, ref: mapping.c:545-608,
-  // gmapper.c:2657-2662 use_mp_region_counts = 1) and no unpaired rescue runs afterwards (gmapper.c:2678-2683)
-  // match_mode (the reference's -n in paired mode, gmapper.c:2652-2673): 4 as above; 3: the lookup also keeps the entries of regions marked once that the mate reaches
-  // with a region it marked twice (GmMpDev; without half-paired the filter then applies rule 3), the window kernel runs hit-list mode 3; 2: no region counts, a window
-  // per anchor.  pass 1 asks for two matches only in mode 4 (:2673); the unpaired rescue always does (:2708).
-  const int pmode = O.match_mode == 0 ? 4 : O.match_mode;
-  if (pmode < 2 || pmode > 4) { gm_set_error("gm_map_pairs: match_mode %d (2, 3 or 4 in paired mode, ref: gmapper.c:2495-2498)", O.match_mode); return GM_E_ARG; }
-  const bool mp_counts = !O.half_paired && pmode == 4;
-  struct BothStrands { gm_session* s; int v; explicit BothStrands(gm_session* s_) : s(s_), v(s_->sc.skip_strands) { s->sc.skip_strands = 0; } ~BothStrands() { s->sc.skip_strands = v; } }
-    both_strands(s);                                           // -C / -F do not apply in paired mode (ref: gmapper.c:2448-2451)
-  GmScoreDev scp = s->sc; scp.match_mode = pmode == 4 ? 2 : (pmode == 3 ? 3 : 1); scp.min_matches = pmode == 4 ? 2 : 1;      // hit_list.match_mode, pass1.min_matches of the paired set
-  GmScoreDev scr = s->sc; scr.min_matches = 2;                                                                                // the half-paired rescue's pass 1
-  const int len[2] = {len1, len2}; const uint32_t* mates[2] = {m1, m2};
-  for (int m = 0; m < 2; m++)
-    if (len[m] > s->P.longest_read_len || len[m] >= 32768 / std::max(1, s->P.match_score)) { gm_set_error("read length %d out of range (ref: sw-vector.c:393-398)", len[m]); return GM_E_RANGE; }
-  GM_HIP(hipSetDevice(s->ix->device));
-  if (stats) memset(stats, 0, sizeof *stats);
-  s->last_lookup_ms = 0; s->last_lookup_bytes = 0; s->last_lookup_launches = 0;
-  const gm_index* ix = s->ix;
-  const GmIndexDev dv = ix->dev_view();
-  // colour space: a mate the pair mode reverses (read_reverse, ref: gmapper.c:174-185,561-570) keeps its colours and swaps its strand labels (GmIndexDev::cs_flip);
-  // letter space: it is stored reverse-complemented (k_revcomp_reads)
-  GmIndexDev dvm[2] = {dv, dv};
-  hipStream_t q = s->stream_b;                                  // everything after the front
-  static const bool pair_reverse[5][2] = {{0, 0}, {0, 0}, {1, 1}, {0, 1}, {1, 0}};   // ref: gmapper-defaults.h:184-191
-  int rwords[2], W[2], ovl[2], in_st[2];
-  for (int m = 0; m < 2; m++) {
-    rwords[m] = (len[m] + 7) / 8; W[m] = window_len_of(s->P, len[m]);
-    ovl[m] = (int)(unsigned int)(s->P.window_overlap < 0 ? -s->P.window_overlap : W[m] * (s->P.window_overlap / 100.0));
-    in_st[m] = pair_reverse[O.pair_mode][m] ? 1 : 0;
-    if (cs) dvm[m].cs_flip = in_st[m];
-    DevSet& D = s->set[m];
-    if (D.cur_len != len[m] || D.d_pmin == nullptr || (D.caps_pair_mode != pmode && (pmode != 4 || D.caps_pair_mode != 0))) { choose_caps(s, D, len[m], pmode); D.caps_pair_mode = pmode; int rc = alloc_buffers(s, D, len[m], true); if (rc) return rc; }
-  }
-  // Two pairs of buffer sets: the front (K1, K1b, K2 of both mates; stream A) of sub-batch i + 1 is queued before the host turns to the rest of
-  // sub-batch i (stream B), as in map_impl.  GM_OVERLAP=0: one pair, in order.
-  DevSet* PS[2][2] = {{&s->set[0], &s->set[1]}, {&s->set2[0], &s->set2[1]}};
-  bool overlap = n_pairs > std::min(s->set[0].eff_batch, s->set[1].eff_batch);
-  if (const char* e = getenv("GM_OVERLAP")) overlap = overlap && atoi(e) != 0;
-  if (overlap)
+  // validation, then the set-up (map_pairs_impl has checked s, n_pairs, the lengths and the read pointers)
+  int init(gm_session* s_, int n_pairs_, int len1, const uint32_t* m1, int len2, const uint32_t* m2, const char* names1, const char* names2, const gm_pair_opts_t* opts,
+           gm_map_stats_t* stats_, const char* quals1, const char* quals2, int qual_delta_, const uint8_t* initbp1, const uint8_t* initbp2, uint32_t* per_pair_bytes_) {
+    s = s_; n_pairs = n_pairs_; stats = stats_; qual_delta = qual_delta_; per_pair_bytes = per_pair_bytes_;
+    GM_HIP(hipSetDevice(s->ix->device));
+    int rc = ensure_host_genome(s); if (rc) return rc;
+    cs = s->P.colour_space != 0;
+    initbp_in[0] = initbp1; initbp_in[1] = initbp2;
+    if (cs && n_pairs > 0 && (!initbp1 || !initbp2)) { gm_set_error("gm_map_pairs_cs: no primer letters"); return GM_E_ARG; }
+    if (opts) O = *opts; else gm_pair_opts_default(&O);
+    if (O.pair_mode < GM_PAIR_OPP_IN || O.pair_mode > GM_PAIR_COL_BW) { gm_set_error("gm_map_pairs: pair_mode %d", O.pair_mode); return GM_E_ARG; }
+    // half_paired = 0 (--no-half-paired): each mate's list entries are filtered by the other mate's region counts (k_mp_filter, ref: mapping.c:545-608,
+    // gmapper.c:2657-2662 use_mp_region_counts = 1) and no unpaired rescue runs afterwards (gmapper.c:2678-2683)
+    // match_mode (the reference's -n in paired mode, gmapper.c:2652-2673): 4 as above; 3: the lookup also keeps the entries of regions marked once that the mate reaches
+    // with a region it marked twice (GmMpDev; without half-paired the filter then applies rule 3), the window kernel runs hit-list mode 3; 2: no region counts, a window
+    // per anchor.  pass 1 asks for two matches only in mode 4 (:2673); the unpaired rescue always does (:2708).
+    pmode = O.match_mode == 0 ? 4 : O.match_mode;
+    if (pmode < 2 || pmode > 4) { gm_set_error("gm_map_pairs: match_mode %d (2, 3 or 4 in paired mode, ref: gmapper.c:2495-2498)", O.match_mode); return GM_E_ARG; }
+    mp_counts = !O.half_paired && pmode == 4;
+    both_strands.emplace(s);
+    scp = s->sc; scp.match_mode = pmode == 4 ? 2 : (pmode == 3 ? 3 : 1); scp.min_matches = pmode == 4 ? 2 : 1;      // hit_list.match_mode, pass1.min_matches of the paired set
+    scr = s->sc; scr.min_matches = 2;                                                                                // the half-paired rescue's pass 1
+    len[0] = len1; len[1] = len2; mates[0] = m1; mates[1] = m2;
+    for (int m = 0; m < 2; m++) { rc = check_read_len(s, len[m]); if (rc) return rc; }
+    GM_HIP(hipSetDevice(s->ix->device));
+    if (stats) memset(stats, 0, sizeof *stats);
+    s->last_lookup_ms = 0; s->last_lookup_bytes = 0; s->last_lookup_launches = 0;
+    ix = s->ix; dv = ix->dev_view();
+    // colour space: a mate the pair mode reverses (read_reverse, ref: gmapper.c:174-185,561-570) keeps its colours and swaps its strand labels (GmIndexDev::cs_flip);
+    // letter space: it is stored reverse-complemented (k_revcomp_reads)
+    dvm[0] = dvm[1] = dv;
+    qa = s->stream; q = s->stream_b;
+    static const bool pair_reverse[5][2] = {{0, 0}, {0, 0}, {1, 1}, {0, 1}, {1, 0}};   // ref: gmapper-defaults.h:184-191
     for (int m = 0; m < 2; m++) {
-      DevSet& D = s->set2[m]; const DevSet& R = s->set[m];
-      if (D.cur_len != len[m] || D.d_pmin == nullptr || D.scap != R.scap || D.scap2 != R.scap2 || D.hcap < R.hcap || D.rcap_per_read < R.rcap_per_read) {
-        D.scap = R.scap; D.scap2 = R.scap2; D.hcap = std::max(D.hcap, R.hcap); D.rcap_per_read = std::max(D.rcap_per_read, R.rcap_per_read);
-        int rc = alloc_buffers(s, D, len[m], true); if (rc) return rc;
-      }
+      rwords[m] = (len[m] + 7) / 8; W[m] = window_len_of(s->P, len[m]);
+      ovl[m] = (int)(unsigned int)(s->P.window_overlap < 0 ? -s->P.window_overlap : W[m] * (s->P.window_overlap / 100.0));
+      in_st[m] = pair_reverse[O.pair_mode][m] ? 1 : 0;
+      if (cs) dvm[m].cs_flip = in_st[m];
+      DevSet& D = s->set[m];
+      if (D.cur_len != len[m] || D.d_pmin == nullptr || (D.caps_pair_mode != pmode && (pmode != 4 || D.caps_pair_mode != 0))) { choose_caps(s, D, len[m], pmode); D.caps_pair_mode = pmode; rc = alloc_buffers(s, D, len[m], true); if (rc) return rc; }
     }
-  hipStream_t qa = s->stream;
-  // readpair_compute_mp_ranges, ref: mapping.c:2317-2442 (only the delta_g_off part is used without mate-pair region counts)
-  int dmin[2], dmax[2];
-  {
+    // Two pairs of buffer sets: the front (K1, K1b, K2 of both mates; stream A) of sub-batch i + 1 is queued before the host turns to the rest of
+    // sub-batch i (stream B), as in map_impl.  GM_OVERLAP=0: one pair, in order.
+    PS[0][0] = &s->set[0]; PS[0][1] = &s->set[1]; PS[1][0] = &s->set2[0]; PS[1][1] = &s->set2[1];
+    overlap = n_pairs > std::min(s->set[0].eff_batch, s->set[1].eff_batch);
+    if (const char* e = getenv("GM_OVERLAP")) overlap = overlap && atoi(e) != 0;
+    if (overlap)
+      for (int m = 0; m < 2; m++) {
+        DevSet& D = s->set2[m]; const DevSet& R = s->set[m];
+        if (D.cur_len != len[m] || D.d_pmin == nullptr || D.scap != R.scap || D.scap2 != R.scap2 || D.hcap < R.hcap || D.rcap_per_read < R.rcap_per_read) {
+          D.scap = R.scap; D.scap2 = R.scap2; D.hcap = std::max(D.hcap, R.hcap); D.rcap_per_read = std::max(D.rcap_per_read, R.rcap_per_read);
+          rc = alloc_buffers(s, D, len[m], true); if (rc) return rc;
+        }
+      }
+    // readpair_compute_mp_ranges, ref: mapping.c:2317-2442 (only the delta_g_off part is used without mate-pair region counts)
     const int mn = O.min_insert_size, mx = O.max_insert_size;
     int a = mn - W[1], b = mx + (W[0] - len[0]) - len[1], c = -mx + len[0] + (len[1] - W[1]), d = -mn + W[0];
     switch (O.pair_mode) {
@@ -407,257 +415,348 @@ static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* 
       default: a += len[0]; b += len[0]; c -= len[0]; d -= len[0]; break;
     }
     dmin[0] = a; dmax[0] = b; dmin[1] = c; dmax[1] = d;
-  }
-  int dmin2[2], dmax2[2];                                      // the second mate's ranges (ref: mapping.c:2340-2343,2366-2369,2381-2384,2407-2410)
-  if (O.pair_mode == GM_PAIR_OPP_IN || O.pair_mode == GM_PAIR_OPP_OUT) { dmin2[0] = -dmax[1]; dmax2[0] = -dmin[1]; dmin2[1] = -dmax[0]; dmax2[1] = -dmin[0]; }
-  else { dmin2[0] = -dmax[0]; dmax2[0] = -dmin[0]; dmin2[1] = -dmax[1]; dmax2[1] = -dmin[1]; }
-  PairCtx C; C.s = s; C.O = O; C.len[0] = len1; C.len[1] = len2; C.rwords[0] = rwords[0]; C.rwords[1] = rwords[1]; C.total_genome_size = (double)ix->total_len;
-  // names
-  std::vector<const char*> nptr[2]; std::vector<int> nlen[2];
-  const char* names[2] = {names1, names2};
-  for (int m = 0; m < 2; m++)
-    if (names[m]) { const char* p = names[m]; for (int i = 0; i < n_pairs; i++) { const char* e = strchr(p, '\n'); if (!e) e = p + strlen(p); nptr[m].push_back(p); nlen[m].push_back((int)(e - p)); p = *e ? e + 1 : e; } }
-  std::vector<const char*> qptr[2];                            // FASTQ input: QUAL string of every mate
-  const char* qualsv[2] = {quals1, quals2};
-  if ((quals1 != nullptr) != (quals2 != nullptr)) { gm_set_error("gm_map_pairs_fastq: QUAL strings for both mates or for none"); return GM_E_ARG; }
-  for (int m = 0; m < 2; m++)
-    if (qualsv[m]) {
-      const char* p = qualsv[m];
-      for (int i = 0; i < n_pairs; i++) {
-        const char* e = strchr(p, '\n'); if (!e) e = p + strlen(p);
-        if ((int)(e - p) != len[m]) { gm_set_error("pair %d, mate %d: QUAL string of %d characters for %d bases", i, m + 1, (int)(e - p), len[m]); return GM_E_ARG; }
-        qptr[m].push_back(p); p = *e ? e + 1 : e;
+    // the second mate's ranges (ref: mapping.c:2340-2343,2366-2369,2381-2384,2407-2410)
+    if (O.pair_mode == GM_PAIR_OPP_IN || O.pair_mode == GM_PAIR_OPP_OUT) { dmin2[0] = -dmax[1]; dmax2[0] = -dmin[1]; dmin2[1] = -dmax[0]; dmax2[1] = -dmin[0]; }
+    else { dmin2[0] = -dmax[0]; dmax2[0] = -dmin[0]; dmin2[1] = -dmax[1]; dmax2[1] = -dmin[1]; }
+    C.s = s; C.O = O; C.len[0] = len1; C.len[1] = len2; C.rwords[0] = rwords[0]; C.rwords[1] = rwords[1]; C.total_genome_size = (double)ix->total_len;
+    const char* names[2] = {names1, names2}; const char* qualsv[2] = {quals1, quals2};
+    for (int m = 0; m < 2; m++) if (names[m]) split_lines(names[m], n_pairs, nptr[m], &nlen[m]);
+    named = names1 && names2;
+    if ((quals1 != nullptr) != (quals2 != nullptr)) { gm_set_error("gm_map_pairs_fastq: QUAL strings for both mates or for none"); return GM_E_ARG; }
+    quals = quals1 != nullptr;                                 // FASTQ input: QUAL string of every mate
+    for (int m = 0; m < 2; m++)
+      if (qualsv[m]) {
+        char fmt[96]; snprintf(fmt, sizeof fmt, "pair %%d, mate %d: QUAL string of %%d characters for %%d bases", m + 1);
+        rc = split_lines(qualsv[m], n_pairs, qptr[m], nullptr, len[m], fmt); if (rc) return rc;
       }
+    nthreads = gm_host_threads(16);
+    sc_half = s->sc;                                                                    // per-mate threshold of the paired pass 2, ref: gmapper.c:2677
+    if (s->P.sw_full_threshold < 0) { sc_half.full_thr_frac = -1.0; sc_half.full_abs = (int)(-(s->P.sw_full_threshold * 0.5)); }
+    else sc_half.full_thr_frac = (s->P.sw_full_threshold * 0.5) / 100.0;
+    const int c9[9] = {s->P.match_score, s->P.mismatch_score, s->P.crossover_score, -s->P.a_gap_open_score, -s->P.a_gap_extend_score,
+                       -s->P.b_gap_open_score, -s->P.b_gap_extend_score, s->P.anchor_width, s->P.indel_taboo_len};   // sw_full_cs_setup's arguments (ref: gmapper.c:2944-2947)
+    memcpy(cs9, c9, sizeof cs9);
+    timing = gm_tune("GM_TIMING") != nullptr;
+    return GM_OK;
+  }
+};
+// One sub-batch from the paired pass 2 on: the calling thread fills it stage by stage, then the output thread owns it.  resP / opsP, resU / opsU: the paired and
+// the unpaired results in one of the session's two pinned sets (pinned: the copies run at link rate beside the kernels)
+struct PairOut {
+  int base = 0, n = 0, chunk = 2048, nchunks = 0, NO = 1, ops_stride[2] = {0, 0};
+  Finalizer F[2];
+  GmPinVec<GmFullRes>* resP = nullptr; GmPinVec<uint8_t>* opsP = nullptr; GmPinVec<GmFullRes>* resU = nullptr; GmPinVec<uint8_t>* opsU = nullptr;
+  std::vector<FHit> fhP[2]; std::vector<PPair> fpairs; std::vector<int> fcnt; std::vector<uint32_t> offP[2], cntU[2], offU[2];
+};
+struct PairScratch { std::vector<FHit> fhU[2]; std::vector<FHit*> U[2]; };      // a worker's unpaired mappings of the pair in hand, reused from pair to pair
+// What is printed for a pair: paired records [first2, last2) of fp, unpaired ones [firstU[m], lastU[m]) of each mate; --single-best-mapping narrows them by the mapping
+// qualities (set by now) and may add one improper pair of two unpaired mappings, imp[] (ref: output.c:1086-1235)
+struct PairPlan { int first2, last2, firstU[2], lastU[2]; const FHit* imp[2]; };
+static PairPlan plan_pair_output(const gm_params_t& P, FHit* const HP[2], const PPair* fp, int nfp, const std::vector<FHit*> U[2]) {
+  PairPlan p = {0, nfp, {0, 0}, {(int)U[0].size(), (int)U[1].size()}, {nullptr, nullptr}};
+  if (!gm_mqv_on(P) || !P.single_best_mapping || !(nfp > 0 || !U[0].empty() || !U[1].empty())) return p;
+  int max_idx_unpaired[2] = {-1, -1}, max_mqv_unpaired[2] = {-1, -1}, max_mqv_paired[2] = {-1, -1}; const FHit* max_hit_paired[2] = {nullptr, nullptr};
+  for (int nip = 0; nip < 2; nip++) {
+    for (int i = 0; i < (int)U[nip].size(); i++) if (U[nip][i]->mqv > max_mqv_unpaired[nip]) { max_mqv_unpaired[nip] = U[nip][i]->mqv; max_idx_unpaired[nip] = i; }
+    // the pool of paired hits in the order readpair_save_final_hits builds it: first appearance over the pairs (a repeated hit compares equal: strict >)
+    for (int j = 0; j < nfp; j++) { const FHit* h = &HP[nip][fp[j].h[nip]]; if (h->mqv > max_mqv_paired[nip]) { max_mqv_paired[nip] = h->mqv; max_hit_paired[nip] = h; } }
+  }
+  // get_idx_mp_max_mqv (ref: output.c:1049-1067): of the pairs that hold hit h of mate nip, the first whose other mate has the best quality
+  auto pair_of = [&](int nip, const FHit* h) { int best = -1, idx = -1; for (int j = 0; j < nfp; j++) if (&HP[nip][fp[j].h[nip]] == h) { const int q = HP[1 - nip][fp[j].h[1 - nip]].mqv; if (q > best) { best = q; idx = j; } } return idx; };
+  if (!P.all_contigs) {
+    for (int nip = 0; nip < 2; nip++) if (max_idx_unpaired[nip] >= 0) { p.firstU[nip] = max_idx_unpaired[nip]; p.lastU[nip] = p.firstU[nip] + 1; }
+    const int best_nip = max_mqv_paired[0] > max_mqv_paired[1] ? 0 : 1;
+    if (max_mqv_paired[best_nip] >= 0) { p.first2 = pair_of(best_nip, max_hit_paired[best_nip]); p.last2 = p.first2 + 1; }
+    return p;
+  }
+  int max_mqv[2]; bool max_is_paired[2];
+  for (int nip = 0; nip < 2; nip++) {
+    if (max_mqv_unpaired[nip] > max_mqv_paired[nip]) { max_mqv[nip] = max_mqv_unpaired[nip]; max_is_paired[nip] = false; }
+    else { max_mqv[nip] = max_mqv_paired[nip]; max_is_paired[nip] = true; }
+  }
+  const int best_nip = max_mqv[0] >= max_mqv[1] ? 0 : 1;
+  if (max_is_paired[best_nip]) { p.lastU[0] = p.lastU[1] = 0; p.first2 = pair_of(best_nip, max_hit_paired[best_nip]); p.last2 = p.first2 + 1; return p; }
+  int idx_best_other = -1; double max_other_z0 = 0.0;
+  const auto& OU = U[1 - best_nip];
+  for (int i = 0; i < (int)OU.size(); i++) if (OU[i]->z0 > max_other_z0) { max_other_z0 = OU[i]->z0; idx_best_other = i; }
+  int best_other_mqv = -1;
+  if (idx_best_other >= 0) best_other_mqv = qv_from_pr_corr(max_other_z0 / OU[idx_best_other]->z1);
+  if (P.no_improper_mappings || max_mqv_unpaired[best_nip] < 10 || best_other_mqv < 10) {
+    p.last2 = 0; p.lastU[1 - best_nip] = 0; p.firstU[best_nip] = max_idx_unpaired[best_nip]; p.lastU[best_nip] = p.firstU[best_nip] + 1;
+  } else {                                                            // both good: one improper pair, possibly across contigs
+    p.imp[best_nip] = U[best_nip][max_idx_unpaired[best_nip]]; p.imp[1 - best_nip] = OU[idx_best_other];
+    p.last2 = 0; p.lastU[0] = p.lastU[1] = 0;
+  }
+  return p;
+}
+
+// readpair_output for pair pr of the sub-batch (ref: output.c:1070-1291): the mates' unpaired selection, the paired mapping qualities, the text.  Returns the number of
+// records; t.U holds the unpaired mappings afterwards.
+static uint64_t emit_pair(const PairCall& c, PairOut& b, int pr, std::string& o, PairScratch& t) {
+  const gm_params_t& P = c.s->P;
+  const long gp = (long)b.base + pr;
+  FHit* HP[2] = {b.fhP[0].data() + b.offP[0][pr], b.fhP[1].data() + b.offP[1][pr]};
+  std::vector<FHit*>* const U = t.U;
+  for (int m = 0; m < 2; m++) b.F[m].select_hits(b.cntU[m][pr] ? &b.resU[m][b.offU[m][pr]] : nullptr, b.opsU[m].data(), (int)b.cntU[m][pr], t.fhU[m], U[m]);
+  const PPair* fp = &b.fpairs[(size_t)pr * b.NO]; const int nfp = b.fcnt[pr];
+  if (gm_mqv_on(P)) compute_paired_mqv(c.C, HP, fp, nfp, U);                  // --local / --no-mapping-qualities: none (ref: gmapper.c:2258,2325-2328, output.c:1092)
+  const PairPlan p = plan_pair_output(P, HP, fp, nfp, U);
+  // QNAME = common prefix of the two names, minus a trailing ':' or '/' (ref: output.c:365-378)
+  const char* qn; size_t qnl; char qbuf[40];
+  if (c.named) {
+    const char* a = c.nptr[0][gp]; const char* z = c.nptr[1][gp]; const size_t na = (size_t)c.nlen[0][gp], nb = (size_t)c.nlen[1][gp];
+    size_t i = 0; while (i < std::min(na, nb) && a[i] == z[i]) i++;
+    if (i > 0 && (a[i - 1] == ':' || a[i - 1] == '/')) i--;
+    qn = a; qnl = i;
+  } else { qnl = (size_t)snprintf(qbuf, sizeof qbuf, "p%ld", gp); qn = qbuf; }
+  const uint32_t* rw[2]; const char* ql[2]; int ib[2];
+  for (int m = 0; m < 2; m++) { rw[m] = c.mates[m] + (size_t)gp * c.rwords[m]; ql[m] = c.quals ? c.qptr[m][gp] : nullptr; ib[m] = c.cs ? (int)c.initbp_in[m][gp] : -1; }
+  uint64_t k = 0;
+  if (P.output_format) {
+    // --shrimp-format / -P: one line (block) per mapped mate under the mate's own name, ">name" for the unmapped mate of a half-paired
+    // mapping (ref: gmapper/output.c:270-296, hit_output called per mate by readpair_output :1070-1291)
+    std::string db, qr;
+    auto one = [&](int m, const FHit* rh) {
+      const char* nm = qn; size_t nl = qnl;
+      if (c.named) { nm = c.nptr[m][gp]; nl = (size_t)c.nlen[m][gp]; }
+      if (!rh) { o += '>'; o.append(nm, nl); o += '\n'; return; }
+      const Finalizer& F = b.F[m];
+      if (c.cs) F.emit_shrimp(*rh, nm, nl, pr, rw[m], rh->db, rh->qr, o);
+      else { F.ls_alignment_strings(*rh->r, rh->ops, std::min(rh->r->n_ops, b.ops_stride[m]), rw[m], db, qr); F.emit_shrimp(*rh, nm, nl, pr, rw[m], db, qr, o); }
+    };
+    for (int j = p.first2; j < p.last2; j++) { one(0, &HP[0][fp[j].h[0]]); one(1, &HP[1][fp[j].h[1]]); k += 2; }
+    if (p.imp[0]) { one(0, p.imp[0]); one(1, p.imp[1]); k += 2; }
+    for (int i = p.firstU[0]; i < p.lastU[0]; i++) { one(0, U[0][i]); one(1, nullptr); k += 2; }
+    for (int i = p.firstU[1]; i < p.lastU[1]; i++) { one(0, nullptr); one(1, U[1][i]); k += 2; }
+    return k;
+  }
+  // --sam-r2: every record carries the MATE's sequence as given (re_mp->seq: letters, or primer + colours; ref: output.c:452-460,729-737)
+  std::string mseq[2]; const std::string* ms[2] = {nullptr, nullptr};
+  if (P.sam_r2) {
+    for (int m = 0; m < 2; m++) {
+      const int L = c.len[m];
+      if (c.cs) { mseq[m] += "ACGT"[ib[m] & 3]; for (int i = 0; i < L; i++) { const int cc = (rw[m][i >> 3] >> ((i & 7) * 4)) & 0xf; mseq[m] += (cc < 4) ? (char)('0' + cc) : '.'; } }
+      else for (int i = 0; i < L; i++) { const int cc = (rw[m][i >> 3] >> ((i & 7) * 4)) & 0xf; mseq[m] += (cc < 4) ? "ACGT"[cc] : (cc == 4 ? 'U' : 'N'); }
     }
-  int nthreads = (int)std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
-  if (const char* e = getenv("GM_HOST_THREADS")) nthreads = std::max(1, atoi(e));
-  auto parallel_chunks = [&](int nchunks, const std::function<void(int)>& fn) {
-    std::atomic<int> next(0);
-    auto worker = [&]() { for (;;) { int c = next.fetch_add(1); if (c >= nchunks) break; fn(c); } };
-    gm_run_on_threads(std::min(nthreads, nchunks), worker);
+    ms[0] = &mseq[1]; ms[1] = &mseq[0];                                        // (mate 1's records carry mate 2's sequence and the other way round)
+  }
+  // the two records of one line of the output: mate 0's mapping h0 and mate 1's h1 (null: that mate is unmapped)
+  auto two = [&](const FHit* h0, const FHit* h1, bool improper) {
+    emit_pair_record(c.C, o, qn, qnl, rw[0], c.len[0], b.ops_stride[0], h0, h1, true, improper, ql[0], c.qual_delta, ib[0], ms[0]);
+    emit_pair_record(c.C, o, qn, qnl, rw[1], c.len[1], b.ops_stride[1], h1, h0, false, improper, ql[1], c.qual_delta, ib[1], ms[1]);
+    k += 2;
   };
-  GmScoreDev sc_half = s->sc;                                                         // per-mate threshold of the paired pass 2, ref: gmapper.c:2677
-  if (s->P.sw_full_threshold < 0) { sc_half.full_thr_frac = -1.0; sc_half.full_abs = (int)(-(s->P.sw_full_threshold * 0.5)); }
-  else sc_half.full_thr_frac = (s->P.sw_full_threshold * 0.5) / 100.0;
-  const int cs9[9] = {s->P.match_score, s->P.mismatch_score, s->P.crossover_score, -s->P.a_gap_open_score, -s->P.a_gap_extend_score,
-                      -s->P.b_gap_open_score, -s->P.b_gap_extend_score, s->P.anchor_width, s->P.indel_taboo_len};   // sw_full_cs_setup's arguments (ref: gmapper.c:2944-2947)
-  std::vector<std::string> pieces_all; uint64_t matched = 0, records = 0;
-  std::vector<unsigned long long> hraw((size_t)GS_STRIPES * GS_STRIDE); unsigned long long hs[GS_N];
-  auto fold = [&]() { for (int k = 0; k < GS_N; k++) { hs[k] = 0; for (int t = 0; t < GS_STRIPES; t++) hs[k] += hraw[(size_t)t * GS_STRIDE + k]; } };
-  const bool timing = gm_tune("GM_TIMING") != nullptr;
-  // front of one sub-batch on buffer pair k: reads in (stream C, so that the call never queues behind kernels), K1 + K1b + K2 for both mates
+  for (int j = p.first2; j < p.last2; j++) two(&HP[0][fp[j].h[0]], &HP[1][fp[j].h[1]], false);
+  if (p.imp[0]) two(p.imp[0], p.imp[1], true);
+  for (int ui = p.firstU[0]; ui < p.lastU[0]; ui++) two(U[0][ui], nullptr, false);
+  for (int ui = p.firstU[1]; ui < p.lastU[1]; ui++) two(nullptr, U[1][ui], false);
+  if (nfp == 0 && U[0].empty() && U[1].empty() && P.sam_unaligned) two(nullptr, nullptr, false);      // ref: mapping.c:2627-2633
+  return k;
+}
+
+// The output stage of a sub-batch (unpaired selection, mapping qualities, text: ~6 of a sub-batch's ~70 ms, all host) runs on a thread of its own beside the device work of
+// the next sub-batch; at most one is outstanding, and its text is appended -- in order -- before the next one starts.
+struct OutJob { std::thread th; std::vector<std::string> outs; std::vector<uint64_t> cm, cr; double ms = 0; bool failed = false; ~OutJob() { if (th.joinable()) th.join(); } };
+static void pair_output(const PairCall& c, PairOut& b, OutJob& J) {
+  const auto t0 = std::chrono::steady_clock::now();
+  c.parallel_chunks(b.nchunks, [&](int ch) {
+    PairScratch t; std::string& o = J.outs[ch]; o.reserve((size_t)b.chunk * (c.len[0] + c.len[1] + 300));
+    for (int pr = ch * b.chunk; pr < std::min(b.n, (ch + 1) * b.chunk); pr++) {
+      const size_t o_before = o.size();
+      J.cr[ch] += emit_pair(c, b, pr, o, t);
+      if (b.fcnt[pr] > 0 || !t.U[0].empty() || !t.U[1].empty()) J.cm[ch]++;
+      if (c.per_pair_bytes) c.per_pair_bytes[(long)b.base + pr] = (uint32_t)(o.size() - o_before);
+    }
+  });
+  J.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+static const int GM_REDO = 1;     // a stage's answer besides GM_OK and the error codes: the sub-batch is run again from its front (as pipeline_back's 1)
+// what the paired pass hands from stage to stage on the calling thread
+struct PairSel { uint32_t n_work[2] = {0, 0}; std::vector<uint32_t> cntP[2], plist, pcnt; std::vector<std::vector<uint32_t>> saved_chunks[2]; };
+// The call's state that changes from sub-batch to sub-batch, and the stages of a sub-batch in the order map_pairs_impl calls them.  Each stage queues its HIP calls on
+// qa (front) or q (the rest) and returns GM_OK, GM_REDO or an error.
+struct PairRun : PairCall {
   // -n 4 without half-paired: k_mp_filter works on the survivor lists in LDS; a sub-batch in which some pair did not fit its tiers (or a read-strand went to the heavy
   // tier, which re-emits without the mate's counts) is redone through the generic kernel's mate-pair modes (rows of regions marked twice, then rule 1: GmMpDev mode 5),
   // and so is the rest of the call
   bool mp_exact = gm_tune("GM_MP_EXACT") != nullptr;
-  GmIndexDev dkm[2][2] = {{dvm[0], dvm[1]}, {dvm[0], dvm[1]}};     // match modes 3 / 2: each mate's view with its mate-pair fields, per buffer pair (the heavy tier reads it again)
-  auto front = [&](int k, int base, int n) -> int {
-    unsigned long long* dst = s->d_pstats[k];
-    GM_HIP(hipMemsetAsync(dst, 0, (size_t)GS_STRIPES * GS_STRIDE * 8, qa));
+  GmIndexDev dkm[2][2];           // match modes 3 / 2: each mate's view with its mate-pair fields, per buffer pair (the heavy tier reads it again)
+  std::vector<unsigned long long> hraw = std::vector<unsigned long long>((size_t)GS_STRIPES * GS_STRIDE); unsigned long long hs[GS_N];
+  std::vector<std::string> pieces_all; uint64_t matched = 0, records = 0;
+  bool out_failed = false;         // (an allocation failed on the output thread: no exception leaves a thread; the call ends with GM_E_NOMEM)
+  int cur = 0; DevSet* S[2] = {nullptr, nullptr}; unsigned long long* dst = nullptr;      // the buffer pair of the sub-batch in hand, its counters
+  std::chrono::steady_clock::time_point tw;
+  std::unique_ptr<OutJob> pending; // (last: its thread reads the PairCall part, and is joined before anything here goes away)
+  void fold() { for (int k = 0; k < GS_N; k++) { hs[k] = 0; for (int t = 0; t < GS_STRIPES; t++) hs[k] += hraw[(size_t)t * GS_STRIDE + k]; } }
+  int lap(const char* what) { if (timing) { GM_HIP(hipStreamSynchronize(q)); auto n2 = std::chrono::steady_clock::now(); fprintf(stderr, "  pairs %-18s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(n2 - tw).count()); tw = n2; } return 0; }
+  // stage times of the back part (gm_map_stats_t, as the unpaired path fills them): events on the back stream, read behind the synchronisation points that exist anyway
+  int stage_ms(int e0, int e1, double gm_map_stats_t::* field) { float ms = 0; GM_HIP(hipEventElapsedTime(&ms, s->ev[e0], s->ev[e1])); if (stats) stats->*field += ms; return GM_OK; }
+  // the stages after the front work on buffer pair k from here on; B: the pairs a sub-batch on it can hold
+  int use_pair(int k, int B) {
+    cur = k; S[0] = PS[k][0]; S[1] = PS[k][1]; dst = s->d_pstats[k]; tw = std::chrono::steady_clock::now();
+    if (s->pairs_cap >= B) return GM_OK;
+    if (s->d_pairs) (void)hipFree(s->d_pairs);
+    if (s->d_pair_cnt) (void)hipFree(s->d_pair_cnt);
+    s->d_pairs = nullptr; s->d_pair_cnt = nullptr; s->pairs_cap = 0;
+    GM_HIP(hipMalloc(&s->d_pairs, (size_t)B * GM_SEL_MAX * 4)); GM_HIP(hipMalloc(&s->d_pair_cnt, (size_t)B * 4)); s->pairs_cap = B;
+    return GM_OK;
+  }
+  // a mate's reads: RNA flags (before the mate is turned: its complement of U is A), then read_reverse in letter space (ref: gmapper.c:174-185,567-570)
+  int prep_mate(DevSet& D, int m, int n) {
+    int rc;
+    if (D.d_read_rna) { rc = gm_launch_read_rna_flags(D.d_reads, n, len[m], rwords[m], D.d_read_rna, qa); if (rc) return rc; }
+    if (in_st[m] && !cs) { rc = gm_launch_revcomp_reads(D.d_reads, n, len[m], rwords[m], qa, D.d_read_rna); if (rc) return rc; }
+    return GM_OK;
+  }
+  // K1 of mate m through the generic entry with the view given; timed: the launch whose survivors K2 takes (slab segments out, K1 events around it)
+  int lookup(int k, int m, int n, const GmIndexDev& view, bool timed) {
+    DevSet& D = *PS[k][m];
+    if (timed) GM_HIP(hipEventRecord(s->pkev[k][2 * m], qa));
+    int rc = gm_launch_lookup(gm_view_of(view, D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, s->d_pstats[k], qa, &s->k1, timed ? D.d_surv_seg : nullptr, nullptr);
+    if (rc) return rc;
+    if (timed) GM_HIP(hipEventRecord(s->pkev[k][2 * m + 1], qa));
+    return GM_OK;
+  }
+  // Anchors of mate m's survivors, then the heavy count to its pinned word.  rows (match modes 3 / 2): K2 takes the lookup's rows as they are, with the paired score set.
+  // Otherwise the prune rules hold: K2 straight on the survivors when its LDS tier can take a whole row (small and medium genomes), else K1b + K2 -- K1b's overflow goes to
+  // the heavy tier, which re-emits a read-strand's survivors from the index without the mate's counts: a heavy read-strand then has the anchors of the half-paired run
+  // (a superset: the filter only removes list entries that cannot pair up), or, on the exact path, runs mode 5 too.
+  int anchors(int k, int m, int n, const GmIndexDev* rows = nullptr) {
+    DevSet& D = *PS[k][m]; unsigned long long* const dst = s->d_pstats[k];
+    int rc;
+    if (rows) rc = gm_launch_anchors(*rows, scp, n, len[m], W[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, dst, qa);
+    else if (D.scap <= 4096) rc = gm_launch_anchors(dv, s->sc, n, len[m], W[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, dst, qa);
+    else rc = launch_prune_anchors(s, D, dv, n, len[m], W[m], dst, 0);
+    if (rc) return rc;
+    GM_HIP(hipMemcpyAsync(&s->h_pin[2 + 2 * k + m], D.d_heavy_cnt, 4, hipMemcpyDeviceToHost, qa));
+    return GM_OK;
+  }
+  // -n 2: the lookup keeps every list entry.  -n 3: a first lookup pass lists, per read-strand, the regions it marked twice; the second keeps the entries of such
+  // regions and of regions within reach of one the mate (other strand) marked twice -- count_main >= 2 || count_mp >= 2, use_mp_region_counts == 2; without
+  // half-paired a pass in between flags, in each row, the regions the mate reaches at all, and the rule is count_mp >= 1 && count_main + count_mp >= 3
+  // (GmMpDev modes 1, 2 / 3 + 4).  No prune rules in either mode: K2 takes the rows as they are.  Also the exact path of -n 4 without half-paired (mode 5).
+  int front_rows(int k, int n) {
+    const MpDelta dl = gm_mp_region_deltas(ix->params.region_bits, dmin, dmax, dmin2, dmax2);
+    int rc;
+    for (int m = 0; m < 2; m++) {
+      DevSet& D = *PS[k][m];
+      rc = prep_mate(D, m, n); if (rc) return rc;
+      dkm[k][m] = dvm[m];
+      if (pmode == 2) dkm[k][m].no_region_counts = 1;
+      else if (D.mp_rows_for < 2 * D.eff_batch) {      // (-n 3, and the exact path of -n 4 without half-paired)
+        if (D.d_mp_rows) (void)hipFree(D.d_mp_rows);
+        if (D.d_mp_cnt) (void)hipFree(D.d_mp_cnt);
+        D.d_mp_rows = nullptr; D.d_mp_cnt = nullptr; D.mp_rows_for = 0;
+        GM_HIP(hipMalloc(&D.d_mp_rows, (size_t)2 * D.eff_batch * GM_MP_CAP * 4)); GM_HIP(hipMalloc(&D.d_mp_cnt, (size_t)2 * D.eff_batch * 4));
+        D.mp_rows_for = 2 * D.eff_batch;
+      }
+    }
+    if (pmode != 2) {
+      for (int m = 0; m < 2; m++) {
+        DevSet& D = *PS[k][m];
+        GM_HIP(hipMemsetAsync(D.d_mp_cnt, 0, (size_t)2 * n * 4, qa));
+        GmIndexDev d1 = dvm[m]; d1.mp.mode = 1; d1.mp.out_rows = D.d_mp_rows; d1.mp.out_cnt = D.d_mp_cnt;
+        rc = lookup(k, m, n, d1, false); if (rc) return rc;
+      }
+      for (int m = 0; m < 2; m++) {
+        GmMpDev& M = dkm[k][m].mp; const DevSet& Mate = *PS[k][1 - m];
+        M.mode = pmode == 4 ? 5 : (O.half_paired ? 2 : 4); M.rows = Mate.d_mp_rows; M.cnt = Mate.d_mp_cnt; M.out_rows = PS[k][m]->d_mp_rows; M.out_cnt = PS[k][m]->d_mp_cnt;
+        for (int st = 0; st < 2; st++) {
+          M.dmin[st] = m ? dl.bmin[st] : dl.amin[st]; M.dmax[st] = m ? dl.bmax[st] : dl.amax[st];
+          M.mate_dmin[st] = m ? dl.amin[st] : dl.bmin[st]; M.mate_dmax[st] = m ? dl.amax[st] : dl.bmax[st];
+        }
+      }
+      if (pmode == 3 && !O.half_paired)      // rule 3 asks count_mp >= 1 of a region marked twice: both mates flag each other's rows first
+        for (int m = 0; m < 2; m++) { GmIndexDev d3 = dkm[k][m]; d3.mp.mode = 3; rc = lookup(k, m, n, d3, false); if (rc) return rc; }
+    }
+    for (int m = 0; m < 2; m++) { rc = lookup(k, m, n, dkm[k][m], true); if (rc) return rc; }
+    for (int m = 0; m < 2; m++) {
+      GmIndexDev dk2 = dv; dk2.mp = dkm[k][m].mp;
+      rc = anchors(k, m, n, pmode != 4 ? &dk2 : nullptr); if (rc) return rc;      // (-n 4: the prune rules hold)
+    }
+    return GM_OK;
+  }
+  // The front of one sub-batch on buffer pair k: reads in (stream C, so that the call never queues behind kernels), K1 + K1b + K2 for both mates
+  int front(int k, int base, int n) {
+    GM_HIP(hipMemsetAsync(s->d_pstats[k], 0, (size_t)GS_STRIPES * GS_STRIDE * 8, qa));
     for (int m = 0; m < 2; m++)
       GM_HIP(hipMemcpyAsync(PS[k][m]->d_reads, mates[m] + (size_t)base * rwords[m], (size_t)n * rwords[m] * 4, hipMemcpyHostToDevice, s->stream_c));
     if (cs) for (int m = 0; m < 2; m++) GM_HIP(hipMemcpyAsync(PS[k][m]->d_initbp, initbp_in[m] + base, (size_t)n, hipMemcpyHostToDevice, s->stream_c));
     for (int m = 0; m < 2; m++) PS[k][m]->xover_on = false;
-    if (cs && quals1) for (int m = 0; m < 2; m++) {              // per-position crossover scores from the QVs, ref: gmapper.c:532-544 (as in map_impl)
+    if (cs && quals) for (int m = 0; m < 2; m++) {               // per-position crossover scores from the QVs (as in map_impl)
       std::vector<int8_t> xbuf((size_t)n * len[m]);
-      for (int i = 0; i < n; i++) {
-        const char* qv_s = qptr[m][base + i];
-        for (int j = 0; j < len[m]; j++) {
-          const int qv = (int)qv_s[j] - qual_delta;
-          const double pe = qv <= 0 ? .99999999 : (qv >= 250 ? 1E-25 : pow(10.0, -(double)qv / 10.0));   // pr_err_from_qv, ref: util.h:285-293
-          int cx = (int)(s->score_alpha * log(pe / 3.0) / log(2.0));
-          if (cx > -1) cx = -1; else if (cx < 2 * s->P.crossover_score) cx = 2 * s->P.crossover_score;
-          xbuf[(size_t)i * len[m] + j] = (int8_t)cx;
-        }
-      }
+      xover_from_quals(s, qptr[m].data() + base, n, len[m], qual_delta, xbuf.data(), nullptr);
       GM_HIP(hipMemcpyAsync(PS[k][m]->d_xover, xbuf.data(), xbuf.size(), hipMemcpyHostToDevice, s->stream_c));
       GM_HIP(hipStreamSynchronize(s->stream_c));                // xbuf goes out of scope
       PS[k][m]->xover_on = true;
     }
     GM_HIP(hipEventRecord(s->pev[k][8], s->stream_c));
     GM_HIP(hipStreamWaitEvent(qa, s->pev[k][8], 0));
-    if (pmode != 4 || (mp_counts && mp_exact)) {
-      // -n 2: the lookup keeps every list entry.  -n 3: a first lookup pass lists, per read-strand, the regions it marked twice; the second keeps the entries of such
-      // regions and of regions within reach of one the mate (other strand) marked twice -- count_main >= 2 || count_mp >= 2, use_mp_region_counts == 2; without
-      // half-paired a pass in between flags, in each row, the regions the mate reaches at all, and the rule is count_mp >= 1 && count_main + count_mp >= 3
-      // (GmMpDev modes 1, 2 / 3 + 4).  No prune rules in either mode: K2 takes the rows as they are.
-      const MpDelta dl = gm_mp_region_deltas(ix->params.region_bits, dmin, dmax, dmin2, dmax2);
-      int rc;
-      for (int m = 0; m < 2; m++) {
-        DevSet& D = *PS[k][m];
-        if (D.d_read_rna) { rc = gm_launch_read_rna_flags(D.d_reads, n, len[m], rwords[m], D.d_read_rna, qa); if (rc) return rc; }      // (before the mate is turned: its complement of U is A)
-        if (in_st[m] && !cs) { rc = gm_launch_revcomp_reads(D.d_reads, n, len[m], rwords[m], qa, D.d_read_rna); if (rc) return rc; }
-        dkm[k][m] = dvm[m];
-        if (pmode == 2) dkm[k][m].no_region_counts = 1;
-        else if (D.mp_rows_for < 2 * D.eff_batch) {      // (-n 3, and the exact path of -n 4 without half-paired)
-          if (D.d_mp_rows) (void)hipFree(D.d_mp_rows);
-          if (D.d_mp_cnt) (void)hipFree(D.d_mp_cnt);
-          D.d_mp_rows = nullptr; D.d_mp_cnt = nullptr; D.mp_rows_for = 0;
-          GM_HIP(hipMalloc(&D.d_mp_rows, (size_t)2 * D.eff_batch * GM_MP_CAP * 4)); GM_HIP(hipMalloc(&D.d_mp_cnt, (size_t)2 * D.eff_batch * 4));
-          D.mp_rows_for = 2 * D.eff_batch;
-        }
-      }
-      if (pmode != 2) {
-        for (int m = 0; m < 2; m++) {
-          DevSet& D = *PS[k][m];
-          GM_HIP(hipMemsetAsync(D.d_mp_cnt, 0, (size_t)2 * n * 4, qa));
-          GmIndexDev d1 = dvm[m]; d1.mp.mode = 1; d1.mp.out_rows = D.d_mp_rows; d1.mp.out_cnt = D.d_mp_cnt;
-          rc = gm_launch_lookup(gm_view_of(d1, D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, &s->k1, nullptr, nullptr);
-          if (rc) return rc;
-        }
-        for (int m = 0; m < 2; m++) {
-          GmMpDev& M = dkm[k][m].mp; const DevSet& Mate = *PS[k][1 - m];
-          M.mode = pmode == 4 ? 5 : (O.half_paired ? 2 : 4); M.rows = Mate.d_mp_rows; M.cnt = Mate.d_mp_cnt; M.out_rows = PS[k][m]->d_mp_rows; M.out_cnt = PS[k][m]->d_mp_cnt;
-          for (int st = 0; st < 2; st++) {
-            M.dmin[st] = m ? dl.bmin[st] : dl.amin[st]; M.dmax[st] = m ? dl.bmax[st] : dl.amax[st];
-            M.mate_dmin[st] = m ? dl.amin[st] : dl.bmin[st]; M.mate_dmax[st] = m ? dl.amax[st] : dl.bmax[st];
-          }
-        }
-        if (pmode == 3 && !O.half_paired)      // rule 3 asks count_mp >= 1 of a region marked twice: both mates flag each other's rows first
-          for (int m = 0; m < 2; m++) {
-            DevSet& D = *PS[k][m];
-            GmIndexDev d3 = dkm[k][m]; d3.mp.mode = 3;
-            rc = gm_launch_lookup(gm_view_of(d3, D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, &s->k1, nullptr, nullptr);
-            if (rc) return rc;
-          }
-      }
-      for (int m = 0; m < 2; m++) {
-        DevSet& D = *PS[k][m];
-        GM_HIP(hipEventRecord(s->pkev[k][2 * m], qa));
-        rc = gm_launch_lookup(gm_view_of(dkm[k][m], D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, &s->k1, D.d_surv_seg, nullptr);
-        if (rc) return rc;
-        GM_HIP(hipEventRecord(s->pkev[k][2 * m + 1], qa));
-      }
-      for (int m = 0; m < 2; m++) {
-        DevSet& D = *PS[k][m];
-        GmIndexDev dk2 = dv; dk2.mp = dkm[k][m].mp;
-        if (pmode != 4) rc = gm_launch_anchors(dk2, scp, n, len[m], W[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, dst, qa);
-        else if (D.scap <= 4096) rc = gm_launch_anchors(dv, s->sc, n, len[m], W[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, dst, qa);
-        else rc = launch_prune_anchors(s, D, dv, n, len[m], W[m], dst, 0);         // (-n 4: the prune rules hold; what K1b cannot hold goes to the heavy tier, which runs mode 5 too)
-        if (rc) return rc;
-        GM_HIP(hipMemcpyAsync(&s->h_pin[2 + 2 * k + m], D.d_heavy_cnt, 4, hipMemcpyDeviceToHost, qa));
-      }
-    } else
-    if (mp_counts) {   // K1 of both mates (never fused with the prune: the filter needs every survivor), the mate-pair filter, then K1b + K2 of both
-      for (int m = 0; m < 2; m++) {
-        DevSet& D = *PS[k][m];
-        int rc;
-        if (D.d_read_rna) { rc = gm_launch_read_rna_flags(D.d_reads, n, len[m], rwords[m], D.d_read_rna, qa); if (rc) return rc; }      // (before the mate is turned: its complement of U is A)
-        if (in_st[m] && !cs) { rc = gm_launch_revcomp_reads(D.d_reads, n, len[m], rwords[m], qa, D.d_read_rna); if (rc) return rc; }
-        GM_HIP(hipEventRecord(s->pkev[k][2 * m], qa));
-        rc = gm_launch_lookup(gm_view_of(dvm[m], D), D.d_reads, n, len[m], rwords[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_heavy_list, D.d_heavy_cnt, 2 * D.eff_batch, dst, qa, &s->k1, D.d_surv_seg, nullptr);
-        if (rc) return rc;
-        GM_HIP(hipEventRecord(s->pkev[k][2 * m + 1], qa));
-      }
-      int rc = gm_launch_mp_filter(n, ix->params.region_bits, ix->params.region_overlap, PS[k][0]->d_surv, PS[k][0]->d_surv_cnt, PS[k][0]->scap,
-                                   PS[k][1]->d_surv, PS[k][1]->d_surv_cnt, PS[k][1]->scap, dmin, dmax, dmin2, dmax2, PS[k][0]->d_surv_seg, PS[k][1]->d_surv_seg, ix->n_slabs, dst, qa);
-      if (rc) return rc;
-      for (int m = 0; m < 2; m++) {
-        DevSet& D = *PS[k][m];
-        // K2 straight on the filtered survivors when its LDS tier can take a whole row (small and medium genomes): K1b's overflow goes to the heavy tier,
-        // which re-emits a read-strand's survivors from the index -- without the mate's counts.  Larger rows keep K1b; a heavy read-strand then has
-        // the anchors of the half-paired run (a superset: the filter only removes list entries that cannot pair up).
-        if (D.scap <= 4096) rc = gm_launch_anchors(dv, s->sc, n, len[m], W[m], D.d_surv, D.d_surv_cnt, D.scap, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, dst, qa);
-        else rc = launch_prune_anchors(s, D, dv, n, len[m], W[m], dst, 0);
-        if (rc) return rc;
-        GM_HIP(hipMemcpyAsync(&s->h_pin[2 + 2 * k + m], D.d_heavy_cnt, 4, hipMemcpyDeviceToHost, qa));
-      }
-    } else
-    for (int m = 0; m < 2; m++) {
-      DevSet& D = *PS[k][m];
-      int rc;
-      if (D.d_read_rna) { rc = gm_launch_read_rna_flags(D.d_reads, n, len[m], rwords[m], D.d_read_rna, qa); if (rc) return rc; }      // (before the mate is turned: its complement of U is A)
-      if (in_st[m] && !cs) { rc = gm_launch_revcomp_reads(D.d_reads, n, len[m], rwords[m], qa, D.d_read_rna); if (rc) return rc; }   // read_reverse, ref: gmapper.c:174-185,567-570
-      rc = stage_windows_async(s, D, dvm[m], n, len[m], dst, &s->h_pin[2 + 2 * k + m], s->pkev[k][2 * m], s->pkev[k][2 * m + 1]); if (rc) return rc;
+    int rc = GM_OK;
+    if (pmode != 4 || (mp_counts && mp_exact)) rc = front_rows(k, n);
+    else if (mp_counts) {   // K1 of both mates (never fused with the prune: the filter needs every survivor), the mate-pair filter, then K1b + K2 of both
+      for (int m = 0; m < 2; m++) { rc = prep_mate(*PS[k][m], m, n); if (rc) return rc; rc = lookup(k, m, n, dvm[m], true); if (rc) return rc; }
+      rc = gm_launch_mp_filter(n, ix->params.region_bits, ix->params.region_overlap, PS[k][0]->d_surv, PS[k][0]->d_surv_cnt, PS[k][0]->scap,
+                               PS[k][1]->d_surv, PS[k][1]->d_surv_cnt, PS[k][1]->scap, dmin, dmax, dmin2, dmax2, PS[k][0]->d_surv_seg, PS[k][1]->d_surv_seg, ix->n_slabs, s->d_pstats[k], qa);
+      for (int m = 0; m < 2 && !rc; m++) rc = anchors(k, m, n);
+    } else for (int m = 0; m < 2 && !rc; m++) {
+      rc = prep_mate(*PS[k][m], m, n);
+      if (!rc) rc = stage_windows_async(s, *PS[k][m], dvm[m], n, len[m], s->d_pstats[k], &s->h_pin[2 + 2 * k + m], s->pkev[k][2 * m], s->pkev[k][2 * m + 1]);
     }
+    if (rc) return rc;
     GM_HIP(hipEventRecord(s->pev[k][6], qa));
     return GM_OK;
-  };
-  // The output stage of a sub-batch (unpaired selection, mapping qualities, text: ~6 of a sub-batch's ~70 ms, all host) runs on a thread of its own beside the device work of
-  // the next sub-batch; at most one is outstanding, and its text is appended -- in order -- before the next one starts.
-  struct OutJob { std::thread th; std::vector<std::string> outs; std::vector<uint64_t> cm, cr; double ms = 0; bool failed = false; ~OutJob() { if (th.joinable()) th.join(); } };
-  std::unique_ptr<OutJob> pending;
-  bool out_failed = false;                                    // (an allocation failed on the output thread: no exception leaves a thread; the call ends with GM_E_NOMEM)
-  auto finish_pending = [&]() {
-    if (!pending) return;
-    if (pending->th.joinable()) pending->th.join();
-    out_failed = out_failed || pending->failed;
-    if (stats) stats->ms_host += pending->ms;
-    for (size_t c = 0; c < pending->outs.size(); c++) { matched += pending->cm[c]; records += pending->cr[c]; pieces_all.push_back(std::move(pending->outs[c])); }
-    pending.reset();
-  };
-  int cur = 0, front_n = 0, out_idx = 0; bool have_front = false;
-  for (int base = 0; base < n_pairs;) {
-    const int pinset = (out_idx & 1) * 4;
-    auto tw = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) { if (timing) { GM_HIP(hipStreamSynchronize(q)); auto n2 = std::chrono::steady_clock::now(); fprintf(stderr, "  pairs %-18s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(n2 - tw).count()); tw = n2; } return 0; };
-    DevSet& A = *PS[cur][0]; DevSet& Bs = *PS[cur][1]; DevSet* S[2] = {&A, &Bs};
-    unsigned long long* const dst = s->d_pstats[cur];
-    const int B = std::min(A.eff_batch, Bs.eff_batch);
-    const int n = have_front ? front_n : std::min(B, n_pairs - base);
-    if (s->pairs_cap < B) {
-      if (s->d_pairs) (void)hipFree(s->d_pairs);
-      if (s->d_pair_cnt) (void)hipFree(s->d_pair_cnt);
-      s->d_pairs = nullptr; s->d_pair_cnt = nullptr; s->pairs_cap = 0;
-      GM_HIP(hipMalloc(&s->d_pairs, (size_t)B * GM_SEL_MAX * 4)); GM_HIP(hipMalloc(&s->d_pair_cnt, (size_t)B * 4)); s->pairs_cap = B;
-    }
+  }
+
+  // a capacity of this pair grew, or the exact mate-pair path is needed: the sub-batch is redone from its front, and the front queued for the next one is dropped
+  int redo() { GM_HIP(hipStreamSynchronize(qa)); GM_HIP(hipStreamSynchronize(q)); if (stats) stats->retries++; return GM_OK; }
+  int grow(bool hits_ovf, const uint32_t n_work[2]) {
     bool retry = false;
-    auto grow = [&](bool hits_ovf, const uint32_t n_work[2]) -> int {
-      for (int m = 0; m < 2; m++) {
-        DevSet& D = *S[m];
-        bool g = false;
-        if (hits_ovf) { if (D.hcap >= 32768) { gm_set_error("window list overflow at capacity %d", D.hcap); return GM_E_OVERFLOW; } D.hcap *= 4; g = true; }
-        if (n_work[m] > (size_t)D.eff_batch * D.rcap_per_read) {
-          if (D.rcap_per_read >= GM_SEL_MAX) { gm_set_error("pass-2 work overflow"); return GM_E_OVERFLOW; }
-          D.rcap_per_read = std::min(GM_SEL_MAX, D.rcap_per_read * 2); g = true;
-        }
-        if (g) { retry = true; int rc = alloc_buffers(s, D, len[m], true); if (rc) return rc; }
+    for (int m = 0; m < 2; m++) {
+      DevSet& D = *S[m];
+      bool g = false;
+      if (hits_ovf) { if (D.hcap >= 32768) { gm_set_error("window list overflow at capacity %d", D.hcap); return GM_E_OVERFLOW; } D.hcap *= 4; g = true; }
+      if (n_work[m] > (size_t)D.eff_batch * D.rcap_per_read) {
+        if (D.rcap_per_read >= GM_SEL_MAX) { gm_set_error("pass-2 work overflow"); return GM_E_OVERFLOW; }
+        D.rcap_per_read = std::min(GM_SEL_MAX, D.rcap_per_read * 2); g = true;
       }
-      return GM_OK;
-    };
-    int rc;
-    if (!have_front) { rc = front(cur, base, n); if (rc) return rc; }
-    bool have_next = false; int next_n = 0;
-    if (overlap && base + n < n_pairs) {
-      next_n = std::min(std::min(PS[cur ^ 1][0]->eff_batch, PS[cur ^ 1][1]->eff_batch), n_pairs - (base + n));
-      rc = front(cur ^ 1, base + n, next_n); if (rc) return rc;
-      have_next = true;
+      if (g) { retry = true; int rc = alloc_buffers(s, D, len[m], true); if (rc) return rc; }
     }
-    // a capacity of this pair grew: the sub-batch is redone from its front, and the front queued for the next one is dropped
-    auto redo = [&]() -> int { GM_HIP(hipStreamSynchronize(qa)); GM_HIP(hipStreamSynchronize(q)); have_front = false; if (stats) stats->retries++; return GM_OK; };
+    return retry ? GM_REDO : GM_OK;
+  }
+  // The front's end: K1's times, the heavy tier of each mate (then the front's end event again), the back stream behind it
+  int finish_front(int n) {
     GM_HIP(hipEventSynchronize(s->pev[cur][6]));
-    {
-      float k1 = 0;
-      for (int m = 0; m < 2; m++) {                            // K1's own time for both mate sets of this sub-batch (bench.py's roofline leg)
-        float ms = 0; GM_HIP(hipEventElapsedTime(&ms, s->pkev[cur][2 * m], s->pkev[cur][2 * m + 1]));
-        if (stats) stats->ms_lookup += ms;
-        s->last_lookup_ms += ms; s->last_lookup_launches++; k1 += ms;
-      }
-      // the rest of the front (K1b, K2, the mate-pair filter of --no-half-paired): from the first K1's begin to the front's end, minus the two K1s
-      float span = 0; GM_HIP(hipEventElapsedTime(&span, s->pkev[cur][0], s->pev[cur][6]));
-      if (stats) stats->ms_anchors += std::max(0.0f, span - k1);
+    float k1 = 0;
+    for (int m = 0; m < 2; m++) {                              // K1's own time for both mate sets of this sub-batch (bench.py's roofline leg)
+      float ms = 0; GM_HIP(hipEventElapsedTime(&ms, s->pkev[cur][2 * m], s->pkev[cur][2 * m + 1]));
+      if (stats) stats->ms_lookup += ms;
+      s->last_lookup_ms += ms; s->last_lookup_launches++; k1 += ms;
     }
-    // stage times of the back part (gm_map_stats_t, as the unpaired path fills them): events on the back stream, read behind the synchronisation points that exist anyway
-    auto stage_ms = [&](int e0, int e1, double gm_map_stats_t::* field) -> int {
-      float ms = 0; GM_HIP(hipEventElapsedTime(&ms, s->ev[e0], s->ev[e1])); if (stats) stats->*field += ms; return GM_OK; };
-    if (mp_counts && !mp_exact && (s->h_pin[2 + 2 * cur] || s->h_pin[2 + 2 * cur + 1])) { mp_exact = true; rc = redo(); if (rc) return rc; continue; }   // (see mp_exact)
-    {
-      bool heavy = false;
-      for (int m = 0; m < 2; m++) {
-        const uint32_t n_heavy = s->h_pin[2 + 2 * cur + m];
-        if (n_heavy) {
-          rc = (pmode == 4 && !mp_exact) ? run_heavy_tier(s, *S[m], dvm[m], n, len[m], rwords[m], W[m], (int)n_heavy, dst)
-                          : run_heavy_tier(s, *S[m], dkm[cur][m], n, len[m], rwords[m], W[m], (int)n_heavy, dst, pmode == 4 ? nullptr : &scp);
-          if (rc) return rc; heavy = true;
-        }
+    // the rest of the front (K1b, K2, the mate-pair filter of --no-half-paired): from the first K1's begin to the front's end, minus the two K1s
+    float span = 0; GM_HIP(hipEventElapsedTime(&span, s->pkev[cur][0], s->pev[cur][6]));
+    if (stats) stats->ms_anchors += std::max(0.0f, span - k1);
+    if (mp_counts && !mp_exact && (s->h_pin[2 + 2 * cur] || s->h_pin[2 + 2 * cur + 1])) { mp_exact = true; return GM_REDO; }   // (see mp_exact)
+    bool heavy = false;
+    for (int m = 0; m < 2; m++) {
+      const uint32_t n_heavy = s->h_pin[2 + 2 * cur + m];
+      if (n_heavy) {
+        int rc = (pmode == 4 && !mp_exact) ? run_heavy_tier(s, *S[m], dvm[m], n, len[m], rwords[m], W[m], (int)n_heavy, dst)
+                        : run_heavy_tier(s, *S[m], dkm[cur][m], n, len[m], rwords[m], W[m], (int)n_heavy, dst, pmode == 4 ? nullptr : &scp);
+        if (rc) return rc; heavy = true;
       }
-      if (heavy) GM_HIP(hipEventRecord(s->pev[cur][6], qa));
     }
+    if (heavy) GM_HIP(hipEventRecord(s->pev[cur][6], qa));
     GM_HIP(hipStreamWaitEvent(q, s->pev[cur][6], 0));
     lap("K1+K1b+K2 x2");
+    return GM_OK;
+  }
+  // pair-up, pass 1 of both mates over the paired windows, the pair top-K, the pass-2 work lists; then the counters, and what they ask to be redone
+  int pass1_select(int n, uint32_t n_work[2]) {
+    DevSet& A = *S[0]; DevSet& Bs = *S[1];
     GM_HIP(hipEventRecord(s->ev[0], q));
-    rc = gm_launch_pair_up(n, A.d_hits, A.d_perm, A.d_hit_cnt, A.hcap, Bs.d_hits, Bs.d_perm, Bs.d_hit_cnt, Bs.hcap,
-                           A.d_pmin, A.d_pmax, Bs.d_pmin, Bs.d_pmax, dmin, dmax, q);
+    int rc = gm_launch_pair_up(n, A.d_hits, A.d_perm, A.d_hit_cnt, A.hcap, Bs.d_hits, Bs.d_perm, Bs.d_hit_cnt, Bs.hcap,
+                               A.d_pmin, A.d_pmax, Bs.d_pmin, Bs.d_pmax, dmin, dmax, q);
     if (rc) return rc;
     for (int m = 0; m < 2; m++) {
       DevSet& D = *S[m];
@@ -670,7 +769,6 @@ static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* 
                                Bs.d_hits, Bs.d_perm, Bs.d_hit_cnt, Bs.hcap, A.d_sel, A.d_sel_sidx, A.d_sel_cnt, Bs.d_sel, Bs.d_sel_sidx, Bs.d_sel_cnt,
                                s->d_pairs, s->d_pair_cnt, q);
     if (rc) return rc;
-    uint32_t n_work[2] = {0, 0};
     for (int m = 0; m < 2; m++) {
       DevSet& D = *S[m];
       rc = gm_launch_build_work(n, D.d_sel_cnt, D.d_sel_off, D.d_work, D.d_n_work, q); if (rc) return rc;
@@ -686,298 +784,186 @@ static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* 
     if ((pmode == 3 || (mp_counts && mp_exact)) && hs[GS_MP_UNFILTERED]) {   // a row of regions marked twice beyond GM_MP_CAP: no exact answer
       gm_set_error("gm_map_pairs: mate-pair region counts: %llu read-strands beyond the row capacity (%d regions marked twice)", hs[GS_MP_UNFILTERED], GM_MP_CAP); return GM_E_OVERFLOW;
     }
-    if (mp_counts && !mp_exact && hs[GS_MP_UNFILTERED]) { mp_exact = true; rc = redo(); if (rc) return rc; continue; }   // (see mp_exact)
+    if (mp_counts && !mp_exact && hs[GS_MP_UNFILTERED]) { mp_exact = true; return GM_REDO; }   // (see mp_exact)
     rc = grow(hs[GS_OVERFLOW_HITS] != 0, n_work); if (rc) return rc;
-    if (retry) { rc = redo(); if (rc) return rc; continue; }
     lap("pair_select");
-    // paired pass 2 on the unique windows of the selected pairs
-    GmPinVec<GmFullRes>* const resP = &s->pin_res[pinset]; GmPinVec<uint8_t>* const opsP = &s->pin_ops[pinset]; std::vector<uint32_t> cntP[2], offP[2];      // (pinned: the copies run at link rate beside the kernels)
-    std::vector<uint32_t> plist((size_t)n * GM_SEL_MAX), pcnt(n);
-    GM_HIP(hipEventRecord(s->ev[3], q));
+    return GM_OK;
+  }
+  // Pass 2 of both mates, letter or colour, and each mate's four result copies.  paired: the windows of the selected pairs (sel_sidx, the pair flag) -- with sc_half --
+  // or the rescue's own selection with the session's score set.  Events ev[e0] before mate 0, ev[e0 + 1] between the mates (the first one's copies are queued behind
+  // it), ev[e0 + 2] behind mate 1's kernel.
+  int pass2_both(int n, const GmScoreDev& sc, bool paired, int e0, const uint32_t n_work[2], GmPinVec<GmFullRes>* res, GmPinVec<uint8_t>* ops, std::vector<uint32_t> cnt[2], std::vector<uint32_t> off[2]) {
+    GM_HIP(hipEventRecord(s->ev[e0], q));
     for (int m = 0; m < 2; m++) {
-      DevSet& D = *S[m];
-      if (m == 1) GM_HIP(hipEventRecord(s->ev[4], q));          // (between the mates: the first one's copies are queued behind this)
-      if (cs) rc = gm_launch_pass2_cs(dvm[m], sc_half, cs9, D.d_reads, D.d_initbp, n, len[m], rwords[m], W[m], D.d_hits, D.hcap, D.d_sel, D.d_work, D.d_n_work,
-                                      D.d_res, D.d_ops, D.ops_stride, (uint32_t*)D.d_back, D.back_stride / 4, D.p2_grid, dst, q, D.xover_on ? D.d_xover : nullptr, D.d_sel_sidx, D.d_p2_order, D.d_p2_cls);
-      else
-      rc = gm_launch_pass2(gm_view_of(dv, D), sc_half, D.d_reads, n, len[m], rwords[m], W[m], D.d_hits, D.d_perm, D.hcap, D.d_sel, D.d_sel_cnt, D.d_work, D.d_n_work,
-                           D.d_res, D.d_ops, D.ops_stride, D.d_back, D.back_stride, D.p2_grid, dst, q, D.d_sel_sidx, in_st[m], 1, D.d_p2_order, D.d_p2_cls);
+      DevSet& D = *S[m]; int rc;
+      if (m == 1) GM_HIP(hipEventRecord(s->ev[e0 + 1], q));
+      if (cs) rc = gm_launch_pass2_cs(dvm[m], sc, cs9, D.d_reads, D.d_initbp, n, len[m], rwords[m], W[m], D.d_hits, D.hcap, D.d_sel, D.d_work, D.d_n_work,
+                                      D.d_res, D.d_ops, D.ops_stride, (uint32_t*)D.d_back, D.back_stride / 4, D.p2_grid, dst, q, D.xover_on ? D.d_xover : nullptr, paired ? D.d_sel_sidx : nullptr, D.d_p2_order, D.d_p2_cls);
+      else rc = gm_launch_pass2(gm_view_of(dv, D), sc, D.d_reads, n, len[m], rwords[m], W[m], D.d_hits, D.d_perm, D.hcap, D.d_sel, D.d_sel_cnt, D.d_work, D.d_n_work,
+                                D.d_res, D.d_ops, D.ops_stride, D.d_back, D.back_stride, D.p2_grid, dst, q, paired ? D.d_sel_sidx : nullptr, in_st[m], paired ? 1 : 0, D.d_p2_order, D.d_p2_cls);
       if (rc) return rc;
-      if (m == 1) GM_HIP(hipEventRecord(s->ev[5], q));
-      rc = resP[m].resize(n_work[m]); if (rc) return rc; rc = opsP[m].resize((size_t)n_work[m] * D.ops_stride); if (rc) return rc; cntP[m].resize(n); offP[m].resize(n);
+      if (m == 1) GM_HIP(hipEventRecord(s->ev[e0 + 2], q));
+      rc = res[m].resize(n_work[m]); if (rc) return rc; rc = ops[m].resize((size_t)n_work[m] * D.ops_stride); if (rc) return rc; cnt[m].resize(n); off[m].resize(n);
       if (n_work[m]) {
-        GM_HIP(hipMemcpyAsync(resP[m].data(), D.d_res, (size_t)n_work[m] * sizeof(GmFullRes), hipMemcpyDeviceToHost, q));
-        GM_HIP(hipMemcpyAsync(opsP[m].data(), D.d_ops, (size_t)n_work[m] * D.ops_stride, hipMemcpyDeviceToHost, q));
+        GM_HIP(hipMemcpyAsync(res[m].data(), D.d_res, (size_t)n_work[m] * sizeof(GmFullRes), hipMemcpyDeviceToHost, q));
+        GM_HIP(hipMemcpyAsync(ops[m].data(), D.d_ops, (size_t)n_work[m] * D.ops_stride, hipMemcpyDeviceToHost, q));
       }
-      GM_HIP(hipMemcpyAsync(cntP[m].data(), D.d_sel_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, q));
-      GM_HIP(hipMemcpyAsync(offP[m].data(), D.d_sel_off, (size_t)n * 4, hipMemcpyDeviceToHost, q));
+      GM_HIP(hipMemcpyAsync(cnt[m].data(), D.d_sel_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, q));
+      GM_HIP(hipMemcpyAsync(off[m].data(), D.d_sel_off, (size_t)n * 4, hipMemcpyDeviceToHost, q));
     }
-    GM_HIP(hipMemcpyAsync(plist.data(), s->d_pairs, plist.size() * 4, hipMemcpyDeviceToHost, q));
-    GM_HIP(hipMemcpyAsync(pcnt.data(), s->d_pair_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, q));
+    return GM_OK;
+  }
+  // paired pass 2 on the unique windows of the selected pairs, at half the threshold per mate; the pair lists with it
+  int paired_pass2(PairOut& b, PairSel& t) {
+    t.plist.resize((size_t)b.n * GM_SEL_MAX); t.pcnt.resize(b.n);
+    int rc = pass2_both(b.n, sc_half, true, 3, t.n_work, b.resP, b.opsP, t.cntP, b.offP); if (rc) return rc;
+    GM_HIP(hipMemcpyAsync(t.plist.data(), s->d_pairs, t.plist.size() * 4, hipMemcpyDeviceToHost, q));
+    GM_HIP(hipMemcpyAsync(t.pcnt.data(), s->d_pair_cnt, (size_t)b.n * 4, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
     rc = stage_ms(3, 4, &gm_map_stats_t::ms_pass2); if (rc) return rc;        // (mate 0's pass 2 with its result copies, then mate 1's kernel)
     rc = stage_ms(4, 5, &gm_map_stats_t::ms_pass2); if (rc) return rc;
     lap("pass2 (pairs)+copy");
-    // host: pair selection
-    const int chunk = 2048, nchunks = (n + chunk - 1) / chunk;
-    std::vector<FHit> fhP[2]; fhP[0].resize(n_work[0]); fhP[1].resize(n_work[1]);
-    const int NO = std::max(1, s->P.num_outputs);
-    std::vector<PPair> fpairs((size_t)n * NO); std::vector<int> fcnt(n, 0);
-    std::vector<std::vector<uint32_t>> saved_chunks[2]; saved_chunks[0].resize(nchunks); saved_chunks[1].resize(nchunks);
-    Finalizer F0{s, len[0], rwords[0], nullptr, nullptr, nullptr, 0}, F1{s, len[1], rwords[1], nullptr, nullptr, nullptr, 0};
-    if (s->P.output_format) F0.hgen = F1.hgen = s->h_genome.data();
+    return GM_OK;
+  }
+  // host: pair selection (readpair_pass2 per pair) on the host threads; the windows of the final pairs are saved from the rescue
+  void select_pairs_host(PairOut& b, PairSel& t) {
+    b.nchunks = (b.n + b.chunk - 1) / b.chunk;
+    b.fhP[0].resize(t.n_work[0]); b.fhP[1].resize(t.n_work[1]);
+    b.NO = std::max(1, s->P.num_outputs);
+    b.fpairs.resize((size_t)b.n * b.NO); b.fcnt.assign(b.n, 0);
+    t.saved_chunks[0].resize(b.nchunks); t.saved_chunks[1].resize(b.nchunks);
+    for (int m = 0; m < 2; m++) b.F[m] = Finalizer{s, len[m], rwords[m], nullptr, nullptr, nullptr, 0};
+    if (s->P.output_format) b.F[0].hgen = b.F[1].hgen = s->h_genome.data();
     if (cs) {   // post_sw needs the colours and the primer letter of each read (ref: sw-post.c:448-528)
-      F0.reads = mates[0] + (size_t)base * rwords[0]; F1.reads = mates[1] + (size_t)base * rwords[1];
-      F0.initbp = initbp_in[0] + base; F1.initbp = initbp_in[1] + base;
-      F0.ops_half = A.ops_stride / 2; F1.ops_half = Bs.ops_stride / 2; F0.csk = F1.csk = cs_post_consts(s);
-      if (quals1) { F0.qual_ptr = qptr[0].data() + base; F1.qual_ptr = qptr[1].data() + base; F0.qual_delta = F1.qual_delta = qual_delta; }   // post_sw with the reads' QVs (ref: sw-post.c:486-491)
+      for (int m = 0; m < 2; m++) {
+        Finalizer& F = b.F[m];
+        F.reads = mates[m] + (size_t)b.base * rwords[m]; F.initbp = initbp_in[m] + b.base; F.ops_half = S[m]->ops_stride / 2; F.csk = cs_post_consts(s);
+        if (quals) { F.qual_ptr = qptr[m].data() + b.base; F.qual_delta = qual_delta; }      // post_sw with the reads' QVs (ref: sw-post.c:486-491)
+      }
     }
-    parallel_chunks(nchunks, [&](int c) {
+    parallel_chunks(b.nchunks, [&](int c) {
       std::vector<PPair> v;
-      for (int pr = c * chunk; pr < std::min(n, (c + 1) * chunk); pr++) {
-        FHit* H[2] = {fhP[0].data() + offP[0][pr], fhP[1].data() + offP[1][pr]};
-        for (uint32_t a = 0; a < cntP[0][pr]; a++) F0.post_sw(H[0][a], &resP[0][offP[0][pr] + a], opsP[0].data());
-        for (uint32_t b = 0; b < cntP[1][pr]; b++) F1.post_sw(H[1][b], &resP[1][offP[1][pr] + b], opsP[1].data());
-        pair_pass2(C, H, plist.data() + (size_t)pr * GM_SEL_MAX, (int)pcnt[pr], v);
-        fcnt[pr] = (int)v.size();
+      for (int pr = c * b.chunk; pr < std::min(b.n, (c + 1) * b.chunk); pr++) {
+        FHit* H[2] = {b.fhP[0].data() + b.offP[0][pr], b.fhP[1].data() + b.offP[1][pr]};
+        for (int m = 0; m < 2; m++) for (uint32_t a = 0; a < t.cntP[m][pr]; a++) b.F[m].post_sw(H[m][a], &b.resP[m][b.offP[m][pr] + a], b.opsP[m].data());
+        pair_pass2(C, H, t.plist.data() + (size_t)pr * GM_SEL_MAX, (int)t.pcnt[pr], v);
+        b.fcnt[pr] = (int)v.size();
         for (size_t j = 0; j < v.size(); j++) {
-          fpairs[(size_t)pr * NO + j] = v[j];
-          for (int m = 0; m < 2; m++) saved_chunks[m][c].push_back(H[m][v[j].h[m]].r->hit_slot);   // ref: mapping.c:2304-2310
+          b.fpairs[(size_t)pr * b.NO + j] = v[j];
+          for (int m = 0; m < 2; m++) t.saved_chunks[m][c].push_back(H[m][v[j].h[m]].r->hit_slot);   // ref: mapping.c:2304-2310
         }
       }
     });
     lap("host pair select");
-    // device: half-paired fall-back -- handle_read per mate with the windows already there (ref: mapping.c:2598-2625, gmapper.c:2700-2714)
-    GmPinVec<GmFullRes>* const resU = &s->pin_res[pinset + 2]; GmPinVec<uint8_t>* const opsU = &s->pin_ops[pinset + 2]; std::vector<uint32_t> cntU[2], offU[2];
-    if (O.half_paired) {
-      uint32_t n_work2[2] = {0, 0};
-      for (int m = 0; m < 2; m++) {
-        DevSet& D = *S[m];
-        std::vector<uint32_t> sl; for (auto& v : saved_chunks[m]) sl.insert(sl.end(), v.begin(), v.end());
-        GM_HIP(hipMemsetAsync(D.d_saved, 0, (size_t)n * 2 * D.hcap, q));
-        if (!sl.empty()) {
-          GM_HIP(hipMemcpyAsync(D.d_saved_list, sl.data(), sl.size() * 4, hipMemcpyHostToDevice, q));
-          rc = gm_launch_mark_saved(D.d_saved, D.d_saved_list, (int)sl.size(), q); if (rc) return rc;
-          GM_HIP(hipStreamSynchronize(q));   // sl goes out of scope
-        }
-        GM_HIP(hipEventRecord(s->ev[6 + 3 * m], q));
-        rc = gm_launch_pass1(gm_view_of(dvm[m], D), scr, D.d_reads, n, len[m], rwords[m], W[m], ovl[m], D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, D.d_slots, dst, q, nullptr, D.d_saved, cs ? D.d_initbp : nullptr,
-                             true);      // (handle_read per mate: a score below the unpaired threshold is never read again -- the pair sums were formed before)
-        if (rc) return rc;
-        GM_HIP(hipEventRecord(s->ev[7 + 3 * m], q));
-        rc = gm_launch_select(s->sc, n, len[m], D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, D.d_sel, D.d_sel_cnt, D.d_sel_off, D.d_work, D.d_n_work, q, D.d_saved);
-        if (rc) return rc;
-        GM_HIP(hipEventRecord(s->ev[8 + 3 * m], q));
-        GM_HIP(hipMemcpyAsync(&n_work2[m], D.d_n_work, 4, hipMemcpyDeviceToHost, q));
+  }
+  // device: half-paired fall-back -- handle_read per mate with the windows already there (ref: mapping.c:2598-2625, gmapper.c:2700-2714)
+  int rescue(PairOut& b, PairSel& t) {
+    const int n = b.n;
+    if (!O.half_paired) { for (int m = 0; m < 2; m++) { b.cntU[m].assign(n, 0); b.offU[m].assign(n, 0); } return GM_OK; }
+    uint32_t n_work2[2] = {0, 0}; int rc;
+    for (int m = 0; m < 2; m++) {
+      DevSet& D = *S[m];
+      std::vector<uint32_t> sl; for (auto& v : t.saved_chunks[m]) sl.insert(sl.end(), v.begin(), v.end());
+      GM_HIP(hipMemsetAsync(D.d_saved, 0, (size_t)n * 2 * D.hcap, q));
+      if (!sl.empty()) {
+        GM_HIP(hipMemcpyAsync(D.d_saved_list, sl.data(), sl.size() * 4, hipMemcpyHostToDevice, q));
+        rc = gm_launch_mark_saved(D.d_saved, D.d_saved_list, (int)sl.size(), q); if (rc) return rc;
+        GM_HIP(hipStreamSynchronize(q));   // sl goes out of scope
       }
-      GM_HIP(hipStreamSynchronize(q));
-      for (int m = 0; m < 2; m++) {                            // the rescue's pass 1 and selection, per mate
-        rc = stage_ms(6 + 3 * m, 7 + 3 * m, &gm_map_stats_t::ms_pass1); if (rc) return rc;
-        rc = stage_ms(7 + 3 * m, 8 + 3 * m, &gm_map_stats_t::ms_select); if (rc) return rc;
-      }
-      rc = grow(false, n_work2); if (rc) return rc;
-      if (retry) { rc = redo(); if (rc) return rc; continue; }
-      GM_HIP(hipEventRecord(s->ev[0], q));
-      for (int m = 0; m < 2; m++) {
-        DevSet& D = *S[m];
-        if (m == 1) GM_HIP(hipEventRecord(s->ev[1], q));
-        if (cs) rc = gm_launch_pass2_cs(dvm[m], s->sc, cs9, D.d_reads, D.d_initbp, n, len[m], rwords[m], W[m], D.d_hits, D.hcap, D.d_sel, D.d_work, D.d_n_work,
-                                        D.d_res, D.d_ops, D.ops_stride, (uint32_t*)D.d_back, D.back_stride / 4, D.p2_grid, dst, q, D.xover_on ? D.d_xover : nullptr, nullptr, D.d_p2_order, D.d_p2_cls);
-        else
-        rc = gm_launch_pass2(gm_view_of(dv, D), s->sc, D.d_reads, n, len[m], rwords[m], W[m], D.d_hits, D.d_perm, D.hcap, D.d_sel, D.d_sel_cnt, D.d_work, D.d_n_work,
-                             D.d_res, D.d_ops, D.ops_stride, D.d_back, D.back_stride, D.p2_grid, dst, q, nullptr, in_st[m], 0, D.d_p2_order, D.d_p2_cls);
-        if (rc) return rc;
-        if (m == 1) GM_HIP(hipEventRecord(s->ev[2], q));
-        rc = resU[m].resize(n_work2[m]); if (rc) return rc; rc = opsU[m].resize((size_t)n_work2[m] * D.ops_stride); if (rc) return rc; cntU[m].resize(n); offU[m].resize(n);
-        if (n_work2[m]) {
-          GM_HIP(hipMemcpyAsync(resU[m].data(), D.d_res, (size_t)n_work2[m] * sizeof(GmFullRes), hipMemcpyDeviceToHost, q));
-          GM_HIP(hipMemcpyAsync(opsU[m].data(), D.d_ops, (size_t)n_work2[m] * D.ops_stride, hipMemcpyDeviceToHost, q));
-        }
-        GM_HIP(hipMemcpyAsync(cntU[m].data(), D.d_sel_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, q));
-        GM_HIP(hipMemcpyAsync(offU[m].data(), D.d_sel_off, (size_t)n * 4, hipMemcpyDeviceToHost, q));
-      }
-    } else { for (int m = 0; m < 2; m++) { cntU[m].assign(n, 0); offU[m].assign(n, 0); } }
+      GM_HIP(hipEventRecord(s->ev[6 + 3 * m], q));
+      rc = gm_launch_pass1(gm_view_of(dvm[m], D), scr, D.d_reads, n, len[m], rwords[m], W[m], ovl[m], D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, D.d_slots, dst, q, nullptr, D.d_saved, cs ? D.d_initbp : nullptr,
+                           true);      // (handle_read per mate: a score below the unpaired threshold is never read again -- the pair sums were formed before)
+      if (rc) return rc;
+      GM_HIP(hipEventRecord(s->ev[7 + 3 * m], q));
+      rc = gm_launch_select(s->sc, n, len[m], D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, D.d_sel, D.d_sel_cnt, D.d_sel_off, D.d_work, D.d_n_work, q, D.d_saved);
+      if (rc) return rc;
+      GM_HIP(hipEventRecord(s->ev[8 + 3 * m], q));
+      GM_HIP(hipMemcpyAsync(&n_work2[m], D.d_n_work, 4, hipMemcpyDeviceToHost, q));
+    }
+    GM_HIP(hipStreamSynchronize(q));
+    for (int m = 0; m < 2; m++) {                            // the rescue's pass 1 and selection, per mate
+      rc = stage_ms(6 + 3 * m, 7 + 3 * m, &gm_map_stats_t::ms_pass1); if (rc) return rc;
+      rc = stage_ms(7 + 3 * m, 8 + 3 * m, &gm_map_stats_t::ms_select); if (rc) return rc;
+    }
+    rc = grow(false, n_work2); if (rc) return rc;
+    return pass2_both(n, s->sc, false, 0, n_work2, b.resU, b.opsU, b.cntU, b.offU);
+  }
+  int collect_stats() {
     GM_HIP(hipMemcpyAsync(hraw.data(), dst, hraw.size() * 8, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
     fold();
-    if (O.half_paired) { rc = stage_ms(0, 1, &gm_map_stats_t::ms_pass2); if (rc) return rc; rc = stage_ms(1, 2, &gm_map_stats_t::ms_pass2); if (rc) return rc; }      // the rescue's pass 2
-    if (stats) {
-      stats->lookups += hs[GS_LOOKUPS]; stats->list_entries += hs[GS_ENTRIES]; stats->list_bytes += 12ull * hs[GS_LOOKUPS] + 4ull * hs[GS_ENTRIES];
-      stats->survivors += hs[GS_SURVIVORS]; stats->anchors += hs[GS_ANCHORS]; stats->windows += hs[GS_WINDOWS];
-      stats->vec_calls += hs[GS_VEC_CALLS]; stats->vec_cells += hs[GS_VEC_CELLS]; stats->vec_bypassed += hs[GS_VEC_BYPASSED];
-      stats->full_calls += hs[GS_FULL_CALLS]; stats->full_cells += hs[GS_FULL_CELLS]; stats->exact_order_reads += hs[GS_EXACT_ORDER]; stats->survivors_pruned += hs[GS_PRUNED];
-      stats->mp_unfiltered += hs[GS_MP_UNFILTERED];
-    }
+    if (O.half_paired) { int rc = stage_ms(0, 1, &gm_map_stats_t::ms_pass2); if (rc) return rc; rc = stage_ms(1, 2, &gm_map_stats_t::ms_pass2); if (rc) return rc; }      // the rescue's pass 2
+    if (stats) { add_device_stats(stats, hs); stats->mp_unfiltered += hs[GS_MP_UNFILTERED]; }
     lap("rescue p1+sel+p2");
-    // host: unpaired selection, mapping qualities, SAM text (readpair_output, ref: output.c:1070-1291) -- on its own thread, see OutJob above
-    finish_pending();                                              // (the sub-batch before this one: its text comes first, and its pinned result set is free again after this)
-    {
-      struct OutState { std::vector<FHit> fhP[2]; std::vector<PPair> fpairs; std::vector<int> fcnt; std::vector<uint32_t> offP[2], cntU[2], offU[2]; };
-      auto st = std::make_shared<OutState>();
-      for (int m = 0; m < 2; m++) { st->fhP[m] = std::move(fhP[m]); st->offP[m] = std::move(offP[m]); st->cntU[m] = std::move(cntU[m]); st->offU[m] = std::move(offU[m]); }
-      st->fpairs = std::move(fpairs); st->fcnt = std::move(fcnt);
-      std::unique_ptr<OutJob> J(new OutJob());
-      J->outs.assign(nchunks, std::string()); J->cm.assign(nchunks, 0); J->cr.assign(nchunks, 0);
-      OutJob* const jp = J.get();
-      const int os0 = A.ops_stride, os1 = Bs.ops_stride;
-      const PairCtx* const Cp = &C; const std::vector<const char*>* const nptr_p = nptr; const std::vector<int>* const nlen_p = nlen; const std::vector<const char*>* const qptr_p = qptr;
-      const uint32_t* const mates0 = mates[0]; const uint32_t* const mates1 = mates[1]; const uint8_t* const ib_in0 = initbp_in[0]; const uint8_t* const ib_in1 = initbp_in[1];
-      const int len0 = len[0], len1_ = len[1], rw0n = rwords[0], rw1n = rwords[1];
-      const auto* const pc = &parallel_chunks;
-      jp->th = std::thread([jp, st, n, base, chunk, nchunks, NO, F0, F1, resU, opsU, os0, os1, Cp, nptr_p, nlen_p, qptr_p, mates0, mates1, ib_in0, ib_in1, len0, len1_, rw0n, rw1n, pc,
-                            s, names1, names2, quals1, quals2, cs, qual_delta, per_pair_bytes]() {
-        try {
-        const auto t0 = std::chrono::steady_clock::now();
-        const PairCtx& C = *Cp; const std::vector<const char*>* nptr = nptr_p; const std::vector<int>* nlen = nlen_p; const std::vector<const char*>* qptr = qptr_p;
-        const uint32_t* const mates[2] = {mates0, mates1}; const uint8_t* const initbp_in[2] = {ib_in0, ib_in1};
-        const int len[2] = {len0, len1_}, rwords[2] = {rw0n, rw1n};
-        std::vector<FHit>* const fhP = st->fhP; std::vector<uint32_t>* const offP = st->offP; std::vector<uint32_t>* const cntU = st->cntU; std::vector<uint32_t>* const offU = st->offU;
-        std::vector<PPair>& fpairs = st->fpairs; std::vector<int>& fcnt = st->fcnt;
-        std::vector<std::string>& outs = jp->outs; std::vector<uint64_t>& cm = jp->cm; std::vector<uint64_t>& cr = jp->cr;
-        const int ops_stride[2] = {os0, os1};
-        const auto& parallel_chunks = *pc;
-    parallel_chunks(nchunks, [&](int c) {
-          std::vector<FHit> fhU[2]; std::vector<FHit*> U[2];
-          std::string& o = outs[c]; o.reserve((size_t)chunk * (len[0] + len[1] + 300));
-          char qbuf[40];
-          for (int pr = c * chunk; pr < std::min(n, (c + 1) * chunk); pr++) {
-            const size_t o_before = o.size();
-            const long gp = (long)base + pr;
-            FHit* HP[2] = {fhP[0].data() + offP[0][pr], fhP[1].data() + offP[1][pr]};
-            F0.select_hits(cntU[0][pr] ? &resU[0][offU[0][pr]] : nullptr, opsU[0].data(), (int)cntU[0][pr], fhU[0], U[0]);
-            F1.select_hits(cntU[1][pr] ? &resU[1][offU[1][pr]] : nullptr, opsU[1].data(), (int)cntU[1][pr], fhU[1], U[1]);
-            const PPair* fp = &fpairs[(size_t)pr * NO]; const int nfp = fcnt[pr];
-            // what is printed: paired records [first2, last2) of fp, unpaired ones [firstU[m], lastU[m]) of each mate; --single-best-mapping narrows them and may add
-            // one improper pair of two unpaired mappings (ref: output.c:1086-1235)
-            int first2 = 0, last2 = nfp, firstU[2] = {0, 0}, lastU[2] = {(int)U[0].size(), (int)U[1].size()};
-            const FHit* imp[2] = {nullptr, nullptr};
-            if (gm_mqv_on(s->P)) {                                                      // --local / --no-mapping-qualities: none (ref: gmapper.c:2258,2325-2328, output.c:1092)
-              compute_paired_mqv(C, HP, fp, nfp, U);
-              if (s->P.single_best_mapping && (nfp > 0 || !U[0].empty() || !U[1].empty())) {
-                int max_idx_unpaired[2] = {-1, -1}, max_mqv_unpaired[2] = {-1, -1}, max_mqv_paired[2] = {-1, -1}; const FHit* max_hit_paired[2] = {nullptr, nullptr};
-                for (int nip = 0; nip < 2; nip++) {
-                  for (int i = 0; i < (int)U[nip].size(); i++) if (U[nip][i]->mqv > max_mqv_unpaired[nip]) { max_mqv_unpaired[nip] = U[nip][i]->mqv; max_idx_unpaired[nip] = i; }
-                  // the pool of paired hits in the order readpair_save_final_hits builds it: first appearance over the pairs (a repeated hit compares equal: strict >)
-                  for (int j = 0; j < nfp; j++) { const FHit* h = &HP[nip][fp[j].h[nip]]; if (h->mqv > max_mqv_paired[nip]) { max_mqv_paired[nip] = h->mqv; max_hit_paired[nip] = h; } }
-                }
-                // get_idx_mp_max_mqv (ref: output.c:1049-1067): of the pairs that hold hit h of mate nip, the first whose other mate has the best quality
-                auto pair_of = [&](int nip, const FHit* h) { int best = -1, idx = -1; for (int j = 0; j < nfp; j++) if (&HP[nip][fp[j].h[nip]] == h) { const int q = HP[1 - nip][fp[j].h[1 - nip]].mqv; if (q > best) { best = q; idx = j; } } return idx; };
-                if (!s->P.all_contigs) {
-                  for (int nip = 0; nip < 2; nip++) if (max_idx_unpaired[nip] >= 0) { firstU[nip] = max_idx_unpaired[nip]; lastU[nip] = firstU[nip] + 1; }
-                  const int best_nip = max_mqv_paired[0] > max_mqv_paired[1] ? 0 : 1;
-                  if (max_mqv_paired[best_nip] >= 0) { first2 = pair_of(best_nip, max_hit_paired[best_nip]); last2 = first2 + 1; }
-                } else {
-                  int max_mqv[2]; bool max_is_paired[2];
-                  for (int nip = 0; nip < 2; nip++) {
-                    if (max_mqv_unpaired[nip] > max_mqv_paired[nip]) { max_mqv[nip] = max_mqv_unpaired[nip]; max_is_paired[nip] = false; }
-                    else { max_mqv[nip] = max_mqv_paired[nip]; max_is_paired[nip] = true; }
-                  }
-                  const int best_nip = max_mqv[0] >= max_mqv[1] ? 0 : 1;
-                  if (max_is_paired[best_nip]) { lastU[0] = lastU[1] = 0; first2 = pair_of(best_nip, max_hit_paired[best_nip]); last2 = first2 + 1; }
-                  else {
-                    int idx_best_other = -1; double max_other_z0 = 0.0;
-                    const auto& OU = U[1 - best_nip];
-                    for (int i = 0; i < (int)OU.size(); i++) if (OU[i]->z0 > max_other_z0) { max_other_z0 = OU[i]->z0; idx_best_other = i; }
-                    int best_other_mqv = -1;
-                    if (idx_best_other >= 0) best_other_mqv = qv_from_pr_corr(max_other_z0 / OU[idx_best_other]->z1);
-                    if (s->P.no_improper_mappings || max_mqv_unpaired[best_nip] < 10 || best_other_mqv < 10) {
-                      last2 = 0; lastU[1 - best_nip] = 0; firstU[best_nip] = max_idx_unpaired[best_nip]; lastU[best_nip] = firstU[best_nip] + 1;
-                    } else {                                                            // both good: one improper pair, possibly across contigs
-                      imp[best_nip] = U[best_nip][max_idx_unpaired[best_nip]]; imp[1 - best_nip] = OU[idx_best_other];
-                      last2 = 0; lastU[0] = lastU[1] = 0;
-                    }
-                  }
-                }
-              }
-            }
-            // QNAME = common prefix of the two names, minus a trailing ':' or '/' (ref: output.c:365-378)
-            const char* qn; size_t qnl;
-            if (names1 && names2) {
-              const char* a = nptr[0][gp]; const char* b = nptr[1][gp]; const size_t na = (size_t)nlen[0][gp], nb = (size_t)nlen[1][gp];
-              size_t i = 0; while (i < std::min(na, nb) && a[i] == b[i]) i++;
-              if (i > 0 && (a[i - 1] == ':' || a[i - 1] == '/')) i--;
-              qn = a; qnl = i;
-            } else { qnl = (size_t)snprintf(qbuf, sizeof qbuf, "p%ld", gp); qn = qbuf; }
-            const uint32_t* rw0 = mates[0] + (size_t)gp * rwords[0]; const uint32_t* rw1 = mates[1] + (size_t)gp * rwords[1];
-            const char* ql0 = quals1 ? qptr[0][gp] : nullptr; const char* ql1 = quals2 ? qptr[1][gp] : nullptr;
-            const int ib0 = cs ? (int)initbp_in[0][gp] : -1, ib1 = cs ? (int)initbp_in[1][gp] : -1;
-            // --sam-r2: every record carries the MATE's sequence as given (re_mp->seq: letters, or primer + colours; ref: output.c:452-460,729-737)
-            std::string mseq[2]; const std::string* ms0 = nullptr; const std::string* ms1 = nullptr;
-            if (s->P.sam_r2) {
-              for (int m = 0; m < 2; m++) {
-                const uint32_t* rw = m ? rw1 : rw0; const int L = len[m];
-                if (cs) { mseq[m] += "ACGT"[(m ? ib1 : ib0) & 3]; for (int i = 0; i < L; i++) { const int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; mseq[m] += (c < 4) ? (char)('0' + c) : '.'; } }
-                else for (int i = 0; i < L; i++) { const int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; mseq[m] += (c < 4) ? "ACGT"[c] : (c == 4 ? 'U' : 'N'); }
-              }
-              ms0 = &mseq[1]; ms1 = &mseq[0];                                            // (mate 1's records carry mate 2's sequence and the other way round)
-            }
-            uint64_t k = 0;
-            if (s->P.output_format) {
-              // --shrimp-format / -P: one line (block) per mapped mate under the mate's own name, ">name" for the unmapped mate of a half-paired
-              // mapping (ref: gmapper/output.c:270-296, hit_output called per mate by readpair_output :1070-1291)
-              std::string db, qr;
-              auto one = [&](int m, const FHit* rh) {
-                const char* nm = qn; size_t nl = qnl;
-                if (names1 && names2) { nm = nptr[m][gp]; nl = (size_t)nlen[m][gp]; }
-                if (!rh) { o += '>'; o.append(nm, nl); o += '\n'; return; }
-                const Finalizer& F = m ? F1 : F0; const uint32_t* rw = m ? rw1 : rw0;
-                if (cs) F.emit_shrimp(*rh, nm, nl, pr, rw, rh->db, rh->qr, o);
-                else { F.ls_alignment_strings(*rh->r, rh->ops, std::min(rh->r->n_ops, ops_stride[m]), rw, db, qr); F.emit_shrimp(*rh, nm, nl, pr, rw, db, qr, o); }
-              };
-              for (int j = first2; j < last2; j++) { one(0, &HP[0][fp[j].h[0]]); one(1, &HP[1][fp[j].h[1]]); k += 2; }
-              if (imp[0]) { one(0, imp[0]); one(1, imp[1]); k += 2; }
-              for (int i = firstU[0]; i < lastU[0]; i++) { one(0, U[0][i]); one(1, nullptr); k += 2; }
-              for (int i = firstU[1]; i < lastU[1]; i++) { one(0, nullptr); one(1, U[1][i]); k += 2; }
-              if (nfp > 0 || !U[0].empty() || !U[1].empty()) cm[c]++;
-              cr[c] += k;
-              if (per_pair_bytes) per_pair_bytes[gp] = (uint32_t)(o.size() - o_before);
-              continue;
-            }
-            for (int j = first2; j < last2; j++) {
-              const FHit* h1 = &HP[0][fp[j].h[0]]; const FHit* h2 = &HP[1][fp[j].h[1]];
-              emit_pair_record(C, o, qn, qnl, rw0, len[0], ops_stride[0], h1, h2, true, false, ql0, qual_delta, ib0, ms0);
-              emit_pair_record(C, o, qn, qnl, rw1, len[1], ops_stride[1], h2, h1, false, false, ql1, qual_delta, ib1, ms1);
-              k += 2;
-            }
-            if (imp[0]) {
-              emit_pair_record(C, o, qn, qnl, rw0, len[0], ops_stride[0], imp[0], imp[1], true, true, ql0, qual_delta, ib0, ms0);
-              emit_pair_record(C, o, qn, qnl, rw1, len[1], ops_stride[1], imp[1], imp[0], false, true, ql1, qual_delta, ib1, ms1);
-              k += 2;
-            }
-            for (int ui = firstU[0]; ui < lastU[0]; ui++) { FHit* h = U[0][ui]; emit_pair_record(C, o, qn, qnl, rw0, len[0], ops_stride[0], h, nullptr, true, false, ql0, qual_delta, ib0, ms0); emit_pair_record(C, o, qn, qnl, rw1, len[1], ops_stride[1], nullptr, h, false, false, ql1, qual_delta, ib1, ms1); k += 2; }
-            for (int ui = firstU[1]; ui < lastU[1]; ui++) { FHit* h = U[1][ui]; emit_pair_record(C, o, qn, qnl, rw0, len[0], ops_stride[0], nullptr, h, true, false, ql0, qual_delta, ib0, ms0); emit_pair_record(C, o, qn, qnl, rw1, len[1], ops_stride[1], h, nullptr, false, false, ql1, qual_delta, ib1, ms1); k += 2; }
-            const bool any = nfp > 0 || !U[0].empty() || !U[1].empty();
-            if (!any && s->P.sam_unaligned) {                                               // ref: mapping.c:2627-2633
-              emit_pair_record(C, o, qn, qnl, rw0, len[0], ops_stride[0], nullptr, nullptr, true, false, ql0, qual_delta, ib0, ms0);
-              emit_pair_record(C, o, qn, qnl, rw1, len[1], ops_stride[1], nullptr, nullptr, false, false, ql1, qual_delta, ib1, ms1);
-              k += 2;
-            }
-            if (any) cm[c]++;
-            cr[c] += k;
-            if (per_pair_bytes) per_pair_bytes[gp] = (uint32_t)(o.size() - o_before);
-          }
-        });
-        jp->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        } catch (...) { jp->failed = true; }
-      });
-      pending = std::move(J);
-      out_idx++;
-    }
+    return GM_OK;
+  }
+  void finish_pending() {
+    if (!pending) return;
+    if (pending->th.joinable()) pending->th.join();
+    out_failed = out_failed || pending->failed;
+    if (stats) stats->ms_host += pending->ms;
+    for (size_t c = 0; c < pending->outs.size(); c++) { matched += pending->cm[c]; records += pending->cr[c]; pieces_all.push_back(std::move(pending->outs[c])); }
+    pending.reset();
+  }
+  void start_output(std::shared_ptr<PairOut> b) {
+    finish_pending();                                            // (the sub-batch before this one: its text comes first, and its pinned result set is free again after this)
+    std::unique_ptr<OutJob> J(new OutJob());
+    J->outs.assign(b->nchunks, std::string()); J->cm.assign(b->nchunks, 0); J->cr.assign(b->nchunks, 0);
+    OutJob* const jp = J.get(); const PairCall& call = *this;
+    jp->th = std::thread([&call, b, jp]() { try { pair_output(call, *b, *jp); } catch (...) { jp->failed = true; } });
+    pending = std::move(J);
     lap("host output");
+  }
+};
+}  // namespace
+
+static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* m1, int len2, const uint32_t* m2,
+                          const char* names1, const char* names2, const gm_pair_opts_t* opts, char** sam, size_t* sam_len, gm_map_stats_t* stats,
+                          const char* quals1 = nullptr, const char* quals2 = nullptr, int qual_delta = 33,
+                          const uint8_t* initbp1 = nullptr, const uint8_t* initbp2 = nullptr, uint32_t* per_pair_bytes = nullptr) {
+  if (!s || n_pairs < 0 || len1 < 1 || len2 < 1 || (n_pairs > 0 && (!m1 || !m2))) { gm_set_error("gm_map_pairs: bad arguments"); return GM_E_ARG; }
+  GmDevTurn dev_turn(s);
+  PairRun R;
+  int rc = R.init(s, n_pairs, len1, m1, len2, m2, names1, names2, opts, stats, quals1, quals2, qual_delta, initbp1, initbp2, per_pair_bytes); if (rc) return rc;
+  for (int k = 0; k < 2; k++) for (int m = 0; m < 2; m++) R.dkm[k][m] = R.dvm[m];
+  int cur = 0, front_n = 0, out_idx = 0; bool have_front = false;
+  for (int base = 0; base < n_pairs;) {
+    const int B = std::min(R.PS[cur][0]->eff_batch, R.PS[cur][1]->eff_batch);
+    const int n = have_front ? front_n : std::min(B, n_pairs - base);
+    rc = R.use_pair(cur, B); if (rc) return rc;
+    if (!have_front) { rc = R.front(cur, base, n); if (rc) return rc; }
+    bool have_next = false; int next_n = 0;
+    if (R.overlap && base + n < n_pairs) {
+      next_n = std::min(std::min(R.PS[cur ^ 1][0]->eff_batch, R.PS[cur ^ 1][1]->eff_batch), n_pairs - (base + n));
+      rc = R.front(cur ^ 1, base + n, next_n); if (rc) return rc;
+      have_next = true;
+    }
+    auto b = std::make_shared<PairOut>(); PairSel t;
+    const int pinset = (out_idx & 1) * 4;
+    b->base = base; b->n = n; b->resP = &s->pin_res[pinset]; b->opsP = &s->pin_ops[pinset]; b->resU = &s->pin_res[pinset + 2]; b->opsU = &s->pin_ops[pinset + 2];
+    for (int m = 0; m < 2; m++) b->ops_stride[m] = R.S[m]->ops_stride;
+    rc = R.finish_front(n);
+    if (!rc) rc = R.pass1_select(n, t.n_work);
+    if (!rc) rc = R.paired_pass2(*b, t);
+    if (!rc) { R.select_pairs_host(*b, t); rc = R.rescue(*b, t); }
+    if (rc == GM_REDO) { rc = R.redo(); if (rc) return rc; have_front = false; continue; }
+    if (!rc) rc = R.collect_stats();
+    if (rc) return rc;
+    R.start_output(b); out_idx++;
     base += n;
-    if (overlap) cur ^= 1;
+    if (R.overlap) cur ^= 1;
     have_front = have_next; front_n = next_n;
   }
-  finish_pending();
-  if (out_failed) { gm_set_error("gm_map_pairs: out of memory in the output stage"); return GM_E_NOMEM; }
-  if (stats) { stats->reads = 2ull * (uint64_t)n_pairs; stats->reads_matched = matched; stats->sam_records = records; }
-  size_t total = 0; for (auto& p : pieces_all) total += p.size();
+  R.finish_pending();
+  if (R.out_failed) { gm_set_error("gm_map_pairs: out of memory in the output stage"); return GM_E_NOMEM; }
+  if (stats) { stats->reads = 2ull * (uint64_t)n_pairs; stats->reads_matched = R.matched; stats->sam_records = R.records; }
+  size_t total = 0; for (auto& p : R.pieces_all) total += p.size();
   if (sam) {
     size_t cap = 0; char* r = outcache_take(total + 1, &cap);      // the text buffer of the last call, if it was given back (gm_free parks large ones)
     if (!r) { cap = total + 1 + total / 16; r = (char*)malloc(cap); }      // (some room: the next call's text is a little longer half of the time, and a parked buffer that is too small is a fresh one's page faults)
     if (!r) return GM_E_NOMEM;
     outcache_track(r, cap);
-    size_t o = 0; for (auto& p : pieces_all) { memcpy(r + o, p.data(), p.size()); o += p.size(); }
+    size_t o = 0; for (auto& p : R.pieces_all) { memcpy(r + o, p.data(), p.size()); o += p.size(); }
     r[total] = 0; *sam = r; if (sam_len) *sam_len = total;
   }
   return GM_OK;
