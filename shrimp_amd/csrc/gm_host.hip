@@ -28,6 +28,7 @@
 #include "gm_common.h"
 #include "gm_internal.h"
 #include "gm_devmem.h"
+#include "gm_textout.h"
 
 // ---- errors -----------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -48,28 +49,10 @@ hipError_t gm_lds_at_least(const void* kernel, size_t bytes) {
   if (e == hipSuccess) cur = bytes;
   return e;
 }
-// The SAM text of a large call is hundreds of megabytes: allocating it afresh for every call (page faults on first touch) and unmapping it in gm_free cost 20+ ms per
-// 1 M reads that nothing overlaps.  One freed text buffer of >= 16 MB is therefore parked here and handed to the next call (gm_release_cache() drops it).
-static struct { std::mutex m; char* p = nullptr; size_t cap = 0; char* live = nullptr; size_t live_cap = 0; } g_outcache;
-static char* outcache_take(size_t want, size_t* cap) {
-  std::lock_guard<std::mutex> g(g_outcache.m);
-  if (g_outcache.p && g_outcache.cap >= want) { char* r = g_outcache.p; *cap = g_outcache.cap; g_outcache.p = nullptr; g_outcache.cap = 0; return r; }
-  return nullptr;
-}
-static void outcache_track(char* p, size_t cap) { std::lock_guard<std::mutex> g(g_outcache.m); g_outcache.live = p; g_outcache.live_cap = cap; }
+static GmTextCacheT<> g_outcache;      // the text buffer parked between calls (gm_textout.h; gm_release_cache() drops it)
 static void gm_text_pool_drop();
-extern "C" void gm_release_cache(void) { { std::lock_guard<std::mutex> g(g_outcache.m); free(g_outcache.p); g_outcache.p = nullptr; g_outcache.cap = 0; } gm_text_pool_drop(); }
-extern "C" void gm_free(void* p) {
-  if (!p) return;
-  { std::lock_guard<std::mutex> g(g_outcache.m);
-    if (p == g_outcache.live && g_outcache.live_cap >= ((size_t)16 << 20)) {
-      g_outcache.live = nullptr;
-      if (g_outcache.p && g_outcache.cap >= g_outcache.live_cap) { /* a larger one is parked already */ }
-      else { free(g_outcache.p); g_outcache.p = (char*)p; g_outcache.cap = g_outcache.live_cap; return; }
-    } else if (p == g_outcache.live) g_outcache.live = nullptr;
-  }
-  free(p);
-}
+extern "C" void gm_release_cache(void) { g_outcache.drop(); gm_text_pool_drop(); }
+extern "C" void gm_free(void* p) { if (p) g_outcache.give_back(p); }
 
 extern "C" void gm_params_default(gm_params_t* p) {
   memset(p, 0, sizeof *p);
@@ -1508,68 +1491,80 @@ static void add_device_stats(gm_map_stats_t* st, const unsigned long long* hs) {
   st->full_calls += hs[GS_FULL_CALLS]; st->full_cells += hs[GS_FULL_CELLS]; st->exact_order_reads += hs[GS_EXACT_ORDER]; st->survivors_pruned += hs[GS_PRUNED];
 }
 
-// Back, stream B: heavy tier if any (stream A, rare), pass 1, selection, pass 2, results to the host slot.  Returns 1 when a capacity grew
-// (the buffers of set k were re-allocated: the caller re-submits the sub-batch from the front).
-static int pipeline_back(gm_session* s, int k, HostSlot& H, int n, int read_len, gm_map_stats_t* st, float* lookup_ms, bool next_front_queued = false,
-                         const std::function<int()>* after_pass2 = nullptr) {
-  DevSet& D = s->set[k];
-  const GmIndexDev dv = session_view(s);
-  const int read_words = (read_len + 7) / 8;
-  const int W = window_len_of(s->P, read_len);
-  const int overlap_abs = (int)(unsigned int)(s->P.window_overlap < 0 ? -s->P.window_overlap : W * (s->P.window_overlap / 100.0));   // ref: mapping.c:1289
-  hipStream_t q = s->stream_b;
-  unsigned long long* d_stats = s->d_pstats[k];
-  {
+// the striped stage counters as the device leaves them (raw[GS_STRIPES][GS_STRIDE]) into one row hs[GS_N]
+static void fold_stats(const unsigned long long* raw, unsigned long long* hs) { for (int c = 0; c < GS_N; c++) { hs[c] = 0; for (int t = 0; t < GS_STRIPES; t++) hs[c] += raw[(size_t)t * GS_STRIDE + c]; } }
+// sw_full_cs_setup's arguments (ref: gmapper.c:2944-2947)
+static void cs_setup_args(const gm_params_t& P, int* cs9) {
+  const int c9[9] = {P.match_score, P.mismatch_score, P.crossover_score, -P.a_gap_open_score, -P.a_gap_extend_score, -P.b_gap_open_score, -P.b_gap_extend_score, P.anchor_width, P.indel_taboo_len};
+  memcpy(cs9, c9, sizeof c9);
+}
+// set 0 for unpaired reads of this length: kept when it has that length and unpaired capacities, else chosen and allocated anew
+static int prepare_unpaired_set(gm_session* s, int read_len) {
+  DevSet& D = s->set[0];
+  if (D.cur_len == read_len && (D.caps_pair_mode == 0 || D.caps_pair_mode == 4)) return GM_OK;
+  choose_caps(s, D, read_len); D.caps_pair_mode = 0;
+  return alloc_buffers(s, D, read_len);
+}
+static double gm_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static const int GM_REDO = 1;     // a stage's answer besides GM_OK and the error codes: the sub-batch is run again from its front
+
+namespace {
+// Back, stream B, of the sub-batch whose front ran on set k: its stages in the order they are called, and what they share.  Each returns GM_OK or an error; grow also
+// GM_REDO (the buffers of set k were re-allocated: the caller re-submits the sub-batch from the front).  Between copy_out and finish_back nothing of this set that the
+// FRONT writes is read any more, so the caller may queue the front of the sub-batch after next onto it there (ReadRun::back).
+struct BackStages {
+  gm_session* s; int k; HostSlot& H; int n, read_len; gm_map_stats_t* st;
+  DevSet& D = s->set[k]; const GmIndexDev dv = session_view(s); int read_words = (read_len + 7) / 8, W = window_len_of(s->P, read_len);
+  hipStream_t q = s->stream_b; unsigned long long* d_stats = s->d_pstats[k];
+  uint32_t n_work = 0; unsigned long long hs[GS_N]; float ms[5];      // pass 2's work items, the folded counters, the five stage times
+  std::vector<unsigned long long> hraw = std::vector<unsigned long long>((size_t)GS_STRIPES * GS_STRIDE);
+  size_t rcap() const { return (size_t)D.eff_batch * D.rcap_per_read; }
+  // the front's end and times, the heavy tier if any (stream A, rare); next_front_queued: the other set's front is in flight
+  int wait_front(bool next_front_queued) {
     GM_HIP(hipEventSynchronize(s->pev[k][6]));
     const uint32_t n_heavy = s->h_pin[k];
-    int rc;
-    float ms[5];                                                     // (the front's times now: its events are recorded again when this set takes the sub-batch after next)
-    GM_HIP(hipEventElapsedTime(&ms[0], s->pev[k][0], s->pev[k][1]));
+    GM_HIP(hipEventElapsedTime(&ms[0], s->pev[k][0], s->pev[k][1]));      // (the front's times now: its events are recorded again when this set takes the sub-batch after next)
     GM_HIP(hipEventElapsedTime(&ms[1], s->pev[k][1], s->pev[k][2]));
-    if (n_heavy) {
-      rc = run_heavy_tier(s, D, dv, n, read_len, read_words, W, (int)n_heavy, d_stats); if (rc) return rc;
-      GM_HIP(hipEventRecord(s->pev[k][6], s->stream));
-    }
+    if (n_heavy) { int rc = run_heavy_tier(s, D, dv, n, read_len, read_words, W, (int)n_heavy, d_stats); if (rc) return rc; GM_HIP(hipEventRecord(s->pev[k][6], s->stream)); }
     GM_HIP(hipStreamWaitEvent(q, s->pev[k][6], 0));
     if (next_front_queued && s->front_flag_grid[k ^ 1] > 0) {
       // K1 of the next sub-batch becomes runnable at the same moment as this pass 1.  Its persistent workgroups need a whole CU's LDS each; pass-1 waves
       // that get there first keep them off the CUs until pass 1 is over.  So: wait (bounded) until all of them have raised their flag.
       volatile uint32_t* f = s->h_pin + 16; const uint32_t want = s->front_epoch[k ^ 1]; const int g = s->front_flag_grid[k ^ 1];
-      const auto t0 = std::chrono::steady_clock::now();
-      for (;;) {
-        int up = 0; for (int i = 0; i < g; i++) up += f[i] == want;
-        if (up == g || std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > 5.0) break;
-      }
+      const double t0 = gm_now_ms();
+      for (int up = 0; up < g && gm_now_ms() - t0 <= 5.0;) { up = 0; for (int i = 0; i < g; i++) up += f[i] == want; }
     }
+    return GM_OK;
+  }
+  int pass1_select() {
+    const int overlap_abs = (int)(unsigned int)(s->P.window_overlap < 0 ? -s->P.window_overlap : W * (s->P.window_overlap / 100.0));   // ref: mapping.c:1289
     GM_HIP(hipEventRecord(s->pev[k][3], q));
-    rc = gm_launch_pass1(gm_view_of(dv, D), s->sc, D.d_reads, n, read_len, read_words, W, overlap_abs, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, D.d_slots, d_stats, q,
-                         nullptr, nullptr, D.d_initbp, true);
-    if (rc) return rc;
+    int rc = gm_launch_pass1(gm_view_of(dv, D), s->sc, D.d_reads, n, read_len, read_words, W, overlap_abs, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, D.d_slots, d_stats, q,
+                             nullptr, nullptr, D.d_initbp, true); if (rc) return rc;
     GM_HIP(hipEventRecord(s->pev[k][4], q));
-    rc = gm_launch_select(s->sc, n, read_len, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, D.d_sel, D.d_sel_cnt, D.d_sel_off, D.d_work, D.d_n_work, q);
-    if (rc) return rc;
+    rc = gm_launch_select(s->sc, n, read_len, D.d_hits, D.d_perm, D.d_hit_cnt, D.hcap, D.d_sel, D.d_sel_cnt, D.d_sel_off, D.d_work, D.d_n_work, q); if (rc) return rc;
     GM_HIP(hipEventRecord(s->pev[k][5], q));
-    unsigned long long hs[GS_N]; uint32_t n_work = 0;
-    std::vector<unsigned long long> hraw((size_t)GS_STRIPES * GS_STRIDE);
-    auto fold = [&]() { for (int c = 0; c < GS_N; c++) { hs[c] = 0; for (int t = 0; t < GS_STRIPES; t++) hs[c] += hraw[(size_t)t * GS_STRIDE + c]; } };
     GM_HIP(hipMemcpyAsync(&n_work, D.d_n_work, 4, hipMemcpyDeviceToHost, q));
     GM_HIP(hipMemcpyAsync(hraw.data(), d_stats, hraw.size() * 8, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
-    fold();
-    const size_t rcap = (size_t)D.eff_batch * D.rcap_per_read;
+    fold_stats(hraw.data(), hs);
+    return GM_OK;
+  }
+  int grow() {
     bool retry = false;
     if (hs[GS_OVERFLOW_SURV]) { gm_set_error("heavy list overflow"); return GM_E_OVERFLOW; }
     if (hs[GS_OVERFLOW_HITS]) { if (D.hcap >= 32768) { gm_set_error("window list overflow at capacity %d", D.hcap); return GM_E_OVERFLOW; } D.hcap *= 4; retry = true; }
-    if (n_work > rcap) { if (D.rcap_per_read >= 32) { gm_set_error("pass-2 work overflow"); return GM_E_OVERFLOW; } D.rcap_per_read = std::min(32, D.rcap_per_read * 2); retry = true; }
-    if (retry) {   // capacities grew: re-allocate and let the caller re-submit (the sub-batch size may have shrunk)
-      if (st) st->retries++;
-      GM_HIP(hipStreamSynchronize(s->stream));           // the other set's front may be in flight; nothing may touch freed buffers
-      rc = alloc_buffers(s, D, read_len); if (rc) return rc;
-      return 1;
-    }
-    if (s->P.colour_space) {
-      const int cs9[9] = {s->P.match_score, s->P.mismatch_score, s->P.crossover_score, -s->P.a_gap_open_score, -s->P.a_gap_extend_score,
-                          -s->P.b_gap_open_score, -s->P.b_gap_extend_score, s->P.anchor_width, s->P.indel_taboo_len};   // sw_full_cs_setup's arguments (ref: gmapper.c:2944-2947)
+    if (n_work > rcap()) { if (D.rcap_per_read >= 32) { gm_set_error("pass-2 work overflow"); return GM_E_OVERFLOW; } D.rcap_per_read = std::min(32, D.rcap_per_read * 2); retry = true; }
+    if (!retry) return GM_OK;
+    // capacities grew: re-allocate and let the caller re-submit (the sub-batch size may have shrunk)
+    if (st) st->retries++;
+    GM_HIP(hipStreamSynchronize(s->stream));           // the other set's front may be in flight; nothing may touch freed buffers
+    const int rc = alloc_buffers(s, D, read_len);
+    return rc ? rc : GM_REDO;
+  }
+  int pass2() {
+    int rc; if (s->P.colour_space) {
+      int cs9[9]; cs_setup_args(s->P, cs9);
       rc = gm_launch_pass2_cs(dv, s->sc, cs9, D.d_reads, D.d_initbp, n, read_len, read_words, W, D.d_hits, D.hcap, D.d_sel, D.d_work, D.d_n_work,
                               D.d_res, D.d_ops, D.ops_stride, (uint32_t*)D.d_back, D.back_stride / 4, D.p2_grid, d_stats, q, D.xover_on ? D.d_xover : nullptr, nullptr, D.d_p2_order, D.d_p2_cls);
       // post_sw of every result on the device (with the reads' quality values where they have them: per-colour error rates from the host's table, base qualities back), unless
@@ -1581,30 +1576,35 @@ static int pipeline_back(gm_session* s, int k, HostSlot& H, int n, int read_len,
         GmCsPostDev K; K.let_m = c.let_m; K.let_x = c.let_x; K.col_m[0] = c.col_m[0]; K.col_m[1] = c.col_m[1]; K.col_x[0] = c.col_x[0]; K.col_x[1] = c.col_x[1];
         K.pr_del_open = c.pr_del_open; K.pr_del_extend = c.pr_del_extend; K.pr_ins_open = c.pr_ins_open; K.pr_ins_extend = c.pr_ins_extend;
         K.qv = H.post_bq_on ? D.d_qv : nullptr; K.qtab = H.post_bq_on ? s->d_qtab : nullptr; K.bq = H.post_bq_on ? D.d_post_bq : nullptr;
-        rc = gm_launch_post_sw_cs(K, D.d_reads, D.d_initbp, read_len, read_words, D.d_res, D.d_ops, D.ops_stride, D.d_n_work, (uint32_t)rcap, D.d_post, D.d_post_fw, D.d_post_info,
+        rc = gm_launch_post_sw_cs(K, D.d_reads, D.d_initbp, read_len, read_words, D.d_res, D.d_ops, D.ops_stride, D.d_n_work, (uint32_t)rcap(), D.d_post, D.d_post_fw, D.d_post_info,
                                   D.post_threads, q);
       }
-    } else
-    rc = gm_launch_pass2(gm_view_of(dv, D), s->sc, D.d_reads, n, read_len, read_words, W, D.d_hits, D.d_perm, D.hcap, D.d_sel, D.d_sel_cnt, D.d_work, D.d_n_work,
-                         D.d_res, D.d_ops, D.ops_stride, D.d_back, D.back_stride, D.p2_grid, d_stats, q, nullptr, 0, 0, D.d_p2_order, D.d_p2_cls);
+    } else {
+      rc = gm_launch_pass2(gm_view_of(dv, D), s->sc, D.d_reads, n, read_len, read_words, W, D.d_hits, D.d_perm, D.hcap, D.d_sel, D.d_sel_cnt, D.d_work, D.d_n_work,
+                           D.d_res, D.d_ops, D.ops_stride, D.d_back, D.back_stride, D.p2_grid, d_stats, q, nullptr, 0, 0, D.d_p2_order, D.d_p2_cls);
+      H.post_on = false;
+    }
     if (rc) return rc;
-    GM_HIP(hipEventRecord(s->pev[k][7], q));
-    { size_t cap;
-      cap = H.res_cap; rc = slot_reserve((void**)&H.res, &cap, (size_t)n_work * sizeof(GmFullRes)); H.res_cap = cap; if (rc) return rc;
-      cap = H.ops_cap; rc = slot_reserve((void**)&H.ops, &cap, (size_t)n_work * D.ops_stride); H.ops_cap = cap; if (rc) return rc;
-      cap = H.n_cap; rc = slot_reserve((void**)&H.sel_cnt, &cap, (size_t)n * 4); if (rc) return rc;
-      cap = H.n_cap; rc = slot_reserve((void**)&H.sel_off, &cap, (size_t)n * 4); H.n_cap = cap; if (rc) return rc; }
-    H.n_work = n_work;
-    if (!s->P.colour_space) H.post_on = false;
     if (!H.post_on) H.post_bq_on = false;
-    if (H.post_on) { size_t cap = H.post_cap; rc = slot_reserve((void**)&H.post, &cap, (size_t)n_work * sizeof(GmPostRes)); H.post_cap = cap; if (rc) return rc; }
-    if (H.post_bq_on) { size_t cap = H.post_bq_cap; rc = slot_reserve((void**)&H.post_bq, &cap, (size_t)n_work * read_len + 64); H.post_bq_cap = cap; if (rc) return rc; }
+    GM_HIP(hipEventRecord(s->pev[k][7], q));
+    return GM_OK;
+  }
+  // the results to the host slot
+  int copy_out() {
+    int rc; size_t cap;
+    cap = H.res_cap; rc = slot_reserve((void**)&H.res, &cap, (size_t)n_work * sizeof(GmFullRes)); H.res_cap = cap; if (rc) return rc;
+    cap = H.ops_cap; rc = slot_reserve((void**)&H.ops, &cap, (size_t)n_work * D.ops_stride); H.ops_cap = cap; if (rc) return rc;
+    cap = H.n_cap; rc = slot_reserve((void**)&H.sel_cnt, &cap, (size_t)n * 4); if (rc) return rc;
+    cap = H.n_cap; rc = slot_reserve((void**)&H.sel_off, &cap, (size_t)n * 4); H.n_cap = cap; if (rc) return rc;
+    H.n_work = n_work;
+    if (H.post_on) { cap = H.post_cap; rc = slot_reserve((void**)&H.post, &cap, (size_t)n_work * sizeof(GmPostRes)); H.post_cap = cap; if (rc) return rc; }
+    if (H.post_bq_on) { cap = H.post_bq_cap; rc = slot_reserve((void**)&H.post_bq, &cap, (size_t)n_work * read_len + 64); H.post_bq_cap = cap; if (rc) return rc; }
     // The stage counters first, then an event: from there on nothing of this set that the FRONT writes is read any more (the copies below take d_res / d_ops / d_sel_* /
-    // d_post only), so the front of the sub-batch after next may be queued onto this set before the host waits for the results (after_pass2, see map_impl).
-    { size_t cap = H.stats_cap; rc = slot_reserve((void**)&H.stats, &cap, hraw.size() * 8); H.stats_cap = cap; if (rc) return rc; }
+    // d_post only), so the front of the sub-batch after next may be queued onto this set before the host waits for the results.
+    cap = H.stats_cap; rc = slot_reserve((void**)&H.stats, &cap, hraw.size() * 8); H.stats_cap = cap; if (rc) return rc;
     GM_HIP(hipMemcpyAsync(H.stats, d_stats, hraw.size() * 8, hipMemcpyDeviceToHost, q));
     if (H.want_reads) {                                              // reads handed over in device memory: the host's finalisation needs this sub-batch's letters too
-      size_t cap = H.reads_cap; rc = slot_reserve((void**)&H.reads, &cap, (size_t)n * read_words * 4); H.reads_cap = cap; if (rc) return rc;
+      cap = H.reads_cap; rc = slot_reserve((void**)&H.reads, &cap, (size_t)n * read_words * 4); H.reads_cap = cap; if (rc) return rc;
       GM_HIP(hipMemcpyAsync(H.reads, D.d_reads, (size_t)n * read_words * 4, hipMemcpyDeviceToHost, q));
     }
     GM_HIP(hipEventRecord(s->pev[k][9], q));
@@ -1616,29 +1616,32 @@ static int pipeline_back(gm_session* s, int k, HostSlot& H, int n, int read_len,
     }
     GM_HIP(hipMemcpyAsync(H.sel_cnt, D.d_sel_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, q));
     GM_HIP(hipMemcpyAsync(H.sel_off, D.d_sel_off, (size_t)n * 4, hipMemcpyDeviceToHost, q));
-    if (after_pass2) { rc = (*after_pass2)(); if (rc) return rc; }
+    return GM_OK;
+  }
+  int finish_back(float* lookup_ms) {
     GM_HIP(hipStreamSynchronize(q));
-    memcpy(hraw.data(), H.stats, hraw.size() * 8);
-    fold();
+    fold_stats(H.stats, hs);
     GM_HIP(hipEventElapsedTime(&ms[2], s->pev[k][3], s->pev[k][4]));
     GM_HIP(hipEventElapsedTime(&ms[3], s->pev[k][4], s->pev[k][5]));
     GM_HIP(hipEventElapsedTime(&ms[4], s->pev[k][5], s->pev[k][7]));
     *lookup_ms = ms[0];
-    if (st) {
-      add_device_stats(st, hs);
-      st->ms_lookup += ms[0]; st->ms_anchors += ms[1]; st->ms_pass1 += ms[2]; st->ms_select += ms[3]; st->ms_pass2 += ms[4];
-    }
+    if (st) { add_device_stats(st, hs); st->ms_lookup += ms[0]; st->ms_anchors += ms[1]; st->ms_pass1 += ms[2]; st->ms_select += ms[3]; st->ms_pass2 += ms[4]; }
     s->last_lookup_bytes += 12ull * hs[GS_LOOKUPS] + 4ull * hs[GS_ENTRIES];
     return GM_OK;
   }
-}
+  // the first five stages, as far as the queued result copies
+  int through_copy_out(bool next_front_queued) {
+    int rc = wait_front(next_front_queued); if (!rc) rc = pass1_select(); if (!rc) rc = grow(); if (!rc) rc = pass2();
+    return rc ? rc : copy_out();
+  }
+};
+}  // namespace
 
 // both halves back to back on set 0 (stage dumps)
-static int run_device_pipeline(gm_session* s, DevSet& D, HostSlot& H, int n, int read_len, gm_map_stats_t* st, float* lookup_ms) {
-  (void)D;
-  int rc = pipeline_front(s, 0, n, read_len);
-  if (rc) return rc;
-  return pipeline_back(s, 0, H, n, read_len, st, lookup_ms);
+static int run_device_pipeline(gm_session* s, HostSlot& H, int n, int read_len, float* lookup_ms) {
+  BackStages B{s, 0, H, n, read_len, nullptr};
+  int rc = pipeline_front(s, 0, n, read_len); if (!rc) rc = B.through_copy_out(false);
+  return rc ? rc : B.finish_back(lookup_ms);
 }
 
 // Admission of mapping calls per device: at most TWO in flight on a device (a single call already fills the GPU), e.g. the two sessions the file entry alternates its
@@ -1696,60 +1699,137 @@ static int check_read_len(const gm_session* s, int read_len) {
   return GM_OK;
 }
 
-static int map_impl(gm_session* s, int n_reads, int read_len, const uint32_t* reads_host, const void* reads_dev,
-                    const char* names, int emit_sam, char** sam, size_t* sam_len, gm_map_stats_t* stats, const uint8_t* initbp_host = nullptr,
-                    const char* quals = nullptr, int qual_delta = 33, const char* seq_text = nullptr, uint32_t* per_read_bytes = nullptr) {
-  if (!s || n_reads < 0 || read_len < 1) { gm_set_error("gm_map_reads: bad arguments"); return GM_E_ARG; }
-  if ((s->P.colour_space != 0) != (initbp_host != nullptr)) {
-    gm_set_error(s->P.colour_space ? "colour-space session: use gm_map_reads_cs (colours + primer letters)" : "gm_map_reads_cs needs a colour-space session"); return GM_E_ARG; }
-  if (int rc = check_read_len(s, read_len)) return rc;
-  const double tl_in = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  GmDevTurn dev_turn(s);
-  const double tl_turn = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  GM_HIP(hipSetDevice(s->ix->device));
-  DevSet& D = s->set[0];
-  if (stats) memset(stats, 0, sizeof *stats);
-  if (D.cur_len != read_len || (D.caps_pair_mode != 0 && D.caps_pair_mode != 4)) { choose_caps(s, D, read_len); D.caps_pair_mode = 0; int rc = alloc_buffers(s, D, read_len); if (rc) return rc; }
-  const int read_words = (read_len + 7) / 8;
-  if (int rc = ensure_host_genome(s)) return rc;
-  s->last_lookup_ms = 0; s->last_lookup_bytes = 0; s->last_lookup_launches = 0;
-  // names
-  std::vector<const char*> nptr; std::vector<int> nlen;
-  std::vector<const char*> qptr; std::vector<int8_t> xbuf; std::vector<uint8_t> qvbuf; std::vector<const char*> sptr;
-  auto lines_of = [&](const char* text, int want, std::vector<const char*>& ptr, const char* bad_len_fmt) -> int {      // one line of `want` characters per read
+namespace {                                                    // (the call's own types: nothing of them is exported)
+// One gm_map_reads call: what init() settles before the first sub-batch and nothing changes after it (the job threads read it beside the calling thread).
+struct ReadCall {
+  gm_session* s = nullptr; int n_reads = 0, read_len = 0, read_words = 0; gm_map_stats_t* stats = nullptr;
+  const uint32_t* reads_host = nullptr; const void* reads_dev = nullptr; const uint8_t* initbp = nullptr;      // the reads: in host memory (with the primer letters in colour space) or on the device
+  std::vector<const char*> nptr, qptr, sptr; std::vector<int> nlen; bool named = false, quals = false, seq_text = false;      // name, QUAL and text line of every read
+  int qual_delta = 33, emit_sam = 0, nthreads = 1, ops_stride = 0, ramp_min = 8192; uint32_t* per_read_bytes = nullptr;
+  bool overlap = false, timeline = false; const char* guard_tol = nullptr;      // guard_tol: GM_POST_GUARD_TOL (tests: a huge tolerance sends every result through the redo path)
+  static int check_args(const gm_session* s, int n_reads, int read_len, const uint8_t* initbp_host) {
+    if (!s || n_reads < 0 || read_len < 1) { gm_set_error("gm_map_reads: bad arguments"); return GM_E_ARG; }
+    if ((s->P.colour_space != 0) != (initbp_host != nullptr)) { gm_set_error(s->P.colour_space ? "colour-space session: use gm_map_reads_cs (colours + primer letters)" : "gm_map_reads_cs needs a colour-space session"); return GM_E_ARG; }
+    return check_read_len(s, read_len);
+  }
+  int lines_of(const char* text, int want, std::vector<const char*>& ptr, const char* bad_len_fmt) const {      // one line of `want` characters per read
     if (!gm_fixed_lines(text, (size_t)n_reads, (size_t)want)) return split_lines(text, n_reads, ptr, nullptr, want, bad_len_fmt);
     ptr.resize(n_reads); for (int i = 0; i < n_reads; i++) ptr[i] = text + (size_t)i * ((size_t)want + 1);      // (the usual case: no search for the line ends)
     return GM_OK;
-  };
-  if (seq_text) { if (int rc = lines_of(seq_text, read_len + (s->P.colour_space ? 1 : 0), sptr, "read %d: %d characters, expected %d")) return rc; }   // letters, or primer + colours
-  if (quals) { if (int rc = lines_of(quals, read_len, qptr, "read %d: QUAL string of %d characters for %d bases")) return rc; }
-  if (names) split_lines(names, n_reads, nptr, &nlen);
-  // Sub-batches are pipelined: while the GPU works on sub-batch i+1, host threads finish sub-batch i
-  // (pass-2 selection, MAPQ, SAM text).  Output stays in input order.
-  struct Job {
-    int idx = 0;
-    HostSlot* hs = nullptr;
-    const uint32_t* hreads = nullptr; int base = 0, n = 0;
-    std::vector<std::string> outs; std::vector<uint64_t> cm, cr; double ms = 0;
-    std::thread th;
-  };
-  std::vector<std::unique_ptr<Job>> jobs;
-  const int nthreads = gm_host_threads(32);                  // a multi-rank job divides the cores itself: GM_HOST_THREADS (bench.py: cores / ranks of this node)
-  const int ops_stride = D.ops_stride;
-  // The SAM text is assembled as the jobs finish, in input order (each job appends after its predecessor), so that the copy -- and the
-  // first touch of the output pages -- overlaps the device work instead of following it.
-  struct OutBuf { char* p = nullptr; size_t len = 0, cap = 0; int turn = 0; bool failed = false; std::mutex m; std::condition_variable cv; ~OutBuf() { free(p); } } ob;
-  std::atomic<uint64_t> post_redo(0);
-  auto run_job = [&, nthreads, ops_stride](Job* J) {
+  }
+  int match_sets(int from) const {                             // give the other set the capacities of set `from`
+    DevSet& a = s->set[from]; DevSet& b = s->set[from ^ 1];
+    if (a.cur_len == b.cur_len && a.scap == b.scap && a.scap2 == b.scap2 && a.hcap == b.hcap && a.rcap_per_read == b.rcap_per_read && a.eff_batch == b.eff_batch && b.d_pmin == nullptr) return GM_OK;
+    b.scap = a.scap; b.scap2 = a.scap2; b.hcap = a.hcap; b.rcap_per_read = a.rcap_per_read;
+    return alloc_buffers(s, b, read_len);
+  }
+  // the set-up, behind check_args and the device's turn (map_impl)
+  int init(gm_session* s_, int n_reads_, int read_len_, const uint32_t* reads_host_, const void* reads_dev_, const char* names, int emit_sam_, gm_map_stats_t* stats_,
+           const uint8_t* initbp_host, const char* quals_, int qual_delta_, const char* seq, uint32_t* per_read_bytes_) {
+    s = s_; n_reads = n_reads_; read_len = read_len_; reads_host = reads_host_; reads_dev = reads_dev_; emit_sam = emit_sam_; stats = stats_; initbp = initbp_host;
+    qual_delta = qual_delta_; per_read_bytes = per_read_bytes_; named = names != nullptr; quals = quals_ != nullptr; seq_text = seq != nullptr;
+    GM_HIP(hipSetDevice(s->ix->device));
+    if (stats) memset(stats, 0, sizeof *stats);
+    read_words = (read_len + 7) / 8;
+    int rc = prepare_unpaired_set(s, read_len); if (!rc) rc = ensure_host_genome(s); if (rc) return rc;
+    s->last_lookup_ms = 0; s->last_lookup_bytes = 0; s->last_lookup_launches = 0;
+    if (seq) { rc = lines_of(seq, read_len + (s->P.colour_space ? 1 : 0), sptr, "read %d: %d characters, expected %d"); if (rc) return rc; }   // letters, or primer + colours
+    if (quals_) { rc = lines_of(quals_, read_len, qptr, "read %d: QUAL string of %d characters for %d bases"); if (rc) return rc; }
+    if (names) split_lines(names, n_reads, nptr, &nlen);
+    nthreads = gm_host_threads(32);                            // a multi-rank job divides the cores itself: GM_HOST_THREADS (bench.py: cores / ranks of this node)
+    ops_stride = s->set[0].ops_stride; guard_tol = gm_tune("GM_POST_GUARD_TOL");
+    // Two buffer sets: the front of sub-batch i + 1 (stream A) is queued before the host turns to the back of sub-batch i (stream B),
+    // so K1 of the next sub-batch and pass 1 / pass 2 of this one share the CUs (see pipeline_front).  GM_OVERLAP=0: one set, in order.
+    overlap = n_reads > s->set[0].eff_batch;
+    if (const char* e = getenv("GM_OVERLAP")) overlap = overlap && atoi(e) != 0;
+    if (overlap) { rc = match_sets(0); if (rc) return rc; if (s->set[1].eff_batch != s->set[0].eff_batch) overlap = false; }
+    if (const char* e = gm_tune("GM_RAMP_MIN")) ramp_min = std::max(64, atoi(e));
+    timeline = getenv("GM_TIMELINE") != nullptr;               // GM_TIMELINE=1: where the calling thread's time goes, per sub-batch (stderr)
+    return GM_OK;
+  }
+  // Sub-batch sizes: while the two halves overlap, the first sub-batch's front and the last one's back (and its host work) have nothing to
+  // run beside, so the sizes ramp up from 8 192 at the start and halve towards the end (results do not depend on the split).
+  int size_at(int base, int eff) const {
+    const int R = n_reads - base;
+    int n = std::min(eff, R);
+    if (!overlap || ramp_min >= eff) return n;
+    n = std::min(n, std::max(ramp_min, base + ramp_min));
+    n = std::min(n, std::max(ramp_min, R / 2));
+    return R - n < ramp_min / 2 ? std::min(eff, R) : n;
+  }
+};
+// The host work of one sub-batch (pass-2 selection, MAPQ, SAM text) on a thread of its own, while the GPU works on the next sub-batch
+struct ReadJob {
+  int idx = 0, base = 0, n = 0; HostSlot* hs = nullptr; const uint32_t* hreads = nullptr;
+  std::vector<std::string> outs; std::vector<uint64_t> cm, cr; double ms = 0; bool failed = false; std::thread th;
+  ~ReadJob() { if (th.joinable()) th.join(); }
+};
+// The call's state that changes from sub-batch to sub-batch, and the stages in the order map_impl calls them.
+// Sub-batch i lives in set i & 1.  Its front is queued as early as the set allows: the first two at once, the front of i + 2 from the back of i -- behind pass 2
+// and the copy of the counters, in front of the wait for the result copies (the device orders it behind event pev[.][9]).  Short fronts
+// (the bucket kernel on a small genome: 6 ms a sub-batch) then follow each other without the gap of a host round trip.
+struct ReadRun : ReadCall {
+  int q_base = 0, q_idx = 0;                                  // next sub-batch whose front is not queued yet: its first read, its number
+  int fr_n[2] = {0, 0};                                       // reads of the sub-batch whose front is queued on set k
+  std::vector<int8_t> xbuf; std::vector<uint8_t> qvbuf;       // colour space with QVs: a sub-batch's crossover scores and quality values on their way up
+  std::atomic<uint64_t> post_redo{0};
+  size_t joined = 0; double tl_join = 0, tl_spawn = 0;        // jobs joined so far; GM_TIMELINE: the last start_job's wait for a job, and its spawn
+  // The SAM text is assembled as the jobs finish, in input order (each job appends after its predecessor)
+  GmTextOut out;
+  std::vector<std::unique_ptr<ReadJob>> jobs;                 // (last: their threads read the ReadCall part, post_redo and out, and are joined before anything here goes away)
+  explicit ReadRun(size_t n_reads_) : out(g_outcache, n_reads_) {}
+  // copies of one sub-batch into set k; host memory goes through stream C so that the call never waits behind queued kernels
+  int queue_inputs(int k, int base, int n) {
+    DevSet& S = s->set[k];
+    S.xover_on = false;
+    if (!reads_host) { GM_HIP(hipMemcpyAsync(S.d_reads, (const uint32_t*)reads_dev + (size_t)base * read_words, (size_t)n * read_words * 4, hipMemcpyDeviceToDevice, s->stream)); return GM_OK; }
+    hipStream_t c = s->stream_c;
+    GM_HIP(hipMemcpyAsync(S.d_reads, reads_host + (size_t)base * read_words, (size_t)n * read_words * 4, hipMemcpyHostToDevice, c));
+    if (initbp) GM_HIP(hipMemcpyAsync(S.d_initbp, initbp + base, (size_t)n, hipMemcpyHostToDevice, c));
+    if (initbp && quals) {                                   // per-position crossover scores from the QVs, ref: gmapper.c:532-544
+      xbuf.resize((size_t)n * read_len); qvbuf.resize((size_t)n * read_len);
+      xover_from_quals(s, qptr.data() + base, n, read_len, qual_delta, xbuf.data(), qvbuf.data());
+      GM_HIP(hipMemcpyAsync(S.d_xover, xbuf.data(), xbuf.size(), hipMemcpyHostToDevice, c));
+      GM_HIP(hipMemcpyAsync(S.d_qv, qvbuf.data(), qvbuf.size(), hipMemcpyHostToDevice, c));
+      GM_HIP(hipStreamSynchronize(c));                      // xbuf is reused by the next sub-batch
+      S.xover_on = true;
+    }
+    GM_HIP(hipEventRecord(s->pev[k][8], c));
+    GM_HIP(hipStreamWaitEvent(s->stream, s->pev[k][8], 0));
+    return GM_OK;
+  }
+  int queue_front(bool behind_back) {                         // queues the front of sub-batch q_idx, if there is one
+    if (q_base >= n_reads) return GM_OK;
+    const int k = overlap ? (q_idx & 1) : 0;
+    const int n = size_at(q_base, s->set[k].eff_batch);
+    if (behind_back) { GM_HIP(hipStreamWaitEvent(s->stream, s->pev[k][9], 0)); GM_HIP(hipStreamWaitEvent(s->stream_c, s->pev[k][9], 0)); }
+    int rc = queue_inputs(k, q_base, n); if (!rc) rc = pipeline_front(s, k, n, read_len); if (rc) return rc;
+    fr_n[k] = n; q_base += n; q_idx++;
+    return GM_OK;
+  }
+  // The back of the sub-batch on set k.  go_ahead: the front of the sub-batch after next is queued onto this set in front of the wait for the result copies -- only when
+  // the capacities are settled (a re-allocation frees the set's buffers), i.e. not for the first sub-batches
+  int back(int k, HostSlot& H, int n, bool have_next, bool go_ahead, float* lookup_ms) {
+    BackStages B{s, k, H, n, read_len, stats};
+    int rc = B.through_copy_out(have_next); if (!rc && go_ahead) rc = queue_front(true);
+    return rc ? rc : B.finish_back(lookup_ms);
+  }
+  // capacities of set `cur` grew: same for the other set, then again from the front of sub-batch idx (its first read: base)
+  int redo(int cur, int base, int idx) {
+    GM_HIP(hipStreamSynchronize(s->stream));
+    if (overlap) { const int rc = match_sets(cur); if (rc) return rc; }
+    q_base = base; q_idx = idx;
+    return GM_OK;
+  }
+  void finalize(ReadJob* J) {
     auto t0 = std::chrono::steady_clock::now();
     const int n = J->n; const int chunk = std::max(256, std::min(4096, n / (2 * nthreads)));   // small sub-batches (the ramp) still use every thread
     const int nchunks = (n + chunk - 1) / chunk;
     J->outs.assign(nchunks, std::string()); J->cm.assign(nchunks, 0); J->cr.assign(nchunks, 0);
     std::atomic<int> next(0);
-    Finalizer F{s, read_len, read_words, J->hreads, names ? nptr.data() + J->base : nullptr, names ? nlen.data() + J->base : nullptr, (long)J->base};
-    if (s->P.colour_space) { F.initbp = initbp_host + J->base; F.ops_half = ops_stride / 2; F.csk = cs_post_consts(s); if (J->hs->post_on) { F.res_base = J->hs->res; F.post_base = J->hs->post; if (J->hs->post_bq_on) F.bq_base = J->hs->post_bq; } }
-    F.redo_ctr = &post_redo;
-    if (const char* e = gm_tune("GM_POST_GUARD_TOL")) F.guard_tol = atof(e);          // (tests: a huge tolerance sends every result through the redo path)
+    Finalizer F{s, read_len, read_words, J->hreads, named ? nptr.data() + J->base : nullptr, named ? nlen.data() + J->base : nullptr, (long)J->base};
+    if (s->P.colour_space) { F.initbp = initbp + J->base; F.ops_half = ops_stride / 2; F.csk = cs_post_consts(s); if (J->hs->post_on) { F.res_base = J->hs->res; F.post_base = J->hs->post; if (J->hs->post_bq_on) F.bq_base = J->hs->post_bq; } }
+    F.redo_ctr = &post_redo; if (guard_tol) F.guard_tol = atof(guard_tol);
     if (quals) { F.qual_ptr = qptr.data() + J->base; F.qual_delta = qual_delta; }
     if (seq_text) F.seq_ptr = sptr.data() + J->base;
     if (s->P.output_format || s->P.extra_sam_fields) F.hgen = s->h_genome.data();
@@ -1763,170 +1843,87 @@ static int map_impl(gm_session* s, int n_reads, int read_len, const uint32_t* re
           const size_t before = o.size();
           int k = F.finalize_read(rd, cnt ? &J->hs->res[off] : nullptr, J->hs->ops, ops_stride, (int)cnt, o, fh, p2);
           if (per_read_bytes) per_read_bytes[J->base + rd] = (uint32_t)(o.size() - before);
-          if (!p2.empty()) J->cm[c]++;
-          J->cr[c] += k;
+          if (!p2.empty()) J->cm[c]++;  J->cr[c] += k;
           if (!emit_sam) o.clear();
         }
       }
     };
     gm_run_on_threads(nthreads, worker);
     J->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (emit_sam) {
-      size_t sz = 0; for (auto& o : J->outs) sz += o.size();
-      std::unique_lock<std::mutex> lk(ob.m);
-      ob.cv.wait(lk, [&] { return ob.turn == J->idx; });
-      if (!ob.failed && ob.len + sz + 1 > ob.cap) {
-        // first guess: this job's bytes per read for all reads, then geometric growth (large blocks move by remapping)
-        size_t want = std::max(ob.len + sz + 1, ob.cap + ob.cap / 2);
-        if (!ob.cap) want = std::max(want, (size_t)((double)sz / std::max(1, n) * 1.02 * n_reads) + 4096);
-        // the buffer of the last call, if it was given back and is about large enough: the first guess is an estimate (+- 1 % from one call to the next), a parked buffer just
-        // below it would be thrown away for a fresh one (300 MB of page faults, ~25 ms a call on the calling thread's path), and a buffer that turns out short grows below anyway
-        size_t ccap = 0; char* np = ob.p ? nullptr : outcache_take(std::max(ob.len + sz + 1, want - want / 8), &ccap);
-        if (np) want = ccap; else { if (!ob.p) want += want / 16; np = (char*)realloc(ob.p, want); }
-        if (!np) ob.failed = true; else { ob.p = np; ob.cap = want; }
-      }
-      if (!ob.failed) {
-        char* dst = ob.p + ob.len;
-        std::vector<size_t> off(J->outs.size()); size_t a = 0; for (size_t c = 0; c < J->outs.size(); c++) { off[c] = a; a += J->outs[c].size(); }
-        std::atomic<size_t> nextc(0);
-        auto copier = [&]() { for (;;) { const size_t c = nextc.fetch_add(1); if (c >= J->outs.size()) break; memcpy(dst + off[c], J->outs[c].data(), J->outs[c].size()); gm_text_pool().give(std::move(J->outs[c])); J->outs[c] = std::string(); } };
-        gm_run_on_threads(std::min(nthreads, 4), copier);
-        ob.len += sz;
-      }
-      ob.turn = J->idx + 1;
-      lk.unlock(); ob.cv.notify_all();
-    }
-    for (auto& o : J->outs) gm_text_pool().give(std::move(o));          // (what the copy above did not hand back already)
-  };
-  size_t joined = 0;
-  // Two buffer sets: the front of sub-batch i + 1 (stream A) is queued before the host turns to the back of sub-batch i (stream B),
-  // so K1 of the next sub-batch and pass 1 / pass 2 of this one share the CUs (see pipeline_front).  GM_OVERLAP=0: one set, in order.
-  bool overlap = n_reads > D.eff_batch;
-  if (const char* e = getenv("GM_OVERLAP")) overlap = overlap && atoi(e) != 0;
-  auto same_caps = [&](const DevSet& a, const DevSet& b) { return a.cur_len == b.cur_len && a.scap == b.scap && a.scap2 == b.scap2 && a.hcap == b.hcap &&
-                                                                  a.rcap_per_read == b.rcap_per_read && a.eff_batch == b.eff_batch && b.d_pmin == nullptr; };
-  auto match_sets = [&](int from) -> int {                       // give the other set the capacities of set `from`
-    DevSet& a = s->set[from]; DevSet& b = s->set[from ^ 1];
-    if (same_caps(a, b)) return GM_OK;
-    b.scap = a.scap; b.scap2 = a.scap2; b.hcap = a.hcap; b.rcap_per_read = a.rcap_per_read;
-    return alloc_buffers(s, b, read_len);
-  };
-  if (overlap) { int rc = match_sets(0); if (rc) return rc; if (s->set[1].eff_batch != D.eff_batch) overlap = false; }
-  auto join_all = [&]() { for (auto& j : jobs) if (j->th.joinable()) j->th.join(); };
-  // copies of one sub-batch into set k; host memory goes through stream C so that the call never waits behind queued kernels
-  auto queue_inputs = [&](int k, int base, int n) -> int {
-    DevSet& S = s->set[k];
-    if (!reads_host) {
-      GM_HIP(hipMemcpyAsync(S.d_reads, (const uint32_t*)reads_dev + (size_t)base * read_words, (size_t)n * read_words * 4, hipMemcpyDeviceToDevice, s->stream));
-      S.xover_on = false;
-      return GM_OK;
-    }
-    hipStream_t c = s->stream_c;
-    GM_HIP(hipMemcpyAsync(S.d_reads, reads_host + (size_t)base * read_words, (size_t)n * read_words * 4, hipMemcpyHostToDevice, c));
-    if (initbp_host) GM_HIP(hipMemcpyAsync(S.d_initbp, initbp_host + base, (size_t)n, hipMemcpyHostToDevice, c));
-    S.xover_on = false;
-    if (initbp_host && quals) {                              // per-position crossover scores from the QVs, ref: gmapper.c:532-544
-      xbuf.resize((size_t)n * read_len); qvbuf.resize((size_t)n * read_len);
-      xover_from_quals(s, qptr.data() + base, n, read_len, qual_delta, xbuf.data(), qvbuf.data());
-      GM_HIP(hipMemcpyAsync(S.d_xover, xbuf.data(), xbuf.size(), hipMemcpyHostToDevice, c));
-      GM_HIP(hipMemcpyAsync(S.d_qv, qvbuf.data(), qvbuf.size(), hipMemcpyHostToDevice, c));
-      GM_HIP(hipStreamSynchronize(c));                      // xbuf is reused by the next sub-batch
-      S.xover_on = true;
-    }
-    GM_HIP(hipEventRecord(s->pev[k][8], c));
-    GM_HIP(hipStreamWaitEvent(s->stream, s->pev[k][8], 0));
-    return GM_OK;
-  };
-  // Sub-batch sizes: while the two halves overlap, the first sub-batch's front and the last one's back (and its host work) have nothing to
-  // run beside, so the sizes ramp up from 8 192 at the start and halve towards the end (results do not depend on the split).
-  int ramp_min = 8192; if (const char* e = gm_tune("GM_RAMP_MIN")) ramp_min = std::max(64, atoi(e));
-  auto size_at = [&](int base, int eff) {
-    const int R = n_reads - base;
-    int n = std::min(eff, R);
-    if (overlap && ramp_min < eff) {
-      n = std::min(n, std::max(ramp_min, base + ramp_min));
-      n = std::min(n, std::max(ramp_min, R / 2));
-      if (R - n < ramp_min / 2) n = std::min(eff, R);
-    }
-    return n;
-  };
-  // GM_TIMELINE=1: where the calling thread's time goes, per sub-batch (stderr)
-  const bool timeline = getenv("GM_TIMELINE") != nullptr;
-  auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tl0 = now_ms();
-  if (timeline) fprintf(stderr, "[timeline] before the first sub-batch: %.2f ms waiting for the device's turn, %.2f ms set-up\n", tl_turn - tl_in, tl0 - tl_turn);
-  // Sub-batch i lives in set i & 1.  Its front is queued as early as the set allows: the first two at once, the front of i + 2 from inside the back of i -- behind pass 2
-  // and the copy of the counters, in front of the wait for the result copies (pipeline_back's after_pass2; the device orders it behind event pev[.][9]).  Short fronts
-  // (the bucket kernel on a small genome: 6 ms a sub-batch) then follow each other without the gap of a host round trip.
-  int q_base = 0, q_idx = 0;                                  // next sub-batch whose front is not queued yet: its first read, its number
-  int fr_n[2] = {0, 0};                                       // reads of the sub-batch whose front is queued on set k
-  auto queue_front = [&](bool behind_back) -> int {           // queues the front of sub-batch q_idx, if there is one
-    if (q_base >= n_reads) return GM_OK;
-    const int k = overlap ? (q_idx & 1) : 0;
-    const int n = size_at(q_base, s->set[k].eff_batch);
-    if (behind_back) { GM_HIP(hipStreamWaitEvent(s->stream, s->pev[k][9], 0)); GM_HIP(hipStreamWaitEvent(s->stream_c, s->pev[k][9], 0)); }
-    int rc = queue_inputs(k, q_base, n); if (!rc) rc = pipeline_front(s, k, n, read_len);
-    if (rc) return rc;
-    fr_n[k] = n; q_base += n; q_idx++;
-    return GM_OK;
-  };
-  const std::function<int()> ahead = [&]() -> int { return queue_front(true); };
-  int base = 0, idx = 0;
-  while (base < n_reads) {
-    const int cur = overlap ? (idx & 1) : 0;
-    int rc = GM_OK; float lk = 0;
-    const double tl_a = now_ms();
-    while (!rc && q_idx <= idx + (overlap ? 1 : 0) && q_base < n_reads) rc = queue_front(false);      // (the start of the call, and after a re-allocation)
-    const int n = fr_n[cur];
-    const bool have_next = q_idx > idx + 1;
-    HostSlot& HS = s->slot[jobs.size() % 3];
-    HS.want_reads = reads_host == nullptr;
-    const double tl_b = now_ms();
-    // (the front of i + 2 from inside this back only when the capacities are settled -- a re-allocation frees the set's buffers -- i.e. not for the first sub-batches)
-    const bool go_ahead = overlap && idx >= 2;
-    if (!rc) rc = pipeline_back(s, cur, HS, n, read_len, stats, &lk, have_next, go_ahead ? &ahead : nullptr);
-    const double tl_c = now_ms();
-    if (rc == 1) {                                            // capacities of set `cur` grew: same for the other set, then again from the front of this sub-batch
-      GM_HIP(hipStreamSynchronize(s->stream));
-      if (overlap) { rc = match_sets(cur); if (rc) { join_all(); return rc; } }
-      q_base = base; q_idx = idx;
-      continue;
-    }
-    if (rc) { (void)hipStreamSynchronize(s->stream); (void)hipStreamSynchronize(s->stream_b); join_all(); return rc; }
-    s->last_lookup_ms += lk; s->last_lookup_launches++;
-    std::unique_ptr<Job> J(new Job());
-    J->base = base; J->n = n; J->idx = (int)jobs.size();
-    J->hs = &HS;
-    J->hreads = reads_host ? reads_host + (size_t)base * read_words : HS.reads;
-    // at most two host jobs outstanding
-    const double tl_d = now_ms();
+    if (emit_sam) out.append(J->idx, J->outs, (size_t)n, std::min(nthreads, 4), gm_run_on_threads, [J](size_t c) { gm_text_pool().give(std::move(J->outs[c])); J->outs[c] = std::string(); });
+  }
+  // a job thread's body: no exception leaves it, and on every path the output turn passes to the next job
+  void run_job(ReadJob* J) {
+    try { finalize(J); } catch (...) { J->failed = true; if (emit_sam) out.fail(J->idx); }
+    for (auto& o : J->outs) gm_text_pool().give(std::move(o));          // (what the copy did not hand back already)
+  }
+  // the host job of the sub-batch in slot H: at most two outstanding
+  void start_job(HostSlot& H, int base, int n) {
+    std::unique_ptr<ReadJob> J(new ReadJob());
+    J->base = base; J->n = n; J->idx = (int)jobs.size(); J->hs = &H; J->hreads = reads_host ? reads_host + (size_t)base * read_words : H.reads;
+    const double t0 = gm_now_ms();
     while (jobs.size() - joined >= 2) { jobs[joined]->th.join(); joined++; }
-    const double tl_e = now_ms();
-    Job* jp = J.get();
-    J->th = std::thread(run_job, jp);
+    const double t1 = gm_now_ms();
+    jobs.reserve(jobs.size() + 1);                             // (nothing throws between the thread's start and its owner's place in jobs)
+    J->th = std::thread([this, jp = J.get()]() { run_job(jp); });
     jobs.push_back(std::move(J));
-    if (timeline) fprintf(stderr, "[timeline] t %8.2f  n %7d  fronts %6.2f  back %6.2f  join-wait %6.2f  spawn %5.2f  (K1 %.2f ms, %u read-strands through the heavy tier)\n",
-                          tl_a - tl0, n, tl_b - tl_a, tl_c - tl_b, tl_e - tl_d, now_ms() - tl_e, lk, s->h_pin[cur]);
-    base += n; idx++;
+    tl_join = t1 - t0; tl_spawn = gm_now_ms() - t1;
   }
-  const double tl_f = now_ms();
-  for (auto& j : jobs) if (j->th.joinable()) j->th.join();
-  if (timeline) { fprintf(stderr, "[timeline] t %8.2f  final join %6.2f; host jobs:", tl_f - tl0, now_ms() - tl_f); for (auto& j : jobs) fprintf(stderr, " %.1f", j->ms); fprintf(stderr, "\n"); }
-  uint64_t matched = 0, records = 0;
-  for (auto& j : jobs) {
-    for (size_t c = 0; c < j->cm.size(); c++) { matched += j->cm[c]; records += j->cr[c]; }
-    if (stats) stats->ms_host += j->ms;
+  // join, totals, statistics, the text to the caller
+  int finish(double tl0, char** sam, size_t* sam_len) {
+    const double tl_f = gm_now_ms();
+    bool job_failed = false; uint64_t matched = 0, records = 0;
+    for (auto& j : jobs) if (j->th.joinable()) j->th.join();
+    if (timeline) { fprintf(stderr, "[timeline] t %8.2f  final join %6.2f; host jobs:", tl_f - tl0, gm_now_ms() - tl_f); for (auto& j : jobs) fprintf(stderr, " %.1f", j->ms); fprintf(stderr, "\n"); }
+    for (auto& j : jobs) {
+      for (size_t c = 0; c < j->cm.size(); c++) { matched += j->cm[c]; records += j->cr[c]; }
+      if (stats) stats->ms_host += j->ms;
+      job_failed = job_failed || j->failed;
+    }
+    if (job_failed) { gm_set_error("gm_map_reads: out of memory in the output stage"); return GM_E_NOMEM; }
+    if (stats) { stats->reads = n_reads; stats->reads_matched = matched; stats->sam_records = records; stats->post_sw_host_redo = post_redo.load(); }
+    size_t len = 0;
+    if (sam) { *sam = emit_sam ? out.hand_over(&len) : nullptr; if (emit_sam && !*sam) return GM_E_NOMEM; }
+    if (sam_len) *sam_len = len;
+    return GM_OK;
   }
-  if (stats) { stats->reads = n_reads; stats->reads_matched = matched; stats->sam_records = records; stats->post_sw_host_redo = post_redo.load(); }
-  if (emit_sam && sam) {
-    if (ob.failed) return GM_E_NOMEM;
-    char* r = ob.p;                                            // (not shrunk: gm_free parks a large buffer for the next call)
-    if (!r || ob.cap < ob.len + 1) { r = (char*)realloc(ob.p, ob.len + 1); if (!r) return GM_E_NOMEM; ob.cap = ob.len + 1; }
-    ob.p = nullptr;
-    outcache_track(r, ob.cap);
-    r[ob.len] = 0; *sam = r; if (sam_len) *sam_len = ob.len;
-  } else { if (sam) *sam = nullptr; if (sam_len) *sam_len = 0; }
-  return GM_OK;
+};
+}  // namespace
+
+// Sub-batches are pipelined: while the GPU works on sub-batch i+1, host threads finish sub-batch i (pass-2 selection, MAPQ, SAM text).  Output stays in input order.
+static int map_impl(gm_session* s, int n_reads, int read_len, const uint32_t* reads_host, const void* reads_dev, const char* names, int emit_sam, char** sam, size_t* sam_len,
+                    gm_map_stats_t* stats, const uint8_t* initbp_host = nullptr, const char* quals = nullptr, int qual_delta = 33, const char* seq_text = nullptr, uint32_t* per_read_bytes = nullptr) {
+  if (int rc = ReadCall::check_args(s, n_reads, read_len, initbp_host)) return rc;
+  const double tl_in = gm_now_ms();
+  GmDevTurn dev_turn(s);
+  const double tl_turn = gm_now_ms();
+  try {
+    ReadRun R((size_t)n_reads);                                // (inside the try block: its job threads are joined before an exception is answered)
+    int rc = R.init(s, n_reads, read_len, reads_host, reads_dev, names, emit_sam, stats, initbp_host, quals, qual_delta, seq_text, per_read_bytes); if (rc) return rc;
+    const double tl0 = gm_now_ms();
+    if (R.timeline) fprintf(stderr, "[timeline] before the first sub-batch: %.2f ms waiting for the device's turn, %.2f ms set-up\n", tl_turn - tl_in, tl0 - tl_turn);
+    int base = 0, idx = 0;
+    while (base < n_reads) {
+      const int cur = R.overlap ? (idx & 1) : 0; float lk = 0;
+      const double tl_a = gm_now_ms();
+      while (!rc && R.q_idx <= idx + (R.overlap ? 1 : 0) && R.q_base < n_reads) rc = R.queue_front(false);      // (the start of the call, and after a re-allocation)
+      const int n = R.fr_n[cur];
+      const bool have_next = R.q_idx > idx + 1;
+      HostSlot& HS = s->slot[R.jobs.size() % 3];
+      HS.want_reads = reads_host == nullptr;
+      const double tl_b = gm_now_ms();
+      if (!rc) rc = R.back(cur, HS, n, have_next, R.overlap && idx >= 2, &lk);
+      const double tl_c = gm_now_ms();
+      if (rc == GM_REDO) { rc = R.redo(cur, base, idx); if (rc) return rc; continue; }
+      if (rc) { (void)hipStreamSynchronize(s->stream); (void)hipStreamSynchronize(s->stream_b); return rc; }
+      s->last_lookup_ms += lk; s->last_lookup_launches++;
+      R.start_job(HS, base, n);
+      if (R.timeline) fprintf(stderr, "[timeline] t %8.2f  n %7d  fronts %6.2f  back %6.2f  join-wait %6.2f  spawn %5.2f  (K1 %.2f ms, %u read-strands through the heavy tier)\n",
+                              tl_a - tl0, n, tl_b - tl_a, tl_c - tl_b, R.tl_join, R.tl_spawn, lk, s->h_pin[cur]);
+      base += n; idx++;
+    }
+    return R.finish(tl0, sam, sam_len);
+  } catch (const std::exception& e) { gm_set_error("gm_map_reads: %s", e.what()); return GM_E_NOMEM; }
 }
 
 extern "C" int gm_map_reads(gm_session_t* s, int n_reads, int read_len, const uint32_t* reads_packed, const char* names,
@@ -2033,16 +2030,15 @@ static int debug_tophits_impl(gm_session_t* s, int n_reads, int read_len, const 
   GmDevTurn dev_turn(s);     // (admitted like the mapping entries)
   GM_HIP(hipSetDevice(s->ix->device));
   DevSet& D = s->set[0];
-  if (D.cur_len != read_len || (D.caps_pair_mode != 0 && D.caps_pair_mode != 4)) { choose_caps(s, D, read_len); D.caps_pair_mode = 0; int rc = alloc_buffers(s, D, read_len); if (rc) return rc; }
-  if (n_reads > D.eff_batch) { gm_set_error("gm_debug_tophits: at most %d reads per call", D.eff_batch); return GM_E_ARG; }
+  if (int rc = prepare_unpaired_set(s, read_len)) return rc;
   const int read_words = (read_len + 7) / 8;
   float lk; int rc;
   do {
     if (n_reads > D.eff_batch) { gm_set_error("gm_debug_tophits: at most %d reads per call", D.eff_batch); return GM_E_ARG; }
     GM_HIP(hipMemcpyAsync(D.d_reads, reads_packed, (size_t)n_reads * read_words * 4, hipMemcpyHostToDevice, s->stream));
     if (initbp) GM_HIP(hipMemcpyAsync(D.d_initbp, initbp, (size_t)n_reads, hipMemcpyHostToDevice, s->stream));
-    rc = run_device_pipeline(s, D, s->slot[0], n_reads, read_len, nullptr, &lk);
-  } while (rc == 1);
+    rc = run_device_pipeline(s, s->slot[0], n_reads, read_len, &lk);
+  } while (rc == GM_REDO);
   if (rc) return rc;
   std::vector<int32_t> sel((size_t)n_reads * GM_SEL_MAX); std::vector<GmHit> hits((size_t)n_reads * 2 * D.hcap);
   GM_HIP(hipMemcpy(sel.data(), D.d_sel, sel.size() * 4, hipMemcpyDeviceToHost));

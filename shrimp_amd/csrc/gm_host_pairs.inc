@@ -433,9 +433,7 @@ struct PairCall {
     sc_half = s->sc;                                                                    // per-mate threshold of the paired pass 2, ref: gmapper.c:2677
     if (s->P.sw_full_threshold < 0) { sc_half.full_thr_frac = -1.0; sc_half.full_abs = (int)(-(s->P.sw_full_threshold * 0.5)); }
     else sc_half.full_thr_frac = (s->P.sw_full_threshold * 0.5) / 100.0;
-    const int c9[9] = {s->P.match_score, s->P.mismatch_score, s->P.crossover_score, -s->P.a_gap_open_score, -s->P.a_gap_extend_score,
-                       -s->P.b_gap_open_score, -s->P.b_gap_extend_score, s->P.anchor_width, s->P.indel_taboo_len};   // sw_full_cs_setup's arguments (ref: gmapper.c:2944-2947)
-    memcpy(cs9, c9, sizeof cs9);
+    cs_setup_args(s->P, cs9);
     timing = gm_tune("GM_TIMING") != nullptr;
     return GM_OK;
   }
@@ -570,7 +568,6 @@ static void pair_output(const PairCall& c, PairOut& b, OutJob& J) {
   });
   J.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
-static const int GM_REDO = 1;     // a stage's answer besides GM_OK and the error codes: the sub-batch is run again from its front (as pipeline_back's 1)
 // what the paired pass hands from stage to stage on the calling thread
 struct PairSel { uint32_t n_work[2] = {0, 0}; std::vector<uint32_t> cntP[2], plist, pcnt; std::vector<std::vector<uint32_t>> saved_chunks[2]; };
 // The call's state that changes from sub-batch to sub-batch, and the stages of a sub-batch in the order map_pairs_impl calls them.  Each stage queues its HIP calls on
@@ -587,7 +584,6 @@ struct PairRun : PairCall {
   int cur = 0; DevSet* S[2] = {nullptr, nullptr}; unsigned long long* dst = nullptr;      // the buffer pair of the sub-batch in hand, its counters
   std::chrono::steady_clock::time_point tw;
   std::unique_ptr<OutJob> pending; // (last: its thread reads the PairCall part, and is joined before anything here goes away)
-  void fold() { for (int k = 0; k < GS_N; k++) { hs[k] = 0; for (int t = 0; t < GS_STRIPES; t++) hs[k] += hraw[(size_t)t * GS_STRIDE + k]; } }
   int lap(const char* what) { if (timing) { GM_HIP(hipStreamSynchronize(q)); auto n2 = std::chrono::steady_clock::now(); fprintf(stderr, "  pairs %-18s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(n2 - tw).count()); tw = n2; } return 0; }
   // stage times of the back part (gm_map_stats_t, as the unpaired path fills them): events on the back stream, read behind the synchronisation points that exist anyway
   int stage_ms(int e0, int e1, double gm_map_stats_t::* field) { float ms = 0; GM_HIP(hipEventElapsedTime(&ms, s->ev[e0], s->ev[e1])); if (stats) stats->*field += ms; return GM_OK; }
@@ -777,7 +773,7 @@ struct PairRun : PairCall {
     GM_HIP(hipEventRecord(s->ev[2], q));
     GM_HIP(hipMemcpyAsync(hraw.data(), dst, hraw.size() * 8, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
-    fold();
+    fold_stats(hraw.data(), hs);
     rc = stage_ms(0, 1, &gm_map_stats_t::ms_pass1); if (rc) return rc;        // (pair_up + the mates' own pass 1)
     rc = stage_ms(1, 2, &gm_map_stats_t::ms_select); if (rc) return rc;
     if (hs[GS_OVERFLOW_SURV]) { gm_set_error("heavy list overflow"); return GM_E_OVERFLOW; }
@@ -891,7 +887,7 @@ struct PairRun : PairCall {
   int collect_stats() {
     GM_HIP(hipMemcpyAsync(hraw.data(), dst, hraw.size() * 8, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
-    fold();
+    fold_stats(hraw.data(), hs);
     if (O.half_paired) { int rc = stage_ms(0, 1, &gm_map_stats_t::ms_pass2); if (rc) return rc; rc = stage_ms(1, 2, &gm_map_stats_t::ms_pass2); if (rc) return rc; }      // the rescue's pass 2
     if (stats) { add_device_stats(stats, hs); stats->mp_unfiltered += hs[GS_MP_UNFILTERED]; }
     lap("rescue p1+sel+p2");
@@ -959,10 +955,10 @@ static int map_pairs_impl(gm_session* s, int n_pairs, int len1, const uint32_t* 
   if (stats) { stats->reads = 2ull * (uint64_t)n_pairs; stats->reads_matched = R.matched; stats->sam_records = R.records; }
   size_t total = 0; for (auto& p : R.pieces_all) total += p.size();
   if (sam) {
-    size_t cap = 0; char* r = outcache_take(total + 1, &cap);      // the text buffer of the last call, if it was given back (gm_free parks large ones)
+    size_t cap = 0; char* r = g_outcache.take(total + 1, &cap);      // the text buffer of the last call, if it was given back (gm_free parks large ones)
     if (!r) { cap = total + 1 + total / 16; r = (char*)malloc(cap); }      // (some room: the next call's text is a little longer half of the time, and a parked buffer that is too small is a fresh one's page faults)
     if (!r) return GM_E_NOMEM;
-    outcache_track(r, cap);
+    g_outcache.track(r, cap);
     size_t o = 0; for (auto& p : R.pieces_all) { memcpy(r + o, p.data(), p.size()); o += p.size(); }
     r[total] = 0; *sam = r; if (sam_len) *sam_len = total;
   }

@@ -1,6 +1,6 @@
 // gm_host_windows.inc -- gm_read_windows: the front of the pipeline (K1, K1b, K2) as a public seam; part of gm_host.hip.
 //
-// Per sub-batch: the reads go up, pipeline_front runs on set 0, the heavy tier follows where K1 listed read-strands for it (the first lines of pipeline_back), the stage
+// Per sub-batch: the reads go up, pipeline_front runs on set 0, the heavy tier follows where K1 listed read-strands for it (as BackStages::wait_front does), the stage
 // counters are read BEFORE anything looks at d_hits (a window list that overflowed grows hcap x4 and the sub-batch is redone from the upload), and only then the counts are
 // scanned and the windows exported (gm_windows.hip).  What crosses the bus: the counters, the scan's total (8 bytes), the 2 n + 1 offsets and the tight records --
 // nothing is sized by hcap.
@@ -23,7 +23,7 @@ extern "C" int gm_read_windows(gm_session_t* s, int n_reads, int read_len, const
   GmDevTurn dev_turn(s);     // (admitted like the mapping entries)
   GM_HIP(hipSetDevice(s->ix->device));
   DevSet& D = s->set[0];
-  if (D.cur_len != read_len || (D.caps_pair_mode != 0 && D.caps_pair_mode != 4)) { choose_caps(s, D, read_len); D.caps_pair_mode = 0; int rc = alloc_buffers(s, D, read_len); if (rc) return rc; }
+  if (int rc = prepare_unpaired_set(s, read_len)) return rc;
   const int read_words = (read_len + 7) / 8;
   const int W = window_len_of(s->P, read_len);
   hipStream_t q = s->stream;
@@ -48,9 +48,9 @@ extern "C" int gm_read_windows(gm_session_t* s, int n_reads, int read_len, const
     unsigned long long hs[GS_N];
     GM_HIP(hipMemcpyAsync(hraw.data(), d_stats, hraw.size() * 8, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
-    for (int c = 0; c < GS_N; c++) { hs[c] = 0; for (int t = 0; t < GS_STRIPES; t++) hs[c] += hraw[(size_t)t * GS_STRIDE + c]; }
+    fold_stats(hraw.data(), hs);
     if (hs[GS_OVERFLOW_SURV]) { gm_set_error("heavy list overflow"); return GM_E_OVERFLOW; }
-    if (hs[GS_OVERFLOW_HITS]) {      // as pipeline_back: a larger row, new buffers, the sub-batch again from the upload (fewer reads of it if the sub-batch size shrank)
+    if (hs[GS_OVERFLOW_HITS]) {      // as BackStages::grow: a larger row, new buffers, the sub-batch again from the upload (fewer reads of it if the sub-batch size shrank)
       if (D.hcap >= 32768) { gm_set_error("window list overflow at capacity %d", D.hcap); return GM_E_OVERFLOW; }
       D.hcap *= 4;
       if (stats) stats->retries++;
