@@ -45,12 +45,12 @@ typedef __attribute__((address_space(3))) uint16_t k5_lds_u16;
 #ifndef K5_Q
 #define K5_Q 4            // list chunks in flight per wave (r03 sweep, ms per 262 144 reads: 1: 87.3, 2: 71.0, 3: 68.6, 4: 65.2, 5: see DESIGN, 6: 69.9, 10: 74.3)
 #endif
-enum { C_NCAND = 0, C_OVERFLOW, C_NMEMB, C_NKEEP, C_NSTRIP, C_NEDGE, C_NLISTS /* two words: read-strands alternate */, C_SINK = 8, C_NRAW = 9, C_NDEFER = 10, C_NCAND0 = 11 /* rounds: the candidates of part 0 */, C_SPILL = 12 /* K5_MAX_ROUNDS - 1 words */, C_WORDS = 16 };
+enum { C_NCAND = 0, C_OVERFLOW, C_NMEMB, C_NKEEP, C_WLISTED /* tuning builds: items of the waves' lists */, C_NEDGE, C_NLISTS /* two words: read-strands alternate */, C_SINK = 8, C_NRAW = 9, C_WSPOT = 10 /* tuning builds: items taken on the spot */, C_NCAND0 = 11 /* rounds: the candidates of part 0 */, C_SPILL = 12 /* K5_MAX_ROUNDS - 1 words */, C_WORDS = 16 };
 #define K5_MAX_ROUNDS 4
 
 // Diagnostic build (-DK5_STAMPS): thread 0 of every workgroup adds the cycles between the phase boundaries of each read-strand to k5_stamps[]
 // (0-5: setup, pass A, pass B, region table, rules + output, clears; 6, 7: candidates, fallbacks; 8-11: parts of set-up / the exact stages, taken out of
-// the phase they sit in); gm_debug_k5_stamps() reads and resets all 16.  No stamp executes in the normal build.
+// the phase they sit in -- 10, a wave's own step (a) of stage 1, is the view of thread 0's wave: no barrier stands behind it); gm_debug_k5_stamps() reads and resets all 16.  No stamp executes in the normal build.
 #ifdef K5_STAMPS
 __device__ unsigned long long k5_stamps[16];
 #define K5_STAMP(i) do { if (tid == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); atomicAdd(&k5_stamps[i], t_ - t_prev); t_prev = t_; } } while (0)
@@ -74,6 +74,15 @@ extern "C" int gm_debug_k5_paths(unsigned long long* out) {
   if (hipMemcpyToSymbol(HIP_SYMBOL(k5_paths), z, sizeof z) != hipSuccess) return GM_E_NODEVICE;
   return GM_OK;
 }
+// The per-wave lists of exact stage 1: [0] items that went through a wave's list, [1] items taken on the spot because the list was full (GM_K5_WLIST caps a wave's list
+// below what fits, 0: no list at all), added by thread 0 once per read-strand.  gm_debug_k5_wave_lists() reads and resets the two.
+__device__ unsigned long long k5_wave_lists[2];
+extern "C" int gm_debug_k5_wave_lists(unsigned long long* out) {
+  unsigned long long z[2] = {0, 0};
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(k5_wave_lists), sizeof z) != hipSuccess) return GM_E_NODEVICE;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(k5_wave_lists), z, sizeof z) != hipSuccess) return GM_E_NODEVICE;
+  return GM_OK;
+}
 #endif
 
 struct K5Args {
@@ -82,6 +91,7 @@ struct K5Args {
   int cand_cap, hbits;      // candidate records and log2(slots of the region table), both inside the seen[] area
   int cand_limit;
   int xrec;                 // chunk records beyond one per list
+  int wlist;                // tuning builds: the most words a wave's list of exact stage 1 may take (GM_K5_WLIST; the release build takes what fits)
   int rounds; uint32_t round_regs;      // the exact stages run `rounds` times, each over `round_regs` regions of the genome (+ one region either side)
   uint2* spill; int spill_cap;          // rounds > 1: (rounds - 1) rows of spill_cap candidates (position, y / seed) per workgroup
   uint64_t* out; uint32_t* out_cnt; int out_cap; uint32_t* surv_cnt;
@@ -334,6 +344,8 @@ int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads
   a.fb_list = K->k5_fb; a.fb_cnt = fb_cnt_p; a.fb_cap = fb_cap;
   a.raw_out = prune ? d_raw : nullptr; a.raw_cap = raw_cap; a.surv_seg = d_surv_seg; a.n_slabs = ix.n_slabs; a.pl_list = K->k5_pl; a.pl_cnt = pl_cnt_p; a.pl_cap = fb_cap;
   a.spill = nullptr; a.spill_cap = cand_cap;
+  a.wlist = 0x7FFFFFFF;
+  if (const char* e = gm_tune("GM_K5_WLIST")) a.wlist = std::max(0, atoi(e));
   if (rounds > 1) {
     const size_t need = (size_t)grid * (size_t)(rounds - 1) * (size_t)cand_cap;
     if (need > K->k5_spill_n) {

@@ -38,6 +38,17 @@ K5_KERNEL_HEAD {
   uint32_t* rec = seen + (1u << lsw);
   const int RC = a.NL + a.xrec;                                  // records: one per chunk of at most 256 positions (a longer list takes several)
   uint32_t* srec = rec + 4 * RC;                                // strip list of a record's list: offset inside its seed's strip array, length (the seed is in the record's y word)
+  // The lists of exact stage 1 live in rec[] / srec[] (6 * RC words, dead since pass B), a segment per wave: wseg words, of which the wave uses wcap (see stage 1)
+  const uint32_t wseg = 6u * (uint32_t)RC / (uint32_t)nwv;
+  uint32_t* const wlist = rec + (uint32_t)wv * wseg;
+#ifdef GM_TUNING
+  const uint32_t wcap = min(wseg, (uint32_t)__builtin_amdgcn_readfirstlane(a.wlist));      // (GM_K5_WLIST: a shorter list, down to none)
+  // (a wave's items, listed and taken on the spot, go to two control words; thread 0 hands them on with the read-strand's other counts: gm_debug_k5_wave_lists)
+#define K5_WL_COUNT(listed, spot) do { if (lane == 0) { atomicAdd(&ctrl[C_WLISTED], (listed)); atomicAdd(&ctrl[C_WSPOT], (spot)); } } while (0)
+#else
+  const uint32_t wcap = wseg;
+#define K5_WL_COUNT(listed, spot) do { } while (0)
+#endif
   uint8_t* codes = (uint8_t*)(srec + 2 * RC);
   uint32_t* ctrl = (uint32_t*)(codes + 2 * ((a.read_len + 15) & ~15));           // two code buffers (this read-strand's and the next one's)
   const uint32_t smask4 = wmask << 2, tmask4 = tmask << 2, swb = 4u << ltw;
@@ -541,7 +552,7 @@ K5_KERNEL_HEAD {
           for (int k = 0; k < 6; k++) { const uint32_t i = i0 + (uint32_t)k * (uint32_t)nthr + (uint32_t)tid; if (i < nsp) { candp[i] = (uint32_t)v[k]; candy[i] = (uint16_t)(v[k] >> 32); } }
         }
         { uint4* h4 = (uint4*)htag; for (int w = tid; w < hclr_q; w += nthr) h4[w] = make_uint4(0, 0, 0, 0); }
-        if (tid == 0) { ctrl[C_NCAND] = ns_raw; ctrl[C_NSTRIP] = 0; ctrl[C_NEDGE] = 0; ctrl[C_NDEFER] = 0; }
+        if (tid == 0) { ctrl[C_NCAND] = ns_raw; ctrl[C_NEDGE] = 0; }
       }
       if (rd > 0) __syncthreads();          // (part 0: the barrier behind pass B / the dealing of the candidates)
       K5_STAMP(2);
@@ -554,12 +565,16 @@ K5_KERNEL_HEAD {
       // A wave pays the longest chain of LDS round trips among its lanes, so the rare cases are taken out of the main loops and worked off
       // densely afterwards: the overlap-strip marks here (2 % of the candidates, but some lane of most waves), the neighbour-region look-ups of
       // stage 2 below.  Their lists (region numbers, then candidate indexes) live in rec[] / srec[], dead since pass B.
-      uint32_t* const elist = rec; const uint32_t ecap = 6u * (uint32_t)RC;
+      uint32_t* const elist = rec; const uint32_t ecap = 6u * (uint32_t)RC;                 // (stage 2's list: the whole area, one list for the workgroup)
       // Stage 1 in two steps.  (a) every candidate tries the FIRST slot of its region's probe sequence, in straight-line code: one compare-and-swap, and when the slot holds the
       // region already, the flag update -- the same three LDS round trips for every lane.  Two thirds of the candidates are done with that (the table is a third full).
       // (b) the others -- another region sits in their first slot -- are listed and probed on from the second slot, densely, together with the strip marks: a probing loop
       // costs a wave the longest sequence among its lanes (five at this load), and it now pays that once per 64 LISTED candidates, not once per 64 candidates.
-      uint32_t* const dlist = elist + (uint32_t)RC; const uint32_t scap = (uint32_t)RC, dcap = ecap - scap;
+      // The lists are PER WAVE (wlist: this wave's wcap words of rec[] / srec[], its count a scalar): no counter in LDS, and no barrier between the two steps -- a wave
+      // works its own list off right behind its own iterations of (a), next to the waves still in (a).  Nothing orders the table's updates: a slot's tag never changes once
+      // set, a region's probe sequence is fixed, and the flags and min / max are OR / MAX (tests/test_k5_table_order.py runs the interleavings on a host model).
+      // A word of the list is a candidate index (below 2^16) or, with bit 31 set, the region a strip mark goes to.  An item beyond wcap is worked off on the spot by its
+      // own lane: a full list costs a wave one divergent chain, never the read-strand a trip through the fall-back kernels.
       auto settle = [&](const uint32_t i, const uint32_t h, const uint32_t off) {      // candidate i sits in slot h
         atomicMax(&hmin[h], 0x10000u - off); atomicMax(&hmax[h], off + 1u);
         candp[i] = (h << 16) | off;                              // slot and offset: stage 2 reads the region back from the tag (no second probe sequence)
@@ -573,6 +588,7 @@ K5_KERNEL_HEAD {
         } else ctrl[C_OVERFLOW] = 1u;
       };
       if (!fallback) {
+        uint32_t wn = 0;                                         // items of this wave so far (a scalar; it runs past wcap: those were taken on the spot)
         for (uint32_t i0 = 0; i0 < nc; i0 += nthr) {
           const uint32_t i = i0 + tid;
           const bool live = i < nc;
@@ -586,32 +602,27 @@ K5_KERNEL_HEAD {
             settle(i, h0, off);
           }
           const bool strip = hit && off < ovl && r > 0, later = live && !hit;      // the overlap strip also counts for the region before (ref: mapping.c:521-533)
-          const unsigned long long bs = __ballot(strip), bd = __ballot(later);
-          if (bs | bd) {
-            uint32_t sb = 0, db = 0;
-            if (lane == 0) { if (bs) sb = atomicAdd(&ctrl[C_NSTRIP], (uint32_t)__popcll(bs)); if (bd) db = atomicAdd(&ctrl[C_NDEFER], (uint32_t)__popcll(bd)); }
-            sb = __builtin_amdgcn_readfirstlane(sb); db = __builtin_amdgcn_readfirstlane(db);
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (strip) { const uint32_t j = sb + (uint32_t)__popcll(bs & below); if (j < scap) elist[j] = r - 1u; else ctrl[C_OVERFLOW] = 1u; }
-            if (later) { const uint32_t j = db + (uint32_t)__popcll(bd & below); if (j < dcap) dlist[j] = i; else probe_on(i); }      // (a full list: probed on the spot)
+          const unsigned long long bi = __ballot(strip | later);                  // (a lane has at most one item: a strip mark needs the hit)
+          if (bi) {
+            const uint32_t j = wn + (uint32_t)__popcll(bi & ((1ull << lane) - 1ull));
+            wn += (uint32_t)__popcll(bi);
+            if (strip | later) {
+              if (j < wcap) wlist[j] = later ? i : (0x80000000u | (r - 1u));
+              else if (later) probe_on(i);
+              else if (k5_insert(htag, hmask, hshift, r - 1u, false) == 0xFFFFFFFFu) ctrl[C_OVERFLOW] = 1u;
+            }
           }
         }
-      }
-      __syncthreads();
-      K5_STAMP(10);
-      if (!fallback) {
-        const uint32_t ns = min(ctrl[C_NSTRIP], scap), nd = min(ctrl[C_NDEFER], dcap);
-#ifdef K5_1B_TWO_LOOPS     // (diagnostic builds: the two lists one after the other, as before)
-        for (uint32_t j = tid; j < nd; j += nthr) probe_on(dlist[j]);
-        for (uint32_t j = tid; j < ns; j += nthr)
-          if (k5_insert(htag, hmask, hshift, elist[j], false) == 0xFFFFFFFFu) ctrl[C_OVERFLOW] = 1u;
-#else
-        // ONE index space, the strip marks behind the deferred candidates, and one probing loop for both kinds (a lane's kind is data: which flags it sets, where its
-        // sequence starts): the first threads no longer run a second probing loop behind their share of the first, the strip marks ride in the lanes behind the last deferred
-        // candidate.  The table's updates are single-shot atomics, their outcome does not depend on the order.
-        for (uint32_t j = tid; j < nd + ns; j += nthr) {
-          const bool own = j < nd;
-          const uint32_t v = *(own ? dlist + j : elist + (j - nd));      // candidate index / region number
+        K5_STAMP(10);
+        // (b) ONE probing loop for both kinds (a lane's kind is data: which flags it sets, where its sequence starts).  The words were stored by other lanes of this wave:
+        // a wave's LDS operations execute in order, so nothing but the compiler has to be told.
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t nw = min(wn, wcap);
+        K5_WL_COUNT(nw, wn - nw);
+        for (uint32_t j = lane; j < nw; j += GM_WAVE) {
+          const uint32_t w = wlist[j];
+          const bool own = (w >> 31) == 0u;
+          const uint32_t v = w & 0x7FFFFFFFu;                    // candidate index / region number
           const uint32_t p = candp[own ? v : 0u], r = own ? p >> rb : v, off = p & rmask;
           const uint32_t h = k5_insert(htag, hmask, hshift, r, own, own);
           if (h == 0xFFFFFFFFu) ctrl[C_OVERFLOW] = 1u;
@@ -620,9 +631,8 @@ K5_KERNEL_HEAD {
             if (off < ovl && r > 0 && k5_insert(htag, hmask, hshift, r - 1u, false) == 0xFFFFFFFFu) ctrl[C_OVERFLOW] = 1u;
           }
         }
-#endif
       }
-      __syncthreads();
+      __syncthreads();                                        // stage 2 needs every insert
       K5_STAMP(3);
       fallback = fallback || rec_over || ctrl[C_OVERFLOW] != 0u;
       // ================= exact stage 2: the reference's rule (ref: mapping.c:733-742), prune rules (gm_prune.hip), output =================
@@ -804,6 +814,7 @@ K5_KERNEL_HEAD {
 #endif
 #ifdef GM_TUNING
     if (tid == 0 && (fallback || prune_only)) atomicAdd(&k5_paths[fallback ? 1 : 2], 1ull);      // (the read-strands taken: once per workgroup, behind the loop)
+    if (tid == 0) { atomicAdd(&k5_wave_lists[0], (unsigned long long)ctrl[C_WLISTED]); atomicAdd(&k5_wave_lists[1], (unsigned long long)ctrl[C_WSPOT]); ctrl[C_WSPOT] = 0; }      // (C_WLISTED: zeroed below)
 #endif
     if (tid == 0) {
       if (fallback) {                                          // candidates beyond the LDS tiers: the slab-sweep kernel redoes this read-strand
@@ -828,7 +839,7 @@ K5_KERNEL_HEAD {
         }
       }
       for (int c = 0; c < C_NLISTS; c++) ctrl[c] = 0;
-      *cnl = 0; ctrl[C_NRAW] = 0; ctrl[C_NDEFER] = 0; if (MULTI) ctrl[C_NCAND0] = 0;
+      *cnl = 0; ctrl[C_NRAW] = 0; if (MULTI) ctrl[C_NCAND0] = 0;
       if (MULTI) for (int d = 0; d < K5_MAX_ROUNDS - 1; d++) ctrl[C_SPILL + d] = 0;
     }
     { uint4* t4 = (uint4*)smem; for (int w = tid; w < tab_q; w += nthr) t4[w] = make_uint4(0, 0, 0, 0); }
@@ -840,3 +851,4 @@ K5_KERNEL_HEAD {
   for (int d = GM_WAVE / 2; d > 0; d >>= 1) { my_lookups += __shfl_down(my_lookups, d); my_entries += __shfl_down(my_entries, d); }
   if (lane == 0) { GS_ADD(a.stats, GS_LOOKUPS, my_lookups); GS_ADD(a.stats, GS_ENTRIES, my_entries); }
 }
+#undef K5_WL_COUNT

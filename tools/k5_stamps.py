@@ -32,6 +32,10 @@ for nk in (os.environ.get("GM_STAMPS_NK_SWEEP", "").split(",") if os.environ.get
       names = ["setup(+clear wait)", "pass A", "pass B", "region table", "rules+output", "bookkeeping+clear"]
       tot = sum(v[:6]) or 1
       for nm, x in zip(names, v): print("%-20s %6.2f %%  %8.0f ticks per read-strand" % (nm, 100.0 * x / tot, x / (2.0 * n)))
-      for nm, x in zip(["  set-up: to the first barrier", "  set-up: k-mers ahead", "  region table: main loop", "  rules: main loop (2a)"], v[8:12]): print("%-32s %8.0f ticks per read-strand (not in the phase above)" % (nm, x / (2.0 * n)))
+      # (no barrier stands behind a wave's own step (a) of stage 1: that split is what thread 0's wave saw; 2a ends at a barrier.  The phases themselves -- stage 1 to its
+      # barrier = "region table: step (a)" + "region table", stage 2 to the final barrier = "rules: 2a" + "rules+output" -- are the workgroup's)
+      for nm, x in zip(["  set-up: to the first barrier", "  set-up: k-mers ahead", "  region table: step (a), one wave's view", "  rules: main loop (2a)"], v[8:12]): print("%-42s %8.0f ticks per read-strand (not in the phase above)" % (nm, x / (2.0 * n)))
+      print("%-42s %8.0f ticks per read-strand" % ("stage 1 to its barrier", (v[10] + v[3]) / (2.0 * n)))
+      print("%-42s %8.0f ticks per read-strand" % ("stage 2 to the final barrier", (v[11] + v[4]) / (2.0 * n)))
       print("candidates per read-strand %.1f, fallbacks %d of %d" % (v[6] / (2.0 * n), v[7], 2 * n))
       if v[12]: print("pass A, first of two runs (K5_ABL_A_TWICE: lists from HBM; the line 'pass A' above is then the second run, lists from the caches) %8.0f ticks per read-strand" % (v[12] / (2.0 * n)))
