@@ -680,7 +680,7 @@ int gm_read_windows(gm_session_t *s, int n_reads, int read_len, const uint32_t *
                     gm_read_window_t **wins, uint64_t *n_wins, uint64_t *off, gm_map_stats_t *stats);
 
 /* The two selections of a read batch, so that a chunk is a chain of batch calls on arrays with nothing per read on the CPU in between:
- *   gm_read_windows -> gm_sw_vector_batch_ix (-U: gm_sw_gapless_batch_ix) -> gm_select_pass1 -> gm_sw_full_ls_batch_ix (colour space: gm_sw_full_cs_batch_ix, then
+ *   gm_read_windows -> gm_score_windows (or, a read per window: gm_sw_vector_batch_ix; -U: gm_sw_gapless_batch_ix) -> gm_select_pass1[_f1] -> gm_sw_full_ls_batch_ix (colour space: gm_sw_full_cs_batch_ix, then
  *   gm_post_sw_batch_ix) -> gm_select_pass2 -> gm_sw_full_batch_text_ix.
  * Both take their rules from the session's gm_params_t, read neither the genome nor the reads, make a fixed number of device allocations, copies and launches whatever
  * n is, take their turn on the device like gm_read_windows and leave the session ready for any other call.  Unpaired sessions only (see gm_read_windows); the mapping
@@ -702,8 +702,11 @@ int gm_read_windows(gm_session_t *s, int n_reads, int read_len, const uint32_t *
  *   input order of pass 2 and of its stable sorts; hit_off: n_reads + 1 entries, the caller's.  A hit of strand 1 has been turned as reverse_hit turns it (gen_st = 1,
  *   g_off = contig_len - g_off - w_len, the anchor box through anchor_reverse); strand 0 keeps gen_st = 0: (cn, gen_st, g_off, w_len), the box and the read as given
  *   are what gm_sw_full_ls_batch_ix / gm_sw_full_cs_batch_ix take, nothing is left for the caller to turn.  win: the record's window in wins.
- *   NOT emulated: the f1 cache (hash_filter_calls).  The seam takes the scores it is given, so the result is the reference's under -Z; with the cache on the two differ
- *   only where two windows of one read-strand share a cache slot and differ in score.
+ *   NOT emulated here: the f1 call cache (hash_filter_calls, on by default).  This entry takes the scores it is given, so its result is the reference's under -Z.
+ *   The cache matters wherever two windows of one read-strand share a cache slot and differ in score, and that takes no hash collision: hash_genome_window (ref:
+ *   common/util.h:221-241) hashes base & 3, so S, Y, K and N fold onto A, C, G and T, and a window and its copy with such IUPAC letters (twins) ALWAYS share a slot
+ *   while they score differently -- a perfect read whose damaged copy comes first in list order takes the copy's score and can come out unmapped
+ *   (tests/golden/f1_twins_60bp: 49 of 300 reads).  gm_select_pass1_f1 and gm_read_hits below emulate the cache, as the mapping entries do.
  *   Refusals: num_tmp_outputs > 64: GM_E_RANGE (the mapping entries select at most 64 and say nothing; a seam must not); 2^31 windows or more: GM_E_RANGE.  Offsets
  *   that do not ascend from 0, off[2 n_reads] != n_wins, a window whose read / st contradicts its slot, cn outside the index, w_len < 1, a window that ends beyond
  *   its contig, read_len < 1: GM_E_ARG, before anything is uploaded.  n_reads <= 0: GM_OK, hit_off[0] = 0, *hits = NULL. */
@@ -720,6 +723,49 @@ typedef struct gm_pass1_hit {        /* 16 x 32 bits = 64 bytes, no padding */
 int gm_pass1_hit_size(void);         /* sizeof(gm_pass1_hit_t), for the Python mirror */
 int gm_select_pass1(gm_session_t *s, int n_reads, int read_len, const gm_read_window_t *wins, uint64_t n_wins, const uint64_t *off, const int *scores,
                     gm_pass1_hit_t **hits, uint64_t *n_hits, uint64_t *hit_off);
+
+/* Pass 1 as a seam: the scores pass 1 gives the windows, the selection with the f1 call cache, and both behind gm_read_windows' front in one call.
+ *
+ * gm_score_windows: scores[i] = what f1_run computes for window i in read_pass1_per_strand (ref: mapping.c:1297-1329) under the session's scores and `ungapped` flag,
+ * never cut short by the early stop; a window with matches < match_mode is scored like any other (the selection passes over it).
+ *   reads    n_reads, read_len, reads_packed, initbp as gm_read_windows takes them: the batch goes up once and the kernel fetches a window's read by wins[i].read; no
+ *            copy of a read per window is made on the host or the device, and nothing is turned by the caller.
+ *   wins, n_wins, off[2 n_reads + 1]   as gm_read_windows returned them, or the caller's own (checked as gm_select_pass1 checks them).
+ *   Letter space: (cn, g_off, w_len) on the forward contig against the read, for a strand-1 window against the read's reverse complement, made on the device (a read
+ *   with U and no T through the RNA complement table).  Colour space: the window turned onto the read's input strand (strand 1: contig_len - g_off - w_len on the
+ *   reverse-complement contig) against the read as given, with its primer letter.  `ungapped` sessions: sw_gapless over the whole contig on the diagonal through
+ *   g_idx = g_off + ax, r_idx = ay -- letter space: the box as the record holds it, the read turned; colour space: the hit and its box turned by reverse_hit /
+ *   anchor_reverse first.
+ *   slots (n_wins, or NULL): hash_genome_window(array, goff, w_len) % 1048576 of the array and offset f1_run is handed (ref: common/util.h:221-241, f1-wrapper.h:27,
+ *   106) -- letter space the forward letters, colour space the colour translation of the turned strand: the window's f1 cache slot.
+ *   Refusals, on the host before anything is uploaded: the read arguments as gm_read_windows (GM_E_ARG, GM_E_RANGE), the windows and offsets as gm_select_pass1
+ *   (GM_E_ARG, GM_E_RANGE); a window too long for the kernel's LDS beside these reads (48 KB: about 9 000 positions, 8 000 in colour space): GM_E_RANGE.  n_reads <= 0 or n_wins == 0: GM_OK.
+ *
+ * gm_select_pass1_f1: gm_select_pass1 with the cache rule of f1_run (ref: f1-wrapper.h:97-134) applied per read-strand (the tag advances once per read-strand,
+ * mapping.c:1268).  In list order, a window that gets past the matches check and the overlap check takes the score of the FIRST earlier window of its read-strand that
+ * was itself computed and has the same slot (one bypassed call), else it keeps its own score and is computed; a window passed over, skipped or bypassed is not
+ * computed.  pct, the threshold and score_max are the window's own; the last passing window advances on the TAKEN score; hits carry the taken score.
+ *   slots[n_wins]: gm_score_windows'.  slots == NULL: the call is gm_select_pass1, bit for bit.  bypassed (or NULL): the number of bypassed calls (f1_stats').
+ *   Everything else, the refusals included, as gm_select_pass1.
+ *
+ * gm_read_hits: gm_read_windows -> gm_score_windows -> gm_select_pass1_f1 in one call, byte-equal to the three on the same input (equal windows of a read-strand in no
+ * particular order, as gm_read_windows leaves them).  Per sub-batch the front of gm_read_windows runs unchanged (heavy tier, counter read, capacity growth), then the
+ * scan and scatter, the scoring on the reads and records that are on the device already, the selection -- with the cache rule when and only when the session's
+ * hash_filter_calls is set, so the hits are the reference's by default and its hits under -Z with hash_filter_calls = 0 -- and the emit.  Only the hits and hit_off
+ * come down; hit `win` indices and the offsets are global across sub-batches.
+ *   wins, n_wins, off, scores: all four NULL, or all four given: then the windows (gm_free), off[2 n_reads + 1] (the caller's) and the windows' OWN scores (gm_free;
+ *   before the cache rule) come down too.
+ *   stats (or NULL): as gm_read_windows, and vec_calls / vec_cells (every window is scored, none is bypassed on the device) and vec_bypassed (the cache rule's count).
+ *   Refusals: num_tmp_outputs > 64: GM_E_RANGE; the four optional outputs given in part: GM_E_ARG; all others as gm_read_windows. */
+int gm_score_windows(gm_session_t *s, int n_reads, int read_len, const uint32_t *reads_packed, const uint8_t *initbp,
+                     const gm_read_window_t *wins, uint64_t n_wins, const uint64_t *off,
+                     int *scores /* n_wins */, uint32_t *slots /* n_wins, or NULL */);
+int gm_select_pass1_f1(gm_session_t *s, int n_reads, int read_len, const gm_read_window_t *wins, uint64_t n_wins, const uint64_t *off,
+                       const int *scores, const uint32_t *slots, gm_pass1_hit_t **hits, uint64_t *n_hits, uint64_t *hit_off, uint64_t *bypassed /* or NULL */);
+int gm_read_hits(gm_session_t *s, int n_reads, int read_len, const uint32_t *reads_packed, const uint8_t *initbp,
+                 gm_pass1_hit_t **hits, uint64_t *n_hits, uint64_t *hit_off,
+                 gm_read_window_t **wins, uint64_t *n_wins, uint64_t *off, int **scores /* these four: all NULL, or all given */,
+                 gm_map_stats_t *stats);
 
 /* gm_select_pass2: read_pass2's selection and compute_unpaired_mqv (ref: mapping.c:1628-1750, read_remove_duplicate_hits :1552-1600, hit_run_post_sw :1609-1625,
  * output.c:777-793, 975-984) on the records of ONE full batch call over the hits of gm_select_pass1, in that order.

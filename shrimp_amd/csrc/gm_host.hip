@@ -2066,6 +2066,7 @@ extern "C" int gm_debug_tophits_cs(gm_session_t* s, int n_reads, int n_colours, 
 
 #include "gm_host_windows.inc"
 #include "gm_host_select.inc"
+#include "gm_host_pass1.inc"
 #include "gm_host_sam.inc"
 #include "gm_host_seams.inc"
 #include "gm_host_seams_ix.inc"

@@ -158,6 +158,22 @@ int gm_launch_sel_emit(const GmScoreDev& sc, int n_reads, int read_len, int K, c
 int gm_launch_sel_pass2(int n_reads, int num_outputs, int strata, int max_alignments, const unsigned long long* d_hit_off, const GmSel2Item* d_items,
                         int32_t* d_order, uint32_t* d_cnt, hipStream_t stream);
 
+// Pass 1 as a seam (gm_score_windows / gm_select_pass1_f1 / gm_read_hits).
+//   gm_launch_score_windows (gm_sw.hip): d_scores[i] = the score f1_run computes for window i of d_wins (never cut short), d_slots[i] (or null) = its f1 cache slot;
+//                        window i's read is row d_wins[i].read - read_base of d_reads (d_initbp likewise; ix.read_rna: those rows' RNA flags or null); max_w >= every
+//                        w_len; d_stats (or null): GS_VEC_CALLS / GS_VEC_CELLS are added to.  The host has checked the windows against the index and the batch.
+//   gm_launch_sel_pass1_f1 (gm_select.hip): gm_launch_sel_pass1 with the f1 call cache (ref: f1-wrapper.h:97-134) per read-strand: d_comp, n_wins words of 64 bits,
+//                        holds the (slot, score) pairs of the computed windows of the read-strand being walked; d_byp[r] = read r's bypassed calls.
+#define GM_SCORE_WIN_LDS_LIMIT (48 * 1024)      // LDS a wave of k_score_windows may take (the read, the window, colour space its first-colour row, the carry rows)
+#define GM_SCORE_WIN_CHUNK 1                    // consecutive windows a wave of k_score_windows takes at a time (it keeps the read while they share a read-strand); GM_SCORE_CHUNK in tuning builds
+size_t gm_score_windows_lds(int colour, int read_len, int max_w);
+int gm_launch_score_windows(const GmIndexDev& ix, const GmScoreDev& sc, unsigned long long n, const gm_read_window_t* d_wins, const uint32_t* d_reads, int read_len,
+                            int read_words, int read_base, const uint8_t* d_initbp, int max_w, int* d_scores, uint32_t* d_slots, unsigned long long* d_stats,
+                            hipStream_t stream);
+int gm_launch_sel_pass1_f1(const GmScoreDev& sc, int n_reads, int read_len, int K, int window_len, int overlap_abs, const gm_read_window_t* d_wins,
+                           const unsigned long long* d_off, const int* d_scores, const uint32_t* d_slots, unsigned long long* d_comp, int32_t* d_sel_id,
+                           int32_t* d_sel_score, uint32_t* d_sel_cnt, uint32_t* d_byp, hipStream_t stream);
+
 // K3 pass 1 (vector SW + overlap rule), one wave per read-strand
 int gm_launch_pass1(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                     int window_len, int window_overlap_abs, GmHit* d_hits, const uint16_t* d_perm, const uint32_t* d_hit_cnt, int hcap,

@@ -7,6 +7,7 @@
 //                 last passing window carried in scalars across steps.  What survives goes through the heap, which lane 0 keeps in LDS (insert + percolate-up with
 //                 a strict <, replace-min + percolate-down): typically a handful of windows a read.  Left behind: the heap's ARRAY order as window indices + the
 //                 scores after the rule, K slots a read.
+//   k_sel_pass1_f1: the same with the f1 call cache of the reference (gm_select_pass1_f1, gm_read_hits); a kernel of its own, k_sel_pass1 is what it was.
 //   k_sel_emit:   a wave a read, a lane a selected hit: the 64-byte record, strand 1 turned as reverse_hit / anchor_reverse turn it (mapping.c:254-263, anchors.h:30-34),
 //                 stored as four 16-byte stores at hit_off[read] + slot.
 //   k_sel_pass2:  a wave a read, a lane a pass-2 item (at most 64): the two duplicate-removal passes, the score sort, the cut, strata and max_alignments
@@ -95,6 +96,104 @@ __global__ __launch_bounds__(GM_WAVE) void k_sel_pass1(GmScoreDev sc, int n_read
   if (lane == 0) sel_cnt[rd] = (uint32_t)n;
 }
 
+// the ext-heap of k_sel_pass1 (lane 0's, in LDS) as a routine of the kernel below: insert + percolate-up with a strict <, or replace-min + percolate-down
+__device__ __forceinline__ void sel_heap_offer(int* hk, int* hid, int* hsc, int& load, const int K, const int k, const int me, const int f) {
+  if (load < K) {
+    hk[load] = k; hid[load] = me; hsc[load] = f; load++;
+    int node = load, parent = node / 2;
+    while (node > 1 && hk[node - 1] < hk[parent - 1]) {
+      int t = hk[parent - 1]; hk[parent - 1] = hk[node - 1]; hk[node - 1] = t;
+      t = hid[parent - 1]; hid[parent - 1] = hid[node - 1]; hid[node - 1] = t;
+      t = hsc[parent - 1]; hsc[parent - 1] = hsc[node - 1]; hsc[node - 1] = t;
+      node = parent; parent = node / 2;
+    }
+  } else if (k > hk[0]) {
+    hk[0] = k; hid[0] = me; hsc[0] = f;
+    int node = 1;
+    for (;;) {
+      const int left = node * 2, right = left + 1; int mn = node;
+      if (left <= load && hk[left - 1] < hk[node - 1]) mn = left;
+      if (right <= load && hk[right - 1] < hk[mn - 1]) mn = right;
+      if (mn == node) break;
+      int t = hk[mn - 1]; hk[mn - 1] = hk[node - 1]; hk[node - 1] = t;
+      t = hid[mn - 1]; hid[mn - 1] = hid[node - 1]; hid[node - 1] = t;
+      t = hsc[mn - 1]; hsc[mn - 1] = hsc[node - 1]; hsc[node - 1] = t;
+      node = mn;
+    }
+  }
+}
+
+// k_sel_pass1 with the f1 call cache (hash_filter_calls; ref: f1_run f1-wrapper.h:97-134, the tag advances once per read-strand, mapping.c:1268).  A window that gets
+// past the matches check and the overlap check takes the score of the FIRST earlier window of its read-strand that was itself computed and has the same cache slot
+// (one bypassed call), else keeps its own and becomes computed.  The taken score decides last_good, so the chain runs over EVERY eligible window in list order, not
+// over those at the threshold only: a step ballots the eligible lanes and walks them with ctz.  comp[off[2 r + st] ..]: the (slot | score << 32) pairs of the
+// read-strand's computed windows, written by lane 0 and searched 64 a ballot (as k_pass1 searches its list); a read-strand has at most as many as it has windows.
+__global__ __launch_bounds__(GM_WAVE) void k_sel_pass1_f1(GmScoreDev sc, int n_reads, int read_len, int K, uint32_t W, uint32_t overlap_abs,
+                                                          const gm_read_window_t* __restrict__ wins, const unsigned long long* __restrict__ off,
+                                                          const int* __restrict__ scores, const uint32_t* __restrict__ slots, unsigned long long* comp,
+                                                          int32_t* __restrict__ sel_id, int32_t* __restrict__ sel_score, uint32_t* __restrict__ sel_cnt,
+                                                          uint32_t* __restrict__ byp) {
+  __shared__ int hk[GM_SEL_MAX], hid[GM_SEL_MAX], hsc[GM_SEL_MAX];
+  __shared__ int load_s;
+  const int rd = blockIdx.x, lane = threadIdx.x;
+  if (rd >= n_reads) return;
+  const bool absthr = sc.vect_thr_frac < 0;
+  int load = 0;                                                          // (lane 0's)
+  uint32_t bypassed = 0;
+  for (int st = 0; st < 2; st++) {
+    const unsigned long long a = off[2 * (size_t)rd + st], b = off[2 * (size_t)rd + st + 1];
+    int last_cn = -1; uint32_t last_goff = 0;                            // last_good, reset at every read-strand (wave-uniform)
+    unsigned long long* SL = comp + a; int n_comp = 0;                   // a new tag: nothing of another read-strand is found
+    for (unsigned long long base = a; base < b; base += GM_WAVE) {
+      const unsigned long long i = base + lane;
+      const bool have = i < b;
+      int cn = -1, w_len = 1, matches = 0, score = 0; uint32_t goff = 0, slot = 0;
+      if (have) { const uint4 w0 = *(const uint4*)(wins + i); const uint2 w1 = *(const uint2*)((const uint32_t*)(wins + i) + 4);
+                  cn = (int)w0.z; goff = w0.w; w_len = (int)w1.x; matches = (int)((const uint32_t*)(wins + i))[6]; score = scores[i]; slot = slots[i]; }
+      const int score_max = (read_len < w_len ? read_len : w_len) * sc.match;
+      const int thr = sel_thr_of(sc.vect_thr_frac, sc.vect_abs, score_max);
+      unsigned long long bal = __ballot(have && matches >= sc.min_matches);      // ref: mapping.c:1275
+      bool adm = false; int fin = score;
+      while (bal) {
+        const int l = __builtin_ctzll(bal); bal &= bal - 1;
+        const int cn_l = __shfl(cn, l); const uint32_t goff_l = (uint32_t)__shfl((int)goff, l);
+        const bool skip = last_cn >= 0 && cn_l == last_cn && (unsigned long long)goff_l + overlap_abs <= (unsigned long long)(uint32_t)(last_goff + W);   // ref :1287-1293
+        if (skip) { if (lane == l) { fin = 0; adm = 0 >= thr; } continue; }
+        const uint32_t slot_l = (uint32_t)__shfl((int)slot, l); const int own_l = __shfl(score, l), thr_l = __shfl(thr, l);
+        int found = -1;                                                  // f1_run's look-up, ref: f1-wrapper.h:105-114
+        for (int c0 = 0; c0 < n_comp; c0 += GM_WAVE) {
+          const int c = c0 + lane;
+          const bool hit = c < n_comp && (uint32_t)__hip_atomic_load(&SL[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == slot_l;
+          const unsigned long long hb = __ballot(hit);
+          if (hb) { found = c0 + __builtin_ctzll(hb); break; }
+        }
+        int taken = own_l;
+        if (found >= 0) { taken = (int)(uint32_t)(__hip_atomic_load(&SL[found], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32); bypassed++; }
+        else {                                                           // computed: saved under its slot, ref :128-131
+          if (lane == 0) __hip_atomic_store(&SL[n_comp], (unsigned long long)slot_l | ((unsigned long long)(uint32_t)own_l << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          n_comp++; __syncthreads();
+        }
+        const bool pass_l = taken >= thr_l;
+        if (pass_l) { last_cn = cn_l; last_goff = goff_l; }              // ref: mapping.c:1332-1335
+        if (lane == l) { fin = taken; adm = pass_l; }
+      }
+      const int pct = score_max ? (1000 * 100 * fin) / score_max : 0;
+      const int key = absthr ? fin : pct;
+      unsigned long long ab = __ballot(adm);
+      while (ab) {                                                       // ref: mapping.c:1391-1404, in list order
+        const int l = __builtin_ctzll(ab); ab &= ab - 1;
+        const int k = __shfl(key, l), f = __shfl(fin, l);
+        if (lane == 0) sel_heap_offer(hk, hid, hsc, load, K, k, (int)(base + l), f);
+      }
+    }
+  }
+  if (lane == 0) load_s = load;
+  __syncthreads();
+  const int n = load_s;                                                  // <= K <= 64
+  if (lane < n) { sel_id[(size_t)rd * K + lane] = hid[lane]; sel_score[(size_t)rd * K + lane] = hsc[lane]; }
+  if (lane == 0) { sel_cnt[rd] = (uint32_t)n; byp[rd] = bypassed; }
+}
+
 __global__ __launch_bounds__(GM_WAVE) void k_sel_emit(GmScoreDev sc, int n_reads, int read_len, int K, const gm_read_window_t* __restrict__ wins,
                                                       const uint32_t* __restrict__ contig_off, const int32_t* __restrict__ sel_id, const int32_t* __restrict__ sel_score,
                                                       const uint32_t* __restrict__ sel_cnt, const unsigned long long* __restrict__ hit_off, gm_pass1_hit_t* __restrict__ out) {
@@ -170,6 +269,16 @@ int gm_launch_sel_pass1(const GmScoreDev& sc, int n_reads, int read_len, int K, 
   if (n_reads <= 0 || K < 1 || K > GM_SEL_MAX) { gm_set_error("gm_launch_sel_pass1: %d reads, %d slots", n_reads, K); return GM_E_ARG; }
   hipLaunchKernelGGL(k_sel_pass1, dim3(n_reads), dim3(GM_WAVE), 0, stream, sc, n_reads, read_len, K, (uint32_t)window_len, (uint32_t)overlap_abs, d_wins, d_off, d_scores,
                      d_sel_id, d_sel_score, d_sel_cnt);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_launch_sel_pass1_f1(const GmScoreDev& sc, int n_reads, int read_len, int K, int window_len, int overlap_abs, const gm_read_window_t* d_wins,
+                           const unsigned long long* d_off, const int* d_scores, const uint32_t* d_slots, unsigned long long* d_comp, int32_t* d_sel_id,
+                           int32_t* d_sel_score, uint32_t* d_sel_cnt, uint32_t* d_byp, hipStream_t stream) {
+  if (n_reads <= 0 || K < 1 || K > GM_SEL_MAX || !d_slots || !d_comp || !d_byp) { gm_set_error("gm_launch_sel_pass1_f1: %d reads, %d slots", n_reads, K); return GM_E_ARG; }
+  hipLaunchKernelGGL(k_sel_pass1_f1, dim3(n_reads), dim3(GM_WAVE), 0, stream, sc, n_reads, read_len, K, (uint32_t)window_len, (uint32_t)overlap_abs, d_wins, d_off, d_scores,
+                     d_slots, d_comp, d_sel_id, d_sel_score, d_sel_cnt, d_byp);
   GM_HIP(hipGetLastError());
   return GM_OK;
 }

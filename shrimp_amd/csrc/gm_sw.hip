@@ -2671,3 +2671,93 @@ int gm_launch_sw_gapless_batch_ix(const GmIndexDev& ix, int n, int match, int mi
   GM_HIP(hipGetLastError());
   return GM_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// gm_score_windows / gm_read_hits: the score f1_run computes for every window of a read batch in pass 1 (ref: read_pass1_per_strand mapping.c:1297-1329) and the
+// window's f1 cache slot, from the exported window records and the packed reads of the batch.  A wave a window, grid-stride; the wave fetches the read by the
+// record's `read` (minus read_base: the first read of the uploaded batch), so no copy of a read per window exists anywhere.  The routines are k_pass1's, called with
+// the arguments k_pass1 gives them: letter space turns the READ of a strand-1 window (load_read's rc, the read's own RNA flag) and scores the forward window; colour
+// space turns the WINDOW (load_window_cs' rc) and scores the read as given; -U takes the diagonal through the anchor box on the whole contig.  Never cut short: no
+// early stop.  A wave takes `chunk` consecutive windows at a time and loads the read only where the read-strand changes.  chunk is 1 (GM_SCORE_WIN_CHUNK): plain
+// grid-stride, the read loaded for every window -- with 8 the kernel took 2.29 ms instead of 2.28 ms on 179 175 windows of 131 072 reads of the cfg2 genome
+// (profiles/r17a_pass1_kernel_stats.csv), where most read-strands have one window; the loop form stays for inputs with long lists (GM_SCORE_CHUNK in tuning builds).
+// stats (or null): GS_VEC_CALLS / GS_VEC_CELLS, one striped add a wave.
+// ---------------------------------------------------------------------------------------------
+template <bool CS>
+__global__ void __launch_bounds__(GM_WAVE)
+k_score_windows(GmIndexDev ix, GmScoreDev sc, unsigned long long n, const gm_read_window_t* __restrict__ wins, const uint32_t* __restrict__ reads, int read_len,
+                int read_words, int read_base, const uint8_t* __restrict__ initbp, int max_w, int chunk, int* __restrict__ scores, uint32_t* __restrict__ slots,
+                unsigned long long* __restrict__ stats) {
+  extern __shared__ __align__(16) uint8_t sm[];
+  const int lane = threadIdx.x;
+  uint8_t* qr = sm;                                   // read_len
+  uint8_t* db = sm + ((read_len + 15) & ~15);         // max_w
+  uint8_t* db0 = db + ((max_w + 15) & ~15);           // colour space: first-colour row (max_w)
+  int16_t* carry = (int16_t*)(db0 + (CS ? ((max_w + 15) & ~15) : 0));
+  unsigned long long calls = 0, cells = 0;
+  int have_rd = -1, have_st = -1;                     // the read-strand qr holds
+  const unsigned long long C = (unsigned long long)chunk;
+  for (unsigned long long c0 = (unsigned long long)blockIdx.x * C; c0 < n; c0 += (unsigned long long)gridDim.x * C)
+  for (unsigned long long i = c0; i < c0 + C && i < n; i++) {
+    const uint4* wp = (const uint4*)(wins + i);
+    const uint4 a = wp[0], b = wp[1], c = wp[2];       // read st cn g_off | w_len score_window_gen matches ax | ay alen awidth reserved
+    const int rd = __builtin_amdgcn_readfirstlane((int)a.x) - read_base, st = __builtin_amdgcn_readfirstlane((int)a.y), cn = __builtin_amdgcn_readfirstlane((int)a.z);
+    const uint32_t goff = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.w);
+    const int w_len = __builtin_amdgcn_readfirstlane((int)b.x);
+    const int ax = __builtin_amdgcn_readfirstlane((int)b.w), ay = __builtin_amdgcn_readfirstlane((int)c.x);
+    const int alen = __builtin_amdgcn_readfirstlane((int)c.y), awidth = __builtin_amdgcn_readfirstlane((int)c.z);
+    const int ib = CS ? (int)initbp[rd] : 0;
+    __syncthreads();
+    // colour space scores every window against the read as it was sequenced: the hit is reversed instead (ref: mapping.c:1302-1303)
+    if (rd != have_rd || (!CS && st != have_st)) {    // (windows of a read-strand are adjacent: a chunk often stays on one)
+      load_read(reads + (size_t)rd * read_words, read_len, CS ? false : (st != 0), qr, lane, !CS && ix.read_rna && ix.read_rna[rd]);
+      have_rd = rd; have_st = st;
+    }
+    if (CS) load_window_cs(ix, cn, goff, w_len, st != ix.cs_flip, ib, db, db0, lane);
+    else load_window(ix.genome, (uint64_t)ix.contig_off[cn] + goff, w_len, false, db, lane);
+    __syncthreads();
+    if (slots) { const uint32_t slot = window_hash_slot(db, w_len, lane); if (lane == 0) slots[i] = slot; }
+    int score;
+    if (!CS && sc.gapless) {                                                             // -U: f1_run's ungapped branch, ref: f1-wrapper.h:122-125, mapping.c:1321-1328
+      score = sw_gapless_wave(ix.genome, (uint64_t)ix.contig_off[cn], (long long)ix.contig_off[cn + 1] - ix.contig_off[cn], qr, read_len, (long long)goff + ax, ay, sc, lane);
+      calls++; cells += (unsigned long long)read_len;
+    } else if (CS && sc.gapless) {                                                       // the same in colour space, the hit and its box turned first (as k_pass1)
+      const bool rcw = st != ix.cs_flip;
+      const long long clen = (long long)ix.contig_off[cn + 1] - ix.contig_off[cn];
+      long long go = goff; long long bx = ax, by = ay;
+      if (rcw) {                                                                         // reverse_hit + anchor_reverse, ref: mapping.c:254-263, anchors.h:30-34
+        go = clen - go - w_len;
+        bx = -bx + (w_len - 1) - (alen - 1) - (awidth - 1);
+        by = -by + (read_len - 1) - (alen - 1) + (awidth - 1);
+      }
+      score = sw_gapless_cs_wave(ix, cn, rcw, qr, read_len, go + bx, (int)by, ib, sc, lane);
+      calls++; cells += (unsigned long long)read_len;
+    } else {
+      score = sw_vector_wave_t<CS>(db, db0, w_len, qr, read_len, sc, carry, lane);
+      calls++; cells += (unsigned long long)w_len * read_len;
+    }
+    if (lane == 0) scores[i] = score;
+  }
+  if (stats && lane == 0) { GS_ADD(stats, GS_VEC_CALLS, calls); GS_ADD(stats, GS_VEC_CELLS, cells); }
+}
+
+size_t gm_score_windows_lds(int colour, int read_len, int max_w) {
+  return ((size_t)((read_len + 15) & ~15)) + (colour ? 2 : 1) * (size_t)((max_w + 15) & ~15) + (size_t)max_w * 4 + 64;      // as gm_launch_sw_vector_batch_ix sizes it
+}
+int gm_launch_score_windows(const GmIndexDev& ix, const GmScoreDev& sc, unsigned long long n, const gm_read_window_t* d_wins, const uint32_t* d_reads, int read_len,
+                            int read_words, int read_base, const uint8_t* d_initbp, int max_w, int* d_scores, uint32_t* d_slots, unsigned long long* d_stats,
+                            hipStream_t stream) {
+  if (n == 0) return GM_OK;
+  if ((ix.colour != 0) != (d_initbp != nullptr)) { gm_set_error("gm_launch_score_windows: the primer letters go with colour space"); return GM_E_ARG; }
+  const size_t lds = gm_score_windows_lds(ix.colour, read_len, max_w);
+  if (lds > GM_SCORE_WIN_LDS_LIMIT) { gm_set_error("gm_launch_score_windows: %zu bytes of LDS a wave", lds); return GM_E_RANGE; }
+  int chunk = GM_SCORE_WIN_CHUNK;
+  if (const char* e = gm_tune("GM_SCORE_CHUNK")) chunk = std::max(1, atoi(e));
+  const int grid = (int)std::min<unsigned long long>((n + chunk - 1) / chunk, 256 * 16);
+  if (ix.colour) hipLaunchKernelGGL(k_score_windows<true>, dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, n, d_wins, d_reads, read_len, read_words, read_base, d_initbp,
+                                    max_w, chunk, d_scores, d_slots, d_stats);
+  else hipLaunchKernelGGL(k_score_windows<false>, dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, n, d_wins, d_reads, read_len, read_words, read_base, d_initbp, max_w,
+                          chunk, d_scores, d_slots, d_stats);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}

@@ -161,7 +161,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_index_genome_is_rna", "gm_index_get_windows", "gm_sw_vector_batch_ix", "gm_sw_vector_batch_bounded_ix", "gm_sw_gapless_batch_ix", "gm_sw_full_ls_batch_ix", "gm_sw_full_cs_batch_ix",
            "gm_post_sw_batch_ix", "gm_sw_full_batch_text", "gm_sw_full_batch_text_ix",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits", "gm_debug_tophits_cs",
-           "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size", "gm_sam_records", "gm_sam_input_size",
+           "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size", "gm_score_windows", "gm_select_pass1_f1", "gm_read_hits", "gm_sam_records", "gm_sam_input_size",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
 
@@ -273,6 +273,9 @@ def lib():
     L.gm_mapping_size.argtypes = []; L.gm_mapping_size.restype = C.c_int
     L.gm_select_pass1.argtypes = [vp, C.c_int, C.c_int, vp, C.c_uint64, u64p, ipt, C.POINTER(vp), u64p, u64p]
     L.gm_select_pass2.argtypes = [vp, C.c_int, u64p, vp, vp, vp, C.POINTER(vp), u64p, u64p]
+    L.gm_score_windows.argtypes = [vp, C.c_int, C.c_int, u32p, u8p, vp, C.c_uint64, u64p, ipt, u32p]
+    L.gm_select_pass1_f1.argtypes = [vp, C.c_int, C.c_int, vp, C.c_uint64, u64p, ipt, u32p, C.POINTER(vp), u64p, u64p, u64p]
+    L.gm_read_hits.argtypes = [vp, C.c_int, C.c_int, u32p, u8p, C.POINTER(vp), u64p, u64p, C.POINTER(vp), u64p, u64p, C.POINTER(vp), C.POINTER(MapStats)]
     for fn, dt, what in ((L.gm_pass1_hit_size, PASS1_HIT_DTYPE, "gm_pass1_hit_t"), (L.gm_mapping_size, MAPPING_DTYPE, "gm_mapping_t")):
         if fn() != dt.itemsize:
             raise GmError("%s is %d bytes in the library, %d in its numpy dtype" % (what, fn(), dt.itemsize))
@@ -863,11 +866,38 @@ class Session:
         self.stats = st.as_dict(); self._windows_read_len = Lr
         return wins, off
 
-    def select_pass1(self, wins, off, scores, read_len=None):
+    def _reads_args(self, who, reads_codes, initbp):
+        """[n, L] codes and the primer letters as the read entries take them: -> (n, L, packed, initbp array or None)"""
+        from .synth import pack_reads
+        reads_codes = np.ascontiguousarray(reads_codes, dtype=np.uint8)
+        if reads_codes.ndim != 2: raise GmError("%s: reads_codes is [n, L]" % who)
+        n, Lr = reads_codes.shape
+        packed = np.ascontiguousarray(pack_reads(reads_codes), dtype=np.uint32) if n else np.zeros(1, dtype=np.uint32)
+        ib = None
+        if initbp is not None:
+            ib = np.ascontiguousarray(initbp, dtype=np.uint8)
+            if ib.shape != (n,): raise GmError("%s: one primer letter per read" % who)
+        return n, Lr, packed, ib
+
+    def score_windows(self, reads_codes, wins, off, initbp=None):
+        """The score pass 1 gives every window and its f1 cache slot (gm_score_windows): -> (scores int32[n_wins], slots uint32[n_wins]).  reads_codes / initbp: the batch
+        as read_windows takes it (nothing is gathered per window or turned by the caller); wins / off: read_windows', or the caller's own."""
+        n, Lr, packed, ib = self._reads_args("score_windows", reads_codes, initbp)
+        wins = np.ascontiguousarray(wins, dtype=READ_WINDOW_DTYPE); off = np.ascontiguousarray(off, dtype=np.uint64)
+        if off.shape != (2 * n + 1,): raise GmError("score_windows: off has 2 n + 1 entries")
+        scores = np.zeros(len(wins), dtype=np.int32); slots = np.zeros(len(wins), dtype=np.uint32)
+        _check(lib().gm_score_windows(self.h, n, Lr, packed.ctypes.data_as(C.POINTER(C.c_uint32)), None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      wins.ctypes.data_as(C.c_void_p), len(wins), off.ctypes.data_as(C.POINTER(C.c_uint64)), scores.ctypes.data_as(C.POINTER(C.c_int)),
+                                      slots.ctypes.data_as(C.POINTER(C.c_uint32))), "gm_score_windows")
+        return scores, slots
+
+    def select_pass1(self, wins, off, scores, read_len=None, slots=None, want_bypassed=False):
         """Pass 1's selection (gm_select_pass1) over the windows of read_windows and their vector scores: -> (hits, hit_off).  hits: structured array of
         PASS1_HIT_DTYPE, read r's at hits[hit_off[r]:hit_off[r + 1]] in the heap's array order, strand-1 hits already turned by reverse_hit: (cn, gen_st, g_off, w_len)
         and the box (ax, ay, alen, awidth) go to Index.sw_full_ls_batch / sw_full_cs_batch as they are.  read_len: the reads' length (colours in colour space);
-        None: that of this session's last read_windows call."""
+        None: that of this session's last read_windows call.
+        slots (score_windows'): the selection with the reference's f1 call cache (gm_select_pass1_f1), its default; None: without it (the reference under -Z).
+        want_bypassed: -> (hits, hit_off, bypassed), the number of calls the cache bypassed."""
         if read_len is None: read_len = getattr(self, "_windows_read_len", None)
         if read_len is None: raise GmError("select_pass1: read_len is needed (no read_windows call on this session yet)")
         wins = np.ascontiguousarray(wins, dtype=READ_WINDOW_DTYPE); off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -875,14 +905,48 @@ class Session:
         if off.ndim != 1 or len(off) < 1 or len(off) % 2 != 1: raise GmError("select_pass1: off has 2 n + 1 entries")
         if scores.shape != (len(wins),): raise GmError("select_pass1: one score per window")
         n = (len(off) - 1) // 2
-        L = lib(); out = C.c_void_p(); nh = C.c_uint64(0)
+        L = lib(); out = C.c_void_p(); nh = C.c_uint64(0); byp = C.c_uint64(0)
         hit_off = np.zeros(n + 1, dtype=np.uint64)
-        _check(L.gm_select_pass1(self.h, n, int(read_len), wins.ctypes.data_as(C.c_void_p), len(wins), off.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                 scores.ctypes.data_as(C.POINTER(C.c_int)), C.byref(out), C.byref(nh), hit_off.ctypes.data_as(C.POINTER(C.c_uint64))), "gm_select_pass1")
+        if slots is None and not want_bypassed:
+            _check(L.gm_select_pass1(self.h, n, int(read_len), wins.ctypes.data_as(C.c_void_p), len(wins), off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                     scores.ctypes.data_as(C.POINTER(C.c_int)), C.byref(out), C.byref(nh), hit_off.ctypes.data_as(C.POINTER(C.c_uint64))), "gm_select_pass1")
+        else:
+            sl = None
+            if slots is not None:
+                sl = np.ascontiguousarray(slots, dtype=np.uint32)
+                if sl.shape != (len(wins),): raise GmError("select_pass1: one slot per window")
+                if len(sl) == 0: sl = np.zeros(1, dtype=np.uint32)   # (an empty array still means: with the cache)
+            _check(L.gm_select_pass1_f1(self.h, n, int(read_len), wins.ctypes.data_as(C.c_void_p), len(wins), off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        scores.ctypes.data_as(C.POINTER(C.c_int)), None if sl is None else sl.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(out), C.byref(nh),
+                                        hit_off.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(byp)), "gm_select_pass1_f1")
         hits = np.zeros(nh.value, dtype=PASS1_HIT_DTYPE)
         if nh.value: C.memmove(hits.ctypes.data, out, nh.value * PASS1_HIT_DTYPE.itemsize)
         if out.value: L.gm_free(out)
-        return hits, hit_off
+        return (hits, hit_off, int(byp.value)) if want_bypassed else (hits, hit_off)
+
+    def read_hits(self, reads_codes, initbp=None, want_windows=False):
+        """Reads to pass-1 hits in one call (gm_read_hits: read_windows -> score_windows -> select_pass1 with the cache rule iff the session's hash_filter_calls is set):
+        -> (hits, hit_off), or with want_windows (hits, hit_off, wins, off, scores) -- the windows as read_windows returns them and their OWN scores.  The stage
+        counters of the call are left in self.stats."""
+        n, Lr, packed, ib = self._reads_args("read_hits", reads_codes, initbp)
+        L = lib(); out = C.c_void_p(); nh = C.c_uint64(0); st = MapStats()
+        hit_off = np.zeros(n + 1, dtype=np.uint64)
+        wout = C.c_void_p(); sout = C.c_void_p(); nw = C.c_uint64(0); off = np.zeros(2 * n + 1, dtype=np.uint64)
+        _check(L.gm_read_hits(self.h, n, Lr, packed.ctypes.data_as(C.POINTER(C.c_uint32)), None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_uint8)),
+                              C.byref(out), C.byref(nh), hit_off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                              C.byref(wout) if want_windows else None, C.byref(nw) if want_windows else None,
+                              off.ctypes.data_as(C.POINTER(C.c_uint64)) if want_windows else None, C.byref(sout) if want_windows else None, C.byref(st)), "gm_read_hits")
+        hits = np.zeros(nh.value, dtype=PASS1_HIT_DTYPE)
+        if nh.value: C.memmove(hits.ctypes.data, out, nh.value * PASS1_HIT_DTYPE.itemsize)
+        if out.value: L.gm_free(out)
+        self.stats = st.as_dict(); self._windows_read_len = Lr
+        if not want_windows: return hits, hit_off
+        wins = np.zeros(nw.value, dtype=READ_WINDOW_DTYPE); scores = np.zeros(nw.value, dtype=np.int32)
+        if nw.value:
+            C.memmove(wins.ctypes.data, wout, nw.value * READ_WINDOW_DTYPE.itemsize); C.memmove(scores.ctypes.data, sout, nw.value * 4)
+        if wout.value: L.gm_free(wout)
+        if sout.value: L.gm_free(sout)
+        return hits, hit_off, wins, off, scores
 
     def select_pass2(self, hits, hit_off, recs, post=None):
         """Pass 2's selection and the mapping qualities (gm_select_pass2) over the records of ONE full batch call on the hits of select_pass1: -> (maps, map_off).

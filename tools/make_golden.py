@@ -95,6 +95,41 @@ def n1_noisy_case():
     run_case("n1_onehit_60bp", contigs, one, extra=("-n", "1", "-h", "30%"))
 
 
+F1_TWIN = np.array([8, 9, 10, 15], dtype=np.uint8)      # S Y K N: the letters hash_genome_window (common/util.h:221-241, base & 3) folds onto A C G T
+
+
+def f1_twins_inputs():
+    """A 400-base segment and, EARLIER in list order, its copy with runs of 22 IUPAC twins every 40 bases; 300 exact 60-base reads of the clean segment.  A clean window
+    and its damaged copy share an f1 cache slot, so with the cache on (the default) a read whose damaged copy scores below the threshold takes that score for the
+    clean window too and comes out unmapped; under -Z every read maps 60M."""
+    rng = np.random.default_rng(11)
+    g = rng.integers(0, 4, 40000).astype(np.uint8)
+    seg = g[25000:25400].copy()
+    twin = seg.copy()
+    for lo in range(40, 321, 40): twin[lo:lo + 22] = F1_TWIN[seg[lo:lo + 22]]
+    g[5000:5400] = twin
+    reads = np.stack([seg[o:o + 60] for o in range(20, 320)]).astype(np.uint8)
+    return [g], reads
+
+
+def f1_twins_case():
+    contigs, reads = f1_twins_inputs()
+    run_case("f1_twins_60bp", contigs, reads)                            # the reference's default: the cache on
+    with tempfile.TemporaryDirectory() as d:
+        g = os.path.join(d, "g.fa"); r = os.path.join(d, "r.fa")
+        write_fa_codes(g, [b"contig1"], contigs)
+        write_fa_codes(r, [b"r%d" % i for i in range(len(reads))], list(reads))
+        p = subprocess.run([REF, "-N", "4", "-Z", r, g], capture_output=True, check=True)
+        body = b"".join(l + b"\n" for l in p.stdout.split(b"\n") if l and not l.startswith(b"@PG"))
+    with gzip.open(os.path.join(OUT, "f1_twins_60bp@no_cache.sam.gz"), "wb", compresslevel=9) as f:
+        f.write(body)
+    mapped = lambda text: {l.split(b"\t")[0] for l in text.split(b"\n") if l and not l.startswith(b"@") and not int(l.split(b"\t")[1]) & 4}
+    with gzip.open(os.path.join(OUT, "f1_twins_60bp.sam.gz"), "rb") as f: on = mapped(f.read())
+    off = mapped(body)
+    print("f1_twins_60bp@no_cache: %d reads mapped, %d with the cache, %d only without it" % (len(off), len(on), len(off - on)))
+    assert len(off - on) >= 20, "the draw does not show the cache: fewer than 20 reads map only under -Z"
+
+
 def mirna_case():
     """-M mirna: the mode's option bundle (gmapper.c:1497-1517: -H, -U, anchor width 0, gap opens -255, no f1 cache, -n 1, window 100 %, --local, no mapping
     qualities) with its five default seeds of span 20 / weight 14 (leading and trailing zeros, gmapper-defaults.h:230-238) on 22-base reads"""
@@ -590,6 +625,8 @@ def main():
         mirna_case(); return
     if "--n1-only" in sys.argv:
         n1_noisy_case(); return
+    if "--f1-twins-only" in sys.argv:
+        f1_twins_case(); return
     if "--paired-only" in sys.argv:
         paired_cases(); return
     contigs, reads, _ = synth.make_config("cfg1")
@@ -607,6 +644,7 @@ def main():
     chimeric_pairs_case()
     option_cases()
     n1_noisy_case()
+    f1_twins_case()
     mirna_case()
     cs_option_cases()
     index_cases()
