@@ -1104,7 +1104,8 @@ struct Read {
 };
 
 struct Stats { uint64_t vec_calls = 0, vec_cells = 0, vec_bypassed = 0, full_calls = 0, full_cells = 0, reads_matched = 0, dup_pruned = 0;
-               uint64_t pair_anchors = 0, pair_windows = 0; };   // paired mode: collapsed anchors / windows of both mates (stage check of the mate-pair region counts)
+               uint64_t pair_anchors = 0, pair_windows = 0;      // paired mode: collapsed anchors / windows of both mates (stage check of the mate-pair region counts)
+               uint64_t pair_heap_full = 0, pair_heap_evictions = 0; };   // pairs whose heap in readpair_get_vector_hits reached num_tmp_outputs; window pairs that replaced its root
 
 struct ThreadState {               // the reference's threadprivate state
   std::vector<uint16_t> region_map[2][2];       // region_map[number_in_pair][st]
@@ -1796,7 +1797,7 @@ struct Mapper {
   }
 
   // readpair_get_vector_hits (mapping.c:1877-1932)
-  void readpair_get_vector_hits(Read& re1, Read& re2, std::vector<HitPair>& a, int& load) const {
+  void readpair_get_vector_hits(Read& re1, Read& re2, std::vector<HitPair>& a, int& load, uint64_t* evictions = nullptr) const {
     a.assign(P.num_tmp_outputs, HitPair()); load = 0;
     const bool absthr = GMO_IS_ABSOLUTE(P.sw_vect_threshold);
     for (int st1 = 0; st1 < 2; st1++) {
@@ -1816,7 +1817,7 @@ struct Mapper {
             tmp.rh[0] = &h1; tmp.rh[1] = &h2;
             tmp.insert_size = (int)(st1 == 0 ? h2.g_off - (h1.g_off + h1.w_len) : h1.g_off - (h2.g_off + h2.w_len));
             if (load < P.num_tmp_outputs) { a[load] = tmp; load++; xhp_up(a, load); }
-            else { a[0] = tmp; xhp_down(a, load, 1); }
+            else { a[0] = tmp; xhp_down(a, load, 1); if (evictions) ++*evictions; }
           }
         }
       }
@@ -2234,7 +2235,8 @@ struct Mapper {
     read_pass1(T, re1, 0, true, pair_min_matches()); read_pass1(T, re1, 1, true, pair_min_matches());
     read_pass1(T, re2, 0, true, pair_min_matches()); read_pass1(T, re2, 1, true, pair_min_matches());
     std::vector<HitPair> p1, p2; int n1 = 0;
-    readpair_get_vector_hits(re1, re2, p1, n1);
+    readpair_get_vector_hits(re1, re2, p1, n1, &T.stats.pair_heap_evictions);
+    if (n1 == P.num_tmp_outputs) T.stats.pair_heap_full++;
     readpair_pass2(T, re1, re2, p1, n1, p2);
     if (!p2.empty()) { readpair_save_final_hits(pe, p2); pe.mapped = true; }
     // hits of pass 1 that were not saved lose their alignment (free_sfrp, mapping.c:2590-2595) and are re-aligned if selected again

@@ -37,6 +37,7 @@ struct Session {
 };
 
 static uint64_t g_last_pair_counts[2] = {0, 0};   // anchors, windows of the last paired call
+static uint64_t g_last_pair_heap_counts[2] = {0, 0};   // pairs whose pass-1 pair heap filled, evictions from it, over the last paired call
 static void map_all(const Session& S, std::vector<Read>& reads, int nthreads, std::string& out, Stats* stats_out) {
   const int chunk = 64;   // finer than the reference's 1000-read chunks so that a bounded sample still fills every core
   int nchunks = (int)((reads.size() + chunk - 1) / chunk);
@@ -67,6 +68,8 @@ static void map_all(const Session& S, std::vector<Read>& reads, int nthreads, st
   for (auto& o : outs) out += o;
   g_last_pair_counts[0] = g_last_pair_counts[1] = 0;
   for (auto& s : st) { g_last_pair_counts[0] += s.pair_anchors; g_last_pair_counts[1] += s.pair_windows; }
+  g_last_pair_heap_counts[0] = g_last_pair_heap_counts[1] = 0;
+  for (auto& s : st) { g_last_pair_heap_counts[0] += s.pair_heap_full; g_last_pair_heap_counts[1] += s.pair_heap_evictions; }
   if (stats_out) {
     for (auto& s : st) {
       stats_out->vec_calls += s.vec_calls; stats_out->vec_cells += s.vec_cells; stats_out->vec_bypassed += s.vec_bypassed;
@@ -403,6 +406,7 @@ char* gmo_map_pairs_sam_q(void* s, int n, int L1, const uint8_t* codes1, int L2,
 }
 void gmo_free(void* p) { free(p); }
 void gmo_last_pair_counts(uint64_t* out2) { out2[0] = g_last_pair_counts[0]; out2[1] = g_last_pair_counts[1]; }
+void gmo_last_pair_heap_counts(uint64_t* out2) { out2[0] = g_last_pair_heap_counts[0]; out2[1] = g_last_pair_heap_counts[1]; }
 
 // Stage dump for one batch, for GPU-vs-oracle stage parity: for every read the pass-1 survivors
 // (top-K heap array order) as rows of 12 ints:

@@ -39,6 +39,7 @@ def load():
     L.gmo_session_set.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.gmo_session_set_half_paired.argtypes = [C.c_void_p, C.c_int]
     L.gmo_last_pair_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.gmo_last_pair_heap_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.gmo_map_sam.argtypes = [C.c_void_p, C.c_int, C.c_int, u8p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]; L.gmo_map_sam.restype = C.c_void_p
     L.gmo_session_set_pairing.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.gmo_map_pairs_sam.argtypes = [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int, u8p, C.c_char_p, C.c_char_p, C.c_int]; L.gmo_map_pairs_sam.restype = C.c_void_p
@@ -102,6 +103,10 @@ class Session:
     def last_pair_counts(self):
         """(collapsed anchors, windows) over both mates and strands of the last paired call"""
         o = (C.c_uint64 * 2)(); self.L.gmo_last_pair_counts(o); return int(o[0]), int(o[1])
+
+    def last_pair_heap_counts(self):
+        """(pairs whose pass-1 pair heap reached num_tmp_outputs, evictions from those heaps) over the last paired call"""
+        o = (C.c_uint64 * 2)(); self.L.gmo_last_pair_heap_counts(o); return int(o[0]), int(o[1])
 
     def set(self, hash_filter_calls=True, sam_unaligned=False):
         self.L.gmo_session_set(self.h, int(hash_filter_calls), int(sam_unaligned))

@@ -1022,8 +1022,142 @@ def rna_cases():
             print(tag + ":", len(recs), "records,", sum(1 for l in recs if not int(l.split(b"\t")[1]) & 4), "mapped")
 
 
+# Paired mode at its edges (tests/test_pair_edges.py): mates of 40 and 60 bases under -I 200,400, perfect matches cut from a fragment of f bases.  The reference pairs
+# an opp-in fragment iff 180 <= f <= 420; the other modes' mates are the opp-in mates with one or both reverse-complemented (as cs_pair_case derives them), which moves
+# both transitions up by PE_SHIFT[mode].
+PE_LEN = (40, 60); PE_INS = (200, 400); PE_HALF = 24
+PE_SHIFT = {"opp-in": 0, "opp-out": 100, "col-fw": 60, "col-bw": 40}
+PE_OPTION_SETS = {None: [], "pe_nhp": ["--no-half-paired"], "pe_n3": ["-n", "3"], "pe_n3_nhp": ["-n", "3", "--no-half-paired"]}
+PE_CS_OPTION_SETS = {None: [], "pe_nhp": ["--no-half-paired"]}
+PH_OPTION_SETS = {None: [], "ph_o3_strata": ["-o", "3", "--strata"]}
+
+
+def _rc(x): return synth.COMPLEMENT[x[::-1]]
+
+
+def pe_mates(c1, c2, p, f, strand, mode, shifted=False):
+    """the mates of the fragment [p, p + f): mate 1 (40 bases) from contig c1, mate 2 (60 bases) from contig c2 -- one contig unless the pair is a cross-contig one.
+    strand "m": the fragment's reverse complement was sequenced.  shifted: mate 2 spans 62 bases of the fragment and lacks the two in its middle."""
+    n2 = PE_LEN[1] + (2 if shifted else 0)
+    if strand == "p": a = c1[p:p + PE_LEN[0]]; t = _rc(c2[p + f - n2:p + f])
+    else: a = _rc(c1[p + f - PE_LEN[0]:p + f]); t = c2[p:p + n2]
+    if shifted: t = np.delete(t, [n2 // 2 - 1, n2 // 2])
+    b = t
+    if mode == "opp-out": a, b = _rc(a), _rc(b)
+    elif mode == "col-fw": b = _rc(b)
+    elif mode == "col-bw": a = _rc(a)
+    assert len(a) == PE_LEN[0] and len(b) == PE_LEN[1]
+    return a.astype(np.uint8), b.astype(np.uint8)
+
+
+def pe_pairs(contigs, mode, t_lo, t_hi):
+    """the pairs of one pair_edges fixture and their names, which say what each pair is:
+         lo_<s>_<f> / hi_<s>_<f>    the sweep: f = t - 24 ... t + 24 about the lower / upper transition, fragment strand s (p / m), starts 41 apart on contig 1
+         slo_p_<f> / shi_p_<f>      the shifted series: the same offsets, a 2-base deletion in the middle of mate 2
+         x_<s>_<k>                  cross-contig: mate 1 from contig 1, mate 2 from the same offsets of contig 2, f in the middle of the bounds
+         e_<c><a|b>_<s>_<lo|hi>_<d> ends: the fragment begins d bases behind the first base (a) or ends d bases before the last base (b) of contig c, f just inside a bound"""
+    c1, c2 = contigs
+    out = []; p = 1000
+    for series, t, strands, shifted in (("lo", t_lo, "pm", False), ("hi", t_hi, "pm", False), ("slo", t_lo, "p", True), ("shi", t_hi, "p", True)):
+        for s in strands:
+            for f in range(t - PE_HALF, t + PE_HALF + 1):
+                out.append((b"%s_%s_%d" % (series.encode(), s.encode(), f), pe_mates(c1, c1, p, f, s, mode, shifted))); p += 41
+    for s in "pm":
+        for k in range(10):
+            out.append((b"x_%s_%d" % (s.encode(), k), pe_mates(c1, c2, p, (t_lo + t_hi) // 2, s, mode))); p += 41
+    assert p + t_hi + PE_HALF + 100 < len(c1) - 1000
+    for ci, c in enumerate(contigs):
+        for end in "ab":
+            for s in "pm":
+                for which, f in (("lo", t_lo), ("hi", t_hi)):
+                    for d in (0, 1, 7, 30):
+                        q = d if end == "a" else len(c) - d - f
+                        out.append((b"e_%d%s_%s_%s_%d" % (ci + 1, end.encode(), s.encode(), which.encode(), d), pe_mates(c, c, q, f, s, mode)))
+    names = [n for n, _ in out]
+    return np.stack([m[0] for _, m in out]), np.stack([m[1] for _, m in out]), names
+
+
+def _ref_pairs_body(contigs, cn, m1, m2, names, mode, ins, extra, cs=False):
+    """the reference's SAM body (no @PG / @RG line) for mates adjacent in one file; cs: m1 / m2 are colour reads behind their primer, through gmapper-cs --sam-unaligned"""
+    with tempfile.TemporaryDirectory() as d:
+        g = os.path.join(d, "g.fa"); r = os.path.join(d, "r.csfasta" if cs else "r.fa")
+        write_fa_codes(g, cn, contigs)
+        n1 = [n + b"/1" for n in names]; n2 = [n + b"/2" for n in names]
+        if cs:
+            with open(r, "wb") as f:
+                for i in range(len(m1)):
+                    for nm, row in ((n1[i], m1[i]), (n2[i], m2[i])):
+                        f.write(b">" + nm + b"\n" + b"ACGT"[row[0]:row[0] + 1] + bytes(b"0123"[c] if c < 4 else ord(".") for c in row[1:]) + b"\n")
+        else:
+            write_fa_codes(r, [n for pair in zip(n1, n2) for n in pair], [q for pair in zip(list(m1), list(m2)) for q in pair])
+        exe = os.path.join(ROOT, "oracle", "_ref", "gmapper-cs" if cs else "gmapper-ls")
+        p = subprocess.run([exe, "-N", "4", "-p", mode, "-I", "%d,%d" % ins, *(["--sam-unaligned"] if cs else []), *extra, r, g], capture_output=True, check=True)
+    return b"".join(l + b"\n" for l in p.stdout.split(b"\n") if l and not l.startswith(b"@PG") and not l.startswith(b"@RG"))
+
+
+def _paired_names(body):
+    """names of the pairs the SAM body holds as proper pairs (flag 0x2)"""
+    return {l.split(b"\t")[0] for l in body.split(b"\n") if l and not l.startswith(b"@") and int(l.split(b"\t")[1]) & 2}
+
+
+def _write_pair_fixture(name, contigs, cn, m1, m2, names, mode, ins, option_sets, cs=False):
+    for tag, extra in option_sets.items():
+        body = _ref_pairs_body(contigs, cn, m1, m2, names, mode, ins, extra, cs)
+        with gzip.open(os.path.join(OUT, name + ("@" + tag if tag else "") + ".sam.gz"), "wb", compresslevel=9) as f:
+            f.write(body)
+        print("%s%s: %d pairs -> %d SAM records, %d proper pairs" % (name, "@" + tag if tag else "", len(m1),
+              sum(1 for l in body.split(b"\n") if l and not l.startswith(b"@")), len(_paired_names(body))))
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **{"contig%d" % i: c for i, c in enumerate(contigs)}, mates1=m1, mates2=m2,
+                        names1=np.array([n + b"/1" for n in names]), names2=np.array([n + b"/2" for n in names]), contig_names=np.array(cn),
+                        mode=np.array(mode), ins=np.array(ins))
+
+
+def pair_edges_cases():
+    """pair_edges_<mode> (letter space, four option sets), pair_edges_cs_opp-in / _col-bw (colour space, two option sets), pair_heap_tandem / pair_heap_ties"""
+    contigs = synth.make_genome([30000, 30000], 77); cn = [b"contig1", b"contig2"]
+    for mode, s in PE_SHIFT.items():
+        t_lo, t_hi = 180 + s, 420 + s
+        m1, m2, names = pe_pairs(contigs, mode, t_lo, t_hi)
+        _write_pair_fixture("pair_edges_" + mode, contigs, cn, m1, m2, names, mode, PE_INS, PE_OPTION_SETS)
+    # colour space: the windows are longer, so the transitions lie elsewhere -- one coarse run over f = 100 ... 600 on one strand finds them
+    for mode in ("opp-in", "col-bw"):
+        fs = list(range(100, 601))
+        mm = [pe_mates(contigs[0], contigs[0], 1000 + 41 * k, f, "p", mode) for k, f in enumerate(fs)]
+        a = synth.cs_from_letters(np.stack([m[0] for m in mm]), 1, p_col=0); b = synth.cs_from_letters(np.stack([m[1] for m in mm]), 2, p_col=0)
+        names = [b"c_%d" % f for f in fs]
+        got = _paired_names(_ref_pairs_body(contigs, cn, a, b, names, mode, PE_INS, [], cs=True))
+        mid = (PE_INS[0] + PE_INS[1]) // 2 + PE_SHIFT[mode]
+        assert b"c_%d" % mid in got, "the coarse colour-space run does not pair the middle of the bounds"
+        t_lo = t_hi = mid
+        while b"c_%d" % (t_lo - 1) in got: t_lo -= 1
+        while b"c_%d" % (t_hi + 1) in got: t_hi += 1
+        print("pair_edges_cs_%s: the reference pairs %d <= f <= %d" % (mode, t_lo, t_hi))
+        m1, m2, names = pe_pairs(contigs, mode, t_lo, t_hi)
+        _write_pair_fixture("pair_edges_cs_" + mode, contigs, cn, synth.cs_from_letters(m1, 1, p_col=0), synth.cs_from_letters(m2, 2, p_col=0), names, mode, PE_INS,
+                            PE_CS_OPTION_SETS, cs=True)
+    # the pair heap: 60 opp-in pairs inside a tandem repeat of 12 copies of a 150-base unit; every copy of mate 1 pairs with every copy of mate 2 within -I 0,2000, far
+    # more window pairs than the 30 slots of the heap of readpair_get_vector_hits.  3 % substitutions per copy give distinct keys, 0 % all ties.
+    for name, div in (("pair_heap_tandem", 0.03), ("pair_heap_ties", 0.0)):
+        rng = np.random.Generator(np.random.PCG64(1207))
+        unit = rng.integers(0, 4, 150, dtype=np.uint8); copies = []
+        for _ in range(12):
+            u = unit.copy(); k = rng.random(150) < div
+            u[k] = (u[k] + rng.integers(1, 4, int(k.sum()))) & 3
+            copies.append(u)
+        c1 = np.concatenate([rng.integers(0, 4, 3000, dtype=np.uint8), *copies, rng.integers(0, 4, 3000, dtype=np.uint8)]).astype(np.uint8)
+        c2 = rng.integers(0, 4, 8000, dtype=np.uint8)
+        m1, m2, names = [], [], []
+        for i in range(60):
+            f = int(rng.integers(150, 321)); p = 3000 + int(rng.integers(0, 1800 - f + 1))
+            a, b = pe_mates(c1, c1, p, f, "pm"[i % 2], "opp-in")
+            m1.append(a); m2.append(b); names.append(b"h%d_%s_%d" % (i, b"pm"[i % 2:i % 2 + 1], f))
+        _write_pair_fixture(name, [c1, c2], cn, np.stack(m1), np.stack(m2), names, "opp-in", (0, 2000), PH_OPTION_SETS)
+
+
 if __name__ == "__main__":
-    if "--pair-file-only" in sys.argv:
+    if "--pair-edges-only" in sys.argv:
+        os.makedirs(OUT, exist_ok=True); pair_edges_cases()
+    elif "--pair-file-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); pair_file_cases()
     elif "--cs-pairs-fq-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); cs_paired_fastq_cases()
