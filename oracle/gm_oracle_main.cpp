@@ -237,6 +237,65 @@ int gmo_sw_full_cs_xover(const uint32_t* genome_ls, int goff, int glen, const ui
   return 0;
 }
 
+// ---- the same kernels with the scores as an argument (the _p family) -------------------------------------------------------------------
+// sc[] = match, mismatch, a_open, a_ext, b_open, b_ext, and in colour space crossover, indel_taboo_len behind them: penalties negative, as the reference's setups
+// take them (the P lines of tests/golden/sw_kat_scores.txt.gz / sw_kat_cs_scores.txt.gz in this order).  The colour-space vector filter's mismatch is
+// match + crossover (gmapper.c:2935).
+static Params params_of(const int* sc) {
+  Params P = default_params();
+  P.match_score = sc[0]; P.mismatch_score = sc[1];
+  P.a_gap_open_score = sc[2]; P.a_gap_extend_score = sc[3]; P.b_gap_open_score = sc[4]; P.b_gap_extend_score = sc[5];
+  return P;
+}
+static CsParams cs_params_of(const int* sc) {
+  CsParams C;
+  C.match = sc[0]; C.mismatch = sc[1]; C.a_go = -sc[2]; C.a_ge = -sc[3]; C.b_go = -sc[4]; C.b_ge = -sc[5]; C.xover = sc[6]; C.indel_taboo_len = sc[7];
+  return C;
+}
+// n windows in one call (OpenMP over the windows): window i is glen[i] positions from g_off[i] of `genome`, read i the row i of reads (read_words words each);
+// genome_ls / initbp non-null: colour space
+void gmo_sw_vector_batch_p(const int* sc, int n, const uint32_t* genome, const uint32_t* genome_ls, const long long* g_off, const int* glen,
+                           const uint32_t* reads, int read_words, const int* rlen, const int* initbp, int* scores) {
+  const Params P = params_of(sc);
+#pragma omp parallel for schedule(dynamic, 16)
+  for (int i = 0; i < n; i++) {
+    const uint32_t* rd = reads + (size_t)i * read_words;
+    scores[i] = genome_ls ? sw_vector_cs(P, sc[0] + sc[6], genome, g_off[i], glen[i], rd, rlen[i], genome_ls, initbp[i])
+                          : sw_vector(P, genome, g_off[i], glen[i], rd, rlen[i]);
+  }
+}
+int gmo_sw_vector_p(const int* sc, const uint32_t* genome, int goff, int glen, const uint32_t* read, int rlen) {
+  return sw_vector(params_of(sc), genome, goff, glen, read, rlen);
+}
+int gmo_sw_vector_cs_p(const int* sc, const uint32_t* genome_cs, int goff, int glen, const uint32_t* read, int rlen, const uint32_t* genome_ls, int initbp) {
+  return sw_vector_cs(params_of(sc), sc[0] + sc[6], genome_cs, goff, glen, read, rlen, genome_ls, initbp);
+}
+// sw_full_ls, either mode: has_anchor = 0 is the threshold band (local mode only); out[9] as gmo_sw_full_ls
+int gmo_sw_full_ls_p(const int* sc, const uint32_t* genome, int goff, int glen, const uint32_t* read, int rlen, int thresh, int maxscore,
+                     long long ax, long long ay, int alen, int awidth, int has_anchor, int revcmpl, int local, int* out, char* dbalign, char* qralign, int cap) {
+  const Params P = params_of(sc);
+  SwFullWorkspace W; SwFullResults s;
+  Anchor a; a.x = ax; a.y = ay; a.length = alen; a.width = awidth; a.weight = 1;
+  sw_full_ls(P, W, genome, goff, glen, read, rlen, thresh, maxscore, &s, revcmpl != 0, has_anchor ? &a : nullptr, has_anchor ? 1 : 0, local);
+  int v[9] = {s.score, s.read_start, s.rmapped, s.genome_start, s.gmapped, s.matches, s.mismatches, s.insertions, s.deletions};
+  memcpy(out, v, sizeof v);
+  if ((int)s.dbalign.size() + 1 > cap) return -1;
+  strcpy(dbalign, s.dbalign.c_str()); strcpy(qralign, s.qralign.c_str());
+  return 0;
+}
+// sw_full_cs, either mode, xover null or one score a read position; out[10] as gmo_sw_full_cs
+int gmo_sw_full_cs_p(const int* sc, const uint32_t* genome_ls, int goff, int glen, const uint32_t* read, int rlen, int initbp, int thresh,
+                     long long ax, long long ay, int alen, int awidth, int revcmpl, int local, const int* xover, int* out, char* dbalign, char* qralign, int cap) {
+  const CsParams C = cs_params_of(sc); SwFullCsResults s;
+  Anchor a; a.x = ax; a.y = ay; a.length = alen; a.width = awidth; a.weight = 1;
+  sw_full_cs(C, genome_ls, goff, glen, read, rlen, initbp, thresh, &s, revcmpl != 0, &a, 1, xover, local);
+  int v[10] = {s.score, s.read_start, s.rmapped, s.genome_start, s.gmapped, s.matches, s.mismatches, s.insertions, s.deletions, s.crossovers};
+  memcpy(out, v, sizeof v);
+  if ((int)s.dbalign.size() + 1 > cap) return -1;
+  strcpy(dbalign, s.dbalign.c_str()); strcpy(qralign, s.qralign.c_str());
+  return 0;
+}
+
 // opts = "key=value;key=value": the reference's command-line options by their long names (gmapper.c:1040-1140):
 // match mismatch open-r ext-r open-q ext-q match-window cmw-overlap cmw-threshold vec-threshold full-threshold
 // cmw-mode report anchor-width cutoff strata max-alignments seeds (comma separated 0/1 strings)

@@ -12,7 +12,11 @@
 //   C / S / L with second argument "rna": the genome holds U for every T (an RNA contig) and both functions get is_rna = true (what gmapper passes for a genome whose last
 //     contig is RNA, ref: genome.c:1063-1064, mapping.c:375-388,1318-1327) -- lstocs reads U as T, cstols hands back U for T (util.h:157-205); global and local mode
 //     -> tests/golden/sw_kat_cs_rna.txt.gz
-// Scores are the binary's colour-space defaults (ref: gmapper-defaults.h:52-58): match 10, mismatch -24, crossover -20,
+// Second argument "scores": the same cases under six other score sets -> tests/golden/sw_kat_cs_scores.txt.gz.  Each set opens with
+//   P name dblen qrlen a_open a_ext b_open b_ext match mismatch crossover indel_taboo_len      (sw_full_cs_setup's arguments; the vector filter's mismatch is match + crossover)
+// and is followed by the C, S (both strands), L, X and Y (one strand each, Y on every other case) records of n cases, thresholds scaled by the set's match score
+// and the per-position crossover scores drawn in [2 * crossover, -1].
+// Otherwise scores are the binary's colour-space defaults (ref: gmapper-defaults.h:52-58): match 10, mismatch -24, crossover -20,
 // gaps -33/-7 (reference) -33/-3 (query); the vector filter's mismatch is match + crossover (ref: gmapper.c:2935).
 #include <cstdio>
 #include <cstdlib>
@@ -29,14 +33,30 @@
 static void put(std::vector<uint32_t>& bf, int i, int v) { bf[i / 8] |= (uint32_t)(v & 0xf) << (4 * (i % 8)); }
 static void dump(const std::vector<uint32_t>& bf) { for (size_t i = 0; i < bf.size(); i++) printf("%s%x", i ? "," : "", bf[i]); }
 
+struct ScoreSet { const char* name; int match, mismatch, xover, a_go, a_ge, b_go, b_ge, taboo; };
+static const ScoreSet DEFAULT_SET = {"default", 10, -24, -20, -33, -7, -33, -3, 0};
+static const ScoreSet SCORE_SETS[] = {      // the letter-space sets of ref_kat.cpp with a crossover score each, and one with an indel taboo
+  {"unit",     1,  -1,  -1,   -1,  -1,  -1,  -1, 0},
+  {"linear",  10, -15, -14,    0, -12,   0,  -9, 0},
+  {"swapped", 10, -15, -20,  -20,  -2, -45,  -9, 0},
+  {"steep",    7, -40, -40,  -60,  -1, -25, -30, 0},
+  {"large",   32, -60, -60, -100, -20, -90, -25, 0},
+  {"swapped_taboo", 10, -15, -20, -20, -2, -45, -9, 3},
+};
+
 int main(int argc, char** argv) {
   int n = argc > 1 ? atoi(argv[1]) : 1500;
   const bool local = argc > 2 && !strcmp(argv[2], "local");     // "L" records: the same cases through sw_full_cs(.., local_alignment = true) (ref: sw-full-cs.c:199-203,315,439-552); no C / S records
   const bool xover = argc > 2 && !strcmp(argv[2], "xover");     // "X" / "Y" records only
   const bool rna = argc > 2 && !strcmp(argv[2], "rna");         // C, S and L records on an RNA genome with is_rna = true
+  const bool score_mode = argc > 2 && !strcmp(argv[2], "scores");   // "P" lines, and C, S, L, X and Y records under each of SCORE_SETS
   std::mt19937_64 rng(20260202), xrng(20261005);
-  sw_vector_setup(1400, 1000, -33, -7, -33, -3, 10, 10 + (-20), 1, true);
-  sw_full_cs_setup(1400, 1000, -33, -7, -33, -3, 10, -24, -20, true, 8, 0);
+  const int n_sets = score_mode ? (int)(sizeof SCORE_SETS / sizeof SCORE_SETS[0]) : 1;
+  for (int si = 0; si < n_sets; si++) {
+  const ScoreSet& S = score_mode ? SCORE_SETS[si] : DEFAULT_SET;
+  sw_vector_setup(1400, 1000, S.a_go, S.a_ge, S.b_go, S.b_ge, S.match, S.match + S.xover, 1, true);
+  sw_full_cs_setup(1400, 1000, S.a_go, S.a_ge, S.b_go, S.b_ge, S.match, S.mismatch, S.xover, true, 8, S.taboo);
+  if (score_mode) printf("P %s 1400 1000 %d %d %d %d %d %d %d %d\n", S.name, S.a_go, S.a_ge, S.b_go, S.b_ge, S.match, S.mismatch, S.xover, S.taboo);
   for (int t = 0; t < n; t++) {
     int rlen = 20 + rng() % 56;                        // 20..75 colours
     int kind = rng() % 8;
@@ -75,13 +95,22 @@ int main(int argc, char** argv) {
     struct anchor a; memset(&a, 0, sizeof a);
     a.x = (start - goff) + (int)(rng() % 7) - 3; a.y = 0; a.length = 10 + rng() % (rlen > 16 ? rlen - 10 : 6); a.width = 1 + rng() % 4; a.weight = 2;
     if (rng() % 4 == 0) { a.y = rng() % 10; a.x += a.y; }
-    int thresh = (rng() % 3 == 0) ? (int)(0.6 * rlen * 10) : (int)(0.3 * rlen * 10);
-    if (xover) {
+    int thresh = (rng() % 3 == 0) ? (int)(0.6 * rlen * S.match) : (int)(0.3 * rlen * S.match);
+    if (xover || score_mode) {
       // per-position scores as the read loop derives them from quality values: most positions good (near the global -20 .. -40), some poor (-1 .. -8)
       std::vector<int> xs(rlen);
       for (int i = 0; i < rlen; i++) { const int u = xrng() % 10; xs[i] = u < 6 ? -(int)(14 + xrng() % 27) : (u < 9 ? -(int)(1 + xrng() % 12) : -40); }
+      if (score_mode) {                                                      // the same three bands, scaled to the set's crossover score and kept in [2 * global, -1]
+        const int gx = -S.xover;
+        for (int i = 0; i < rlen; i++) {
+          const int u = xrng() % 10;
+          int v = u < 6 ? gx * 7 / 10 + (int)(xrng() % (gx * 13 / 10 + 1)) : (u < 9 ? 1 + (int)(xrng() % (gx * 6 / 10 + 1)) : 2 * gx);
+          xs[i] = -(v < 1 ? 1 : (v > 2 * gx ? 2 * gx : v));
+        }
+      }
       for (int md = 0; md < 2; md++) for (int rv = 0; rv < 2; rv++) {
         if (md == 1 && (t & 1)) continue;                                    // local mode on every other case
+        if (score_mode && rv != ((t >> 1) & 1)) continue;                    // one strand a case
         struct sw_full_results sfr; memset(&sfr, 0, sizeof sfr);
         sw_full_cs(gl.data(), goff, glen, rb.data(), rlen, initbp, thresh, &sfr, rv != 0, false, &a, 1, md, xs.data());
         printf("%s %d %d %d %d %lld %lld %d %d %d %d ", md ? "Y" : "X", goff, glen, rlen, initbp, (long long)a.x, (long long)a.y, a.length, a.width, rv, thresh);
@@ -92,10 +121,11 @@ int main(int argc, char** argv) {
                (sfr.dbalign && sfr.dbalign[0]) ? sfr.dbalign : "-", (sfr.qralign && sfr.qralign[0]) ? sfr.qralign : "-");
         free(sfr.dbalign); free(sfr.qralign);
       }
-      continue;
+      if (!score_mode) continue;
     }
-    for (int md = 0; md < (rna ? 2 : 1); md++) for (int rv = 0; rv < 2; rv++) {
-      const bool loc = rna ? md == 1 : local;
+    for (int md = 0; md < (rna || score_mode ? 2 : 1); md++) for (int rv = 0; rv < 2; rv++) {
+      const bool loc = rna || score_mode ? md == 1 : local;
+      if (score_mode && loc && rv != (t & 1)) continue;                      // L records: one strand a case
       struct sw_full_results sfr; memset(&sfr, 0, sizeof sfr);
       sw_full_cs(gl.data(), goff, glen, rb.data(), rlen, initbp, thresh, &sfr, rv != 0, rna, &a, 1, loc ? 1 : 0, NULL);
       printf("%s %d %d %d %d %lld %lld %d %d %d %d ", loc ? "L" : "S", goff, glen, rlen, initbp, (long long)a.x, (long long)a.y, a.length, a.width, rv, thresh);
@@ -105,6 +135,7 @@ int main(int argc, char** argv) {
              (sfr.dbalign && sfr.dbalign[0]) ? sfr.dbalign : "-", (sfr.qralign && sfr.qralign[0]) ? sfr.qralign : "-");
       free(sfr.dbalign); free(sfr.qralign);
     }
+  }
   }
   return 0;
 }

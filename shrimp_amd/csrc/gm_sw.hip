@@ -2306,10 +2306,11 @@ int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs
   const bool want_g4 = !(gm_tune("GM_P2_G4") && atoi(gm_tune("GM_P2_G4")) == 0) && grid >= 8;
   if (want_g4 || sc.local) {
     const size_t q16 = (size_t)((read_len + 15) & ~15), w16 = (size_t)((window_len + 15) & ~15);
-    // no score on a path through the matrix lies further from 0 than `reach`: a path has at most read_len + window_len moves, and a move changes the score by a match or a
-    // mismatch plus a crossover (per-position crossover scores lie in [2 x crossover_score, -1], ref: gmapper.c:532-544; an int8 row), or by a gap's opening + extension, at most
+    // no score on a path through the matrix lies further from 0 than `reach`: a path has at most read_len + window_len moves, and a move changes the score by a match, a
+    // mismatch or a gap's opening + extension, and by a crossover on top of any of the three (sw_full_cs charges one on the gap transitions too; per-position crossover
+    // scores lie in [2 x crossover_score, -1], ref: gmapper.c:532-544; an int8 row), at most
     const int xmax = d_xover ? std::min(127, 2 * std::abs(P.xover)) : std::abs(P.xover);
-    const int big = std::max(std::max(std::abs(P.match), std::abs(P.mismatch)) + xmax, std::max(std::max(std::abs(P.a_go) + std::abs(P.a_ge), std::abs(P.b_go) + std::abs(P.b_ge)), 1));
+    const int big = std::max(std::max(std::abs(P.match), std::abs(P.mismatch)), std::max(std::max(std::abs(P.a_go) + std::abs(P.a_ge), std::abs(P.b_go) + std::abs(P.b_ge)), 1)) + xmax;
     const long long reach = (long long)(read_len + window_len) * big;
     const size_t lds8 = 8 * 5 * q16 + 8 * w16 + 8 * (size_t)window_len * 12 * sizeof(int16_t) + 64;
     const size_t lds4 = 4 * 5 * q16 + 4 * w16 + 4 * (size_t)window_len * 12 * sizeof(int) + 64;

@@ -50,6 +50,15 @@ def load():
     L.gmo_index_selfcheck.argtypes = [C.c_void_p, C.c_int]; L.gmo_index_selfcheck.restype = C.c_int
     L.gmo_set_threads.argtypes = [C.c_int]
     L.gmo_map_tophits.argtypes = [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int, C.POINTER(C.c_longlong), C.c_long]; L.gmo_map_tophits.restype = C.c_long
+    # the _p family: the kernels with the scores as their first argument (score_array)
+    ip = C.POINTER(C.c_int)
+    L.gmo_sw_vector_p.argtypes = [ip, u32p, C.c_int, C.c_int, u32p, C.c_int]; L.gmo_sw_vector_p.restype = C.c_int
+    L.gmo_sw_vector_cs_p.argtypes = [ip, u32p, C.c_int, C.c_int, u32p, C.c_int, u32p, C.c_int]; L.gmo_sw_vector_cs_p.restype = C.c_int
+    L.gmo_sw_vector_batch_p.argtypes = [ip, C.c_int, u32p, u32p, C.POINTER(C.c_longlong), ip, u32p, C.c_int, ip, ip, ip]; L.gmo_sw_vector_batch_p.restype = None
+    L.gmo_sw_full_ls_p.argtypes = [ip, u32p, C.c_int, C.c_int, u32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   ip, C.c_char_p, C.c_char_p, C.c_int]; L.gmo_sw_full_ls_p.restype = C.c_int
+    L.gmo_sw_full_cs_p.argtypes = [ip, u32p, C.c_int, C.c_int, u32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, ip,
+                                   ip, C.c_char_p, C.c_char_p, C.c_int]; L.gmo_sw_full_cs_p.restype = C.c_int
     _LIB = L
     return L
 
@@ -154,6 +163,21 @@ class Session:
         except Exception: pass
 
 
+def sw_vector_batch_p(sc, genome, g_off, glen, reads, rlen, genome_ls=None, initbp=None):
+    """gmo_sw_vector_batch_p: the oracle's vector filter on n windows at the scores sc (score_array); genome_ls / initbp given: colour space (genome holds colours)"""
+    L = load()
+    u32p, ip = C.POINTER(C.c_uint32), C.POINTER(C.c_int)
+    g = np.ascontiguousarray(genome, dtype=np.uint32); r = np.ascontiguousarray(reads, dtype=np.uint32); n = r.shape[0]
+    gl = None if genome_ls is None else np.ascontiguousarray(genome_ls, dtype=np.uint32)
+    go = np.ascontiguousarray(g_off, dtype=np.int64); gn = np.ascontiguousarray(glen, dtype=np.int32); rl = np.ascontiguousarray(rlen, dtype=np.int32)
+    ib = None if initbp is None else np.ascontiguousarray(initbp, dtype=np.int32)
+    assert go.shape == gn.shape == rl.shape == (n,) and (gl is None) == (ib is None)
+    out = np.zeros(n, dtype=np.int32)
+    L.gmo_sw_vector_batch_p(sc, n, g.ctypes.data_as(u32p), None if gl is None else gl.ctypes.data_as(u32p), go.ctypes.data_as(C.POINTER(C.c_longlong)), gn.ctypes.data_as(ip),
+                            r.ctypes.data_as(u32p), r.shape[1], rl.ctypes.data_as(ip), None if ib is None else ib.ctypes.data_as(ip), out.ctypes.data_as(ip))
+    return out
+
+
 def sam_header(contigs, names=None):
     names = names if names is not None else [b"contig%d" % (i + 1) for i in range(len(contigs))]
     return b"@HD\tVN:1.0\tSO:unsorted\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (bytes(nm), len(c)) for nm, c in zip(names, contigs))
@@ -183,15 +207,54 @@ def parse_words(s):
     return np.array([int(x, 16) for x in s.split(",")], dtype=np.uint32)
 
 
+def _kat_ls_record(t):
+    """one line of a letter-space known-answer file (oracle/ref_kat.cpp), split at blanks"""
+    if t[0] == "V":
+        return ("V", int(t[1]), int(t[2]), int(t[3]), parse_words(t[4]), parse_words(t[5]), int(t[6]))
+    if t[0] == "F":
+        return ("F", int(t[1]), int(t[2]), int(t[3]), int(t[4]), int(t[5]), int(t[6]), int(t[7]), int(t[8]),
+                parse_words(t[9]), parse_words(t[10]), [int(x) for x in t[11:20]], t[20], t[21])
+    # L: goff glen rlen ax ay alen awidth rv no_anchor thresh sv | genome read | 9 ints | dbalign qralign
+    return (tuple(int(x) for x in t[1:12]), parse_words(t[12]), parse_words(t[13]), [int(x) for x in t[14:23]], t[23], t[24])
+
+
 def load_kat():
     with gzip.open(os.path.join(ROOT, "tests", "golden", "sw_kat.txt.gz"), "rt") as f:
         for line in f:
-            t = line.split()
-            if t[0] == "V":
-                yield ("V", int(t[1]), int(t[2]), int(t[3]), parse_words(t[4]), parse_words(t[5]), int(t[6]))
-            else:
-                yield ("F", int(t[1]), int(t[2]), int(t[3]), int(t[4]), int(t[5]), int(t[6]), int(t[7]), int(t[8]),
-                       parse_words(t[9]), parse_words(t[10]), [int(x) for x in t[11:20]], t[20], t[21])
+            yield _kat_ls_record(line.split())
+
+
+# name -> match, mismatch, a (open-r, ext-r), b (open-q, ext-q), colour-space crossover: the score sets of the known answers in tests/golden/sw_kat_scores.txt.gz
+SCORE_SETS = {
+    "unit": (1, -1, -1, -1, -1, -1, -1),
+    "linear": (10, -15, 0, -12, 0, -9, -14),
+    "swapped": (10, -15, -20, -2, -45, -9, -20),
+    "steep": (7, -40, -60, -1, -25, -30, -40),
+    "large": (32, -60, -100, -20, -90, -25, -60),
+}
+
+
+def _score_opts(name, colour=False):
+    m, mm, ao, ae, bo, be, x = SCORE_SETS[name]
+    return "match=%d;mismatch=%d;open-r=%d;ext-r=%d;open-q=%d;ext-q=%d" % (m, mm, ao, ae, bo, be) + (";crossover=%d" % x if colour else "")
+
+
+def _score_fields(name, colour=False):
+    m, mm, ao, ae, bo, be, x = SCORE_SETS[name]
+    d = dict(match_score=m, mismatch_score=mm, a_gap_open_score=ao, a_gap_extend_score=ae, b_gap_open_score=bo, b_gap_extend_score=be)
+    if colour: d["crossover_score"] = x
+    return d
+
+
+def sam_mapped_share_and_indels(body, n_reads):
+    """(share of the reads with a mapped record, number of records whose CIGAR holds an I or a D) of a SAM text"""
+    names, indels = set(), 0
+    for l in body.split(b"\n"):
+        if not l or l.startswith(b"@"): continue
+        t = l.split(b"\t")
+        if int(t[1]) & 4: continue
+        names.add((t[0], int(t[1]) & 0xC0)); indels += (b"I" in t[5] or b"D" in t[5])      # (the mates of a pair share their name: the first / second bits tell them apart)
+    return len(names) / n_reads, indels
 
 
 # Non-default option sets whose reference output is committed as <base>@<tag>.sam.gz (tools/make_golden.py OPTION_CASES):
@@ -250,7 +313,15 @@ OPTION_CASES = {
     "pairs_local": ("stress_pairs_2x100", "local=1", dict(local_alignment=1), None),
     "pairs_ungapped": ("stress_pairs_2x100", "local=1;ungapped=1", dict(local_alignment=1, ungapped=1, anchor_width=0, a_gap_open_score=-255, b_gap_open_score=-255,
                                                                         hash_filter_calls=0), None),
+    # the production pass-1 / pass-2 kernels at the score sets of tests/test_sw_score_sets.py (SCORE_SETS below)
+    "scores_unit": ("stress_100bp_unal", _score_opts("unit"), dict(_score_fields("unit"), sam_unaligned=1), None),
+    "scores_swapped": ("stress_100bp_unal", _score_opts("swapped"), dict(_score_fields("swapped"), sam_unaligned=1), None),
+    "scores_large": ("stress_100bp_unal", _score_opts("large"), dict(_score_fields("large"), sam_unaligned=1), None),
+    "scores_linear": ("stress_60bp", _score_opts("linear"), _score_fields("linear"), None),
+    "pairs_scores_swapped": ("stress_pairs_2x100", _score_opts("swapped"), _score_fields("swapped"), None),
 }
+# the option sets above that exist for their scores: the reference's output for each maps at least half of the reads and holds at least 20 records with an indel
+SCORE_CASE_TAGS = ["scores_unit", "scores_swapped", "scores_large", "scores_linear", "pairs_scores_swapped", "cs_scores_swapped", "cs_gate_under", "cs_gate_over"]
 
 
 # paired match modes (tools/make_golden.py OPTION_CASES pairs_n3 ... cfg5_n2): tag -> (base pair golden, oracle option string, gm_pair_opts_t fields)
@@ -281,6 +352,14 @@ CS_OPTION_CASES = {
                        dict(crossover_score=-25, indel_taboo_len=3, pr_xover=0.05, sam_unaligned=1), True),
     "cs_no_mapq": ("cfg4s_50col_2Mbp", "colour=1;no-mapping-qualities=1", dict(no_mapping_qualities=1), False),
     "cs_single_best": ("stress_cs_60col_unal", "colour=1;single-best-mapping=1", dict(single_best_mapping=1, sam_unaligned=1), True),
+    # the production colour-space kernels at other scores.  Pass 2 has two implementations, chosen by gm_launch_pass2_cs: int16_t carry rows while
+    # reach = (read_len + window_len) * big < 16000, big = max(|match|, |mismatch|, a open + ext, b open + ext) + |crossover|; else int.  60 colours, windows of 84: 144 moves.
+    "cs_scores_swapped": ("stress_cs_60col_unal", "colour=1;" + _score_opts("swapped", True), dict(_score_fields("swapped", True), sam_unaligned=1), True),   # reach 144 * (54 + 20) = 10656: int16_t
+    # large gap and crossover penalties on either side of the gate: big = 71 + 40 = 111 and 72 + 40 = 112
+    "cs_gate_under": ("stress_cs_60col_unal", "colour=1;crossover=-40;open-r=-60;ext-r=-11;open-q=-55;ext-q=-10",
+                      dict(crossover_score=-40, a_gap_open_score=-60, a_gap_extend_score=-11, b_gap_open_score=-55, b_gap_extend_score=-10, sam_unaligned=1), True),   # reach 144 * 111 = 15984: int16_t
+    "cs_gate_over": ("stress_cs_60col_unal", "colour=1;crossover=-40;open-r=-60;ext-r=-12;open-q=-55;ext-q=-10",
+                     dict(crossover_score=-40, a_gap_open_score=-60, a_gap_extend_score=-12, b_gap_open_score=-55, b_gap_extend_score=-10, sam_unaligned=1), True),    # reach 144 * 112 = 16128: int
 }
 
 
@@ -326,26 +405,47 @@ def load_kat_local():
         for line in f:
             t = line.split()
             if t[0] != "L": continue
-            # goff glen rlen ax ay alen awidth rv no_anchor thresh sv | genome read | 9 ints | dbalign qralign
-            yield (tuple(int(x) for x in t[1:12]), parse_words(t[12]), parse_words(t[13]), [int(x) for x in t[14:23]], t[23], t[24])
+            yield _kat_ls_record(t)
+
+
+def _kat_cs_record(t):
+    """one line of a colour-space known-answer file (oracle/ref_kat_cs.cpp), split at blanks (bytes)"""
+    words = lambda t: np.array([int(x, 16) for x in t.split(b",")], dtype=np.uint32)
+    if t[0] == b"C":
+        return ("C", int(t[1]), int(t[2]), int(t[3]), int(t[4]), words(t[5]), words(t[6]), words(t[7]), int(t[8]))
+    if t[0] in (b"X", b"Y"):      # per-position crossover scores behind the read words (X: global, Y: local mode)
+        return (t[0].decode(), [int(x) for x in t[1:11]], words(t[11]), words(t[12]), [int(x) for x in t[14:24]],
+                b"" if t[24] == b"-" else t[24], b"" if t[25] == b"-" else t[25], np.array([int(x) for x in t[13].split(b",")], dtype=np.int32))
+    return (t[0].decode(), [int(x) for x in t[1:11]], words(t[11]), words(t[12]), [int(x) for x in t[13:23]],
+            b"" if t[23] == b"-" else t[23], b"" if t[24] == b"-" else t[24])
 
 
 def load_kat_cs(name="sw_kat_cs.txt.gz"):
     """colour-space known answers produced by the reference's own sw_vector(use_colours) / sw_full_cs (oracle/ref_kat_cs.cpp); sw_kat_cs_local.txt.gz: "L" records, sw_full_cs in local mode"""
-    recs = []
-    words = lambda t: np.array([int(x, 16) for x in t.split(b",")], dtype=np.uint32)
     with gzip.open(os.path.join(ROOT, "tests", "golden", name), "rb") as f:
+        return [_kat_cs_record(line.split()) for line in f]
+
+
+def load_kat_scores(colour=False):
+    """the known answers under other score sets than the defaults (oracle/ref_kat.cpp / ref_kat_cs.cpp, mode "scores"): a list of (name, setup, records), one entry a set.
+    setup = dblen, qrlen, a_open, a_ext, b_open, b_ext, match, mismatch (colour space: + crossover, indel_taboo_len) -- the setups' arguments in their order.
+    Letter space: records as load_kat gives them ("V", "F") and as load_kat_local does (the L records: their first field is a tuple);
+    colour space: records as load_kat_cs gives them (C, S, L, X, Y)."""
+    sets = []
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "sw_kat_cs_scores.txt.gz" if colour else "sw_kat_scores.txt.gz"), "rb" if colour else "rt") as f:
         for line in f:
             t = line.split()
-            if t[0] == b"C":
-                recs.append(("C", int(t[1]), int(t[2]), int(t[3]), int(t[4]), words(t[5]), words(t[6]), words(t[7]), int(t[8])))
-            elif t[0] in (b"X", b"Y"):      # sw_kat_cs_xover.txt.gz: per-position crossover scores behind the read words (X: global, Y: local mode)
-                recs.append((t[0].decode(), [int(x) for x in t[1:11]], words(t[11]), words(t[12]), [int(x) for x in t[14:24]],
-                             b"" if t[24] == b"-" else t[24], b"" if t[25] == b"-" else t[25], np.array([int(x) for x in t[13].split(b",")], dtype=np.int32)))
+            if t[0] in ("P", b"P"):
+                sets.append((t[1].decode() if colour else t[1], tuple(int(x) for x in t[2:]), []))
             else:
-                recs.append((t[0].decode(), [int(x) for x in t[1:11]], words(t[11]), words(t[12]), [int(x) for x in t[13:23]],
-                             b"" if t[23] == b"-" else t[23], b"" if t[24] == b"-" else t[24]))
-    return recs
+                sets[-1][2].append(_kat_cs_record(t) if colour else _kat_ls_record(t))
+    return sets
+
+
+def score_array(setup):
+    """the _p entry points' score argument from a setup tuple of load_kat_scores: match, mismatch, a_open, a_ext, b_open, b_ext (, crossover, indel_taboo_len)"""
+    s = list(setup[2:])
+    return (C.c_int * 8)(*([s[4], s[5], s[0], s[1], s[2], s[3]] + (s[6:8] if len(s) > 6 else [0, 0])))
 
 
 # RNA fixtures (tools/make_golden.py rna_cases): tag -> (colour space?, genome file, read files, oracle options, pairing)

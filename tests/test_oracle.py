@@ -93,13 +93,18 @@ def test_oracle_option_sets_match_reference(tag, oracle_lib):
         s = oa.Session(g["contigs"], g["contig_names"], opts=opts)
         s.set_pairing(g["mode"], *g["ins"])
         got = oa.sam_header(g["contigs"], g["contig_names"]) + s.map_pairs_sam(g["m1"], g["m2"], g["names1"], g["names2"], nthreads=4)
+        n_reads = 2 * len(g["m1"])
     else:
         contigs, reads, _ = oa.load_golden(base)
         s = oa.Session(contigs, opts=opts)
         if "unal" in base: s.set("ungapped" not in opts, True)
         got = oa.sam_header(contigs) + s.map_sam(reads, nthreads=4)
+        n_reads = len(reads)
     s.close()
     assert got == want, "oracle SAM differs from the reference for option set %s" % tag
+    if tag in oa.SCORE_CASE_TAGS:                                  # a golden of the score sets must not pass by being empty
+        share, indels = oa.sam_mapped_share_and_indels(want, n_reads)
+        assert share >= 0.5 and indels >= 20, (tag, share, indels)
 
 
 def test_oracle_mirna_mode_matches_reference(oracle_lib):
@@ -372,6 +377,9 @@ def test_colour_space_local_and_ungapped_match_reference(tag):
     o = oa.Session(contigs, opts=opts); o.set(sam_unaligned=unal, hash_filter_calls=("ungapped" not in opts))
     got = oa.sam_header(contigs) + o.map_sam(reads, nthreads=4); o.close()
     assert got == want
+    if tag in oa.SCORE_CASE_TAGS:                                  # a golden of the score sets must not pass by being empty
+        share, indels = oa.sam_mapped_share_and_indels(want, len(reads))
+        assert share >= 0.5 and indels >= 20, (tag, share, indels)
 
 
 @pytest.mark.parametrize("tag", sorted(oa.RNA_CASES))

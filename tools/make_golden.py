@@ -272,6 +272,12 @@ OPTION_CASES = {
     "pairs_hashed_n3": ("stress_pairs_2x100", ["-H", "-n", "3"]),                       # hashed seeds under the mate-pair modes of the generic lookup kernel
     "pairs_local_n3_nhp": ("stress_pairs_2x100", ["--local", "-n", "3", "--no-half-paired"]),
     "cfg5_n2": ("cfg5s_2x150_1Mbp", ["-n", "2"]),
+    # the score sets of tests/golden/sw_kat_scores.txt.gz through the whole program (-m match, -i mismatch, -g / -e open / extend along the genome, -q / -f along the read)
+    "scores_unit": ("stress_100bp_unal", ["-m", "1", "-i", "-1", "-g", "-1", "-e", "-1", "-q", "-1", "-f", "-1", "--sam-unaligned"]),
+    "scores_swapped": ("stress_100bp_unal", ["-m", "10", "-i", "-15", "-g", "-20", "-e", "-2", "-q", "-45", "-f", "-9", "--sam-unaligned"]),
+    "scores_large": ("stress_100bp_unal", ["-m", "32", "-i", "-60", "-g", "-100", "-e", "-20", "-q", "-90", "-f", "-25", "--sam-unaligned"]),
+    "scores_linear": ("stress_60bp", ["-m", "10", "-i", "-15", "-g", "0", "-e", "-12", "-q", "0", "-f", "-9"]),
+    "pairs_scores_swapped": ("stress_pairs_2x100", ["-m", "10", "-i", "-15", "-g", "-20", "-e", "-2", "-q", "-45", "-f", "-9"]),
 }
 
 
@@ -286,6 +292,11 @@ CS_OPTION_CASES = {
     "cs_no_mapq":      ("cfg4s_50col_2Mbp", ["--no-mapping-qualities"]),         # global sw_full_cs, no post_sw: sw_full_cs's own strings and counts in the output
     "cs_single_best":  ("stress_cs_60col_unal", ["--single-best-mapping", "--sam-unaligned"]),
     "cs_extra_rg":     ("cfg4s_50col_2Mbp", ["--extra-sam-fields", "--read-group", "grp1,sampleA", "--sam-unaligned"]),
+    # other scores in colour space; cs_gate_under / cs_gate_over: large gap and crossover penalties on either side of the gate between the two pass-2 kernels of the
+    # GPU library (60 colours + windows of 84 = 144 moves, a move at most 71 + 40 = 111: 15984, or 72 + 40 = 112: 16128, against 16000)
+    "cs_scores_swapped": ("stress_cs_60col_unal", ["-m", "10", "-i", "-15", "-x", "-20", "-g", "-20", "-e", "-2", "-q", "-45", "-f", "-9", "--sam-unaligned"]),
+    "cs_gate_under":   ("stress_cs_60col_unal", ["-x", "-40", "-g", "-60", "-e", "-11", "-q", "-55", "-f", "-10", "--sam-unaligned"]),
+    "cs_gate_over":    ("stress_cs_60col_unal", ["-x", "-40", "-g", "-60", "-e", "-12", "-q", "-55", "-f", "-10", "--sam-unaligned"]),
 }
 
 
@@ -413,6 +424,21 @@ def cs_kat_cases():
     with gzip.open(os.path.join(OUT, "sw_kat_cs_rna.txt.gz"), "wb", compresslevel=9) as f:
         f.write(katr)
     print("sw_kat_cs_rna:", katr.count(b"\nC ") + 1, "colour-space vector,", katr.count(b"\nS "), "+", katr.count(b"\nL "), "sw_full_cs (global + local), all on an RNA genome with is_rna = true")
+
+
+def score_kat_cases():
+    """the letter- and colour-space known answers once more under other score sets than the defaults (oracle/ref_kat.cpp, ref_kat_cs.cpp, mode "scores"): a P line with the
+    setups' arguments opens each set"""
+    for exe, name in (("ref_kat", "sw_kat_scores"), ("ref_kat_cs", "sw_kat_cs_scores")):
+        kat = subprocess.run([os.path.join(ROOT, "oracle", "_ref", exe), "150", "scores"], capture_output=True, check=True).stdout
+        path = os.path.join(OUT, name + ".txt.gz")
+        with gzip.open(path, "wb", compresslevel=9) as f:
+            f.write(kat)
+        assert os.path.getsize(path) < 350_000, "cut cases per set, not sets"
+        kinds = {}
+        for l in kat.split(b"\n"):
+            if l: kinds[l[:1].decode()] = kinds.get(l[:1].decode(), 0) + 1
+        print("%s: %d sets," % (name, kinds.pop("P")), ", ".join("%d %s" % (v, k) for k, v in sorted(kinds.items())), "records")
 
 
 def post_kat_cases():
@@ -603,6 +629,8 @@ def main():
         local_kat_cases(); return
     if "--post-kat-only" in sys.argv:
         post_kat_cases(); return
+    if "--score-kat-only" in sys.argv:
+        score_kat_cases(); return
     if "--cs-kat-only" in sys.argv:
         cs_kat_cases(); return
     if "--cs-pair-option-tags" in sys.argv:
@@ -651,6 +679,7 @@ def main():
     cs_kat_cases()
     post_kat_cases()
     local_kat_cases()
+    score_kat_cases()
     cs_cases()
     fastq_cases()
     cs_fastq_cases()
