@@ -143,6 +143,13 @@ extern "C" void sw_full_ls_stats(uint64_t* invocs, uint64_t* cells, double* secs
 struct SeamTimer { double* acc; std::chrono::steady_clock::time_point t0; explicit SeamTimer(double* a) : acc(a), t0(std::chrono::steady_clock::now()) {}
                    ~SeamTimer() { *acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } };
 
+// sw_full_ls / sw_full_cs are calls of one item of the batch body (sw_full_batch_impl, gm_host_seams_ix.inc) and take their strings from gm_sw_full_batch_strings.  `seam`:
+// the seam counts and times the call itself (one invocation, window x read cells, also when it refuses), and an anchor box is taken as given, whatever its length.
+static int sw_full_batch_impl(bool colour, int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen, const uint32_t* reads, int read_words,
+                              const int* rlen, const uint8_t* initbp, const struct gm_anchor* anchors, const uint8_t* revcmpl, const int* threshscore, const int* maxscore,
+                              const int* xover, int xover_stride, int is_rna, int local, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len,
+                              const gm_index_t* ix = nullptr, const int* cn = nullptr, const uint8_t* gen_st = nullptr, bool seam = false);
+
 extern "C" void sw_full_ls(uint32_t* genome, int goff, int glen, uint32_t* read, int rlen, int threshscore, int maxscore,
                            struct gm_sw_full_results* sfr, bool revcmpl, struct gm_anchor* anchors, int anchors_cnt, int local_alignment) {
   if (!g_sf.init) abort();   // ref: sw-full-ls.c:649-650
@@ -151,39 +158,21 @@ extern "C" void sw_full_ls(uint32_t* genome, int goff, int glen, uint32_t* read,
     gm_set_error("sw_full_ls: one anchor box (gmapper's call, ref: mapping.c:391-394) or none (the threshold band) is implemented");
     sfr->score = 0; sfr->dbalign = strdup(""); sfr->qralign = strdup(""); return;
   }
-  const uint64_t gw = ((uint64_t)goff + glen + 7) / 8 + 8; const int rwords = (rlen + 7) / 8 + 1;
-  const int ops_cap = glen + rlen + 8;
-  uint32_t *dg = nullptr, *dr = nullptr; uint8_t *dback = nullptr, *dops = nullptr; int* dout = nullptr;
-  GmDevMem mem;      // (any failure below: score 0, empty strings, "HIP failure")
-  bool ok = mem.get(&dg, gw * 4) == hipSuccess && mem.get(&dr, (size_t)rwords * 4) == hipSuccess &&
-            mem.get(&dback, (size_t)glen * rlen + 256) == hipSuccess && mem.get(&dops, ops_cap) == hipSuccess && mem.get(&dout, 16 * 4) == hipSuccess;
-  int out[16] = {0}; std::vector<uint8_t> ops(ops_cap);
-  if (ok) {
-    ok = hipMemset(dg, 0, gw * 4) == hipSuccess && hipMemcpy(dg, genome, (gw - 8) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(dr, read, (size_t)(rwords - 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         gm_launch_sw_full_single(g_sf.sc, dg, goff, glen, dr, rlen, anchors ? anchors[0].x : 0, anchors ? anchors[0].y : 0, anchors ? anchors[0].length : 1,
-                                  anchors ? anchors[0].width : 1, revcmpl ? 1 : 0, dback, dout, dops, ops_cap, 0, anchors ? 1 : 0, threshscore, maxscore,
-                                  local_alignment ? 1 : 0) == GM_OK &&
-         hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, sizeof out, hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(ops.data(), dops, ops_cap, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  if (!ok) { gm_set_error("sw_full_ls: HIP failure"); sfr->score = 0; sfr->dbalign = strdup(""); sfr->qralign = strdup(""); return; }
-  sfr->score = out[0];
-  std::string db, qr;
-  if (out[0] > 0) {
-    sfr->read_start = out[1]; sfr->rmapped = out[2]; sfr->genome_start = out[3]; sfr->gmapped = out[4];
-    sfr->matches += out[5]; sfr->mismatches += out[6]; sfr->insertions += out[7]; sfr->deletions += out[8];
-    int pi = out[1], pj = out[3];   // pretty_print, ref: sw-full-ls.c:524-560 (genome_start already includes goff)
-    auto nib = [](const uint32_t* b, long long i) { return (int)((b[i / 8] >> (4 * (i % 8))) & 0xf); };
-    for (int k = 0; k < out[9]; k++) {
-      if (ops[k] == 'D') { db.push_back('-'); qr.push_back(LSTRANS[nib(read, pi++)]); }
-      else if (ops[k] == 'I') { db.push_back(LSTRANS[nib(genome, pj++)]); qr.push_back('-'); }
-      else { db.push_back(LSTRANS[nib(genome, pj++)]); qr.push_back(LSTRANS[nib(read, pi++)]); }
-    }
+  const int64_t go = goff; const uint8_t rv = revcmpl ? 1 : 0;
+  gm_sw_full_rec_t R; uint8_t* ops = nullptr; uint64_t ops_len = 0;
+  // (the genome bitfield ends with the window's last word; any failure below: score 0, empty strings, the reason in gm_last_error())
+  const bool ok = sw_full_batch_impl(false, 1, genome, ((uint64_t)goff + glen + 7) / 8, &go, &glen, read, (rlen + 7) / 8, &rlen, nullptr, anchors, &rv, &threshscore, &maxscore,
+                                     nullptr, 0, 0, local_alignment, &R, &ops, &ops_len, nullptr, nullptr, nullptr, true) == GM_OK && R.status == 0 &&
+                  gm_sw_full_batch_strings(0, &R, ops, ops_len, genome, (uint64_t)goff + glen, read, rlen, 0, 0, &sfr->dbalign, &sfr->qralign) == GM_OK;
+  free(ops);
+  if (!ok) { sfr->score = 0; sfr->dbalign = strdup(""); sfr->qralign = strdup(""); return; }
+  sfr->score = R.score;
+  if (R.score > 0) {
+    sfr->read_start = R.read_start; sfr->rmapped = R.rmapped; sfr->genome_start = (int)R.genome_start; sfr->gmapped = R.gmapped;      // (genome_start includes goff)
+    sfr->matches += R.matches; sfr->mismatches += R.mismatches; sfr->insertions += R.insertions; sfr->deletions += R.deletions;
   } else {   // the reference backtraces stale scratch here; every caller discards it (score 0 < threshold)
     sfr->rmapped = 1; sfr->gmapped = 1; sfr->genome_start = goff;
   }
-  sfr->dbalign = strdup(db.c_str()); sfr->qralign = strdup(qr.c_str());
 }
 
 extern "C" int gm_sw_vector_batch_cs(int n, const uint32_t* genome_cs, const uint32_t* genome_ls, uint64_t genome_words, const int64_t* g_off,
@@ -228,70 +217,25 @@ extern "C" void sw_full_cs(uint32_t* genome_ls, int goff, int glen, uint32_t* re
   SeamTimer tm(&g_sc.secs); g_sc.invocs++; g_sc.cells += 4ull * (uint64_t)std::max(glen, 0) * (uint64_t)std::max(rlen, 0);
   // A refusal must not read as "no alignment" (score 0 is what a window below the threshold returns): the reason goes to stderr as well as to gm_last_error().
   auto fail = [&](const char* why) { gm_set_error("sw_full_cs: %s", why); fprintf(stderr, "gmapper_hip: sw_full_cs refused: %s\n", why); sfr->score = 0; sfr->dbalign = nullptr; sfr->qralign = nullptr; };
+  // ... and where the batch body or a launcher has refused, its reason stands as it is ("sw_full_cs: item 0 refused: ...", or what the failing call left)
+  auto refused = [&] { fprintf(stderr, "gmapper_hip: %s\n", gm_last_error()); sfr->score = 0; sfr->dbalign = nullptr; sfr->qralign = nullptr; };
   if (anchors == nullptr || anchors_cnt != 1 || glen > g_sc.dblen || rlen > g_sc.qrlen || glen < 1 || rlen < 1 ||
       initbp < 0 || initbp > 3 || g_sc.p[7] < 0) {
     fail("only one anchor box (gmapper's call, ref: mapping.c:375-379) is implemented"); return;
   }
-  // crossover_score: one score per read position (from the QVs, ref: gmapper.c:532-544 -- clamped there to [2 * global, -1]); the kernels keep a row of them in 8 bits
-  std::vector<int8_t> xrow;
-  if (crossover_score) {
-    xrow.resize((size_t)rlen + 16, 0);
-    for (int i = 0; i < rlen; i++) {
-      if (crossover_score[i] < -128 || crossover_score[i] > 127) { fail("a per-position crossover score outside [-128, 127] (the device keeps them in 8 bits)"); return; }
-      xrow[i] = (int8_t)crossover_score[i];
-    }
-  }
-  const uint64_t gw = ((uint64_t)goff + glen + 7) / 8 + 8; const int rwords = (rlen + 7) / 8 + 1;
-  const int ops_cap = glen + rlen + 8;
-  const size_t back_bytes = ((size_t)glen * rlen * 3 + 64) * 4;
-  uint32_t *dg = nullptr, *dr = nullptr, *dback = nullptr; uint8_t* dops = nullptr; int* dout = nullptr; int8_t* dx = nullptr;
-  GmDevMem mem;
-  bool ok = mem.get(&dg, gw * 4) == hipSuccess && mem.get(&dr, (size_t)rwords * 4) == hipSuccess && mem.get(&dback, back_bytes) == hipSuccess &&
-            mem.get(&dops, ops_cap) == hipSuccess && mem.get(&dout, 16 * 4) == hipSuccess && (xrow.empty() || mem.get(&dx, xrow.size()) == hipSuccess);
-  int out[16] = {0}; std::vector<uint8_t> ops(ops_cap);
-  if (ok) {
-    ok = hipMemset(dg, 0, gw * 4) == hipSuccess && hipMemcpy(dg, genome_ls, (gw - 8) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemset(dr, 0, (size_t)rwords * 4) == hipSuccess && hipMemcpy(dr, read, (size_t)(rwords - 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         (!dx || hipMemcpy(dx, xrow.data(), xrow.size(), hipMemcpyHostToDevice) == hipSuccess) &&
-         hipMemset(dback, 0, back_bytes) == hipSuccess &&                                     // out-of-band cells: back == 0 (ref: init_cell)
-         gm_launch_sw_full_cs_single(g_sc.p, dg, goff, glen, dr, rlen, initbp | (is_rna ? GM_SEAM_RNA : 0), threshscore, anchors[0].x, anchors[0].y, anchors[0].length, anchors[0].width,
-                                     revcmpl ? 1 : 0, dback, dout, dops, ops_cap, 0, local_alignment ? 1 : 0, dx) == GM_OK &&
-         hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, 12 * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(ops.data(), dops, ops_cap, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  if (!ok) { fail("HIP failure"); return; }
-  sfr->score = out[0];
-  if (out[0] <= 0) { sfr->score = 0; sfr->dbalign = nullptr; sfr->qralign = nullptr; return; }          // below threshold: no strings (ref :1224-1226)
-  sfr->read_start = out[1]; sfr->rmapped = out[2]; sfr->genome_start = out[3]; sfr->gmapped = out[4];
-  sfr->matches += out[5]; sfr->mismatches += out[6]; sfr->insertions += out[7]; sfr->deletions += out[8]; sfr->crossovers += out[9];
-  // pretty_print, ref :945-1060: the four translations of the colour read, lower case on crossovers, N in the read shows the genome letter
-  auto nib = [](const uint32_t* b, long long i) { return (int)((b[i / 8] >> (4 * (i % 8))) & 0xf); };
-  std::vector<uint8_t> qr[4];
-  for (int k = 0; k < 4; k++) {
-    qr[k].resize(rlen); int letter = (k + initbp) % 4;
-    for (int j = 0; j < rlen; j++) {
-      const int base = nib(read, j);
-      if (base == 15) { qr[k][j] = 15; letter = (k + initbp) % 4; }
-      else {                                                   // cstols(letter, base, is_rna), ref: util.h:157-180
-        const int lt = (is_rna && letter == 4) ? 3 : letter;
-        int l2 = (lt % 2 == 0) ? ((4 + lt + base) % 4) : ((4 + lt - base) % 4); if (is_rna && l2 == 3) l2 = 4;
-        qr[k][j] = (uint8_t)((letter == 15 || base > 3) ? 15 : l2); letter = qr[k][j];
-      }
-    }
-  }
-  std::string db, q;
-  int pi = out[1], pj = out[3];
-  for (int t = 0; t < std::min(out[10], ops_cap); t++) {
-    const int type = ops[t] & 0x0f; const bool xov = (ops[t] & 0x80) != 0;
-    if (type == 1) { db.push_back(LSTRANS[nib(genome_ls, pj++)]); q.push_back('-'); continue; }
-    const bool del = type >= 2 && type <= 5;
-    const int lay = del ? type - 2 : type - 6;
-    char c = LSTRANS[qr[lay][pi++]];
-    if (xov) c = (char)tolower((int)c);
-    if (del) { db.push_back('-'); q.push_back(c); }
-    else { const char d = LSTRANS[nib(genome_ls, pj++)]; if (c == 'n' || c == 'N') c = xov ? (char)tolower((int)d) : d; db.push_back(d); q.push_back(c); }
-  }
-  sfr->dbalign = strdup(db.c_str()); sfr->qralign = strdup(q.c_str());
+  // crossover_score: one score per read position (from the QVs, ref: gmapper.c:532-544 -- clamped there to [2 * global, -1]); the kernels keep a row of them in 8 bits,
+  // and the batch body refuses a score outside them as this seam always has (a window that does not fit LDS likewise: same formula, same limit)
+  const int64_t go = goff; const uint8_t rv = revcmpl ? 1 : 0, ib = (uint8_t)initbp;
+  gm_sw_full_rec_t R; uint8_t* ops = nullptr; uint64_t ops_len = 0;
+  const int rc = sw_full_batch_impl(true, 1, genome_ls, ((uint64_t)goff + glen + 7) / 8, &go, &glen, read, (rlen + 7) / 8, &rlen, &ib, anchors, &rv, &threshscore, nullptr,
+                                    crossover_score, rlen, is_rna ? 1 : 0, local_alignment, &R, &ops, &ops_len, nullptr, nullptr, nullptr, true);
+  if (rc == GM_OK && R.status == 0 && R.score > 0 &&
+      gm_sw_full_batch_strings(1, &R, ops, ops_len, genome_ls, (uint64_t)goff + glen, read, rlen, initbp, is_rna ? 1 : 0, &sfr->dbalign, &sfr->qralign) == GM_OK) {
+    sfr->score = R.score; sfr->read_start = R.read_start; sfr->rmapped = R.rmapped; sfr->genome_start = (int)R.genome_start; sfr->gmapped = R.gmapped;
+    sfr->matches += R.matches; sfr->mismatches += R.mismatches; sfr->insertions += R.insertions; sfr->deletions += R.deletions; sfr->crossovers += R.crossovers;
+  } else if (rc == GM_OK && R.status == 0 && R.score <= 0) { sfr->score = 0; sfr->dbalign = nullptr; sfr->qralign = nullptr; }      // below threshold: no strings (ref :1224-1226)
+  else refused();
+  free(ops);
 }
 
 // ---- S2 batch: gm_sw_full_ls_batch / gm_sw_full_cs_batch -----------------------------------------------------------------------------

@@ -72,18 +72,20 @@ extern "C" int gm_index_get_windows(const gm_index_t* ix, int n, const int* cn, 
   return GM_OK;
 }
 
-// shared body: colour = gm_sw_full_cs_batch; ix: the _ix forms -- window i is (cn, gen_st, g_off, glen) of the resident genome, nothing of it is uploaded
+// shared body: colour = gm_sw_full_cs_batch; ix: the _ix forms -- window i is (cn, gen_st, g_off, glen) of the resident genome, nothing of it is uploaded; seam: sw_full_ls /
+// sw_full_cs with their one item (declared, with the default arguments, in gm_host_seams.inc)
 static int sw_full_batch_impl(bool colour, int n, const uint32_t* genome, uint64_t genome_words, const int64_t* g_off, const int* glen, const uint32_t* reads, int read_words,
                               const int* rlen, const uint8_t* initbp, const struct gm_anchor* anchors, const uint8_t* revcmpl, const int* threshscore, const int* maxscore,
                               const int* xover, int xover_stride, int is_rna, int local, gm_sw_full_rec_t* recs, uint8_t** ops, uint64_t* ops_len,
-                              const gm_index_t* ix = nullptr, const int* cn = nullptr, const uint8_t* gen_st = nullptr) {
-  const char* who = ix ? (colour ? "gm_sw_full_cs_batch_ix" : "gm_sw_full_ls_batch_ix") : (colour ? "gm_sw_full_cs_batch" : "gm_sw_full_ls_batch");
+                              const gm_index_t* ix, const int* cn, const uint8_t* gen_st, bool seam) {
+  const char* who = seam ? (colour ? "sw_full_cs" : "sw_full_ls") : ix ? (colour ? "gm_sw_full_cs_batch_ix" : "gm_sw_full_ls_batch_ix") : (colour ? "gm_sw_full_cs_batch" : "gm_sw_full_ls_batch");
   if (ops) *ops = nullptr; if (ops_len) *ops_len = 0;
   if (colour ? !g_sc.init : !g_sf.init) { gm_set_error("%s called before sw_full_%s_setup", who, colour ? "cs" : "ls"); return GM_E_NOTSETUP; }
   if (n <= 0) return GM_OK;
   if ((ix ? (!cn || !gen_st) : !genome) || !g_off || !glen || !reads || !rlen || !threshscore || !recs || !ops || !ops_len || read_words < 1 || (colour && !initbp) ||
       (xover && xover_stride < 1) || (!colour && local && !maxscore)) { gm_set_error("%s: a required argument is missing", who); return GM_E_ARG; }
-  SeamTimer tm(colour ? &g_sc.secs : &g_sf.secs);
+  double uncounted = 0;
+  SeamTimer tm(seam ? &uncounted : colour ? &g_sc.secs : &g_sf.secs);
   IxScope scope;
   if (ix) { const int rc = scope.enter(ix, is_rna); if (rc) return rc; is_rna = scope.view.genome_is_rna; }
   auto win_of = [&](int i, GmWin* w) -> const char* { return ix_window(ix, cn[i], gen_st[i], g_off[i], glen[i], w); };      // (index forms only)
@@ -107,7 +109,7 @@ static int sw_full_batch_impl(bool colour, int n, const uint32_t* genome, uint64
     if (glen[i] < 1 || rlen[i] < 1 || g_off[i] < 0 || (!ix && (uint64_t)g_off[i] + (uint64_t)glen[i] > genome_words * 8) || ((uint64_t)rlen[i] + 7) / 8 > (uint64_t)read_words) {
       refuse(GM_E_ARG, "window or read outside the bitfields"); continue; }
     if (glen[i] > dblen || rlen[i] > qrlen) { refuse(GM_E_ARG, "window / read longer than the setup sizes"); continue; }
-    const bool has_anchor = anchors && anchors[i].length > 0;
+    const bool has_anchor = anchors && (seam || anchors[i].length > 0);
     if (colour) {
       if (!has_anchor || g_sc.p[7] < 0) { refuse(GM_E_ARG, "colour space needs one anchor box (gmapper's call, ref: mapping.c:375-379)"); continue; }
       if (initbp[i] > 3) { refuse(GM_E_ARG, "initbp outside 0..3"); continue; }
@@ -159,7 +161,7 @@ static int sw_full_batch_impl(bool colour, int n, const uint32_t* genome, uint64
   GM_HIP(hipMemcpyAsync(hops.data(), dops, (size_t)ops_total, hipMemcpyDeviceToHost, 0));
   GM_HIP(hipMemcpyAsync(out.data(), dout, (size_t)n * sizeof(GmFullOut), hipMemcpyDeviceToHost, 0));
   GM_HIP(hipStreamSynchronize(0));
-  for (const GmFullItem& it : items) {                                               // (the items that ran: a refused item, or a call that failed before here, scored nothing)
+  if (!seam) for (const GmFullItem& it : items) {                                    // (the items that ran: a refused item, or a call that failed before here, scored nothing)
     if (colour) { g_sc.invocs++; g_sc.cells += 4ull * (uint64_t)it.glen * (uint64_t)it.rlen; }
     else { g_sf.invocs++; g_sf.cells += (uint64_t)it.glen * (uint64_t)it.rlen; }
   }

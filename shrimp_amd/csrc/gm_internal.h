@@ -256,11 +256,6 @@ int gm_launch_sw_vector_batch(const GmScoreDev& sc, int n, const uint32_t* d_gen
                               const uint32_t* d_reads, int read_words, const int* d_rlen, int max_g, int max_r, int* d_scores, hipStream_t stream,
                               int early_thr = 0, uint8_t* d_stopped = nullptr);   // > 0: pass 1's early stop against this threshold, stopped[i] = 1 where it fired
 
-// S2 single alignment on caller-provided bitfields
-int gm_launch_sw_full_single(const GmScoreDev& sc, const uint32_t* d_genome, long long goff, int glen, const uint32_t* d_read, int rlen,
-                             long long ax, long long ay, int alen, int awidth, int revcmpl, uint8_t* d_back, int* d_out, uint8_t* d_ops, int ops_cap,
-                             hipStream_t stream, int has_anchor = 1, int thresh = 0, int maxscore = 0, int local = 0);   // no anchor: the threshold band; local: Gflag off
-
 // colour space S1/S2 (gm_sw.hip): cs_params9 = match mismatch xover a_go a_ge b_go b_ge anchor_width indel_taboo_len (penalties positive)
 int gm_launch_sw_gapless_batch(int n, int match, int mismatch, const uint32_t* d_genome, const uint32_t* d_genome_ls, const long long* d_woff, const int* d_glen,
                                const uint32_t* d_reads, int read_words, const int* d_rlen, const int* d_gidx, const int* d_ridx, const int* d_initbp, int max_r,
@@ -268,11 +263,8 @@ int gm_launch_sw_gapless_batch(int n, int match, int mismatch, const uint32_t* d
 int gm_launch_sw_vector_batch_cs(const GmScoreDev& sc, int n, const uint32_t* d_genome_cs, const uint32_t* d_genome_ls, const long long* d_goff,
                                  const int* d_glen, const uint32_t* d_reads, int read_words, const int* d_rlen, const int* d_initbp, int max_g, int max_r,
                                  int* d_scores, hipStream_t stream);
-int gm_launch_sw_full_cs_single(const int* cs_params9, const uint32_t* d_genome_ls, long long goff, int glen, const uint32_t* d_read, int rlen, int initbp,
-                                int thresh, long long ax, long long ay, int alen, int awidth, int revcmpl, uint32_t* d_back, int* d_out, uint8_t* d_ops,
-                                int ops_cap, hipStream_t stream, int local = 0, const int8_t* d_xrow = nullptr);
 
-// S2 batch (gm_sw_full_ls_batch / gm_sw_full_cs_batch): one window as the batch kernels read it, and what they write back per window.
+// S2 (sw_full_ls / sw_full_cs are calls of one item; gm_sw_full_ls_batch / gm_sw_full_cs_batch): one window as the batch kernels read it, and what they write back per window.
 // flags: 1 = anchor box given (else the threshold band), 2 = revcmpl, 4 = the window is read on strand 1 (backwards and complemented; goff is then the global position of
 // its lowest forward base), 8 = its contig is RNA (both 0 on caller bitfields); initbp: colour space only, the primer letter | GM_SEAM_RNA; idx: the caller's item
 // (row of reads[] and of the crossover rows, slot of out[]); ops_off / ops_cap: the item's segment of the device ops buffer.

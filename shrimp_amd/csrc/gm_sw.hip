@@ -703,8 +703,79 @@ __device__ __forceinline__ void threshold_band(int glen, int rlen, int match, in
   if ((b_se - b_nw) % 2 != 0) b_se++;
   *rl = (int)((b_se - b_nw) / 2 + 1);
 }
+// The band of one anchor box: anchor_join(1 anchor) + anchor_widen(anchor_width), ref: sw-full-ls.c:176-178, anchors.c:9-61
+__device__ __forceinline__ void anchor_band(long long ax, long long ay, int alen, int awidth, int anchor_width, long long* rx, long long* ry, int* rl, int* rw) {
+  long long nw = ax + ay, sw = ax - ay, ne = sw + 2 * (awidth - 1), se = nw + 2 * (alen - 1);
+  if ((nw + sw) % 2 != 0) nw--;
+  *rx = (nw + sw) / 2; *ry = nw - *rx;
+  if ((ne - sw) % 2 != 0) ne++;
+  *rw = (int)((ne - sw) / 2 + 1);
+  if ((se - nw) % 2 != 0) se++;
+  *rl = (int)((se - nw) / 2 + 1);
+  *rx -= anchor_width / 2; *ry += anchor_width / 2; *rw += anchor_width;
+}
 
-template <bool BACK_LDS, bool LOCAL>
+// do_backtrace, ref: sw-full-ls.c:413-516 -- one lane walks from the cell full_sw_wave / full_sw_g4 returned (score > 0); the ops ('M' / 'I' / 'D') are emitted reversed, then
+// flipped; no counts all of them, ops[] holds the first ops_cap.  back: the walker's scratch, `stride` bytes a read row, read by agent-scope atomic loads.  BANDED: a cell
+// outside the band box is not believed, whatever byte lies there (see the comment above k_sw_full_batch; the pass-2 kernels ask in local mode only, where it is needed).
+struct LsWalk { int no, rstart, gstart, nm, nmm, nin, ndel; };
+template <bool LOCAL, bool BANDED>
+__device__ __forceinline__ LsWalk ls_walk(const FullOut& fo, const uint8_t* back, int stride, const uint8_t* db, const uint8_t* qr,
+                                          long long rx, long long ry, int rl, int rw, uint8_t* ops, int ops_cap) {
+  LsWalk w; w.no = 0; w.rstart = 0; w.gstart = 0; w.nm = 0; w.nmm = 0; w.nin = 0; w.ndel = 0;
+  int i = fo.max_i, j = fo.max_j;
+  // from-state: 0 nw, 1 n, 2 w  (ref :420-427: nw, then w if strictly greater, then n if strictly greater)
+  int state = 0, fs = fo.e_nw;
+  if (fo.e_w > fs) { state = 2; fs = fo.e_w; }
+  if (fo.e_n > fs) state = 1;
+  while (i >= 0 && j >= 0) {
+    // (band test first, load second: all three stops are side-effect-free breaks and every cell with 0 <= i < rlen, 0 <= j < glen lies inside the wave's scratch)
+    if (BANDED) { int bx_min, bx_max; band_range(rx, ry, rl, rw, stride, i, &bx_min, &bx_max); if (j < bx_min || j > bx_max) break; }
+    const uint8_t bb = __hip_atomic_load(&back[(size_t)i * stride + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!(bb & 0x80)) break;                // out-of-band cell: back == 0 in the reference
+    if (LOCAL && ((bb >> (4 + state)) & 1)) break;      // a floored state has a null back pointer
+    int nstate;
+    if (state == 1) {                       // FROM_NORTH_*: BACK_DELETION (gap in the genome)
+      if (w.no < ops_cap) ops[w.no] = 'D'; w.no++; w.ndel++; w.rstart = i; i--;
+      nstate = ((bb >> 2) & 1) ? 1 : 0;
+    } else if (state == 2) {                // FROM_WEST_*: BACK_INSERTION (gap in the read)
+      if (w.no < ops_cap) ops[w.no] = 'I'; w.no++; w.nin++; w.gstart = j; j--;
+      nstate = ((bb >> 3) & 1) ? 2 : 0;
+    } else {                                // FROM_NORTHWEST_*
+      if (w.no < ops_cap) ops[w.no] = 'M'; w.no++;
+      if (db[j] == qr[i]) w.nm++; else w.nmm++;
+      w.rstart = i; w.gstart = j; i--; j--;
+      nstate = (bb & 3);                    // 0 nw, 1 n, 2 w
+    }
+    state = nstate;
+  }
+  const int nov = min(w.no, ops_cap);
+  for (int a = 0, b = nov - 1; a < b; a++, b--) { uint8_t tt = ops[a]; ops[a] = ops[b]; ops[b] = tt; }
+  return w;
+}
+
+// What the four pass-2 kernels do with a selected hit before they align it.  reverse_hit (ref: mapping.c:254-263,337-339) with anchor_reverse (anchors.h:30-34): a hit on the
+// other strand than the one the read is aligned on (`turn`) is taken on the reverse-complement contig -- offset and anchor box; returns gen_st.
+__device__ __forceinline__ int p2_reverse_hit(const GmHit& h, bool turn, long long clen, int read_len, long long* g_off, long long* ax, long long* ay) {
+  *g_off = h.g_off; *ax = h.ax; *ay = h.ay;
+  if (!turn) return 0;
+  *g_off = clen - *g_off - h.w_len;
+  *ax = -*ax + (h.w_len - 1) - (h.alen - 1) - (h.awidth - 1);
+  *ay = -*ay + (read_len - 1) - (h.alen - 1) + (h.awidth - 1);
+  return 1;
+}
+// ... and the record of a window before (or without) its alignment
+__device__ __forceinline__ GmFullRes p2_blank_res(const GmHit& h, int rd, int cs_flip, int gen_st, long long g_off, int score_vector, int score_max, uint32_t ops_off, int sort_idx, size_t slot) {
+  GmFullRes R;
+  R.read_idx = rd; R.st = (int16_t)cs_flip; R.gen_st = (int16_t)gen_st; R.cn = (uint32_t)h.cn; R.g_off = (uint32_t)g_off; R.w_len = h.w_len;
+  R.score_vector = score_vector; R.score_max = score_max; R.matches = h.matches; R.score_window_gen = h.score_window_gen;
+  R.score = 0; R.read_start = 0; R.rmapped = 0; R.genome_start = 0; R.gmapped = 0;
+  R.n_match = R.n_mismatch = R.n_ins = R.n_del = 0; R.n_ops = 0; R.ops_off = ops_off;
+  R.sort_idx = sort_idx; R.hit_slot = (uint32_t)slot; R.n_xover = 0;
+  return R;
+}
+
+template <bool LOCAL>
 __global__ void __launch_bounds__(GM_WAVE)
 k_pass2(GmIndexDev ix, GmScoreDev sc, const uint32_t* __restrict__ reads, int n_reads, int read_len, int read_words,
         GmHit* __restrict__ hits, const uint16_t* __restrict__ perm, int hcap,
@@ -718,8 +789,7 @@ k_pass2(GmIndexDev ix, GmScoreDev sc, const uint32_t* __restrict__ reads, int n_
   uint8_t* qr = sm;
   uint8_t* db = sm + ((read_len + 15) & ~15);
   int* carry = (int*)(db + ((max_w + 15) & ~15));
-  // back pointers: one byte per cell; in LDS when read_len x window fits (short reads), else in a per-wave global scratch
-  uint8_t* back = BACK_LDS ? (uint8_t*)(carry + 3 * max_w) : (back_pool + (size_t)blockIdx.x * back_stride);
+  uint8_t* back = back_pool + (size_t)blockIdx.x * back_stride;      // back pointers: one byte per cell, in a per-wave global scratch (see gm_launch_pass2)
   const uint32_t n_work = *n_work_p;
   unsigned long long vcalls = 0, vcells = 0, fcalls = 0;
   int cur_rd = -1;
@@ -727,20 +797,15 @@ k_pass2(GmIndexDev ix, GmScoreDev sc, const uint32_t* __restrict__ reads, int n_
     const uint32_t wk = work[wi];
     const int rd = (int)(wk >> 6), k = (int)(wk & 63);
     const int id = sel[(size_t)rd * SEL_MAX + k];
-    int st = id >> 16; const int hi = id & 0xFFFF;
+    const int st = id >> 16, hi = id & 0xFFFF;
     const GmHit h = hits[((size_t)rd * 2 + st) * hcap + hi];
     // the read in its input orientation == read[input_strand]; a read_reverse'd mate (ref: gmapper.c:174-185) is stored reverse-complemented
     if (rd != cur_rd) { __syncthreads(); load_read(reads + (size_t)rd * read_words, read_len, input_strand != 0, qr, lane, ix.read_rna && ix.read_rna[rd]); cur_rd = rd; }
     const int cn = h.cn, w_len = h.w_len;
     const long long clen = (long long)ix.contig_off[cn + 1] - ix.contig_off[cn];
-    long long g_off = h.g_off; long long ax = h.ax, ay = h.ay; int gen_st = 0;
     const size_t slot = ((size_t)rd * 2 + st) * hcap + hi;
-    if (st != input_strand) {                                   // reverse_hit, ref: mapping.c:254-263,337-339; anchor_reverse anchors.h:30-34
-      g_off = clen - g_off - w_len;
-      ax = -ax + (w_len - 1) - (h.alen - 1) - (h.awidth - 1);
-      ay = -ay + (read_len - 1) - (h.alen - 1) + (h.awidth - 1);
-      gen_st = 1; st = input_strand;
-    }
+    long long g_off, ax, ay;
+    const int gen_st = p2_reverse_hit(h, st != input_strand, clen, read_len, &g_off, &ax, &ay);
     // the window on the gen_st strand == the + strand window of the original hit, reverse-complemented
     const uint64_t g0 = (uint64_t)ix.contig_off[cn] + h.g_off;
     __syncthreads();
@@ -754,24 +819,12 @@ k_pass2(GmIndexDev ix, GmScoreDev sc, const uint32_t* __restrict__ reads, int n_
     int sv;
     if ((h.flags & 1u) && !GM_ABL(4)) sv = h.score_vector;
     else { sv = sw_vector_wave(db, w_len, qr, read_len, sc, (int16_t*)carry, lane); vcalls++; vcells += (unsigned long long)w_len * read_len; }
-    GmFullRes R;
-    R.read_idx = rd; R.st = (int16_t)ix.cs_flip; R.gen_st = (int16_t)gen_st; R.cn = (uint32_t)cn; R.g_off = (uint32_t)g_off; R.w_len = w_len;
-    R.score_vector = sv; R.score_max = score_max; R.matches = h.matches; R.score_window_gen = h.score_window_gen;
-    R.score = 0; R.read_start = 0; R.rmapped = 0; R.genome_start = 0; R.gmapped = 0;
-    R.n_match = R.n_mismatch = R.n_ins = R.n_del = 0; R.n_ops = 0; R.ops_off = (uint32_t)(wi * (uint32_t)ops_stride);
-    R.sort_idx = sel_sidx ? sel_sidx[(size_t)rd * SEL_MAX + k] : 0; R.hit_slot = (uint32_t)slot;
+    GmFullRes R = p2_blank_res(h, rd, ix.cs_flip, gen_st, g_off, sv, score_max, (uint32_t)(wi * (uint32_t)ops_stride), sel_sidx ? sel_sidx[(size_t)rd * SEL_MAX + k] : 0, slot);
     if (write_back && lane == 0) hits[slot].score_vector = sv;          // hit_run_full_sw keeps the re-scored value in the hit (ref: mapping.c:386-388)
     if (sv >= thresh && !GM_ABL(1)) {
       fcalls++;
-      // rectangle = anchor_join(1 anchor) + anchor_widen(anchor_width), ref: sw-full-ls.c:176-178, anchors.c:9-61
-      long long nw = ax + ay, sw = ax - ay, ne = sw + 2 * (h.awidth - 1), se = nw + 2 * (h.alen - 1);
-      if ((nw + sw) % 2 != 0) nw--;
-      long long rx = (nw + sw) / 2, ry = nw - rx;
-      if ((ne - sw) % 2 != 0) ne++;
-      int rw = (int)((ne - sw) / 2 + 1);
-      if ((se - nw) % 2 != 0) se++;
-      int rl = (int)((se - nw) / 2 + 1);
-      rx -= sc.anchor_width / 2; ry += sc.anchor_width / 2; rw += sc.anchor_width;
+      long long rx, ry; int rl, rw;
+      anchor_band(ax, ay, h.alen, h.awidth, sc.anchor_width, &rx, &ry, &rl, &rw);
       __syncthreads();
       FullOut fo = full_sw_wave<LOCAL>(db, w_len, qr, read_len, sc, (gen_st != 0) && sc.tiebreak_rev, rx, ry, rl, rw, back, carry, lane);
       __syncthreads();
@@ -782,46 +835,11 @@ k_pass2(GmIndexDev ix, GmScoreDev sc, const uint32_t* __restrict__ reads, int n_
         __syncthreads();
       }
       R.score = fo.score;
-      if (fo.score > 0) {
-        // do_backtrace, ref: sw-full-ls.c:413-516 -- lane 0 walks; ops are emitted reversed then flipped
-        if (lane == 0 && !GM_ABL(2)) {
-          int i = fo.max_i, j = fo.max_j;
-          // from-state: 0 nw, 1 n, 2 w  (ref :420-427: nw, then w if strictly greater, then n if strictly greater)
-          int state = 0, fs = fo.e_nw;
-          if (fo.e_w > fs) { state = 2; fs = fo.e_w; }
-          if (fo.e_n > fs) state = 1;
-          uint8_t* o = ops + (size_t)R.ops_off;
-          int no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0;
-          while (i >= 0 && j >= 0) {
-            const uint8_t bb = BACK_LDS ? back[(size_t)i * w_len + j]
-                                        : __hip_atomic_load(&back[(size_t)i * w_len + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!(bb & 0x80)) break;                // out-of-band cell: back == 0 in the reference
-            if (LOCAL) {                            // a floored state has a null back pointer; a cell outside the band was never computed (stale byte)
-              if ((bb >> (4 + state)) & 1) break;
-              int bx_min, bx_max; band_range(rx, ry, rl, rw, w_len, i, &bx_min, &bx_max);
-              if (j < bx_min || j > bx_max) break;
-            }
-            int nstate;
-            if (state == 1) {                       // FROM_NORTH_*: BACK_DELETION (gap in the genome)
-              if (no < ops_stride) o[no] = 'D'; no++; ndel++; rstart = i; i--;
-              nstate = ((bb >> 2) & 1) ? 1 : 0;
-            } else if (state == 2) {                // FROM_WEST_*: BACK_INSERTION (gap in the read)
-              if (no < ops_stride) o[no] = 'I'; no++; nin++; gstart = j; j--;
-              nstate = ((bb >> 3) & 1) ? 2 : 0;
-            } else {                                // FROM_NORTHWEST_*
-              if (no < ops_stride) o[no] = 'M'; no++;
-              if (db[j] == qr[i]) nm++; else nmm++;
-              rstart = i; gstart = j; i--; j--;
-              nstate = (bb & 3);                    // 0 nw, 1 n, 2 w
-            }
-            state = nstate;
-          }
-          const int nov = min(no, ops_stride);
-          for (int a = 0, b = nov - 1; a < b; a++, b--) { uint8_t tt = o[a]; o[a] = o[b]; o[b] = tt; }
-          R.n_ops = no; R.read_start = rstart; R.genome_start = gstart + (int)g_off;
-          R.gmapped = fo.max_j - gstart + 1; R.rmapped = fo.max_i - rstart + 1;
-          R.n_match = nm; R.n_mismatch = nmm; R.n_ins = nin; R.n_del = ndel;
-        }
+      if (fo.score > 0 && lane == 0 && !GM_ABL(2)) {
+        const LsWalk w = ls_walk<LOCAL, LOCAL>(fo, back, w_len, db, qr, rx, ry, rl, rw, ops + (size_t)R.ops_off, ops_stride);
+        R.n_ops = w.no; R.read_start = w.rstart; R.genome_start = w.gstart + (int)g_off;
+        R.gmapped = fo.max_j - w.gstart + 1; R.rmapped = fo.max_i - w.rstart + 1;
+        R.n_match = w.nm; R.n_mismatch = w.nmm; R.n_ins = w.nin; R.n_del = w.ndel;
       }
     }
     if (lane == 0) res[wi] = R;
@@ -1023,18 +1041,13 @@ k_pass2_g4(GmIndexDev ix, GmScoreDev sc, const uint32_t* __restrict__ reads, int
     const uint32_t wk = has ? work[wi] : 0u;
     const int rd = (int)(wk >> 6), k = (int)(wk & 63);
     const int id = has ? sel[(size_t)rd * SEL_MAX + k] : 0;
-    int st = id >> 16; const int hi = id & 0xFFFF;
+    const int st = id >> 16, hi = id & 0xFFFF;
     const size_t slot = ((size_t)rd * 2 + st) * hcap + hi;
     GmHit h; if (has) h = hits[slot]; else { h.g_off = 0; h.ax = h.ay = 0; h.alen = h.awidth = 1; h.score_window_gen = 0; h.score_vector = 0; h.pct_score_vector = 0; h.cn = 0; h.w_len = 1; h.matches = 0; h.flags = 1; }
     const int cn = h.cn, w_len = h.w_len;
     const long long clen = (long long)ix.contig_off[cn + 1] - ix.contig_off[cn];
-    long long g_off = h.g_off; long long ax = h.ax, ay = h.ay; int gen_st = 0;
-    if (st != input_strand) {                                   // reverse_hit, ref: mapping.c:254-263,337-339; anchor_reverse anchors.h:30-34
-      g_off = clen - g_off - w_len;
-      ax = -ax + (w_len - 1) - (h.alen - 1) - (h.awidth - 1);
-      ay = -ay + (read_len - 1) - (h.alen - 1) + (h.awidth - 1);
-      gen_st = 1; st = input_strand;
-    }
+    long long g_off, ax, ay;
+    const int gen_st = p2_reverse_hit(h, st != input_strand, clen, read_len, &g_off, &ax, &ay);
     const uint64_t g0 = (uint64_t)ix.contig_off[cn] + h.g_off;
     const int rna_bits = ((ix.contig_rna && has && ix.contig_rna[cn]) ? 2 : 0) | ((ix.read_rna && has && ix.read_rna[rd]) ? 4 : 0);
     __syncthreads();
@@ -1058,25 +1071,12 @@ k_pass2_g4(GmIndexDev ix, GmScoreDev sc, const uint32_t* __restrict__ reads, int
       __syncthreads();
       if (g == gg) { sv = v; if (l == 0) { vcalls++; vcells += (unsigned long long)w_len * read_len; } }
     }
-    GmFullRes R;
-    R.read_idx = rd; R.st = (int16_t)ix.cs_flip; R.gen_st = (int16_t)gen_st; R.cn = (uint32_t)cn; R.g_off = (uint32_t)g_off; R.w_len = w_len;
-    R.score_vector = sv; R.score_max = score_max; R.matches = h.matches; R.score_window_gen = h.score_window_gen;
-    R.score = 0; R.read_start = 0; R.rmapped = 0; R.genome_start = 0; R.gmapped = 0;
-    R.n_match = R.n_mismatch = R.n_ins = R.n_del = 0; R.n_ops = 0; R.ops_off = (uint32_t)(wi * (uint32_t)ops_stride);
-    R.sort_idx = (sel_sidx && has) ? sel_sidx[(size_t)rd * SEL_MAX + k] : 0; R.hit_slot = (uint32_t)slot;
+    GmFullRes R = p2_blank_res(h, rd, ix.cs_flip, gen_st, g_off, sv, score_max, (uint32_t)(wi * (uint32_t)ops_stride), (sel_sidx && has) ? sel_sidx[(size_t)rd * SEL_MAX + k] : 0, slot);
     if (write_back && has && l == 0) hits[slot].score_vector = sv;      // hit_run_full_sw keeps the re-scored value in the hit (ref: mapping.c:386-388)
     const bool act = has && sv >= thresh;
     if (act && l == 0) fcalls++;
-    // rectangle = anchor_join(1 anchor) + anchor_widen(anchor_width), ref: sw-full-ls.c:176-178, anchors.c:9-61
     long long rx, ry; int rw, rl;
-    { long long nw = ax + ay, sw = ax - ay, ne = sw + 2 * (h.awidth - 1), se = nw + 2 * (h.alen - 1);
-      if ((nw + sw) % 2 != 0) nw--;
-      rx = (nw + sw) / 2; ry = nw - rx;
-      if ((ne - sw) % 2 != 0) ne++;
-      rw = (int)((ne - sw) / 2 + 1);
-      if ((se - nw) % 2 != 0) se++;
-      rl = (int)((se - nw) / 2 + 1);
-      rx -= sc.anchor_width / 2; ry += sc.anchor_width / 2; rw += sc.anchor_width; }
+    anchor_band(ax, ay, h.alen, h.awidth, sc.anchor_width, &rx, &ry, &rl, &rw);
     __syncthreads();
     FullOut fo = rev_u ? full_sw_g4<G, CT, LOCAL, true>(db, w_len, qr, read_len, sc, act, rx, ry, rl, rw, back, carry, lane)
                        : full_sw_g4<G, CT, LOCAL, false>(db, w_len, qr, read_len, sc, act, rx, ry, rl, rw, back, carry, lane);
@@ -1093,42 +1093,11 @@ k_pass2_g4(GmIndexDev ix, GmScoreDev sc, const uint32_t* __restrict__ reads, int
       }
     }
     R.score = act ? fo.score : 0;
-    if (act && fo.score > 0 && l == 0) {
-      // do_backtrace, ref: sw-full-ls.c:413-516 -- the group's first lane walks; ops are emitted reversed then flipped
-      int i = fo.max_i, j = fo.max_j;
-      int state = 0, fs = fo.e_nw;                               // from-state: 0 nw, 1 n, 2 w  (ref :420-427: nw, then w if strictly greater, then n if strictly greater)
-      if (fo.e_w > fs) { state = 2; fs = fo.e_w; }
-      if (fo.e_n > fs) state = 1;
-      uint8_t* o = ops + (size_t)R.ops_off;
-      int no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0;
-      while (i >= 0 && j >= 0) {
-        const uint8_t bb = __hip_atomic_load(&back[(size_t)i * w_len + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!(bb & 0x80)) break;                // out-of-band cell: back == 0 in the reference
-        if (LOCAL) {                            // a floored state has a null back pointer; a cell outside the band was never computed (stale byte)
-          if ((bb >> (4 + state)) & 1) break;
-          int bx_min, bx_max; band_range(rx, ry, rl, rw, w_len, i, &bx_min, &bx_max);
-          if (j < bx_min || j > bx_max) break;
-        }
-        int nstate;
-        if (state == 1) {                       // FROM_NORTH_*: BACK_DELETION (gap in the genome)
-          if (no < ops_stride) o[no] = 'D'; no++; ndel++; rstart = i; i--;
-          nstate = ((bb >> 2) & 1) ? 1 : 0;
-        } else if (state == 2) {                // FROM_WEST_*: BACK_INSERTION (gap in the read)
-          if (no < ops_stride) o[no] = 'I'; no++; nin++; gstart = j; j--;
-          nstate = ((bb >> 3) & 1) ? 2 : 0;
-        } else {                                // FROM_NORTHWEST_*
-          if (no < ops_stride) o[no] = 'M'; no++;
-          if (db[j] == qr[i]) nm++; else nmm++;
-          rstart = i; gstart = j; i--; j--;
-          nstate = (bb & 3);                    // 0 nw, 1 n, 2 w
-        }
-        state = nstate;
-      }
-      const int nov = min(no, ops_stride);
-      for (int a = 0, b = nov - 1; a < b; a++, b--) { uint8_t tt = o[a]; o[a] = o[b]; o[b] = tt; }
-      R.n_ops = no; R.read_start = rstart; R.genome_start = gstart + (int)g_off;
-      R.gmapped = fo.max_j - gstart + 1; R.rmapped = fo.max_i - rstart + 1;
-      R.n_match = nm; R.n_mismatch = nmm; R.n_ins = nin; R.n_del = ndel;
+    if (act && fo.score > 0 && l == 0) {                         // the group's first lane walks
+      const LsWalk w = ls_walk<LOCAL, LOCAL>(fo, back, w_len, db, qr, rx, ry, rl, rw, ops + (size_t)R.ops_off, ops_stride);
+      R.n_ops = w.no; R.read_start = w.rstart; R.genome_start = w.gstart + (int)g_off;
+      R.gmapped = fo.max_j - w.gstart + 1; R.rmapped = fo.max_i - w.rstart + 1;
+      R.n_match = w.nm; R.n_mismatch = w.nmm; R.n_ins = w.nin; R.n_del = w.ndel;
     }
     if (has && l == 0) res[wi] = R;
   }
@@ -1185,85 +1154,9 @@ k_sw_vector_batch(GmScoreDev sc, int n, const uint32_t* __restrict__ genome, con
 }
 
 // ---------------------------------------------------------------------------------------------
-// S2 single call: sw_full_ls on caller bitfields (ref: common/sw-full-ls.c:637-683), global mode.
-// out[0..12] = score read_start rmapped genome_start gmapped matches mismatches insertions deletions n_ops max_i max_j 0
-// ---------------------------------------------------------------------------------------------
-template <bool LOCAL>
-__global__ void __launch_bounds__(GM_WAVE)
-k_sw_full_single(GmScoreDev sc, const uint32_t* __restrict__ genome, long long goff, int glen, const uint32_t* __restrict__ read, int rlen,
-                 long long ax, long long ay, int alen, int awidth, int has_anchor, int thresh, int maxscore, int revcmpl,
-                 uint8_t* __restrict__ back, int* __restrict__ out, uint8_t* __restrict__ ops, int ops_cap) {
-  extern __shared__ __align__(16) uint8_t sm[];
-  const int lane = threadIdx.x;
-  uint8_t* qr = sm;
-  uint8_t* db = sm + ((rlen + 15) & ~15);
-  int* carry = (int*)(db + ((glen + 15) & ~15));
-  load_read(read, rlen, false, qr, lane);
-  load_window(genome, (uint64_t)goff, glen, false, db, lane);
-  __syncthreads();
-  long long rx, ry; int rw, rl;
-  if (has_anchor) {
-    long long nw = ax + ay, sw = ax - ay, ne = sw + 2 * (awidth - 1), se = nw + 2 * (alen - 1);
-    if ((nw + sw) % 2 != 0) nw--;
-    rx = (nw + sw) / 2; ry = nw - rx;
-    if ((ne - sw) % 2 != 0) ne++;
-    rw = (int)((ne - sw) / 2 + 1);
-    if ((se - nw) % 2 != 0) se++;
-    rl = (int)((se - nw) / 2 + 1);
-    rx -= sc.anchor_width / 2; ry += sc.anchor_width / 2; rw += sc.anchor_width;
-  } else threshold_band(glen, rlen, sc.match, thresh, &rx, &ry, &rl, &rw);       // ref: sw-full-ls.c:179-192
-  FullOut fo = full_sw_wave<LOCAL>(db, glen, qr, rlen, sc, revcmpl != 0, rx, ry, rl, rw, back, carry, lane);
-  __syncthreads();
-  if (LOCAL && has_anchor && fo.score != maxscore) {                              // ref: sw-full-ls.c:395-398
-    threshold_band(glen, rlen, sc.match, thresh, &rx, &ry, &rl, &rw);
-    fo = full_sw_wave<LOCAL>(db, glen, qr, rlen, sc, revcmpl != 0, rx, ry, rl, rw, back, carry, lane);
-    __syncthreads();
-  }
-  if (lane == 0) {
-    int i = fo.max_i, j = fo.max_j, no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0;
-    if (fo.score > 0) {
-      int state = 0, fs = fo.e_nw;
-      if (fo.e_w > fs) { state = 2; fs = fo.e_w; }
-      if (fo.e_n > fs) state = 1;
-      while (i >= 0 && j >= 0) {
-        const uint8_t bb = __hip_atomic_load(&back[(size_t)i * glen + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!(bb & 0x80)) break;
-        if (LOCAL) {
-          if ((bb >> (4 + state)) & 1) break;
-          int bx_min, bx_max; band_range(rx, ry, rl, rw, glen, i, &bx_min, &bx_max);
-          if (j < bx_min || j > bx_max) break;
-        }
-        int nstate;
-        if (state == 1) { if (no < ops_cap) ops[no] = 'D'; no++; ndel++; rstart = i; i--; nstate = ((bb >> 2) & 1) ? 1 : 0; }
-        else if (state == 2) { if (no < ops_cap) ops[no] = 'I'; no++; nin++; gstart = j; j--; nstate = ((bb >> 3) & 1) ? 2 : 0; }
-        else { if (no < ops_cap) ops[no] = 'M'; no++; if (db[j] == qr[i]) nm++; else nmm++; rstart = i; gstart = j; i--; j--; nstate = (bb & 3); }
-        state = nstate;
-      }
-      const int nov = min(no, ops_cap);
-      for (int a = 0, b = nov - 1; a < b; a++, b--) { uint8_t tt = ops[a]; ops[a] = ops[b]; ops[b] = tt; }
-    }
-    out[0] = fo.score; out[1] = rstart; out[2] = fo.max_i - rstart + 1; out[3] = gstart + (int)goff; out[4] = fo.max_j - gstart + 1;
-    out[5] = nm; out[6] = nmm; out[7] = nin; out[8] = ndel; out[9] = no; out[10] = fo.max_i; out[11] = fo.max_j;
-  }
-}
-
-int gm_launch_sw_full_single(const GmScoreDev& sc, const uint32_t* d_genome, long long goff, int glen, const uint32_t* d_read, int rlen,
-                             long long ax, long long ay, int alen, int awidth, int revcmpl, uint8_t* d_back, int* d_out, uint8_t* d_ops, int ops_cap,
-                             hipStream_t stream, int has_anchor, int thresh, int maxscore, int local) {
-  const size_t lds = ((rlen + 15) & ~15) + ((glen + 15) & ~15) + (size_t)glen * 12 + 64;
-  if (local)
-    hipLaunchKernelGGL(k_sw_full_single<true>, dim3(1), dim3(GM_WAVE), lds, stream, sc, d_genome, goff, glen, d_read, rlen, ax, ay, alen, awidth, has_anchor, thresh,
-                       maxscore, revcmpl, d_back, d_out, d_ops, ops_cap);
-  else
-    hipLaunchKernelGGL(k_sw_full_single<false>, dim3(1), dim3(GM_WAVE), lds, stream, sc, d_genome, goff, glen, d_read, rlen, ax, ay, alen, awidth, has_anchor, thresh,
-                       maxscore, revcmpl, d_back, d_out, d_ops, ops_cap);
-  GM_HIP(hipGetLastError());
-  return GM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// S2 batch: n independent sw_full_ls calls on caller bitfields, grid-stride over the items, one wave per item at a time (k_sw_full_single per item:
-// same band arithmetic, same full_sw_wave, same walk on lane 0).  LDS is laid out for the call's longest read and window.
+// S2: n independent sw_full_ls calls on caller bitfields (ref: common/sw-full-ls.c:637-683), grid-stride over the items, one wave per item at a time: the band of
+// the item's anchor box or of its threshold, full_sw_wave, ls_walk on lane 0.  sw_full_ls itself is a call of one item.  LDS is laid out for the call's longest read
+// and window.
 //
 // Back-pointer scratch belongs to the wave (blockIdx.x), not to the item: a wave's items of any shape follow each other through the same bytes, row
 // stride = the current item's glen.  Why stale bytes of an earlier item are never taken for this item's:
@@ -1271,12 +1164,12 @@ int gm_launch_sw_full_single(const GmScoreDev& sc, const uint32_t* d_genome, lon
 //    (`inband`), so a byte the current item did not write belongs to a cell OUTSIDE its band;
 //  * global mode: a cell outside the band holds FS_NEG in all three states, so a state that is finite was derived from finite states only, i.e. from
 //    band cells or the virtual row above the matrix.  The walk starts at a cell of positive score and follows the source of a finite state to a
-//    finite state: it cannot step outside the band.  (That is why the `!(bb & 0x80)` test alone was enough on freshly allocated memory, where
+//    finite state: it cannot step outside the band.  (That is why the `!(bb & 0x80)` test alone is enough in the global-mode pass-2 kernels, where
 //    it never fires for score > 0.)
 //  * local mode: a cell outside the band reads as (0, -b_open, -a_open), a band cell CAN derive from it, and the reference stops there on its
-//    null back pointer.  The walk tests the band box itself (band_range) before it believes a byte -- as k_pass2 / k_pass2_g4 do on their reused scratch.
-// The band test is applied in both modes here, so the stop never depends on what an earlier item left behind.  Reads of the scratch are
-// agent-scope atomic loads (no stale line of an earlier item in the vector cache); an item's stores precede its walk by a barrier, and the next
+//    null back pointer.  The walk tests the band box itself (band_range) before it believes a byte -- in k_pass2 / k_pass2_g4 on their reused scratch too.
+// The band test is applied in both modes here (ls_walk's BANDED), so the stop never depends on what an earlier item left behind.  Reads of the scratch
+// are agent-scope atomic loads (no stale line of an earlier item in the vector cache); an item's stores precede its walk by a barrier, and the next
 // item's stores follow the walk in program order of the same wave.
 // ---------------------------------------------------------------------------------------------
 template <bool LOCAL, bool IX = false>      // IX: gm_sw_full_ls_batch_ix -- the strand / RNA bits of GmFullItem.flags are read (an instantiation of its own)
@@ -1298,16 +1191,8 @@ k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ 
     __syncthreads();
     const bool has_anchor = (flags & 1) != 0, revcmpl = (flags & 2) != 0;
     long long rx, ry; int rw, rl;
-    if (has_anchor) {                                                             // anchor_join(1 anchor) + anchor_widen, as k_sw_full_single
-      long long nw = it.ax + it.ay, sw = it.ax - it.ay, ne = sw + 2 * (it.awidth - 1), se = nw + 2 * (it.alen - 1);
-      if ((nw + sw) % 2 != 0) nw--;
-      rx = (nw + sw) / 2; ry = nw - rx;
-      if ((ne - sw) % 2 != 0) ne++;
-      rw = (int)((ne - sw) / 2 + 1);
-      if ((se - nw) % 2 != 0) se++;
-      rl = (int)((se - nw) / 2 + 1);
-      rx -= sc.anchor_width / 2; ry += sc.anchor_width / 2; rw += sc.anchor_width;
-    } else threshold_band(glen, rlen, sc.match, it.thresh, &rx, &ry, &rl, &rw);  // ref: sw-full-ls.c:179-192
+    if (has_anchor) anchor_band(it.ax, it.ay, it.alen, it.awidth, sc.anchor_width, &rx, &ry, &rl, &rw);
+    else threshold_band(glen, rlen, sc.match, it.thresh, &rx, &ry, &rl, &rw);    // ref: sw-full-ls.c:179-192
     FullOut fo = full_sw_wave<LOCAL>(db, glen, qr, rlen, sc, revcmpl, rx, ry, rl, rw, back, carry, lane);
     __syncthreads();
     if (LOCAL && has_anchor && fo.score != it.maxscore) {                         // ref: sw-full-ls.c:395-398 (per item: the waves diverge, a wave does not)
@@ -1316,30 +1201,11 @@ k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ 
       __syncthreads();
     }
     if (lane == 0) {
-      uint8_t* ops = ops_all + it.ops_off; const int ops_cap = it.ops_cap;
-      int i = fo.max_i, j = fo.max_j, no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0;
-      if (fo.score > 0) {
-        int state = 0, fs = fo.e_nw;
-        if (fo.e_w > fs) { state = 2; fs = fo.e_w; }
-        if (fo.e_n > fs) state = 1;
-        while (i >= 0 && j >= 0) {
-          int bx_min, bx_max; band_range(rx, ry, rl, rw, glen, i, &bx_min, &bx_max);
-          if (j < bx_min || j > bx_max) break;                                    // outside the band: not this item's byte (see above)
-          const uint8_t bb = __hip_atomic_load(&back[(size_t)i * glen + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (!(bb & 0x80)) break;
-          if (LOCAL && ((bb >> (4 + state)) & 1)) break;
-          int nstate;
-          if (state == 1) { if (no < ops_cap) ops[no] = 'D'; no++; ndel++; rstart = i; i--; nstate = ((bb >> 2) & 1) ? 1 : 0; }
-          else if (state == 2) { if (no < ops_cap) ops[no] = 'I'; no++; nin++; gstart = j; j--; nstate = ((bb >> 3) & 1) ? 2 : 0; }
-          else { if (no < ops_cap) ops[no] = 'M'; no++; if (db[j] == qr[i]) nm++; else nmm++; rstart = i; gstart = j; i--; j--; nstate = (bb & 3); }
-          state = nstate;
-        }
-        const int nov = min(no, ops_cap);
-        for (int a = 0, b = nov - 1; a < b; a++, b--) { uint8_t tt = ops[a]; ops[a] = ops[b]; ops[b] = tt; }
-      }
+      LsWalk w; w.no = 0; w.rstart = 0; w.gstart = 0; w.nm = 0; w.nmm = 0; w.nin = 0; w.ndel = 0;
+      if (fo.score > 0) w = ls_walk<LOCAL, true>(fo, back, glen, db, qr, rx, ry, rl, rw, ops_all + it.ops_off, it.ops_cap);
       GmFullOut o;
-      o.v[0] = fo.score; o.v[1] = rstart; o.v[2] = fo.max_i - rstart + 1; o.v[3] = gstart; o.v[4] = fo.max_j - gstart + 1;
-      o.v[5] = nm; o.v[6] = nmm; o.v[7] = nin; o.v[8] = ndel; o.v[9] = 0; o.v[10] = no; o.v[11] = 0;
+      o.v[0] = fo.score; o.v[1] = w.rstart; o.v[2] = fo.max_i - w.rstart + 1; o.v[3] = w.gstart; o.v[4] = fo.max_j - w.gstart + 1;
+      o.v[5] = w.nm; o.v[6] = w.nmm; o.v[7] = w.nin; o.v[8] = w.ndel; o.v[9] = 0; o.v[10] = w.no; o.v[11] = 0;
       out[it.idx] = o;
     }
   }
@@ -1416,17 +1282,16 @@ int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* 
                     const int32_t* d_sel_sidx, int input_strand, int write_back, uint32_t* d_order, uint32_t* d_cls_cnt) {
   if (n_reads == 0) return GM_OK;
   const int p2_ablate = gm_tune("GM_P2_ABLATE") ? atoi(gm_tune("GM_P2_ABLATE")) : 0;
-  size_t lds = ((read_len + 15) & ~15) + ((window_len + 15) & ~15) + (size_t)window_len * 12 + 64;
-  const size_t back_bytes = (size_t)read_len * window_len;
-#define GM_P2_LAUNCH(BL, LOC) hipLaunchKernelGGL((k_pass2<BL, LOC>), dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, d_reads, n_reads, read_len, read_words, \
+  const size_t lds = gm_sw_full_batch_lds(window_len, read_len);
+#define GM_P2_LAUNCH(LOC) hipLaunchKernelGGL((k_pass2<LOC>), dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, d_reads, n_reads, read_len, read_words, \
     d_hits, d_perm, hcap, d_sel, d_sel_sidx, input_strand, write_back, d_sel_cnt, d_work, d_n_work, d_res, d_ops, ops_stride, d_back, back_stride, window_len, d_stats, p2_ablate)
   // Back pointers in LDS (14 KB per wave at 100 bp) cap the CU at ten waves; in a per-wave global scratch (L2-resident) the CU runs at full
-  // occupancy: measured 109 -> 37 ms per 1 M reads on the 3 Gbp workload.  The LDS form stays for comparison (GM_P2_BACK_LDS=1).
+  // occupancy: measured 109 -> 37 ms per 1 M reads on the 3 Gbp workload.  That is why the scratch is global.
   // Four windows per wave (k_pass2_g4) unless GM_P2_G4=0 asks for the one-window kernel; its wave owns that many consecutive back-pointer scratches.  Eight windows (groups of
   // 8 lanes, int16_t carry rows, see cs_carry_ld) were built and measured for letter space too (tuning builds: GM_P2_G=8): 18.9 against 15.8 ms per 1 M 100-base reads -- the
   // letter-space cell is ~30 instructions, so the thirteen stripes' set-up and the carry traffic of every step weigh more than the steps saved; colour space (360 instructions
   // a cell) takes eight.
-  const bool g4 = !(gm_tune("GM_P2_G4") && atoi(gm_tune("GM_P2_G4")) == 0) && !gm_tune("GM_P2_BACK_LDS") && grid >= 8 && d_order && d_cls_cnt;
+  const bool g4 = !(gm_tune("GM_P2_G4") && atoi(gm_tune("GM_P2_G4")) == 0) && grid >= 8 && d_order && d_cls_cnt;
   if (g4) {
     const size_t r16 = (size_t)((read_len + 15) & ~15), w16 = (size_t)((window_len + 15) & ~15);
     // no score on a path through the matrix lies further from 0 than `reach`: a path has at most read_len + window_len moves, and a move changes the score by a match, a
@@ -1454,13 +1319,7 @@ int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* 
 #endif
     { if (sc.local) GM_P2_G4L(16, int, true); else GM_P2_G4L(16, int, false); }
 #undef GM_P2_G4L
-  } else
-  if (back_bytes <= 40 * 1024 && gm_tune("GM_P2_BACK_LDS")) {
-    lds += back_bytes + 16;
-    if (sc.local) GM_P2_LAUNCH(true, true); else GM_P2_LAUNCH(true, false);
-  } else {
-    if (sc.local) GM_P2_LAUNCH(false, true); else GM_P2_LAUNCH(false, false);
-  }
+  } else { if (sc.local) GM_P2_LAUNCH(true); else GM_P2_LAUNCH(false); }
 #undef GM_P2_LAUNCH
   GM_HIP(hipGetLastError());
   return GM_OK;
@@ -1667,92 +1526,63 @@ __device__ CsBest full_sw_cs_wave(const uint8_t* db, int glen, const uint8_t* qr
                  : full_sw_cs_wave_t<false, TABOO>(db, glen, qr4, qstride, rlen, P, rx, ry, rl, rw, back, carry, lane, xrow);
 }
 
-// out[0..11] = score read_start rmapped genome_start gmapped matches mismatches insertions deletions crossovers n_ops 0;
-// ops[] = the reference's backtrace bytes in alignment order (type 1 insertion, 2-5 deletion in layer A-D, 6-9 match/mismatch in layer A-D; | 0x80 crossover)
-// (local mode lives in the four-window routine further down: the single call runs it with one group of 16 lanes)
-template <int G, typename CT, bool REV, bool TABOO, bool LOCAL>
-__device__ CsBest full_sw_cs_g4(const uint8_t* db, int glen, const uint8_t* qr4, int qstride, int rlen, const GmCsDev& P, bool act,
-                                int rx, int ry, int rl, int rw, uint32_t* back, CT* carry, int lane, const int8_t* xrow);
-__global__ void __launch_bounds__(GM_WAVE)
-k_sw_full_cs_single(GmCsDev P, const uint32_t* __restrict__ genome_ls, long long goff, int glen, const uint32_t* __restrict__ read, int rlen, int initbp,
-                    int thresh, long long ax, long long ay, int alen, int awidth, int revcmpl, uint32_t* __restrict__ back, int* __restrict__ out,
-                    uint8_t* __restrict__ ops, int ops_cap, int local, const int8_t* __restrict__ xrow) {
-  extern __shared__ __align__(16) uint8_t sm[];
-  const int lane = threadIdx.x;
-  const int qstride = (rlen + 15) & ~15;
-  uint8_t* rc = sm;                                   // colours
-  uint8_t* qr4 = rc + qstride;                        // four translations
-  uint8_t* db = qr4 + 4 * qstride;
-  int* carry = (int*)(db + ((glen + 15) & ~15));
-  load_read(read, rlen, false, rc, lane);
-  load_window(genome_ls, (uint64_t)goff, glen, false, db, lane);
-  __syncthreads();
-  const bool is_rna = (initbp & GM_SEAM_RNA) != 0; initbp &= 0xff;      // (is_rna rides in bit 8 of the primer word)
-  if (lane < 4) {                                     // ref :1182-1197
-    int letter = (lane + initbp) % 4;
-    for (int j = 0; j < rlen; j++) {
-      const int base = rc[j];
-      if (base == 15) { qr4[lane * qstride + j] = 15; letter = (lane + initbp) % 4; }
-      else { const int l2 = cs_cstols(letter, base, is_rna); qr4[lane * qstride + j] = (uint8_t)l2; letter = l2; }
-    }
-  }
-  __syncthreads();
-  long long nw = ax + ay, sw = ax - ay, ne = sw + 2 * (awidth - 1), se = nw + 2 * (alen - 1);      // anchor_join + anchor_widen, ref: anchors.c:9-61
-  if ((nw + sw) % 2 != 0) nw--;
-  long long rx = (nw + sw) / 2, ry = nw - rx;
-  if ((ne - sw) % 2 != 0) ne++;
-  int rw = (int)((ne - sw) / 2 + 1);
-  if ((se - nw) % 2 != 0) se++;
-  int rl = (int)((se - nw) / 2 + 1);
-  rx -= P.anchor_width / 2; ry += P.anchor_width / 2; rw += P.anchor_width;
-  CsBest fo;
-  if (local) {                                        // ref: sw-full-cs.c:199-203,315,439-552
-    const bool act = lane < 16;
-    if (revcmpl) fo = P.taboo > 0 ? full_sw_cs_g4<16, int, true, true, true>(db, glen, qr4, qstride, rlen, P, act, (int)rx, (int)ry, rl, rw, back, carry, lane, xrow)
-                                  : full_sw_cs_g4<16, int, true, false, true>(db, glen, qr4, qstride, rlen, P, act, (int)rx, (int)ry, rl, rw, back, carry, lane, xrow);
-    else fo = P.taboo > 0 ? full_sw_cs_g4<16, int, false, true, true>(db, glen, qr4, qstride, rlen, P, act, (int)rx, (int)ry, rl, rw, back, carry, lane, xrow)
-                          : full_sw_cs_g4<16, int, false, false, true>(db, glen, qr4, qstride, rlen, P, act, (int)rx, (int)ry, rl, rw, back, carry, lane, xrow);
-  } else fo = full_sw_cs_wave<true>(db, glen, qr4, qstride, rlen, P, revcmpl != 0, rx, ry, rl, rw, back, carry, lane, xrow);
-  __syncthreads();
-  __threadfence();
-  if (lane == 0) {
-    int res[12] = {0};
-    if (fo.score >= 0 && fo.score >= thresh) {         // ref :1216; do_backtrace :633-937
-      auto code_at = [&](int ci, int cj, int word, int lay) -> int {
-        const uint32_t w = __hip_atomic_load(&back[((size_t)ci * glen + cj) * 3 + word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return (int)((w >> (8 * lay)) & 0xFFu);
-      };
-      int i = fo.i, j = fo.j, k = fo.k;
-      int from = code_at(i, j, 0, k), fromscore = fo.e_nw;
-      if (fo.e_w > fromscore) { from = code_at(i, j, 2, k); fromscore = fo.e_w; }
-      if (fo.e_n > fromscore) from = code_at(i, j, 1, k);
-      int no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0, nx = 0;
-      while (i >= 0 && j >= 0 && from != 0) {
-        const int dir = from >> 2, lay = from & 3;
-        uint8_t bt;
-        if (dir == 1 || dir == 2) { ndel++; rstart = i--; bt = (uint8_t)(2 + k); }
-        else if (dir == 3 || dir == 4) { nin++; gstart = j--; bt = 1; }
-        else {
-          const int qv = qr4[k * qstride + i];
-          if (db[j] == qv || db[j] == 15 || qv == 15) nm++; else nmm++;
-          rstart = i--; gstart = j--; bt = (uint8_t)(6 + k);
-        }
-        if (k != lay) { bt |= 0x80; nx++; k = lay; }
-        if (no < ops_cap) ops[no] = bt;
-        no++;
-        if (i < 0 || j < 0) break;                    // the virtual row / left sentinel: back == 0 in the reference
-        const int word = (dir == 1 || dir == 5) ? 1 : ((dir == 4 || dir == 7) ? 2 : 0);
-        from = code_at(i, j, word, k);
-      }
-      if (k != 0 && no > 0) { if (no - 1 < ops_cap) ops[no - 1] |= 0x80; nx++; }     // ref :929-932
-      const int nov = min(no, ops_cap);
-      for (int a2 = 0, b2 = nov - 1; a2 < b2; a2++, b2--) { const uint8_t tt = ops[a2]; ops[a2] = ops[b2]; ops[b2] = tt; }
-      res[0] = fo.score; res[1] = rstart; res[2] = fo.i - rstart + 1; res[3] = gstart + (int)goff; res[4] = fo.j - gstart + 1;
-      res[5] = nm; res[6] = nmm; res[7] = nin; res[8] = ndel; res[9] = nx; res[10] = no;
-    }
-    for (int x = 0; x < 12; x++) out[x] = res[x];
+// The four letter translations of a colour read (ref: sw-full-cs.c:1182-1197): lane l < 4 of a wave or group writes the one that starts from letter (l + initbp) % 4
+__device__ __forceinline__ void cs_translate4(const uint8_t* rc, int rlen, int initbp, bool is_rna, uint8_t* qr4, int qstride, int l) {
+  int letter = (l + initbp) % 4;
+  for (int j = 0; j < rlen; j++) {
+    const int base = rc[j];
+    if (base == 15) { qr4[l * qstride + j] = 15; letter = (l + initbp) % 4; }
+    else { const int l2 = cs_cstols(letter, base, is_rna); qr4[l * qstride + j] = (uint8_t)l2; letter = l2; }
   }
 }
+
+// do_backtrace, ref: sw-full-cs.c:633-937 -- one lane walks from the cell full_sw_cs_wave / full_sw_cs_g4 returned.  ops[0 .. cap) = the reference's backtrace bytes in
+// alignment order (type 1 insertion, 2-5 deletion in layer A-D, 6-9 match/mismatch in layer A-D; | 0x80 crossover); no counts all of them.  CODES: ops[cap .. 2 cap) = the two
+// 4-bit codes the reference prints for the column (genome letter << 4 | read letter).  back: the walker's scratch, three words a cell, reused from window to window: a cell
+// outside the band box keeps back == 0 in the reference, so the box is asked before a word is believed (every cell inside it was written for this window).
+struct CsWalk { int no, rstart, gstart, nm, nmm, nin, ndel, nx; };
+template <bool CODES, typename XT>      // XT: long long, or int where the caller has narrowed the box
+__device__ __forceinline__ CsWalk cs_walk(const CsBest& fo, const uint32_t* back, int glen, const uint8_t* db, const uint8_t* qr4, int qstride,
+                                          XT rx, XT ry, int rl, int rw, uint8_t* ops, int cap) {
+  auto code_at = [&](int ci, int cj, int word, int lay) -> int {
+    int x_min, x_max; band_range(rx, ry, rl, rw, glen, ci, &x_min, &x_max);
+    if (cj < x_min || cj > x_max) return 0;
+    const uint32_t w = __hip_atomic_load(&back[((size_t)ci * glen + cj) * 3 + word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (int)((w >> (8 * lay)) & 0xFFu);
+  };
+  CsWalk w; w.no = 0; w.rstart = 0; w.gstart = 0; w.nm = 0; w.nmm = 0; w.nin = 0; w.ndel = 0; w.nx = 0;
+  uint8_t* oc = CODES ? ops + cap : nullptr;
+  int i = fo.i, j = fo.j, k = fo.k;
+  int from = code_at(i, j, 0, k), fromscore = fo.e_nw;
+  if (fo.e_w > fromscore) { from = code_at(i, j, 2, k); fromscore = fo.e_w; }
+  if (fo.e_n > fromscore) from = code_at(i, j, 1, k);
+  while (i >= 0 && j >= 0 && from != 0) {
+    const int dir = from >> 2, lay = from & 3;
+    uint8_t bt, cc = 0;
+    if (dir == 1 || dir == 2) { w.ndel++; if (CODES) cc = qr4[k * qstride + i]; w.rstart = i--; bt = (uint8_t)(2 + k); }
+    else if (dir == 3 || dir == 4) { w.nin++; if (CODES) cc = (uint8_t)(db[j] << 4); w.gstart = j--; bt = 1; }
+    else {
+      const int qv = qr4[k * qstride + i];
+      if (db[j] == qv || db[j] == 15 || qv == 15) w.nm++; else w.nmm++;
+      if (CODES) cc = (uint8_t)((db[j] << 4) | qv);
+      w.rstart = i--; w.gstart = j--; bt = (uint8_t)(6 + k);
+    }
+    if (k != lay) { bt |= 0x80; w.nx++; k = lay; }
+    if (w.no < cap) { ops[w.no] = bt; if (CODES) oc[w.no] = cc; }
+    w.no++;
+    if (i < 0 || j < 0) break;                      // the virtual row / left sentinel: back == 0 in the reference
+    const int word = (dir == 1 || dir == 5) ? 1 : ((dir == 4 || dir == 7) ? 2 : 0);
+    from = code_at(i, j, word, k);
+  }
+  if (k != 0 && w.no > 0) { if (w.no - 1 < cap) ops[w.no - 1] |= 0x80; w.nx++; }     // ref :929-932
+  const int nov = min(w.no, cap);
+  for (int a = 0, b = nov - 1; a < b; a++, b--) {
+    uint8_t tt = ops[a]; ops[a] = ops[b]; ops[b] = tt;
+    if (CODES) { tt = oc[a]; oc[a] = oc[b]; oc[b] = tt; }
+  }
+  return w;
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // K4b in colour space (ref: mapping.c:331-402 with the :375-379 branch): one wave per selected window.  No vector re-score;
@@ -1793,86 +1623,30 @@ k_pass2_cs(GmIndexDev ix, GmScoreDev sc, GmCsDev P, const uint32_t* __restrict__
     if (rd != cur_rd) {
       load_read(reads + (size_t)rd * read_words, read_len, false, rc, lane);
       __syncthreads();
-      if (lane < 4) {                                   // ref: sw-full-cs.c:1182-1197
-        const int ib = (int)initbp[rd];
-        int letter = (lane + ib) % 4;
-        for (int j = 0; j < read_len; j++) {
-          const int base = rc[j];
-          if (base == 15) { qr4[lane * qstride + j] = 15; letter = (lane + ib) % 4; }
-          else { const int l2 = cs_cstols(letter, base, ix.genome_is_rna != 0); qr4[lane * qstride + j] = (uint8_t)l2; letter = l2; }
-        }
-      }
+      if (lane < 4) cs_translate4(rc, read_len, (int)initbp[rd], ix.genome_is_rna != 0, qr4, qstride, lane);
       cur_rd = rd;
     }
     const int cn = h.cn, w_len = h.w_len;
     const long long clen = (long long)ix.contig_off[cn + 1] - ix.contig_off[cn];
-    long long g_off = h.g_off; long long ax = h.ax, ay = h.ay; int gen_st = 0;
-    if (st != ix.cs_flip) {                             // reverse_hit onto the input strand (label cs_flip), ref: mapping.c:254-263; anchor_reverse anchors.h:30-34
-      g_off = clen - g_off - w_len;
-      ax = -ax + (w_len - 1) - (h.alen - 1) - (h.awidth - 1);
-      ay = -ay + (read_len - 1) - (h.alen - 1) + (h.awidth - 1);
-      gen_st = 1;
-    }
+    long long g_off, ax, ay;
+    const int gen_st = p2_reverse_hit(h, st != ix.cs_flip, clen, read_len, &g_off, &ax, &ay);      // onto the input strand (label cs_flip)
     load_window(ix.genome, (uint64_t)ix.contig_off[cn] + h.g_off, w_len, gen_st != 0, db, lane, ix.contig_rna && ix.contig_rna[cn]);
     __syncthreads();
     const int score_max = (read_len < w_len ? read_len : w_len) * sc.match;
     const int thresh = thr_of(sc.full_thr_frac, sc.full_abs, score_max);
-    GmFullRes R;
-    R.read_idx = rd; R.st = (int16_t)ix.cs_flip; R.gen_st = (int16_t)gen_st; R.cn = (uint32_t)cn; R.g_off = (uint32_t)g_off; R.w_len = w_len;
-    R.score_vector = h.score_vector; R.score_max = score_max; R.matches = h.matches; R.score_window_gen = h.score_window_gen;
-    R.score = 0; R.read_start = 0; R.rmapped = 0; R.genome_start = 0; R.gmapped = 0;
-    R.n_match = R.n_mismatch = R.n_ins = R.n_del = 0; R.n_ops = 0; R.ops_off = (uint32_t)(wi * (uint32_t)ops_stride);
-    R.sort_idx = sel_sidx ? sel_sidx[(size_t)rd * SEL_MAX + k] : 0; R.hit_slot = (uint32_t)slot; R.n_xover = 0;
-    long long nw = ax + ay, sw = ax - ay, ne = sw + 2 * (h.awidth - 1), se = nw + 2 * (h.alen - 1);      // anchor_join + anchor_widen, ref: anchors.c:9-61
-    if ((nw + sw) % 2 != 0) nw--;
-    long long rx = (nw + sw) / 2, ry = nw - rx;
-    if ((ne - sw) % 2 != 0) ne++;
-    int rw = (int)((ne - sw) / 2 + 1);
-    if ((se - nw) % 2 != 0) se++;
-    int rl = (int)((se - nw) / 2 + 1);
-    rx -= P.anchor_width / 2; ry += P.anchor_width / 2; rw += P.anchor_width;
+    GmFullRes R = p2_blank_res(h, rd, ix.cs_flip, gen_st, g_off, h.score_vector, score_max, (uint32_t)(wi * (uint32_t)ops_stride), sel_sidx ? sel_sidx[(size_t)rd * SEL_MAX + k] : 0, slot);
+    long long rx, ry; int rl, rw;
+    anchor_band(ax, ay, h.alen, h.awidth, P.anchor_width, &rx, &ry, &rl, &rw);
     fcalls++; fcells += (unsigned long long)w_len * read_len;
     const CsBest fo = full_sw_cs_wave<TABOO>(db, w_len, qr4, qstride, read_len, P, (gen_st != 0) && sc.tiebreak_rev, rx, ry, rl, rw, back, carry, lane,
                                       xover ? xover + (size_t)rd * read_len : nullptr);
     __syncthreads();
     __threadfence();
-    if (lane == 0 && fo.score >= 0 && fo.score >= thresh) {     // ref: sw-full-cs.c:1216; do_backtrace :633-937
-      auto code_at = [&](int ci, int cj, int word, int lay) -> int {
-        int x_min, x_max; band_range(rx, ry, rl, rw, w_len, ci, &x_min, &x_max);
-        if (cj < x_min || cj > x_max) return 0;         // a cell outside the band keeps back == 0 in the reference
-        const uint32_t w = __hip_atomic_load(&back[((size_t)ci * w_len + cj) * 3 + word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return (int)((w >> (8 * lay)) & 0xFFu);
-      };
-      uint8_t* o = ops + (size_t)R.ops_off; uint8_t* oc = o + half;
-      int i = fo.i, j = fo.j, kk = fo.k;
-      int from = code_at(i, j, 0, kk), fromscore = fo.e_nw;
-      if (fo.e_w > fromscore) { from = code_at(i, j, 2, kk); fromscore = fo.e_w; }
-      if (fo.e_n > fromscore) from = code_at(i, j, 1, kk);
-      int no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0, nx = 0;
-      while (i >= 0 && j >= 0 && from != 0) {
-        const int dir = from >> 2, lay = from & 3;
-        uint8_t bt, cc;
-        if (dir == 1 || dir == 2) { ndel++; cc = qr4[kk * qstride + i]; rstart = i--; bt = (uint8_t)(2 + kk); }
-        else if (dir == 3 || dir == 4) { nin++; cc = (uint8_t)(db[j] << 4); gstart = j--; bt = 1; }
-        else {
-          const int qv = qr4[kk * qstride + i];
-          if (db[j] == qv || db[j] == 15 || qv == 15) nm++; else nmm++;
-          cc = (uint8_t)((db[j] << 4) | qv);
-          rstart = i--; gstart = j--; bt = (uint8_t)(6 + kk);
-        }
-        if (kk != lay) { bt |= 0x80; nx++; kk = lay; }
-        if (no < half) { o[no] = bt; oc[no] = cc; }
-        no++;
-        if (i < 0 || j < 0) break;                      // the virtual row / left sentinel: back == 0 in the reference
-        const int word = (dir == 1 || dir == 5) ? 1 : ((dir == 4 || dir == 7) ? 2 : 0);
-        from = code_at(i, j, word, kk);
-      }
-      if (kk != 0 && no > 0) { if (no - 1 < half) o[no - 1] |= 0x80; nx++; }     // ref :929-932
-      const int nov = min(no, half);
-      for (int a2 = 0, b2 = nov - 1; a2 < b2; a2++, b2--) { uint8_t tt = o[a2]; o[a2] = o[b2]; o[b2] = tt; tt = oc[a2]; oc[a2] = oc[b2]; oc[b2] = tt; }
-      R.score = fo.score; R.n_ops = no; R.read_start = rstart; R.genome_start = gstart + (int)g_off;
-      R.gmapped = fo.j - gstart + 1; R.rmapped = fo.i - rstart + 1;
-      R.n_match = nm; R.n_mismatch = nmm; R.n_ins = nin; R.n_del = ndel; R.n_xover = nx;
+    if (lane == 0 && fo.score >= 0 && fo.score >= thresh) {     // ref: sw-full-cs.c:1216
+      const CsWalk w = cs_walk<true>(fo, back, w_len, db, qr4, qstride, rx, ry, rl, rw, ops + (size_t)R.ops_off, half);
+      R.score = fo.score; R.n_ops = w.no; R.read_start = w.rstart; R.genome_start = w.gstart + (int)g_off;
+      R.gmapped = fo.j - w.gstart + 1; R.rmapped = fo.i - w.rstart + 1;
+      R.n_match = w.nm; R.n_mismatch = w.nmm; R.n_ins = w.nin; R.n_del = w.ndel; R.n_xover = w.nx;
     }
     if (lane == 0) res[wi] = R;
   }
@@ -2122,6 +1896,9 @@ struct P2CsG4 {
   const uint32_t* work; GmFullRes* res; uint8_t* ops; int ops_stride, max_w; const int8_t* xover;
   uint8_t* rc_all; uint8_t* qr4_all; uint8_t* db_all; void* carry_all; int qstride, mw16;
 };
+// (The kernel sits at 256 registers.  Its pass keeps its own copy of what p2_reverse_hit, p2_blank_res and anchor_band do -- the box's corner narrowed to 32 bits: through the
+// shared prologue it spilled 112-652 instead of 8-472 bytes a lane, through anchor_band alone 8 bytes more in three of the eight variants, whether the narrowing stood
+// inside anchor_band or behind it; cs_translate4 and cs_walk cost nothing.  profiles/r18a_kernel_regs.txt)
 template <int G, typename CT, bool REV, bool TABOO, bool LOCAL>
 __device__ __forceinline__ void p2cs_g4_pass(const GmIndexDev& ix, const GmScoreDev& sc, const GmCsDev& P, const P2CsG4& A, const uint32_t wi, const bool has, uint32_t* back,
                                              const int lane, unsigned long long& fcalls, unsigned long long& fcells) {
@@ -2158,16 +1935,7 @@ __device__ __forceinline__ void p2cs_g4_pass(const GmIndexDev& ix, const GmScore
     load_window(ix.genome, g0_g, wl_g, (gs_g & 1) != 0, A.db_all + gg * A.mw16, lane, (gs_g & 2) != 0);
   }
   __syncthreads();
-  if (has && l < 4) {                                    // the four letter translations of the group's read, ref: sw-full-cs.c:1182-1197
-    const uint8_t* rc = A.rc_all + g * qstride; uint8_t* q4 = A.qr4_all + g * 4 * qstride;
-    const int ib = (int)A.initbp[rd];
-    int letter = (l + ib) % 4;
-    for (int j = 0; j < read_len; j++) {
-      const int base = rc[j];
-      if (base == 15) { q4[l * qstride + j] = 15; letter = (l + ib) % 4; }
-      else { const int l2 = cs_cstols(letter, base, ix.genome_is_rna != 0); q4[l * qstride + j] = (uint8_t)l2; letter = l2; }
-    }
-  }
+  if (has && l < 4) cs_translate4(A.rc_all + g * qstride, read_len, (int)A.initbp[rd], ix.genome_is_rna != 0, A.qr4_all + g * 4 * qstride, qstride, l);
   const int score_max = (read_len < w_len ? read_len : w_len) * sc.match;
   const int thresh = thr_of(sc.full_thr_frac, sc.full_abs, score_max);
   const uint32_t ops_off = (uint32_t)(wi * (uint32_t)A.ops_stride);
@@ -2198,44 +1966,12 @@ __device__ __forceinline__ void p2cs_g4_pass(const GmIndexDev& ix, const GmScore
   __syncthreads();
   __threadfence();
   P2CS_STAMP(1);
-  if (has && l == 0 && fo.score >= 0 && fo.score >= thresh) {     // ref: sw-full-cs.c:1216; do_backtrace :633-937
-    auto code_at = [&](int ci, int cj, int word, int lay) -> int {
-      int x_min, x_max; band_range(rx, ry, rl, rw, w_len, ci, &x_min, &x_max);
-      if (cj < x_min || cj > x_max) return 0;         // a cell outside the band keeps back == 0 in the reference
-      const uint32_t w = __hip_atomic_load(&back[((size_t)ci * w_len + cj) * 3 + word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return (int)((w >> (8 * lay)) & 0xFFu);
-    };
-    uint8_t* o = A.ops + (size_t)ops_off; uint8_t* oc = o + half;
-    int i = fo.i, j = fo.j, kk = fo.k;
-    int from = code_at(i, j, 0, kk), fromscore = fo.e_nw;
-    if (fo.e_w > fromscore) { from = code_at(i, j, 2, kk); fromscore = fo.e_w; }
-    if (fo.e_n > fromscore) from = code_at(i, j, 1, kk);
-    int no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0, nx = 0;
-    while (i >= 0 && j >= 0 && from != 0) {
-      const int dir = from >> 2, lay = from & 3;
-      uint8_t bt, cc;
-      if (dir == 1 || dir == 2) { ndel++; cc = qr4[kk * qstride + i]; rstart = i--; bt = (uint8_t)(2 + kk); }
-      else if (dir == 3 || dir == 4) { nin++; cc = (uint8_t)(db[j] << 4); gstart = j--; bt = 1; }
-      else {
-        const int qv = qr4[kk * qstride + i];
-        if (db[j] == qv || db[j] == 15 || qv == 15) nm++; else nmm++;
-        cc = (uint8_t)((db[j] << 4) | qv);
-        rstart = i--; gstart = j--; bt = (uint8_t)(6 + kk);
-      }
-      if (kk != lay) { bt |= 0x80; nx++; kk = lay; }
-      if (no < half) { o[no] = bt; oc[no] = cc; }
-      no++;
-      if (i < 0 || j < 0) break;                      // the virtual row / left sentinel: back == 0 in the reference
-      const int word = (dir == 1 || dir == 5) ? 1 : ((dir == 4 || dir == 7) ? 2 : 0);
-      from = code_at(i, j, word, kk);
-    }
-    if (kk != 0 && no > 0) { if (no - 1 < half) o[no - 1] |= 0x80; nx++; }     // ref :929-932
-    const int nov = min(no, half);
-    for (int a2 = 0, b2 = nov - 1; a2 < b2; a2++, b2--) { uint8_t tt = o[a2]; o[a2] = o[b2]; o[b2] = tt; tt = oc[a2]; oc[a2] = oc[b2]; oc[b2] = tt; }
+  if (has && l == 0 && fo.score >= 0 && fo.score >= thresh) {     // ref: sw-full-cs.c:1216
+    const CsWalk w = cs_walk<true>(fo, back, w_len, db, qr4, qstride, rx, ry, rl, rw, A.ops + (size_t)ops_off, half);
     GmFullRes* Rp = &A.res[wi];
-    Rp->score = fo.score; Rp->n_ops = no; Rp->read_start = rstart; Rp->genome_start = gstart + g_off_i;
-    Rp->gmapped = fo.j - gstart + 1; Rp->rmapped = fo.i - rstart + 1;
-    Rp->n_match = nm; Rp->n_mismatch = nmm; Rp->n_ins = nin; Rp->n_del = ndel; Rp->n_xover = nx;
+    Rp->score = fo.score; Rp->n_ops = w.no; Rp->read_start = w.rstart; Rp->genome_start = w.gstart + g_off_i;
+    Rp->gmapped = fo.j - w.gstart + 1; Rp->rmapped = fo.i - w.rstart + 1;
+    Rp->n_match = w.nm; Rp->n_mismatch = w.nmm; Rp->n_ins = w.nin; Rp->n_del = w.ndel; Rp->n_xover = w.nx;
   }
   __builtin_amdgcn_wave_barrier();
   P2CS_STAMP(2);
@@ -2423,27 +2159,12 @@ int gm_launch_sw_vector_batch_cs(const GmScoreDev& sc, int n, const uint32_t* d_
   return GM_OK;
 }
 
-int gm_launch_sw_full_cs_single(const int* cs_params9, const uint32_t* d_genome_ls, long long goff, int glen, const uint32_t* d_read, int rlen, int initbp,
-                                int thresh, long long ax, long long ay, int alen, int awidth, int revcmpl, uint32_t* d_back, int* d_out, uint8_t* d_ops,
-                                int ops_cap, hipStream_t stream, int local, const int8_t* d_xrow) {
-  GmCsDev P; P.match = cs_params9[0]; P.mismatch = cs_params9[1]; P.xover = cs_params9[2]; P.a_go = cs_params9[3]; P.a_ge = cs_params9[4];
-  P.b_go = cs_params9[5]; P.b_ge = cs_params9[6]; P.anchor_width = cs_params9[7]; P.taboo = cs_params9[8];
-  const size_t lds = 5 * (size_t)((rlen + 15) & ~15) + ((glen + 15) & ~15) + (size_t)glen * 48 + 64;
-  if (lds > 160 * 1024) { gm_set_error("sw_full_cs: window of %d does not fit LDS", glen); return GM_E_ARG; }
-  GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_single, lds));
-  hipLaunchKernelGGL(k_sw_full_cs_single, dim3(1), dim3(GM_WAVE), lds, stream, P, d_genome_ls, goff, glen, d_read, rlen, initbp, thresh, ax, ay, alen, awidth,
-                     revcmpl, d_back, d_out, d_ops, ops_cap, local, d_xrow);
-  GM_HIP(hipGetLastError());
-  return GM_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
-// S2 batch in colour space: n independent sw_full_cs calls, grid-stride over the items, one wave per item at a time (k_sw_full_cs_single per item:
-// global mode by full_sw_cs_wave, local mode by one 16-lane group of full_sw_cs_g4).  The back-pointer scratch (three words a cell) belongs to the
-// wave and is reused by its items as in k_sw_full_batch.  The single call clears its scratch first, because the walk takes a cell outside the
-// band for "back == 0"; clearing max(glen x rlen) words per item is what a batch cannot afford, so the walk asks the band box instead (code_at
-// returns 0 outside it, as k_pass2_cs / k_pass2_cs_g4 do on their reused scratch): every cell inside the band is written by the current item
-// before the walk, and no word outside it is ever read.
+// S2 in colour space: n independent sw_full_cs calls, grid-stride over the items, one wave per item at a time: global mode by full_sw_cs_wave, local mode by
+// one 16-lane group of full_sw_cs_g4, cs_walk on lane 0.  sw_full_cs itself is a call of one item.  The back-pointer scratch (three words a cell) belongs to the
+// wave and is reused by its items as in k_sw_full_batch.  It is never cleared -- max(glen x rlen) words per item is what a batch cannot afford: where the
+// reference takes a cell outside the band for "back == 0", the walk asks the band box (cs_walk's code_at returns 0 outside it, in k_pass2_cs / k_pass2_cs_g4
+// on their reused scratch too): every cell inside the band is written by the current item before the walk, and no word outside it is ever read.
 // ---------------------------------------------------------------------------------------------
 template <bool LOCAL, bool IX = false>                // IX: gm_sw_full_cs_batch_ix -- the strand / RNA bits of GmFullItem.flags are read (an instantiation of its own: the host-bitfield
 __global__ void __launch_bounds__(GM_WAVE)          // entry's code stays what it was).  (one wave per SIMD: with a second one the four local-mode variants spill 100+ bytes a lane)
@@ -2469,23 +2190,10 @@ k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ i
     load_read(reads + (size_t)it.idx * read_words, rlen, false, rc, lane);
     load_window(genome_ls, (uint64_t)it.goff, glen, IX && (flags & 4) != 0, db, lane, IX && (flags & 8) != 0);
     __syncthreads();
-    if (lane < 4) {                                   // ref: sw-full-cs.c:1182-1197
-      int letter = (lane + initbp) % 4;
-      for (int j = 0; j < rlen; j++) {
-        const int base = rc[j];
-        if (base == 15) { qr4[lane * qstride + j] = 15; letter = (lane + initbp) % 4; }
-        else { const int l2 = cs_cstols(letter, base, is_rna); qr4[lane * qstride + j] = (uint8_t)l2; letter = l2; }
-      }
-    }
+    if (lane < 4) cs_translate4(rc, rlen, initbp, is_rna, qr4, qstride, lane);
     __syncthreads();
-    long long nw = it.ax + it.ay, sw = it.ax - it.ay, ne = sw + 2 * (it.awidth - 1), se = nw + 2 * (it.alen - 1);      // anchor_join + anchor_widen, ref: anchors.c:9-61
-    if ((nw + sw) % 2 != 0) nw--;
-    long long rx = (nw + sw) / 2, ry = nw - rx;
-    if ((ne - sw) % 2 != 0) ne++;
-    int rw = (int)((ne - sw) / 2 + 1);
-    if ((se - nw) % 2 != 0) se++;
-    int rl = (int)((se - nw) / 2 + 1);
-    rx -= P.anchor_width / 2; ry += P.anchor_width / 2; rw += P.anchor_width;
+    long long rx, ry; int rl, rw;
+    anchor_band(it.ax, it.ay, it.alen, it.awidth, P.anchor_width, &rx, &ry, &rl, &rw);
     CsBest fo;
     if (LOCAL) {                                      // ref: sw-full-cs.c:199-203,315,439-552
       const bool act = lane < 16;
@@ -2499,41 +2207,10 @@ k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ i
     if (lane == 0) {
       GmFullOut o;
       for (int x = 0; x < 12; x++) o.v[x] = 0;
-      if (fo.score >= 0 && fo.score >= it.thresh) {    // ref :1216; do_backtrace :633-937
-        uint8_t* ops = ops_all + it.ops_off; const int ops_cap = it.ops_cap;
-        auto code_at = [&](int ci, int cj, int word, int lay) -> int {
-          int x_min, x_max; band_range(rx, ry, rl, rw, glen, ci, &x_min, &x_max);
-          if (cj < x_min || cj > x_max) return 0;     // a cell outside the band keeps back == 0 in the reference; here the word may be an earlier item's
-          const uint32_t w = __hip_atomic_load(&back[((size_t)ci * glen + cj) * 3 + word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          return (int)((w >> (8 * lay)) & 0xFFu);
-        };
-        int i = fo.i, j = fo.j, kk = fo.k;
-        int from = code_at(i, j, 0, kk), fromscore = fo.e_nw;
-        if (fo.e_w > fromscore) { from = code_at(i, j, 2, kk); fromscore = fo.e_w; }
-        if (fo.e_n > fromscore) from = code_at(i, j, 1, kk);
-        int no = 0, rstart = 0, gstart = 0, nm = 0, nmm = 0, nin = 0, ndel = 0, nx = 0;
-        while (i >= 0 && j >= 0 && from != 0) {
-          const int dir = from >> 2, lay = from & 3;
-          uint8_t bt;
-          if (dir == 1 || dir == 2) { ndel++; rstart = i--; bt = (uint8_t)(2 + kk); }
-          else if (dir == 3 || dir == 4) { nin++; gstart = j--; bt = 1; }
-          else {
-            const int qv = qr4[kk * qstride + i];
-            if (db[j] == qv || db[j] == 15 || qv == 15) nm++; else nmm++;
-            rstart = i--; gstart = j--; bt = (uint8_t)(6 + kk);
-          }
-          if (kk != lay) { bt |= 0x80; nx++; kk = lay; }
-          if (no < ops_cap) ops[no] = bt;
-          no++;
-          if (i < 0 || j < 0) break;                  // the virtual row / left sentinel: back == 0 in the reference
-          const int word = (dir == 1 || dir == 5) ? 1 : ((dir == 4 || dir == 7) ? 2 : 0);
-          from = code_at(i, j, word, kk);
-        }
-        if (kk != 0 && no > 0) { if (no - 1 < ops_cap) ops[no - 1] |= 0x80; nx++; }     // ref :929-932
-        const int nov = min(no, ops_cap);
-        for (int a2 = 0, b2 = nov - 1; a2 < b2; a2++, b2--) { const uint8_t tt = ops[a2]; ops[a2] = ops[b2]; ops[b2] = tt; }
-        o.v[0] = fo.score; o.v[1] = rstart; o.v[2] = fo.i - rstart + 1; o.v[3] = gstart; o.v[4] = fo.j - gstart + 1;
-        o.v[5] = nm; o.v[6] = nmm; o.v[7] = nin; o.v[8] = ndel; o.v[9] = nx; o.v[10] = no;
+      if (fo.score >= 0 && fo.score >= it.thresh) {    // ref :1216
+        const CsWalk w = cs_walk<false>(fo, back, glen, db, qr4, qstride, rx, ry, rl, rw, ops_all + it.ops_off, it.ops_cap);
+        o.v[0] = fo.score; o.v[1] = w.rstart; o.v[2] = fo.i - w.rstart + 1; o.v[3] = w.gstart; o.v[4] = fo.j - w.gstart + 1;
+        o.v[5] = w.nm; o.v[6] = w.nmm; o.v[7] = w.nin; o.v[8] = w.ndel; o.v[9] = w.nx; o.v[10] = w.no;
       }
       out[it.idx] = o;
     }

@@ -277,7 +277,7 @@ def test_against_the_cpu_oracle(gm, oracle_lib, rlen, glen):
 
 # ---- 5: edges ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-def test_edges_empty_one_and_not_set_up(gm):
+def test_edges_empty_one_and_not_set_up(gm, oracle_lib):
     gm.sw_full_ls_setup(*LS_SETUP); gm.sw_full_cs_setup(*CS_SETUP)
     L = gm.lib()
     z32 = np.zeros(1, dtype=np.uint32)
@@ -290,10 +290,15 @@ def test_edges_empty_one_and_not_set_up(gm):
     recs, ops, strings, bases = run_ls(gm, [it])
     got = {k: int(recs[0][k]) for k in LS_FIELDS}
     assert got == f and strings(0) == (db, qr) and f["score"] > 0
+    io = dict(it); _oracle_fill(oracle_lib, [io], "ls")                                                    # both sides run one kernel: the CPU oracle is the independent one
+    check_ls([io], recs, strings, bases)
     ic = next(i for i in items_cs("sw_kat_cs.txt.gz", "S") if i["want"][0] > 0)
     f, db, qr = gm.sw_full_cs(ic["g"], ic["goff"], ic["glen"], ic["r"], ic["rlen"], ic["initbp"], ic["thresh"], ic["anchor"], revcmpl=bool(ic["rv"]))
     recs, ops, strings, bases = run_cs(gm, [ic])
     assert {k: int(recs[0][k]) for k in CS_FIELDS} == f and strings(0) == (db, qr)
+    io = dict(ic); _oracle_fill(oracle_lib, [io], "cs")
+    assert io["want"][0] > 0
+    check_cs([io], recs, strings, bases)
     res = {}                                                                                               # the setup state is per thread: a new thread has none
     def fresh():
         rec = np.zeros(1, dtype=gm.SW_FULL_REC_DTYPE); p = C.c_void_p(); ln = C.c_uint64(0)
@@ -305,6 +310,19 @@ def test_edges_empty_one_and_not_set_up(gm):
         res["msg"] = L.gm_last_error()
     t = threading.Thread(target=fresh); t.start(); t.join()
     assert res["ls"] == -3 and res["cs"] == -3 and b"setup" in res["msg"]                                  # GM_E_NOTSETUP
+
+
+@pytest.mark.gpu
+def test_single_ls_seam_takes_a_window_beyond_64_kb_of_lds(gm, oracle_lib):
+    """sw_full_ls is a batch call of one item, so it takes what the batch entry takes: a window of 5 400 needs 70 KB of LDS (12 bytes a column), more than a launch gets
+    without asking.  Fields and strings against the CPU oracle, anchored, both strand rules."""
+    gm.sw_full_ls_setup(6000, 1000, *LS_SETUP[2:])
+    items = _oracle_items(100, 5400, 3, 77, False); _oracle_fill(oracle_lib, items, "ls")
+    for it in items:
+        f, db, qr = gm.sw_full_ls(it["g"], it["goff"], it["glen"], it["r"], it["rlen"], it["anchor"], revcmpl=bool(it["rv"]))
+        assert [f[k] for k in LS_FIELDS] == it["want"] and (db, qr) == (it["db"], it["qr"]), (f, it["want"], db, it["db"])
+    assert all(it["want"][0] > 0 for it in items)
+    gm.sw_full_ls_setup(*LS_SETUP)
 
 
 @pytest.mark.gpu
