@@ -36,7 +36,7 @@ extern "C" {
 #define GM_E_NODEVICE   -1   /* no HIP device / HIP runtime error (message via gm_last_error) */
 #define GM_E_ARG        -2   /* invalid argument */
 #define GM_E_NOTSETUP   -3   /* call before *_setup (the reference abort()s here, sw-vector.c:463) */
-#define GM_E_RANGE      -4   /* match*qrlen >= 32768 (ref: sw-vector.c:393-398, exit(1) there) */
+#define GM_E_RANGE      -4   /* match*qrlen >= 32768 (ref: sw-vector.c:393-398, exit(1) there); more than GM_MAX_CONTIGS contigs */
 #define GM_E_OVERFLOW   -5   /* a per-read candidate list exceeded every configured capacity */
 #define GM_E_NOMEM      -6
 
@@ -131,6 +131,10 @@ void gm_params_default_cs(gm_params_t *p);     /* colour-space defaults (gmapper
  * sort of (k-mer, position) pairs) and stays resident in HBM.
  * ------------------------------------------------------------------------------------------- */
 typedef struct gm_index gm_index_t;
+/* The most contigs an index holds.  A window carries its contig number in 16 bits (the anchor kernel's aux word and window sort key, the hit record) where the
+ * reference's cn is an int, so gm_index_build, gm_index_build_fasta and gm_index_load refuse a genome of more contigs before they allocate anything that outlives
+ * the call: GM_E_RANGE, gm_last_error() names the count and this limit.  A contig number is never narrowed in silence. */
+#define GM_MAX_CONTIGS 65536
 int  gm_index_build(gm_index_t **out, int device, int n_contigs, const uint32_t *const *contigs,
                     const uint32_t *contig_len, const char *const *contig_names,
                     int n_seeds, const char *const *seeds, const gm_params_t *params);
@@ -144,7 +148,7 @@ void gm_index_free(gm_index_t *ix);
  *   - letters of either case A C G T U M R W S Y K V H D B N -> 0..15, X and '.' -> 15 (gm_sequence_to_bitfield's letter-space table); any other byte of a
  *     sequence line ('\r', blank, tab, digit, a '>' that is not at a line start, ...) fails the call with GM_E_ARG and a message that names the file, the
  *     contig and the byte offset (the reference: "invalid sequence; tag: [..]", genome.c:1094-1097);
- *   - a genome of 2^32 bases or more fails as in gm_index_build.
+ *   - a genome of 2^32 bases or more, or of more than GM_MAX_CONTIGS contigs, fails as in gm_index_build.
  * Deliberate divergence: a file that does not start with a '>' line (after '#' lines), a header with no name and no sequence before the next header or the
  * end, a header line with nothing after the '>', and an unreadable or empty file return GM_E_ARG.  The reference prints a message and silently goes on with
  * the contigs it has so far.  Lines longer than the reference's 8 MiB line buffer are out of scope.  gm_last_error() names the file. */

@@ -450,6 +450,7 @@ int gm_fasta_to_device(int n_files, const char* const* paths, GmFastaGenome* out
   // contig table; an empty contig in the middle shows as two equal starts
   const size_t nc = starts.size();
   if (nc == 0 || names.size() != nc) { gm_set_error("no contig in the genome files"); return GM_E_ARG; }
+  { const int r = gm_refuse_contig_count("gm_index_build_fasta", nc); if (r != GM_OK) return r; }          // (the bitfield and the slots go with B)
   out->names = names; out->lens.resize(nc);
   for (size_t c = 0; c < nc; c++) {
     const uint64_t end = c + 1 < nc ? starts[c + 1] : bases;

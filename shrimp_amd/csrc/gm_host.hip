@@ -138,6 +138,12 @@ static void choose_slabs(GmIndexHost* ix) {
   if (ix->n_slabs < 1) ix->n_slabs = 1;
 }
 
+// more contigs than a window's 16-bit contig number can name (GM_MAX_CONTIGS): refused by every index entry before it builds anything
+int gm_refuse_contig_count(const char* who, unsigned long long n_contigs) {
+  if (n_contigs <= (unsigned long long)GM_MAX_CONTIGS) return GM_OK;
+  gm_set_error("%s: %llu contigs, the limit is %d (a window carries its contig number in 16 bits)", who, n_contigs, GM_MAX_CONTIGS);
+  return GM_E_RANGE;
+}
 // shared by gm_index_build, gm_index_load and gm_index_build_fasta: contig table (host and device), cutoff, slabs, size of the genome bitfield
 static int index_tables(gm_index* ix, int n_contigs, const uint32_t* contig_len, const char* const* contig_names) {
   ix->n_contigs = n_contigs;
@@ -197,6 +203,7 @@ extern "C" int gm_index_build(gm_index_t** out, int device, int n_contigs, const
                               const uint32_t* contig_len, const char* const* contig_names,
                               int n_seeds, const char* const* seeds, const gm_params_t* params) {
   if (!out || n_contigs < 1 || !contigs || !contig_len) { gm_set_error("gm_index_build: bad arguments"); return GM_E_ARG; }
+  { const int rc = gm_refuse_contig_count("gm_index_build", (unsigned long long)n_contigs); if (rc != GM_OK) return rc; }
   if (gm_device_count() <= device) { gm_set_error("no HIP device %d (the seed index lives in HBM; there is no CPU path)", device); return GM_E_NODEVICE; }
   GM_HIP(hipSetDevice(device));
   gm_index* ix = new gm_index();

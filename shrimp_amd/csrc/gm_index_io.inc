@@ -106,6 +106,7 @@ extern "C" int gm_index_load(gm_index_t** out, int device, const char* prefix, c
   if (!ok || mode != want_mode || hflag != want_h || nc == 0) {
     gzclose(fp); gm_set_error("%s: not a gmapper index of the requested mode (mode %u, wanted %u; Hflag %u, wanted %u)", gname.c_str(), mode, want_mode, hflag, want_h); return GM_E_ARG;   // ref: genome.c:705-715
   }
+  { const int rc = gm_refuse_contig_count("gm_index_load", nc); if (rc != GM_OK) { gzclose(fp); return rc; } }
   std::vector<uint32_t> lens(nc), offs(nc);
   ok = gz_get(fp, lens.data(), nc * 4) && gz_get(fp, offs.data(), nc * 4);
   std::vector<std::string> names(nc);

@@ -65,6 +65,8 @@ int gm_index_build_device(GmIndexHost* ix, hipStream_t stream);
 // last base; the allocation may be up to an eighth larger) is the caller's; on failure nothing is left allocated.
 struct GmFastaGenome { uint32_t* d_genome = nullptr; uint64_t words = 0, total = 0; std::vector<std::string> names; std::vector<uint32_t> lens; };
 int gm_fasta_to_device(int n_files, const char* const* paths, GmFastaGenome* out);
+// GM_OK up to GM_MAX_CONTIGS contigs; beyond: GM_E_RANGE and a message with the count and the limit (gm_host.hip)
+int gm_refuse_contig_count(const char* who, unsigned long long n_contigs);
 // extract_name (ref: common/fasta.c:242-283) on a '>' / '@' line without its '\n': what follows the mark up to the first tab, trimmed, cut at the first blank
 static inline std::string gm_extract_name(const std::string& line) {
   size_t b = 1, e = line.find('\t', 1); if (e == std::string::npos) e = line.size();

@@ -1183,8 +1183,301 @@ def pair_edges_cases():
         _write_pair_fixture(name, [c1, c2], cn, np.stack(m1), np.stack(m2), names, "opp-in", (0, 2000), PH_OPTION_SETS)
 
 
+# Many and short contigs (tests/test_many_contigs.py).  One i.i.d. sequence S cut into consecutive contigs: global coordinates are those of the uncut S, only the contig
+# table differs.  These fixtures store S and the contig lengths, not one array per contig: <name>.npz holds S, contig_len, the reads (or mates1 / mates2, names, mode,
+# ins) and, per read, what it was placed on (kind) and where in S (pos).
+CT_SPANS = (14, 19)                                     # the smallest and the largest span of the default seeds
+CT_KINDS = ("random", "first", "last", "fill", "inside", "border", "over")
+CT_FAR = (1, CT_SPANS[0] - 1, 20, 30)                   # bases on the far side of a border
+CT_NAMED = (0, 63, 64, 65, 255, 256, 32767, 32768, 65534, 65535)
+# (-U: the reference refuses it without --local, "cannot use global (or bfast) and ungapped mode at the same time", gmapper.c:2331)
+CT_OPTION_SETS = {None: [], "local": ["--local"], "n1": ["-n", "1"], "ungapped": ["--local", "-U"], "extra": ["--extra-sam-fields"]}
+
+
+def ct_window(L): return L * 140 // 100                 # the default window: 140 % of the read
+
+
+def ct_classes(L):
+    """the short contigs' lengths for reads of L"""
+    W = ct_window(L)
+    return [1, 5, CT_SPANS[0] - 1, CT_SPANS[0], CT_SPANS[1], L - 1, L, L + 1, W - 1, W, W + 1]
+
+
+def ct_layout(rng, L, n_long=85, n_short=215):
+    """contig lengths: every long contig (300 to 2 000 bases) with one to a few short ones behind it, each class of ct_classes at least five times"""
+    cls = ct_classes(L)
+    shorts = [cls[i % len(cls)] for i in range(n_short)]; rng.shuffle(shorts)
+    longs = [int(rng.integers(300, 500)) for _ in range(n_long - 15)] + [int(rng.integers(500, 2001)) for _ in range(15)]; rng.shuffle(longs)
+    k = 1 + rng.multinomial(n_short - n_long, [1.0 / n_long] * n_long)
+    lens, it = [], iter(shorts)
+    for l, kk in zip(longs, k): lens.append(l); lens += [next(it) for _ in range(kk)]
+    lens = np.array(lens, dtype=np.uint32)
+    for c in cls: assert int((lens == c).sum()) >= 5, c
+    assert any(lens[i] >= 300 and lens[i + 1] < L for i in range(len(lens) - 1))
+    return lens
+
+
+def ct_offsets(lens): return np.concatenate([[0], np.cumsum(np.asarray(lens, dtype=np.int64))])
+
+
+def ct_contigs(S, lens): return np.split(S, ct_offsets(lens)[1:-1])
+
+
+def ct_places(rng, lens, L, n_reads):
+    """(kind, position in S) of the reads: the placements the issue lists, then reads anywhere"""
+    off = ct_offsets(lens); n = len(lens); W = ct_window(L); total = int(off[-1])
+    longs = [c for c in range(1, n - 1) if lens[c] >= 300]
+    out = []
+    for c in rng.permutation(longs)[:60]: out.append(("first", off[c]))
+    for c in rng.permutation(longs)[:60]: out.append(("last", off[c + 1] - L))
+    for c in np.nonzero(lens == L)[0]: out += [("fill", off[c])] * 2
+    for c in np.nonzero((lens > L) & (lens < W))[0]: out.append(("inside", off[c] + int(rng.integers(0, lens[c] - L + 1))))
+    for k in CT_FAR:
+        right = [c for c in range(n - 1) if lens[c] >= 300 and lens[c + 1] >= k]          # the far side is contig c + 1
+        left = [c for c in range(n - 1) if lens[c + 1] >= 300 and lens[c] >= k]           # ... contig c
+        for c in rng.permutation(right)[:20]: out.append(("border", off[c + 1] - (L - k)))
+        for c in rng.permutation(left)[:20]: out.append(("border", off[c + 1] - k))
+    over = [c for c in range(1, n - 1) if lens[c] <= CT_SPANS[1]]
+    for c in rng.permutation(over)[:80]: out.append(("over", off[c] - (L - int(lens[c])) // 2))
+    while len(out) < n_reads: out.append(("random", int(rng.integers(0, total - L - 2))))
+    ends = [("random", int(off[c]) + int(rng.integers(0, int(lens[c]) - L - 1))) for c in (0, n - 1) if lens[c] >= L + 2 for _ in range(6)]      # the first and the last contig
+    out = ends + [out[i] for i in rng.permutation(len(out))][:n_reads - len(ends)]
+    out = [(k, min(max(int(p), 0), total - L)) for k, p in out]
+    return [out[i] for i in rng.permutation(len(out))]
+
+
+def ct_draw_reads(rng, S, places, L, p_sub=0.02):
+    """reads of L bases at the places: a fifth exact, the others with 2 % substitutions, one in ten of the reads placed freely or on a contig's end with a 1-base indel;
+    half of them reverse-complemented"""
+    reads = np.empty((len(places), L), dtype=np.uint8)
+    for i, (kind, p) in enumerate(places):
+        src = S[p:p + L + 2].copy()
+        if kind in ("random", "first", "last") and rng.random() < 0.1:
+            at = int(rng.integers(15, L - 15))
+            src = np.delete(src, at) if rng.random() < 0.5 else np.insert(src, at, int(rng.integers(0, 4)))
+        r = src[:L].copy()
+        if rng.random() >= 0.2:
+            m = rng.random(L) < p_sub
+            r[m] = (r[m] + rng.integers(1, 4, int(m.sum()))) & 3
+        if rng.random() < 0.5: r = _rc(r)
+        reads[i] = r
+    return reads
+
+
+def ct_spans(lens, p, L):
+    """the contigs the L bases at p of S lie on: first and last index"""
+    off = ct_offsets(lens)
+    return int(np.searchsorted(off, p, side="right") - 1), int(np.searchsorted(off, p + L - 1, side="right") - 1)
+
+
+def _ct_body(exe, lens, S, write_reads, extra, suffix=".fa"):
+    """the reference's SAM (no @PG / @RG line) on S cut into contigs of lens"""
+    with tempfile.TemporaryDirectory() as d:
+        g = os.path.join(d, "g.fa"); r = os.path.join(d, "r" + suffix)
+        write_fa_codes(g, [b"contig%d" % (i + 1) for i in range(len(lens))], ct_contigs(S, lens))
+        write_reads(r)
+        p = subprocess.run([os.path.join(ROOT, "oracle", "_ref", exe), "-N", "4", *extra, r, g], capture_output=True)
+        if p.returncode != 0: print(p.stderr.decode()[-2000:]); raise SystemExit(1)
+    return b"".join(l + b"\n" for l in p.stdout.split(b"\n") if l and not l.startswith(b"@PG") and not l.startswith(b"@RG"))
+
+
+def _ct_write(name, tag, body):
+    path = os.path.join(OUT, name + ("@" + tag if tag else "") + ".sam.gz")
+    with gzip.open(path, "wb", compresslevel=9) as f: f.write(body)
+    assert os.path.getsize(path) <= 734_000, (path, os.path.getsize(path))
+
+
+def ct_records(body):
+    """mapped records of a SAM text: (name, flag, contig index, 0-based position)"""
+    out = []
+    for l in body.split(b"\n"):
+        if not l or l.startswith(b"@"): continue
+        t = l.split(b"\t")
+        if not int(t[1]) & 4: out.append((t[0], int(t[1]), int(t[2][len(b"contig"):]) - 1, int(t[3]) - 1))
+    return out
+
+
+def ct_split_conditions(lens, L, kinds, pos, default_body, local_body):
+    """the conditions of split_60bp / split_cs_50col (the generator asserts them, tests/test_many_contigs.py asserts them again from the committed files).  A record on a
+    contig shorter than the window has a clipped window (w_len = the contig's length)."""
+    W = ct_window(L)
+    recs = ct_records(default_body)
+    clipped = sum(1 for _, _, cn, _ in recs if lens[cn] < W)
+    mapped = {int(n[1:]) for n, _, _, _ in recs}
+    spanning = [i for i in range(len(kinds)) if CT_KINDS[kinds[i]] in ("border", "over")]
+    for i in spanning: a, b = ct_spans(lens, int(pos[i]), L); assert b > a, i
+    span_mapped = sum(1 for i in spanning if i in mapped)
+    short_local = sum(1 for _, _, cn, _ in ct_records(local_body) if lens[cn] < L)
+    return dict(clipped=clipped, spanning_mapped=span_mapped, spanning_unmapped=len(spanning) - span_mapped, short_local=short_local)
+
+
+def ct_split_case(name, S, lens, L, n_reads, rng, cs=False, option_sets=CT_OPTION_SETS):
+    places = ct_places(rng, lens, L, n_reads)
+    letters = ct_draw_reads(rng, S, places, L)
+    reads = synth.cs_from_letters(letters, 41, p_col=0.02) if cs else letters
+    exe = "gmapper-cs" if cs else "gmapper-ls"
+    wr = (lambda r: synth.write_csfasta_reads(r, reads)) if cs else (lambda r: write_fa_codes(r, [b"r%d" % i for i in range(len(reads))], list(reads)))
+    bodies = {}
+    for tag, extra in option_sets.items():
+        bodies[tag] = _ct_body(exe, lens, S, wr, extra, ".csfasta" if cs else ".fa")
+        _ct_write(name, tag, bodies[tag])
+        print("%s%s: %d reads -> %d mapped records" % (name, "@" + tag if tag else "", len(reads), len(ct_records(bodies[tag]))))
+    kinds = np.array([CT_KINDS.index(k) for k, _ in places], dtype=np.uint8); pos = np.array([p for _, p in places], dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), S=S, contig_len=np.asarray(lens, dtype=np.uint32), reads=reads, kind=kinds, pos=pos)
+    return kinds, pos, bodies
+
+
+def ct_cut(rng, total, n, shorts):
+    """total bases cut into exactly n contigs: the short lengths given, the rest at random"""
+    rest = total - sum(shorts); m = n - len(shorts)
+    cuts = np.sort(rng.choice(np.arange(200, rest - 200), m - 1, replace=False))
+    longs = np.diff(np.concatenate([[0], cuts, [rest]]))
+    lens = [int(x) for x in longs]
+    for s in shorts: lens.insert(int(rng.integers(1, len(lens))), s)
+    assert len(lens) == n and sum(lens) == total
+    return np.array(lens, dtype=np.uint32)
+
+
+def ct_mates(S, p, f, strand, L=60):
+    """opp-in mates of L bases from the fragment [p, p + f) of S; strand "m": the fragment's reverse complement was sequenced"""
+    a, b = S[p:p + L].astype(np.uint8), _rc(S[p + f - L:p + f]).astype(np.uint8)
+    return (a, b) if strand == "p" else (b, a)
+
+
+def ct_pairs_case(rng):
+    """split_pairs_2x60: opp-in mates of 60 bases from fragments of 125 to 260 bases under -I 100,300 (pair_edges: the reference pairs such fragments well inside these
+    bounds).  adj: the mates on two adjacent contigs; one: on either side of a 1-base contig; in: both inside one contig of 130 to 250 bases; ctl: both inside a long one"""
+    L = 60; ins = (100, 300); lens = []
+    for u in range(70):
+        lens.append(int(rng.integers(300, 600)))
+        if u % 3 == 0: lens.append(1)
+        elif u % 3 == 1: lens.append(int(rng.integers(130, 251)))
+    lens.append(int(rng.integers(300, 600)))
+    lens = np.array(lens, dtype=np.uint32); off = ct_offsets(lens); n = len(lens)
+    S = rng.integers(0, 4, int(off[-1]), dtype=np.uint8)
+    frags = []                                                          # (name, p, f)
+    adj = [c for c in range(n - 1) if lens[c] >= L and lens[c + 1] >= L]
+    for i in range(90):
+        c = adj[i % len(adj)]; b = int(off[c + 1])
+        while True:
+            f = int(rng.integers(140, 261)); d = int(rng.integers(L, f - L + 1))
+            if d <= lens[c] and f - d <= lens[c + 1]: break
+        frags.append((b"adj_%d" % i, b - d, f))
+    ones = [c for c in range(1, n - 1) if lens[c] == 1]
+    for i in range(46):
+        c = ones[i % len(ones)]; f = int(rng.integers(140, 261)); d = int(rng.integers(L, f - L))
+        frags.append((b"one_%d" % i, int(off[c]) - d, f))
+    mids = [c for c in range(n) if 130 <= lens[c] <= 250]
+    for i in range(46):
+        c = mids[i % len(mids)]; f = int(rng.integers(125, int(lens[c]) + 1))
+        frags.append((b"in_%d" % i, int(off[c]) + int(rng.integers(0, int(lens[c]) - f + 1)), f))
+    longs = [c for c in range(n) if lens[c] >= 300]
+    for i in range(60):
+        c = longs[i % len(longs)]; f = int(rng.integers(140, 261))
+        frags.append((b"ctl_%d" % i, int(off[c]) + int(rng.integers(0, int(lens[c]) - f + 1)), f))
+    frags = [frags[i] for i in rng.permutation(len(frags))]
+    m1, m2 = [], []
+    for k, (nm, p, f) in enumerate(frags):
+        a, b = ct_mates(S, p, f, "pm"[k % 2], L)
+        a, b = a.copy(), b.copy()
+        for x in (a, b):
+            m = rng.random(L) < 0.01; x[m] = (x[m] + rng.integers(1, 4, int(m.sum()))) & 3
+        m1.append(a); m2.append(b)
+    return lens, S, np.stack(m1), np.stack(m2), [nm for nm, _, _ in frags], np.array([p for _, p, _ in frags], dtype=np.int64), np.array([f for _, _, f in frags], dtype=np.int64), ins
+
+
+def ct_pair_bodies(lens, S, m1, m2, names, ins, option_sets):
+    L = m1.shape[1]
+    def wr(r):
+        n1 = [n + b"/1" for n in names]; n2 = [n + b"/2" for n in names]
+        write_fa_codes(r, [n for pair in zip(n1, n2) for n in pair], [q for pair in zip(list(m1), list(m2)) for q in pair])
+    return {tag: _ct_body("gmapper-ls", lens, S, wr, ["-p", "opp-in", "-I", "%d,%d" % ins, *extra]) for tag, extra in option_sets.items()}
+
+
+def ct_65536_inputs(rng):
+    """65 536 contigs: fillers of 12 to 24 bases, targets of 80 to 200 at the ten named indices and at 25 pairs (b, b + 32 768) -- for every target c outside the named
+    ones, c & 0x7FFF and c ^ 0x8000 are targets too, each with its own sequence"""
+    N = 65536
+    base = sorted(int(x) for x in rng.choice(np.arange(300, 32700), 25, replace=False))
+    others = sorted(base + [b + 32768 for b in base])
+    for c in others: assert (c & 0x7FFF) in others and (c ^ 0x8000) in others
+    lens = rng.integers(12, 25, N).astype(np.uint32)
+    lens[others] = rng.integers(80, 201, len(others)); lens[list(CT_NAMED)] = rng.integers(140, 201, len(CT_NAMED))
+    off = ct_offsets(lens); S = rng.integers(0, 4, int(off[-1]), dtype=np.uint8)
+    L = 60
+    src = [c for c in CT_NAMED for _ in range(10)]
+    high = [c for c in others if c >= 32768]; low = [c for c in others if c < 32768]
+    src += [high[i % len(high)] for i in range(180)] + [low[i % len(low)] for i in range(120)]
+    src = [src[i] for i in rng.permutation(len(src))]
+    places = [("random", int(off[c]) + int(rng.integers(0, int(lens[c]) - L + 1))) for c in src]
+    reads = ct_draw_reads(rng, S, [("fill", p) for _, p in places], L)                      # (no indels: a target may be no longer than the read + 20)
+    wide = [c for c in list(CT_NAMED) + others if lens[c] >= 130]
+    m1, m2, pt = [], [], []
+    for k in range(100):
+        c = wide[int(rng.integers(0, len(wide)))]; f = int(rng.integers(125, int(lens[c]) + 1)); p = int(off[c]) + int(rng.integers(0, int(lens[c]) - f + 1))
+        a, b = ct_mates(S, p, f, "pm"[k % 2], L); m1.append(a); m2.append(b); pt.append(c)
+    return lens, S, reads, np.array(src, dtype=np.int64), np.stack(m1), np.stack(m2), np.array(pt, dtype=np.int64), (50, 300)
+
+
+def ct_65536_conditions(body, pair_body):
+    recs = ct_records(body) + ct_records(pair_body)
+    per = {c: sum(1 for _, _, cn, _ in recs if cn == c) for c in CT_NAMED}
+    return per, sum(1 for _, _, cn, _ in recs if cn >= 32768)
+
+
+def contigs_cases():
+    rng = np.random.Generator(np.random.PCG64(6553))
+    # split_60bp
+    L = 60
+    lens = ct_layout(rng, L); S = rng.integers(0, 4, int(lens.sum()), dtype=np.uint8)
+    kinds, pos, bodies = ct_split_case("split_60bp", S, lens, L, 600, rng)
+    c = ct_split_conditions(lens, L, kinds, pos, bodies[None], bodies["local"]); print("split_60bp:", len(lens), "contigs,", len(S), "bases;", c)
+    assert c["clipped"] >= 40 and c["spanning_mapped"] >= 20 and c["spanning_unmapped"] >= 10 and c["short_local"] >= 10, c
+    # split_64 / split_65: the same S on either side of the anchor kernel's lane-gather limit
+    for n in (64, 65):
+        ln = ct_cut(rng, len(S), n, [1, CT_SPANS[0], L, L + 1, ct_window(L) - 1])
+        k2, p2, b2 = ct_split_case("split_%d" % n, S, ln, L, 200, rng, option_sets={None: []})
+        hi = sum(1 for _, _, cn, _ in ct_records(b2[None]) if cn >= 33); last = sum(1 for _, _, cn, _ in ct_records(b2[None]) if cn == n - 1)
+        print("split_%d: %d mapped records on contigs 34 and up, %d on the last" % (n, hi, last))
+        assert hi >= 40 and last >= 1
+    # split_cs_50col
+    L = 50
+    lens = ct_layout(rng, L)
+    Sc = S[:int(lens.sum())] if int(lens.sum()) <= len(S) else np.concatenate([S, rng.integers(0, 4, int(lens.sum()) - len(S), dtype=np.uint8)])
+    kinds, pos, bodies = ct_split_case("split_cs_50col", Sc, lens, L, 600, rng, cs=True, option_sets={None: [], "local": ["--local"]})
+    c = ct_split_conditions(lens, L, kinds, pos, bodies[None], bodies["local"]); print("split_cs_50col:", len(lens), "contigs,", len(Sc), "bases;", c)
+    assert c["clipped"] >= 40, c
+    # split_pairs_2x60
+    lens, Sp, m1, m2, names, pos, frag, ins = ct_pairs_case(rng)
+    bodies = ct_pair_bodies(lens, Sp, m1, m2, names, ins, {None: [], "nhp": ["--no-half-paired"]})
+    for tag, body in bodies.items(): _ct_write("split_pairs_2x60", tag, body)
+    proper = _paired_names(bodies[None])
+    adj_not = sum(1 for nm in names if nm.startswith(b"adj_") and nm + b"/1" not in proper and nm not in proper)
+    ctl = [nm for nm in names if nm.startswith(b"ctl_")]; ctl_ok = sum(1 for nm in ctl if nm in proper or nm + b"/1" in proper)
+    print("split_pairs_2x60: %d contigs, %d pairs, %d proper; %d adjacent-contig pairs not proper; %d of %d controls proper" % (len(lens), len(names), len(proper), adj_not, ctl_ok, len(ctl)))
+    assert adj_not >= 30 and 10 * ctl_ok >= 8 * len(ctl)
+    np.savez_compressed(os.path.join(OUT, "split_pairs_2x60.npz"), S=Sp, contig_len=lens, mates1=m1, mates2=m2, names=np.array(names), pos=pos, frag=frag,
+                        mode=np.array("opp-in"), ins=np.array(ins))
+    # contigs_65536: the SAM bodies only (the header is 65 536 @SQ lines the tests build themselves)
+    lens, S6, reads, src, m1, m2, pt, ins = ct_65536_inputs(rng)
+    strip = lambda body: b"".join(l + b"\n" for l in body.split(b"\n") if l and not l.startswith(b"@"))
+    body = strip(_ct_body("gmapper-ls", lens, S6, lambda r: write_fa_codes(r, [b"r%d" % i for i in range(len(reads))], list(reads)), []))
+    names = [b"p%d" % i for i in range(len(m1))]
+    pbody = strip(ct_pair_bodies(lens, S6, m1, m2, names, ins, {None: []})[None])
+    _ct_write("contigs_65536", None, body); _ct_write("contigs_65536", "pairs", pbody)
+    per, high = ct_65536_conditions(body, pbody)
+    print("contigs_65536: %d bases; mapped records per named index %s; %d on indices of 32 768 or more" % (len(S6), per, high))
+    assert min(per.values()) >= 5 and high >= 150
+    np.savez_compressed(os.path.join(OUT, "contigs_65536.npz"), S=S6, contig_len=lens, reads=reads, target=src, mates1=m1, mates2=m2, names=np.array(names),
+                        pair_target=pt, mode=np.array("opp-in"), ins=np.array(ins))
+    for f in ("split_60bp", "split_64", "split_65", "split_cs_50col", "split_pairs_2x60", "contigs_65536"):
+        assert os.path.getsize(os.path.join(OUT, f + ".npz")) <= 734_000, f
+
+
 if __name__ == "__main__":
-    if "--pair-edges-only" in sys.argv:
+    if "--contigs-only" in sys.argv:
+        os.makedirs(OUT, exist_ok=True); contigs_cases()
+    elif "--pair-edges-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); pair_edges_cases()
     elif "--pair-file-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); pair_file_cases()
