@@ -58,6 +58,9 @@ static inline const char* gm_tune(const char* name) { return getenv(name); }
 static inline const char* gm_tune(const char*) { return nullptr; }
 #define GM_ABL(bits) (false)
 #endif
+#include "gm_lookup_plan.h"
+// the knobs of the seed lookup's plan (GM_K1_*, GM_K4_*, GM_K5_*, GM_NO_V5, GM_NO_BUCKETS, GM_BKT_*): all unset in the release build
+static inline K1Tune gm_k1_tune() { return k1_tune_read(gm_tune); }
 
 // ---- kernel launchers (one per .hip file) -----------------------------------------------------
 int gm_index_build_device(GmIndexHost* ix, hipStream_t stream);
@@ -93,8 +96,8 @@ struct GmK1Scratch {
   uint32_t* k1b_list = nullptr; int k1b_cap = 0;                  // k_prune_v2: read-strands left to k_prune (+ their counter)
   // in: pinned words the persistent K1 grid raises when its workgroups are resident (null: none), and this launch's epoch
   uint32_t* start_flags = nullptr; int flag_cap = 0; uint32_t epoch = 0;
-  // out, of the last launch: workgroups that will raise a flag (0: none); k_lookup_v5's rounds and half-size shape; the K1 variant chosen
-  int flag_grid = 0, rounds = 1, half = 0; const char* kernel = nullptr;
+  // out, of the last launch: workgroups that will raise a flag (0: none); the K1 variant chosen
+  int flag_grid = 0; const char* kernel = nullptr;
   void release() {
     void* ptrs[] = {k4_bins, k4_fb, k5_fb, k5_pl, k5_spill, k1b_list};
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -113,14 +116,17 @@ int gm_launch_lookup(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads,
                      const GmFusePrune* fuse = nullptr);
 int gm_index_derive_rna(GmIndexHost* ix, hipStream_t stream);        // per-contig RNA flags (gm_index.hip); idempotent
 int gm_index_derive_strips(GmIndexHost* ix, hipStream_t stream);     // strip lists for k_lookup_v5 (gm_lookup5.hip); idempotent
-int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words, int max_n_kmers, int NL,
-                      uint64_t* d_out, uint32_t* d_out_cnt, int out_cap, uint32_t* d_surv_cnt, int prune, uint32_t D, int e_max,
-                      uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap, unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K,
-                      uint64_t* d_raw = nullptr, int raw_cap = 0, uint32_t* d_surv_seg = nullptr);   // (its fall-back lists: K->k5_fb, K->k5_pl)
+// One lookup call as the host describes it to its kernel launches: index view, reads, geometry of a read-strand, output rows (stride scap), counters, heavy list, stats, stream
+struct K1Call {
+  const GmIndexDev& ix; const uint32_t* reads; int n_reads, read_len, read_words; K1Geom g; uint64_t* surv; uint32_t* surv_cnt; int scap;
+  uint32_t* heavy_list; uint32_t* heavy_cnt; int heavy_cap; unsigned long long* stats; uint32_t* surv_seg; hipStream_t stream;
+};
+// k_lookup_v5 in the shape the plan gave: allocates, clears, launches.  1: launched; 0: no scratch; < 0: error.  The kept keys go to d_out (stride out_cap) / d_out_cnt -- with
+// sh.prune K2's rows, c.surv then takes the raw members of read-strands that keep too many.  Its fall-back lists: K->k5_fb, K->k5_pl.  wlist: GM_K5_WLIST of the tuning build.
+int gm_lookup5_launch(const K1Call& c, const K5Shape& sh, int wlist, uint64_t* d_out, uint32_t* d_out_cnt, int out_cap, GmK1Scratch* K);
 int gm_launch_lookup_redo(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                           int n_heavy, const uint32_t* d_redo_list, const uint64_t* d_redo_off, uint64_t* d_out,
                           unsigned long long* d_stats, hipStream_t stream);
-size_t gm_lookup_lds_bytes(const GmIndexDev& ix, int read_len);
 
 // K1b: exact removal of survivors with no other survivor within window_len + read_len (gm_prune.hip); the kept
 // ones go to d_surv2 (stride scap2), d_surv_cnt2 = their number, or 0xFFFFFFFF for read-strands of the heavy tier

@@ -18,9 +18,8 @@
 // reading the (rare) entries of the neighbouring slices that can mark a border region.
 #include <algorithm>
 #include "gm_common.h"
-#include "gm_internal.h"
+#include "gm_internal.h"      // (K1_THREADS and the choice of the kernel: gm_lookup_plan.h)
 
-#define K1_THREADS 256
 #define K1_SHORT 64u      // slices up to this many entries are streamed by their own lane
 #ifndef K1_UNROLL
 #define K1_UNROLL 8       // positions in flight per lane (two dwordx4 per 8)
@@ -53,7 +52,7 @@ __device__ __forceinline__ bool k1_has2(const uint32_t* bm, uint32_t rloc) {
 // MP (paired -n 3): the modes of GmMpDev -- 1 lists the regions this read-strand marks twice, 2 / 4 / 5 widen or narrow the survival rule by the mate's rows, 3 flags the
 // mate's rows; 6: GmIndexDev.no_region_counts, every list entry survives.  (A template parameter, not a run-time switch: one more live scalar in the default
 // instantiation tips its SGPR spills into scratch memory, and a kernel with scratch takes 0.95 ms to dispatch instead of 0.07 -- measured on the fall-back launch.)
-template <bool BKT, int MP = 0>
+template <int MP = 0>
 __device__ __forceinline__ void
 k_lookup_body(const int item, GmIndexDev ix, const uint32_t* __restrict__ reads, int n_reads, int read_len, int read_words, int max_n_kmers,
          int NL, int bm_words, uint64_t* __restrict__ surv, uint32_t* __restrict__ surv_cnt, int scap_all,
@@ -64,7 +63,7 @@ k_lookup_body(const int item, GmIndexDev ix, const uint32_t* __restrict__ reads,
   extern __shared__ __align__(16) uint32_t smem[];
   __shared__ K1Smem sh;
   const int tid = threadIdx.x;
-  const int nthr = blockDim.x;       // 256, or NL rounded up to a wave in bucket mode (one list per thread)
+  const int nthr = blockDim.x;       // 256 (redo and list mode), else NL rounded up to a wave, at most 1024: one list per lane where a workgroup holds them
   // normal mode: block b = read-strand b, output slot surv[b*scap_all .. +scap_all).
   // redo mode (redo_list != 0): block b re-runs heavy read-strand redo_list[b] into surv[redo_off[b] .. redo_off[b+1])
   const bool redo = (redo_list != nullptr);
@@ -133,14 +132,8 @@ k_lookup_body(const int item, GmIndexDev ix, const uint32_t* __restrict__ reads,
   };
 
   // ---- 1. map indexes + whole-list bounds (ref: mapping.c:53-66, KMER_TO_MAPIDX gmapper.h:349-368) ----
-  // BKT (small genomes, one slab, one list per thread): the probe is ONE 64-byte bucket per k-mer holding the
-  // list length and its first 15 positions, so a lookup costs one HBM sector instead of directory + list.
   unsigned long long my_lookups = 0, my_entries = 0;
-  uint32_t bp[16];                        // BKT: bp[0] = list length, bp[1..15] = first positions (registers)
-  uint32_t blen = 0;                      // BKT: entries held in registers (0 when the list is long or skipped)
-#pragma unroll
-  for (int q = 0; q < 16; q++) bp[q] = 0;
-  for (int off = tid; off < NL; off += (BKT ? NL : nthr)) {     // bucket mode: exactly one list per thread
+  for (int off = tid; off < NL; off += nthr) {
     const int sn = off / max_n_kmers, i = off - sn * max_n_kmers;
     uint32_t k = 0, b = 0, e = 0;
     const int span = ix.seed[sn].span;
@@ -149,23 +142,10 @@ k_lookup_body(const int item, GmIndexDev ix, const uint32_t* __restrict__ reads,
       const uint32_t mapidx = gm_mapidx(ix, mask, span, codes + i);
       k = mapidx * (uint32_t)S;
       my_lookups++;
-      if (BKT) {
-        const uint4* bk = (const uint4*)(ix.seed[sn].bkt + (size_t)mapidx * 16);
-        const uint4 q0 = bk[0], q1 = bk[1], q2 = bk[2], q3 = bk[3];
-        bp[0] = q0.x; bp[1] = q0.y; bp[2] = q0.z; bp[3] = q0.w; bp[4] = q1.x; bp[5] = q1.y; bp[6] = q1.z; bp[7] = q1.w;
-        bp[8] = q2.x; bp[9] = q2.y; bp[10] = q2.z; bp[11] = q2.w; bp[12] = q3.x; bp[13] = q3.y; bp[14] = q3.z; bp[15] = q3.w;
-        const uint32_t len = bp[0];
-        if (len <= ix.list_cutoff) {        // ref: mapping.c:497 (longer lists are skipped, not deleted)
-          my_entries += len;
-          if (len <= 15u) blen = len;
-          else { const uint32_t* dir = ix.seed[sn].dir; b = dir[k]; e = dir[k + 1]; }   // rare: stream the list itself
-        }
-      } else {
-        const uint32_t* dir = ix.seed[sn].dir;
-        b = dir[k]; e = dir[k + S];
-        if (e - b > ix.list_cutoff) { b = 0; e = 0; }    // ref: mapping.c:497 (skipped, not deleted)
-        my_entries += (e - b);
-      }
+      const uint32_t* dir = ix.seed[sn].dir;
+      b = dir[k]; e = dir[k + S];
+      if (e - b > ix.list_cutoff) { b = 0; e = 0; }    // ref: mapping.c:497 (skipped, not deleted)
+      my_entries += (e - b);
     }
     kS[off] = k; lbeg[off] = b; lend[off] = e;
   }
@@ -196,15 +176,6 @@ k_lookup_body(const int item, GmIndexDev ix, const uint32_t* __restrict__ reads,
     __syncthreads();
     // -- phase 0: mark --
     bool any_long = false;
-    if (BKT) {
-#pragma unroll
-      for (int u = 0; u < 15; u++)
-        if ((uint32_t)u < blen) {
-          const uint32_t pv = bp[u + 1]; const uint32_t reg = pv >> rb, rloc = reg - rbase + 1u;
-          k1_mark(bm, rloc);
-          if (((pv & rmask) < ovl) && reg > 0) k1_mark(bm, rloc - 1u);
-        }
-    }
     for (int off = tid; off < NL; off += nthr) {
       uint32_t l = 0, h = 0, c = 0;
       const uint32_t lb = lbeg[off], le = lend[off];
@@ -262,24 +233,6 @@ k_lookup_body(const int item, GmIndexDev ix, const uint32_t* __restrict__ reads,
       total = sh.total;
     }
     for (int phase = 0; phase < (MP == 1 ? 1 : 2); phase++) {
-      if (BKT && phase == 1) {
-        uint32_t alive = 0;                 // bit u: register entry u survives
-#pragma unroll
-        for (int u = 0; u < 15; u++)
-          if ((uint32_t)u < blen) {
-            const uint32_t pv = bp[u + 1]; const uint32_t reg = pv >> rb, rloc = reg - rbase + 1u;
-            const bool strip = ((pv & rmask) < ovl) && reg > 0;
-            if (keep(reg, rloc, strip)) alive |= 1u << u;
-          }
-        if (alive) {
-          const uint32_t cnt = __popc(alive);
-          uint32_t slot = atomicAdd(&sh.n_surv, cnt);
-          const uint32_t sn = (uint32_t)tid / (uint32_t)max_n_kmers, y = (uint32_t)tid - sn * (uint32_t)max_n_kmers;
-#pragma unroll
-          for (int u = 0; u < 15; u++)
-            if (alive & (1u << u)) { if (slot < scap) out[slot] = ((uint64_t)bp[u + 1] << 32) | ((uint64_t)y << 16) | sn; slot++; }
-        }
-      }
       if (phase == 1 && !GM_ABL(1)) {
         // -- phase 1 (short slices): survival test, re-reading the slice from L1/L2 --
         for (int off = tid; off < NL; off += nthr) {
@@ -392,7 +345,7 @@ k_lookup_body(const int item, GmIndexDev ix, const uint32_t* __restrict__ reads,
 
 // One block per read-strand; in list mode (fb_list) a bounded grid walks the list -- one block per possible entry meant hundreds of thousands of empty
 // workgroups per launch, each of which still had to be given its LDS before it could return (1 ms per launch with an empty list).
-template <bool BKT, int MP = 0>
+template <int MP = 0>
 __global__ void __launch_bounds__(1024)
 k_lookup(GmIndexDev ix, const uint32_t* __restrict__ reads, int n_reads, int read_len, int read_words, int max_n_kmers,
          int NL, int bm_words, uint64_t* __restrict__ surv, uint32_t* __restrict__ surv_cnt, int scap_all,
@@ -403,11 +356,11 @@ k_lookup(GmIndexDev ix, const uint32_t* __restrict__ reads, int n_reads, int rea
   if (fb_cnt) {
     const int n_items = (int)*fb_cnt;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-      k_lookup_body<BKT, MP>(item, ix, reads, n_reads, read_len, read_words, max_n_kmers, NL, bm_words, surv, surv_cnt, scap_all, heavy_list, heavy_cnt, heavy_cap,
+      k_lookup_body<MP>(item, ix, reads, n_reads, read_len, read_words, max_n_kmers, NL, bm_words, surv, surv_cnt, scap_all, heavy_list, heavy_cnt, heavy_cap,
                          redo_list, redo_off, fb_list, fb_cnt, stats, ablate, surv_seg);
       __syncthreads();
     }
-  } else k_lookup_body<BKT, MP>((int)blockIdx.x, ix, reads, n_reads, read_len, read_words, max_n_kmers, NL, bm_words, surv, surv_cnt, scap_all, heavy_list, heavy_cnt, heavy_cap,
+  } else k_lookup_body<MP>((int)blockIdx.x, ix, reads, n_reads, read_len, read_words, max_n_kmers, NL, bm_words, surv, surv_cnt, scap_all, heavy_list, heavy_cnt, heavy_cap,
                             redo_list, redo_off, fb_list, fb_cnt, stats, ablate, surv_seg);
 }
 
@@ -1275,83 +1228,91 @@ k_lookup_v4(GmIndexDev ix, const uint32_t* __restrict__ reads, int n_reads, int 
   if ((tid & (GM_WAVE - 1)) == 0) { GS_ADD(stats, GS_LOOKUPS, my_lookups); GS_ADD(stats, GS_ENTRIES, my_entries); }
 }
 
-static void k1_geometry(const GmIndexDev& ix, int read_len, int* max_n_kmers, int* NL, int* bm_words, size_t* lds) {
-  *max_n_kmers = read_len - ix.min_seed_span + 1;
-  if (*max_n_kmers < 0) *max_n_kmers = 0;
-  *NL = ix.n_seeds * (*max_n_kmers);
-  uint64_t slab_len = (ix.n_slabs == 1) ? ix.total_len : (1ull << ix.slab_bits);
-  uint64_t regions = (slab_len >> ix.region_bits) + 3;      // +1 region before, +1 partial, +1 slack
-  *bm_words = (int)((regions + 15) / 16);
-  *bm_words = (*bm_words + 3) & ~3;
-  *lds = (size_t)((((read_len + 3) / 4) + 6 * (*NL) + 1 + 3) & ~3) * 4 + (size_t)(*bm_words) * 4;
+// Host side.  Which kernel runs, and in what shape, is decided by k1_plan (gm_lookup_plan.h) on plain numbers before anything is allocated or launched;
+// what follows fills its inputs, launches what it says and, where a variant's scratch cannot be allocated, goes on to the next one of the plan.
+static_assert(K1P_MAX_SEEDS == GM_MAX_SEEDS && K1P_HASH_TABLE_POWER == GM_HASH_TABLE_POWER && K1P_MP_CAP == GM_MP_CAP, "gm_lookup_plan.h restates these");
+// what the plan reads of the index view and of the call
+static K1PlanIn k1_plan_in(const GmIndexDev& ix, int n_reads, int read_len, const GmFusePrune* fuse, int cus) {
+  K1PlanIn in = K1PlanIn();
+  in.total_len = ix.total_len; in.slab_bits = ix.slab_bits; in.n_slabs = ix.n_slabs; in.region_bits = ix.region_bits; in.region_overlap = ix.region_overlap; in.list_cutoff = ix.list_cutoff;
+  in.colour = ix.colour; in.hflag = ix.hflag; in.no_region_counts = ix.no_region_counts; in.mp_mode = ix.mp.mode; in.n_seeds = ix.n_seeds; in.min_seed_span = ix.min_seed_span;
+  for (int sn = 0; sn < ix.n_seeds; sn++) { in.seed[sn].span = ix.seed[sn].span; in.seed[sn].weight = ix.seed[sn].weight; in.seed[sn].n_pos = ix.seed[sn].n_pos; }
+  in.has_buckets = ix.seed[0].bkt != nullptr; in.has_strips = ix.seed[0].sdir != nullptr; in.n_reads = n_reads; in.read_len = read_len; in.cus = cus;
+  in.want_fuse = fuse && fuse->scap2 > 0; in.window_len = fuse ? fuse->window_len : 0; in.e_max = fuse ? fuse->e_max : -1;
+  return in;
 }
 
-// v4 launch: returns false when the geometry does not fit (the caller falls back to the slab-sweep kernels)
-static bool k4_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words, int max_n_kmers, int NL,
-                      uint64_t* d_surv, uint32_t* d_surv_cnt, int scap, uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap,
-                      unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K, uint32_t* d_surv_seg, size_t lds_generic, int bm_words) {
-  int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return false;
-  const int S = ix.n_slabs;
-  {  // v4's fixed cost per read-strand (two 128 KB table clears, per-bin passes) pays off from ~30 k list entries per read-strand
-     // (measured: 45 k at 100 bp / 3 Gbp 7 % faster than the slab sweep, 17 k at 50 colours 40 % slower)
-    double entries = 0;
-    for (int sn = 0; sn < ix.n_seeds; sn++) {
-      const double lists = std::max(0, read_len - ix.seed[sn].span + 1 - ix.colour);
-      entries += lists * (double)ix.seed[sn].n_pos / (double)(1ull << (ix.hflag ? 2 * GM_HASH_TABLE_POWER : 2 * ix.seed[sn].weight));
-    }
-    if (entries < 30000.0 && !gm_tune("GM_K1_V4")) return false;
-  }
-  int tab_bits = 19; if (const char* e = gm_tune("GM_K4_TABBITS")) tab_bits = std::max(6, std::min(19, atoi(e)));
-  // pass C keeps the exact counters of one bin of 2^cbits positions (+2) in the table's LDS; bins nest inside the index slabs
-  const int cbits = std::min(ix.slab_bits, tab_bits + ix.region_bits - 1);
-  if (cbits < ix.region_bits + 1) return false;
-  const int SC = (int)((ix.total_len + (1ull << cbits) - 1) >> cbits);
-  if (SC < 1 || SC > 4096) return false;
-  int wcap = 4096; if (const char* e = gm_tune("GM_K4_WCAP")) wcap = std::max(2, std::min(4096, atoi(e) & ~1));   // windows with a direct window -> list entry (the rest: binary search)
-  const int fb_cap = 4096;
-  int bin_cap = 4096; if (const char* e = gm_tune("GM_K4_BINCAP")) { const int v = std::max(16, std::min(1 << 20, atoi(e))); bin_cap = 16; while (bin_cap < v) bin_cap <<= 1; }
-  const int code_words = (read_len + 3) / 4;
-  size_t lds = (size_t)(((((code_words + 3) & ~3) + 4 * NL + NL + 1 + SC + (wcap + 1) / 2 + 3) & ~3) + (1 << (tab_bits - 4)) + 4) * 4;
-  if (const char* e = gm_tune("GM_K4_LDS_PAD")) lds += (size_t)std::max(0, atoi(e));   // experiment: what the LDS footprint does to the co-residency with pass 1 / pass 2
-  if (lds > 160 * 1024 - 64) return false;
-  int wgs_per_cu = 1; if (const char* e = gm_tune("GM_K4_WGS")) wgs_per_cu = std::max(1, std::min(8, atoi(e)));
-  if (!K->cus) { if (hipDeviceGetAttribute(&K->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || K->cus < 1) K->cus = 256; }
-  int grid = std::min(2 * n_reads, K->cus * wgs_per_cu);
-  if (const char* e = gm_tune("GM_K4_GRID")) grid = std::max(1, std::min(2 * n_reads, atoi(e)));
-  const size_t need = (size_t)std::max(grid, K->cus) * SC * bin_cap;
+// The one launch of the slab-sweep kernel k_lookup<MP>, in one of its three modes:
+//   K1_NORMAL  block b = read-strand b: grid 2 * n_reads
+//   K1_REDO    block b re-runs read-strand list[b] into c.surv[redo_off[b] .. redo_off[b + 1]): grid n_items
+//   K1_LIST    a bounded grid walks list[0 .. *fb_cnt) as in normal mode: grid min(n_items, 1024), n_items = the list's capacity
+// lds: the instantiation's dynamic LDS (its limit is raised here), with the rows of k1_mp_lds in the mate-pair modes.  (Why 25 scalar arguments and MP as a template parameter: above k_lookup_body.)
+enum K1Mode { K1_NORMAL, K1_REDO, K1_LIST };
+static int k1_launch(const K1Call& c, K1Mode mode, int mp, int threads, size_t lds, int ablate = 0, int n_items = 0, const uint32_t* list = nullptr,
+                     const uint64_t* redo_off = nullptr, const uint32_t* fb_cnt = nullptr) {
+  if (mp >= 1 && mp <= 5 && lds + 64 > 160 * 1024) { gm_set_error("lookup kernel (mate-pair modes) needs %zu bytes of LDS", lds); return GM_E_ARG; }
+  const int grid = mode == K1_NORMAL ? 2 * c.n_reads : mode == K1_REDO ? n_items : std::min(n_items, 1024);
+  const uint32_t* const redo_list = mode == K1_REDO ? list : nullptr; const uint32_t* const fb_list = mode == K1_LIST ? list : nullptr;
+#define K1_GO(MP) GM_HIP(gm_lds_at_least((const void*)k_lookup<MP>, lds)); \
+                  hipLaunchKernelGGL((k_lookup<MP>), dim3(grid), dim3(threads), lds, c.stream, c.ix, c.reads, c.n_reads, c.read_len, c.read_words, c.g.max_n_kmers, c.g.NL, c.g.bm_words, \
+                                     c.surv, c.surv_cnt, c.scap, c.heavy_list, c.heavy_cnt, c.heavy_cap, redo_list, redo_off, fb_list, fb_cnt, c.stats, ablate, c.surv_seg); break
+  switch (mp) { case 1: K1_GO(1); case 2: K1_GO(2); case 3: K1_GO(3); case 4: K1_GO(4); case 5: K1_GO(5); case 6: K1_GO(6); default: K1_GO(0); }
+#undef K1_GO
+  return GM_OK;
+}
+
+// v4 in the shape the plan gave (1: ran, 0: its scratch cannot be had and the next variant of the plan runs, < 0: error)
+static int k4_launch(const K1Call& c, const K4Shape& sh, int ablate, GmK1Scratch* K) {
+  const int fb_cap = 4096; const size_t need = (size_t)std::max(sh.grid, K->cus) * sh.SC * sh.bin_cap;
   if (need > K->k4_words) {
-    if (K->k4_bins) { (void)hipStreamSynchronize(stream); (void)hipFree(K->k4_bins); }
+    if (K->k4_bins) { (void)hipStreamSynchronize(c.stream); (void)hipFree(K->k4_bins); }
     K->k4_bins = nullptr; K->k4_words = 0;
-    if (hipMalloc(&K->k4_bins, need * 8) != hipSuccess) return false;
+    if (hipMalloc(&K->k4_bins, need * 8) != hipSuccess) return 0;
     K->k4_words = need;
   }
-  if (!K->k4_fb) { if (hipMalloc(&K->k4_fb, (size_t)(fb_cap + 4) * 4) != hipSuccess) return false; }
-  if (hipMemsetAsync(K->k4_fb + fb_cap, 0, 4, stream) != hipSuccess) return false;
-  if (gm_lds_at_least((const void*)k_lookup_v4, lds) != hipSuccess || gm_lds_at_least((const void*)k_lookup<false>, lds_generic) != hipSuccess) return false;
-  int k4_threads = 1024; if (const char* e = gm_tune("GM_K1_THREADS")) k4_threads = std::max(64, std::min(1024, atoi(e) & ~63));
-  const bool use_flags = K->start_flags && grid <= K->flag_cap;
-  K->flag_grid = use_flags ? grid : 0;
-  hipLaunchKernelGGL(k_lookup_v4, dim3(grid), dim3(k4_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words, max_n_kmers, NL, tab_bits, cbits, SC, wcap,
-                     d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, d_surv_seg, K->k4_bins, bin_cap, K->k4_fb, K->k4_fb + fb_cap, fb_cap,
-                     gm_tune("GM_K1_ABLATE") ? atoi(gm_tune("GM_K1_ABLATE")) : 0, use_flags ? K->start_flags : nullptr, K->epoch);
+  if (!K->k4_fb && hipMalloc(&K->k4_fb, (size_t)(fb_cap + 4) * 4) != hipSuccess) return 0;
+  if (hipMemsetAsync(K->k4_fb + fb_cap, 0, 4, c.stream) != hipSuccess || gm_lds_at_least((const void*)k_lookup_v4, sh.lds) != hipSuccess) return 0;
+  const bool use_flags = K->start_flags && sh.grid <= K->flag_cap;
+  K->flag_grid = use_flags ? sh.grid : 0;
+  hipLaunchKernelGGL(k_lookup_v4, dim3(sh.grid), dim3(sh.threads), sh.lds, c.stream, c.ix, c.reads, c.n_reads, c.read_len, c.read_words, c.g.max_n_kmers, c.g.NL, sh.tab_bits, sh.cbits, sh.SC,
+                     sh.wcap, c.surv, c.surv_cnt, c.scap, c.heavy_list, c.heavy_cnt, c.heavy_cap, c.stats, c.surv_seg, K->k4_bins, sh.bin_cap, K->k4_fb, K->k4_fb + fb_cap, fb_cap,
+                     ablate, use_flags ? K->start_flags : nullptr, K->epoch);
   // read-strands whose candidates overflowed their bins: the slab-sweep kernel in list mode (blocks beyond the list's end return at once)
-  hipLaunchKernelGGL(k_lookup<false>, dim3(std::min(fb_cap, 1024)), dim3(K1_THREADS), lds_generic, stream, ix, d_reads, n_reads, read_len, read_words,
-                     max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                     (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)K->k4_fb, (const uint32_t*)(K->k4_fb + fb_cap), d_stats, 0, d_surv_seg);
-  return true;
+  const int rc = k1_launch(c, K1_LIST, 0, K1_THREADS, c.g.lds, 0, fb_cap, K->k4_fb, nullptr, K->k4_fb + fb_cap);
+  return rc ? rc : 1;
 }
 
-size_t gm_lookup_lds_bytes(const GmIndexDev& ix, int read_len) {
-  int a, b, c; size_t l; k1_geometry(ix, read_len, &a, &b, &c, &l); return l;
+// v5 in the shape the plan gave (1: ran, 0: its scratch cannot be had, < 0: error), then the read-strands it handed on
+static int k5_run(const K1Call& c, const K5Shape& sh, int wlist, const GmFusePrune* fuse, GmK1Scratch* K) {
+  const bool fused = sh.prune;      // K1b's rules inside the kernel: the kept keys go straight to K2's rows
+  const int r = gm_lookup5_launch(c, sh, wlist, fused ? fuse->d_surv2 : c.surv, fused ? fuse->d_surv_cnt2 : c.surv_cnt, fused ? fuse->scap2 : c.scap, K);
+  if (r != 1) return r;
+  uint32_t* const fbl = K->k5_fb; uint32_t* const fbc = K->k5_fb + K->k5_cap; const int fbcap = K->k5_cap;
+  // read-strands whose candidates did not fit the LDS tiers (none on the benchmark genome): the slab-sweep kernel in list mode (blocks beyond the list's end
+  // return at once), then K1b for those.  (k_lookup_v4 in list mode was tried for them: no faster, and its 134 KB workgroups wait longer for a CU.)
+  { const int rc = k1_launch(c, K1_LIST, 0, K1_THREADS, c.g.lds, 0, fbcap, fbl, nullptr, fbc); if (rc) return rc; }
+  GM_HIP(hipGetLastError());
+  if (fused) {      // K1b for those, then for the read-strands whose members v5 left in their raw rows (more kept than K2's tier under region-sized bins)
+    for (uint32_t* list : {fbl, K->k5_pl}) {
+      const int rc = gm_launch_prune(c.n_reads, c.read_len, fuse->window_len, fuse->e_max, c.ix.n_slabs, c.ix.slab_bits, c.surv, c.surv_cnt, c.surv_seg, c.scap,
+                                     fuse->d_surv2, fuse->d_surv_cnt2, fuse->scap2, c.heavy_list, c.heavy_cnt, c.heavy_cap, c.stats, c.stream, K, list, list + fbcap, fbcap);
+      if (rc) return rc;
+    }
+    if (fuse->fused) *fuse->fused = 1;
+  }
+  return 1;
 }
 
-// the mate-pair modes of the generic kernel: their dynamic LDS limit
-static int k1_mp_lds(size_t& lds) {
-  lds += (size_t)2 * GM_MP_CAP * 4;                                   // the mate's row and this read-strand's own
-  if (lds + 64 > 160 * 1024) { gm_set_error("lookup kernel (mate-pair modes) needs %zu bytes of LDS", lds); return GM_E_ARG; }
-  for (const void* k : {(const void*)k_lookup<false, 1>, (const void*)k_lookup<false, 2>, (const void*)k_lookup<false, 3>, (const void*)k_lookup<false, 4>, (const void*)k_lookup<false, 5>})
-    GM_HIP(gm_lds_at_least(k, lds));
-  return GM_OK;
+static int k1_run_bkt(const K1Call& c, const K1BktForm& b, const K1Tune& tune, GmK1Scratch* K) {
+  GM_HIP(gm_lds_at_least((const void*)k_lookup_bkt, b.lds));      // (a small region size on a bucket-sized genome: the bitmap can pass 48 KB)
+  if (b.lds_p <= 64 * 1024) GM_HIP(gm_lds_at_least((const void*)k_lookup_bkt_p, b.lds_p));
+  int per_cu = 0;                                              // resident workgroups per CU (registers, waves, LDS): the persistent grid is exactly that
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_lookup_bkt_p, b.threads, b.lds_p) != hipSuccess || per_cu < 1) per_cu = 4;
+  if (tune.bkt_per_cu.set) { const int v = tune.bkt_per_cu.v; if (v >= 1 && v < per_cu) { if (getenv("GM_TIMELINE")) fprintf(stderr, "[bkt] %d workgroups a CU fit, %d taken (%d threads, %zu B of LDS)\n", per_cu, v, b.threads, b.lds_p); per_cu = v; } }
+  hipLaunchKernelGGL(b.persistent ? k_lookup_bkt_p : k_lookup_bkt, dim3(b.persistent ? std::min(c.n_reads * 2, K->cus * per_cu) : c.n_reads * 2), dim3(b.threads),
+                     b.persistent ? b.lds_p : b.lds, c.stream, c.ix, c.reads, c.n_reads, c.read_len, c.read_words, c.g.max_n_kmers, c.g.NL, c.g.bm_words, c.surv, c.surv_cnt, c.scap,
+                     c.heavy_list, c.heavy_cnt, c.heavy_cap, c.stats, c.surv_seg);
+  return 1;
 }
 
 static thread_local const char* g_k1_name = "";   // K->kernel of the calling thread's last launch
@@ -1360,168 +1321,49 @@ extern "C" const char* gm_last_lookup_kernel(void) { return g_k1_name; }   // wh
 int gm_launch_lookup(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                      uint64_t* d_surv, uint32_t* d_surv_cnt, int scap, uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap,
                      unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K, uint32_t* d_surv_seg, const GmFusePrune* fuse) {
-  int max_n_kmers, NL, bm_words; size_t lds;
-  k1_geometry(ix, read_len, &max_n_kmers, &NL, &bm_words, &lds);
-  K->flag_grid = 0;
-  if (lds > 160 * 1024) { gm_set_error("lookup kernel needs %zu bytes of LDS (read_len %d, slab_bits %d)", lds, read_len, ix.slab_bits); return GM_E_ARG; }
+  if (!K->cus) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&K->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || K->cus < 1) K->cus = 256; }
+  const K1Tune tune = gm_k1_tune();
+  const K1Plan plan = k1_plan(k1_plan_in(ix, n_reads, read_len, fuse, K->cus), tune);
+  const K1Geom& g = plan.g; K->flag_grid = 0;
+  if (g.lds > 160 * 1024) { gm_set_error("lookup kernel needs %zu bytes of LDS (read_len %d, slab_bits %d)", g.lds, read_len, ix.slab_bits); return GM_E_ARG; }
   GM_HIP(hipMemsetAsync(d_heavy_cnt, 0, 4, stream));
   if (fuse && fuse->fused) *fuse->fused = 0;
-  if (NL == 0 || n_reads == 0) { GM_HIP(hipMemsetAsync(d_surv_cnt, 0, (size_t)n_reads * 2 * 4, stream)); return GM_OK; }
-  GM_HIP(gm_lds_at_least((const void*)k_lookup<false>, lds));
-  if (ix.mp.mode) {   // paired -n 3: the generic slab-sweep kernel in one of its mate-pair modes (GmMpDev)
-    int rc = k1_mp_lds(lds); if (rc) return rc;
-    const int k1_threads = std::min(1024, std::max(256, (NL + 63) & ~63));
-    g_k1_name = K->kernel = "k_lookup";
-    if (ix.mp.mode == 1)
-      hipLaunchKernelGGL((k_lookup<false, 1>), dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                         max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                         (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, (uint32_t*)nullptr);
-    else if (ix.mp.mode == 3)
-      hipLaunchKernelGGL((k_lookup<false, 3>), dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                         max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                         (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, (uint32_t*)nullptr);
-    else if (ix.mp.mode == 5)
-      hipLaunchKernelGGL((k_lookup<false, 5>), dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                         max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                         (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, d_surv_seg);
-    else if (ix.mp.mode == 4)
-      hipLaunchKernelGGL((k_lookup<false, 4>), dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                         max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                         (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, d_surv_seg);
-    else
-      hipLaunchKernelGGL((k_lookup<false, 2>), dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                         max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                         (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, d_surv_seg);
+  if (g.NL == 0 || n_reads == 0) { GM_HIP(hipMemsetAsync(d_surv_cnt, 0, (size_t)n_reads * 2 * 4, stream)); return GM_OK; }
+  const K1Call c = {ix, d_reads, n_reads, read_len, read_words, g, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, d_surv_seg, stream};
+  for (int i = 0; i < plan.n; i++) {
+    int r = 1;      // 1: launched; 0: the variant's scratch could not be allocated, the next one of the plan runs; < 0: error
+    switch (plan.order[i]) {
+      case K1_V5: r = k5_run(c, plan.v5, tune.k5_wlist.set ? std::max(0, tune.k5_wlist.v) : 0x7FFFFFFF, fuse, K); break;
+      case K1_V4: r = k4_launch(c, plan.v4, tune.ablate.v, K); break;      // (read-strands it could not hold were redone in list mode)
+      case K1_BKT: r = k1_run_bkt(c, plan.bkt, tune, K); break;
+      case K1_V3:
+        GM_HIP(gm_lds_at_least((const void*)k_lookup_v3, plan.lds3));
+        hipLaunchKernelGGL(k_lookup_v3, dim3(n_reads * 2), dim3(plan.threads3), plan.lds3, stream, ix, d_reads, n_reads, read_len, read_words,
+                           g.max_n_kmers, g.NL, g.bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, tune.ablate.v, d_surv_seg);
+        break;
+      case K1_SWEEP: {
+        const int mp = plan.sweep_mp; K1Call cs = c; if (mp == 1 || mp == 3) cs.surv_seg = nullptr;      // (modes 1 and 3 emit no survivors)
+        r = k1_launch(cs, K1_NORMAL, mp, plan.sweep_threads, plan.sweep_lds, mp == 0 ? tune.ablate.v : 0);      // (the ablation bits: the default instantiation only)
+        if (r == GM_OK) r = 1;
+        break; }
+    }
+    if (r <= 0) { if (r < 0) return r; continue; }
+    g_k1_name = K->kernel = k1_variant_name(plan, plan.order[i]);
     GM_HIP(hipGetLastError());
     return GM_OK;
   }
-  const bool all = ix.no_region_counts != 0;      // every list entry survives: the generic slab-sweep kernel carries that switch, the filtering kernels do not apply
-  const bool bkt = !all && ix.seed[0].bkt != nullptr && ix.n_slabs == 1 && NL <= 512 && !gm_tune("GM_NO_BUCKETS");
-  if (!all && !bkt && NL < 65536 && !gm_tune("GM_K1_V2") && !gm_tune("GM_K1_V3") && !gm_tune("GM_K1_V4") && !gm_tune("GM_NO_V5")) {
-    // k_lookup_v5 (gm_lookup5.hip): wave-per-list streaming, candidates and the exact rule in LDS, K1b's prune rules fused when the caller allows.
-    // It takes the read-strands with many list entries (gm_lookup5_launch declines the others: 50-colour reads, small genomes) -- round 2: 24 %
-    // fewer VALU instructions than v4 + K1b, 2.09 M reads/s against 1.90 M on the 3 Gbp workload.
-    const bool want_fuse = fuse && fuse->scap2 > 0;
-    const uint32_t D = (uint32_t)std::max(want_fuse ? fuse->window_len : 0, read_len);
-    const int e_max = want_fuse ? std::min(fuse->e_max, read_len) : -1;
-    bool fused = want_fuse;
-    int r = gm_lookup5_launch(ix, d_reads, n_reads, read_len, read_words, max_n_kmers, NL, fused ? fuse->d_surv2 : d_surv, fused ? fuse->d_surv_cnt2 : d_surv_cnt,
-                              fused ? fuse->scap2 : scap, d_surv_cnt, fused ? 1 : 0, D, e_max, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, d_surv, scap, d_surv_seg);
-    if (r == 0 && fused) {   // the prune rules do not fit region-sized bins (very long reads): v5 without them, K1b afterwards
-      fused = false;
-      r = gm_lookup5_launch(ix, d_reads, n_reads, read_len, read_words, max_n_kmers, NL, d_surv, d_surv_cnt, scap, d_surv_cnt, 0, D, -1,
-                            d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K);
-    }
-    if (r < 0) return r;
-    if (r == 1) {
-      g_k1_name = K->kernel = K->half ? "k_lookup_v5_half" : K->rounds > 1 ? "k_lookup_v5_rounds" : "k_lookup_v5";
-      uint32_t* const fbl = K->k5_fb; uint32_t* const fbc = K->k5_fb + K->k5_cap; const int fbcap = K->k5_cap;
-      // read-strands whose candidates did not fit the LDS tiers (none on the benchmark genome): the slab-sweep kernel in list mode (blocks beyond the list's end
-      // return at once), then K1b for those.  (k_lookup_v4 in list mode was tried for them: no faster, and its 134 KB workgroups wait longer for a CU.)
-      hipLaunchKernelGGL(k_lookup<false>, dim3(std::min(fbcap, 1024)), dim3(K1_THREADS), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                         max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                         (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)fbl, (const uint32_t*)fbc, d_stats, 0, d_surv_seg);
-      GM_HIP(hipGetLastError());
-      if (fused) {
-        const int rc = gm_launch_prune(n_reads, read_len, fuse->window_len, fuse->e_max, ix.n_slabs, ix.slab_bits, d_surv, d_surv_cnt, d_surv_seg, scap,
-                                       fuse->d_surv2, fuse->d_surv_cnt2, fuse->scap2, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, fbl, fbc, fbcap);
-        if (rc) return rc;
-        // read-strands whose members v5 left in their raw rows (more kept than K2's tier under region-sized bins): K1b only
-        const int rc2 = gm_launch_prune(n_reads, read_len, fuse->window_len, fuse->e_max, ix.n_slabs, ix.slab_bits, d_surv, d_surv_cnt, d_surv_seg, scap,
-                                        fuse->d_surv2, fuse->d_surv_cnt2, fuse->scap2, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, K->k5_pl, K->k5_pl + K->k5_cap, fbcap);
-        if (rc2) return rc2;
-        if (fuse->fused) *fuse->fused = 1;
-      }
-      return GM_OK;
-    }
-  }
-  if (bkt) {
-    g_k1_name = K->kernel = "k_lookup_bkt";
-    const size_t lds_b = (size_t)((((read_len + 3) / 4) + 3) & ~3) * 4 + (size_t)bm_words * 4;
-    // the persistent form (probes one read-strand ahead) unless GM_BKT_V1 asks for one workgroup per read-strand; its grid: what fits a CU by waves and LDS, times the CUs
-    const int threads_b = (NL + 63) & ~63;
-    const size_t lds_p = lds_b + (size_t)((((read_len + 3) / 4) + 3) & ~3) * 4;
-    int dev_b = 0, cus_b = 256; (void)hipGetDevice(&dev_b); if (hipDeviceGetAttribute(&cus_b, hipDeviceAttributeMultiprocessorCount, dev_b) != hipSuccess || cus_b < 1) cus_b = 256;
-    GM_HIP(gm_lds_at_least((const void*)k_lookup_bkt, lds_b));      // (a small region size on a bucket-sized genome: the bitmap can pass 48 KB)
-    if (lds_p <= 64 * 1024) GM_HIP(gm_lds_at_least((const void*)k_lookup_bkt_p, lds_p));
-    int per_cu = 0;                                              // resident workgroups per CU (registers, waves, LDS): the persistent grid is exactly that
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_lookup_bkt_p, threads_b, lds_p) != hipSuccess || per_cu < 1) per_cu = 4;
-    if (const char* e = gm_tune("GM_BKT_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < per_cu) { if (getenv("GM_TIMELINE")) fprintf(stderr, "[bkt] %d workgroups a CU fit, %d taken (%d threads, %zu B of LDS)\n", per_cu, v, threads_b, lds_p); per_cu = v; } }
-    if (gm_tune("GM_BKT_V1") || threads_b > 512 || lds_p > 64 * 1024)
-    hipLaunchKernelGGL(k_lookup_bkt, dim3(n_reads * 2), dim3(threads_b), lds_b, stream, ix, d_reads, n_reads, read_len, read_words,
-                       max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, d_surv_seg);
-    else
-    hipLaunchKernelGGL(k_lookup_bkt_p, dim3(std::min(n_reads * 2, cus_b * per_cu)), dim3(threads_b), lds_p, stream, ix, d_reads, n_reads, read_len, read_words,
-                       max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, d_surv_seg);
-  } else if (!all && ix.n_slabs > 1 && NL < 65536 && !gm_tune("GM_K1_V2") && !gm_tune("GM_K1_V3") && k4_launch(ix, d_reads, n_reads, read_len, read_words, max_n_kmers, NL, d_surv, d_surv_cnt, scap,
-                                                                                                   d_heavy_list, d_heavy_cnt, heavy_cap, d_stats, stream, K, d_surv_seg, lds, bm_words)) {
-    // k_lookup_v4 ran (hashed pre-count + exact count on the candidates); read-strands it could not hold were redone in list mode
-    g_k1_name = K->kernel = "k_lookup_v4";
-  } else if (!all && ix.list_cutoff < 65536u && !gm_tune("GM_K1_V2") &&
-             (size_t)((((read_len + 3) / 4) + 3 * NL + ix.n_slabs * NL + (ix.n_slabs + 1) / 2 + (NL * (ix.n_slabs + 1) + 1) / 2 + 3) & ~3) * 4 + (size_t)bm_words * 4 <= 160 * 1024) {
-    // (long reads on many slabs: the per-slab window maps outgrow the LDS and the lane-per-list kernel below takes over)
-    g_k1_name = K->kernel = "k_lookup_v3";
-    const size_t lds3 = (size_t)((((read_len + 3) / 4) + 3 * NL + ix.n_slabs * NL + (ix.n_slabs + 1) / 2 + (NL * (ix.n_slabs + 1) + 1) / 2 + 3) & ~3) * 4 + (size_t)bm_words * 4;
-    GM_HIP(gm_lds_at_least((const void*)k_lookup_v3, lds3));
-    int k1_threads = 768;
-    if (const char* e = gm_tune("GM_K1_THREADS")) k1_threads = std::max(64, std::min(768, atoi(e) & ~63));
-    hipLaunchKernelGGL(k_lookup_v3, dim3(n_reads * 2), dim3(k1_threads), lds3, stream, ix, d_reads, n_reads, read_len, read_words,
-                       max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap, d_stats,
-                       gm_tune("GM_K1_ABLATE") ? atoi(gm_tune("GM_K1_ABLATE")) : 0, d_surv_seg);
-  } else {
-    g_k1_name = K->kernel = "k_lookup";
-    // one list per lane when the read-strand's lists fit a workgroup: every list slice is in flight at once
-    int k1_threads = std::min(1024, (NL + 63) & ~63);
-    if (const char* e = gm_tune("GM_K1_THREADS")) k1_threads = std::max(64, std::min(1024, atoi(e) & ~63));
-    if (all) {
-      GM_HIP(gm_lds_at_least((const void*)k_lookup<false, 6>, lds));
-      hipLaunchKernelGGL((k_lookup<false, 6>), dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                         max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                         (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, d_surv_seg);
-    } else
-    hipLaunchKernelGGL(k_lookup<false>, dim3(n_reads * 2), dim3(k1_threads), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                       max_n_kmers, NL, bm_words, d_surv, d_surv_cnt, scap, d_heavy_list, d_heavy_cnt, heavy_cap,
-                       (const uint32_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats,
-                       gm_tune("GM_K1_ABLATE") ? atoi(gm_tune("GM_K1_ABLATE")) : 0, d_surv_seg);
-  }
-  GM_HIP(hipGetLastError());
-  return GM_OK;
+  gm_set_error("lookup: no kernel of the plan could run"); return GM_E_NODEVICE;      // (not reached: the last variant of a plan needs no scratch)
 }
 
-// heavy tier: re-run the listed read-strands, each into its exactly sized slice of d_out
+// heavy tier: re-run the listed read-strands, each into its exactly sized slice of d_out (the slab-sweep kernel in redo mode, K1_THREADS threads)
 int gm_launch_lookup_redo(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                           int n_heavy, const uint32_t* d_redo_list, const uint64_t* d_redo_off, uint64_t* d_out,
                           unsigned long long* d_stats, hipStream_t stream) {
-  int max_n_kmers, NL, bm_words; size_t lds;
-  k1_geometry(ix, read_len, &max_n_kmers, &NL, &bm_words, &lds);
   if (n_heavy == 0) return GM_OK;
-  if (ix.no_region_counts) {
-    GM_HIP(gm_lds_at_least((const void*)k_lookup<false, 6>, lds));
-    hipLaunchKernelGGL((k_lookup<false, 6>), dim3(n_heavy), dim3(K1_THREADS), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                       max_n_kmers, NL, bm_words, d_out, (uint32_t*)nullptr, 0, (uint32_t*)nullptr, (uint32_t*)nullptr, 0,
-                       d_redo_list, d_redo_off, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, (uint32_t*)nullptr);
-  } else
-  if (ix.mp.mode == 5) {
-    int rc = k1_mp_lds(lds); if (rc) return rc;
-    hipLaunchKernelGGL((k_lookup<false, 5>), dim3(n_heavy), dim3(K1_THREADS), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                       max_n_kmers, NL, bm_words, d_out, (uint32_t*)nullptr, 0, (uint32_t*)nullptr, (uint32_t*)nullptr, 0,
-                       d_redo_list, d_redo_off, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, (uint32_t*)nullptr);
-  } else
-  if (ix.mp.mode == 4) {
-    int rc = k1_mp_lds(lds); if (rc) return rc;
-    hipLaunchKernelGGL((k_lookup<false, 4>), dim3(n_heavy), dim3(K1_THREADS), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                       max_n_kmers, NL, bm_words, d_out, (uint32_t*)nullptr, 0, (uint32_t*)nullptr, (uint32_t*)nullptr, 0,
-                       d_redo_list, d_redo_off, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, (uint32_t*)nullptr);
-  } else
-  if (ix.mp.mode == 2) {
-    int rc = k1_mp_lds(lds); if (rc) return rc;
-    hipLaunchKernelGGL((k_lookup<false, 2>), dim3(n_heavy), dim3(K1_THREADS), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                       max_n_kmers, NL, bm_words, d_out, (uint32_t*)nullptr, 0, (uint32_t*)nullptr, (uint32_t*)nullptr, 0,
-                       d_redo_list, d_redo_off, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, (uint32_t*)nullptr);
-  } else
-  hipLaunchKernelGGL(k_lookup<false>, dim3(n_heavy), dim3(K1_THREADS), lds, stream, ix, d_reads, n_reads, read_len, read_words,
-                     max_n_kmers, NL, bm_words, d_out, (uint32_t*)nullptr, 0, (uint32_t*)nullptr, (uint32_t*)nullptr, 0,
-                     d_redo_list, d_redo_off, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_stats, 0, (uint32_t*)nullptr);
+  const K1Geom g = k1_geometry(k1_plan_in(ix, n_reads, read_len, nullptr, 0));
+  const int mp = k1_redo_mp(ix.no_region_counts, ix.mp.mode);      // (mate-pair modes 1 and 3 run MP 0 here)
+  const K1Call c = {ix, d_reads, n_reads, read_len, read_words, g, d_out, nullptr, 0, nullptr, nullptr, 0, d_stats, nullptr, stream};
+  { const int rc = k1_launch(c, K1_REDO, mp, K1_THREADS, (mp >= 2 && mp <= 5) ? k1_mp_lds(g.lds) : g.lds, 0, n_heavy, d_redo_list, d_redo_off); if (rc) return rc; }
   GM_HIP(hipGetLastError());
   return GM_OK;
 }

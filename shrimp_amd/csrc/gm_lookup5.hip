@@ -24,10 +24,9 @@
 //    only keeps more (both rules are monotone: more neighbours => keep), which is still exact.
 //  * 6 workgroup barriers per read-strand (v4: ~25), no candidate scratch in global memory.
 //
-// Read-strands whose candidates do not fit (repeats) are redone by k_lookup<false> in list mode + k_prune in
+// Read-strands whose candidates do not fit (repeats) are redone by k_lookup<0> in list mode + k_prune in
 // list mode (gm_lookup.hip / gm_prune.hip).
 #include <algorithm>
-#include <cmath>
 #include <mutex>
 #include "gm_common.h"
 #include "gm_internal.h"
@@ -46,7 +45,6 @@ typedef __attribute__((address_space(3))) uint16_t k5_lds_u16;
 #define K5_Q 4            // list chunks in flight per wave (r03 sweep, ms per 262 144 reads: 1: 87.3, 2: 71.0, 3: 68.6, 4: 65.2, 5: see DESIGN, 6: 69.9, 10: 74.3)
 #endif
 enum { C_NCAND = 0, C_OVERFLOW, C_NMEMB, C_NKEEP, C_WLISTED /* tuning builds: items of the waves' lists */, C_NEDGE, C_NLISTS /* two words: read-strands alternate */, C_SINK = 8, C_NRAW = 9, C_WSPOT = 10 /* tuning builds: items taken on the spot */, C_NCAND0 = 11 /* rounds: the candidates of part 0 */, C_SPILL = 12 /* K5_MAX_ROUNDS - 1 words */, C_WORDS = 16 };
-#define K5_MAX_ROUNDS 4
 
 // Diagnostic build (-DK5_STAMPS): thread 0 of every workgroup adds the cycles between the phase boundaries of each read-strand to k5_stamps[]
 // (0-5: setup, pass A, pass B, region table, rules + output, clears; 6, 7: candidates, fallbacks; 8-11: parts of set-up / the exact stages, taken out of
@@ -231,92 +229,13 @@ int gm_index_derive_strips(GmIndexHost* ix, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// launch: returns 1 when v5 ran (0: geometry does not fit, the caller takes another kernel; < 0: error)
+// launch, in the shape the plan gave (k5_shape, gm_lookup_plan.h): 1 when v5 was launched (0: its scratch could not be allocated, the caller takes the plan's
+// next kernel; < 0: error)
 // ---------------------------------------------------------------------------------------------
-int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads, int read_len, int read_words, int max_n_kmers, int NL,
-                      uint64_t* d_out, uint32_t* d_out_cnt, int out_cap, uint32_t* d_surv_cnt, int prune, uint32_t D, int e_max,
-                      uint32_t* d_heavy_list, uint32_t* d_heavy_cnt, int heavy_cap, unsigned long long* d_stats, hipStream_t stream, GmK1Scratch* K,
-                      uint64_t* d_raw, int raw_cap, uint32_t* d_surv_seg) {
-  int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (!ix.seed[0].sdir || ix.region_bits < 9 || ix.region_bits > 16 || NL <= 0) return 0;
-  const bool forced = gm_tune("GM_K1_V5") != nullptr;
-  double entries = 0;                                          // expected list entries per read-strand
-  for (int sn = 0; sn < ix.n_seeds; sn++) {
-    const double lists = std::max(0, read_len - ix.seed[sn].span + 1 - ix.colour);
-    entries += lists * (double)ix.seed[sn].n_pos / (double)(1ull << (ix.hflag ? 2 * GM_HASH_TABLE_POWER : 2 * ix.seed[sn].weight));
-  }
-  // the fixed cost per read-strand (144 KB of table clears, the barriers) pays off from several thousand list entries per read-strand: 50-colour reads on
-  // 3 Gbp (17 k entries) take 74 ms per 500 k reads here against 124 ms in the slab-sweep kernel
-  if (!forced && entries < 8000.0) return 0;
-  // LDS: twice (1/8 of seen) | seen | 32 B per list | codes | control words
-  // chunk records beyond one per list: 64, or what is left beside full-size tables when the lists alone nearly fill the rest (150 bp reads: 417 lists)
-  const size_t budget = 160 * 1024 - 512;
-  const size_t fixed0 = (size_t)24 * NL + 2 * (size_t)((read_len + 15) & ~15) + C_WORDS * 4 + GM_MAX_SEEDS * 32;              // (one record per list: 16 + 8 bytes, + the seed table)
-  const size_t full_tables = (size_t)(4u << 15) + (size_t)(4u << 12);
-  // (long reads -- two stripes in the vector filter, 450 B of LDS a wave -- keep the extra records few: what the tables leave of a CU's LDS is what pass 1 runs in beside this kernel)
-  int xrec = read_len > 128 ? 16 : 64;
-  if (fixed0 + 24 * (size_t)xrec + full_tables > budget && fixed0 + 24 * 16 + full_tables <= budget) xrec = (int)((budget - full_tables - fixed0) / 24);
-  const size_t fixed = fixed0 + 24 * (size_t)xrec;
-  int lsw = 15;
-  int threads = 1024;                                          // waves per workgroup: a power of two
-  // Colour space with few list entries per read-strand (50-colour reads on 3 Gbp: 17 k): the half-size shape -- tables of 2^19 + 2^16 bits (72 KB) and 512 threads.  The kernel
-  // itself is slower that way (89 against 70 ms per 500 k reads), but it leaves half of a CU's LDS and 320 of a SIMD's 512 registers free, and k_pass2_cs_g4 (256 registers,
-  // 15 KB of LDS a wave), which cannot run beside the full shape at all, then runs beside it: the step 132 -> 125 ms.  (Letter space: k_pass2_g4 fits beside the full shape.)
-  bool small_shape = false;
-  if (!forced && ix.colour && NL <= 512 && !gm_tune("GM_K5_LSW") && !gm_tune("GM_K1_THREADS") && !(gm_tune("GM_K5_SMALL") && atoi(gm_tune("GM_K5_SMALL")) == 0)) {
-    const double lam = entries * (double)((1u << ix.region_bits) + ix.region_overlap) / std::max(1.0, (double)ix.total_len);
-    const double memb = 2.0 * entries * std::min(1.0, lam), late = 0.5 * entries * std::min(1.0, entries / (double)(32ull << 14));
-    const double first = entries * std::min(1.0, (late + 0.5 * memb) / (double)(32ull << 11));
-    const double cap14 = (double)(((4u << 14) / 4u / 6u) & ~15u);
-    if (memb + late + first <= 0.5 * cap14 && fixed + (size_t)(4u << 14) + (size_t)(4u << 11) <= 96 * 1024) { small_shape = true; lsw = 14; threads = 512; }
-  }
-  // The half-size shape with rounds (k_lookup_v5_half): two 512-thread workgroups per CU, 80 KB of LDS each.  GM_K5_HALF=1 forces it, =2 takes the variant without the
-  // Bloom bits (tuning builds), =0 switches it off.
-  int half = 0;
-  if (const char* e = gm_tune("GM_K5_HALF")) half = atoi(e);
-  const size_t half_budget = 80 * 1024 - 512, half_tables = (size_t)(4u << 14) + (size_t)(4u << 11);
-  if (half && (ix.region_bits < 11 || NL > 512 || fixed0 + 24 * 8 + half_tables > half_budget)) half = 0;
-  if (half) { lsw = 14; threads = 512; xrec = (int)std::min<size_t>(64, (half_budget - half_tables - fixed0) / 24); }
-  if (half) if (const char* e = gm_tune("GM_K5_HALF_THREADS")) threads = std::max(64, std::min(1024, atoi(e) & ~63));      // (probe: 640 = ten waves a workgroup, five a SIMD with two workgroups)
-  const size_t fixed_h = fixed0 + 24 * (size_t)xrec;
-  if (!half)
-  if (const char* e = gm_tune("GM_K5_LSW")) lsw = std::max(8, std::min(15, atoi(e)));
-  while (!half && lsw >= 8 && fixed + (size_t)(4u << lsw) + (size_t)(4u << (lsw - 3)) > budget) lsw--;
-  if (lsw < 8) return 0;
-  if (!half)
-  if (const char* e = gm_tune("GM_K1_THREADS")) { const int v = std::max(64, std::min(1024, atoi(e))); threads = 64; while (threads * 2 <= v) threads *= 2; }
-  const int ltw = lsw - 3;                                     // twice[] = an eighth of seen[]
-  const int hbits = lsw - 2;                                   // the region table (12 B per slot) takes three quarters of the seen[] area,
-  const int cand_cap = (int)(((4u << lsw) / 4u / 6u) & ~15u);   // the candidates (6 B each) the rest
-  if (cand_cap < 16) return 0;
-  int cand_limit = cand_cap - 8, rounds = 1;
-  if (!forced) {
-    // Expected candidates per read-strand: the reference's survivors (entries sharing a region; ~2x the independence estimate with the strip and the
-    // echoes of a real hit) + later arrivals on a shared seen[] bit + first arrivals that meet a set twice[] bit.  Read-strands beyond the candidate
-    // array fall back to the slab-sweep kernel: when that would be the rule (2 x 150 bp reads on 3 Gbp: ~9 k), k_lookup_v4 is the better kernel.
-    const double lam = entries * (double)((1u << ix.region_bits) + ix.region_overlap) / std::max(1.0, (double)ix.total_len);
-    // (the Bloom bits of the half-size shape: the rate of a table of twice the size)
-    const double memb = 2.0 * entries * std::min(1.0, lam), late = 0.5 * entries * std::min(1.0, entries / (double)(32ull << (lsw + (half == 1 ? 1 : 0))));
-    const double first = entries * std::min(1.0, (late + 0.5 * memb) / (double)(32ull << (lsw - 3)));
-    // More than one round (pass B and the exact stages per part of the genome) for long reads, as long as the passes over the lists stay cheaper than the separate
-    // kernels: up to four.
-    // (The estimate is generous for long reads -- 12.8 k against 9.2 k counted for 150-base reads on 3 Gbp -- and a round costs 10 % of the kernel: two parts there, 4.6 k
-    // candidates each against 5 456 slots, no read-strand of 262 144 fell back; one that does is redone exactly by the fall-back kernels.)
-    if (memb + late + first > 0.85 * cand_cap) {
-      rounds = (int)std::ceil((memb + late + first) / ((half ? 0.95 : 1.25) * cand_cap));
-      rounds = std::max(rounds, 2);
-      if (rounds > K5_MAX_ROUNDS || NL > threads || lsw != (half ? 14 : 15)) return 0;
-    }
-  }
-  if (const char* e = gm_tune("GM_K5_ROUNDS")) { rounds = std::max(1, std::min(K5_MAX_ROUNDS, atoi(e))); if (rounds > 1 && (NL > threads || lsw != (half ? 14 : 15))) return 0; }
-  // the genome's regions dealt evenly to the rounds (positions are 32 bits; the last round takes what is left)
-  const uint32_t n_regs = (uint32_t)((ix.total_len + (1ull << ix.region_bits) - 1) >> ix.region_bits);
-  const uint32_t round_regs = std::max(1u, (n_regs + (uint32_t)rounds - 1u) / (uint32_t)rounds);
-  if (const char* e = gm_tune("GM_K5_CANDLIMIT")) cand_limit = std::max(1, std::min(cand_limit, atoi(e)));
-  if (prune && (D + (uint32_t)std::max(0, e_max) > (1u << ix.region_bits) || D > 0xFFFFu)) return 0;   // the prune rules need bins (= regions) of at least D + e_max positions
-  const size_t lds = (half ? fixed_h : fixed) + (size_t)(4u << lsw) + (size_t)(4u << ltw);
-  const int fb_cap = std::max(4096, 2 * n_reads);              // every read-strand may fall back (tiny tables in the tests, repeats)
-  if (!K->cus) { if (hipDeviceGetAttribute(&K->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || K->cus < 1) K->cus = 256; }
+static_assert(K5_CTRL_WORDS == C_WORDS, "gm_lookup_plan.h restates the control words");
+int gm_lookup5_launch(const K1Call& c, const K5Shape& sh, int wlist, uint64_t* d_out, uint32_t* d_out_cnt, int out_cap, GmK1Scratch* K) {
+  const hipStream_t stream = c.stream;
+  const int fb_cap = std::max(4096, 2 * c.n_reads);              // every read-strand may fall back (tiny tables in the tests, repeats)
   if (fb_cap > K->k5_cap) {
     if (K->k5_fb) { (void)hipStreamSynchronize(stream); (void)hipFree(K->k5_fb); (void)hipFree(K->k5_pl); K->k5_fb = nullptr; K->k5_pl = nullptr; K->k5_cap = 0; }
     if (hipMalloc(&K->k5_fb, (size_t)(fb_cap + 4) * 4) != hipSuccess) return 0;
@@ -325,29 +244,24 @@ int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads
   }
   uint32_t* const fb_cnt_p = K->k5_fb + K->k5_cap; uint32_t* const pl_cnt_p = K->k5_pl + K->k5_cap;
   if (hipMemsetAsync(fb_cnt_p, 0, 4, stream) != hipSuccess || hipMemsetAsync(pl_cnt_p, 0, 4, stream) != hipSuccess) return GM_E_NODEVICE;
-  if (gm_lds_at_least((const void*)k_lookup_v5<15>, lds) != hipSuccess || gm_lds_at_least((const void*)k_lookup_v5<14>, lds) != hipSuccess ||
-      gm_lds_at_least((const void*)k_lookup_v5_rounds, lds) != hipSuccess || gm_lds_at_least((const void*)k_lookup_v5_half, lds) != hipSuccess ||
+  if (gm_lds_at_least((const void*)k_lookup_v5<15>, sh.lds) != hipSuccess || gm_lds_at_least((const void*)k_lookup_v5<14>, sh.lds) != hipSuccess ||
+      gm_lds_at_least((const void*)k_lookup_v5_rounds, sh.lds) != hipSuccess || gm_lds_at_least((const void*)k_lookup_v5_half, sh.lds) != hipSuccess ||
 #ifdef GM_TUNING
-      gm_lds_at_least((const void*)k_lookup_v5_half_plain, lds) != hipSuccess ||
+      gm_lds_at_least((const void*)k_lookup_v5_half_plain, sh.lds) != hipSuccess ||
 #endif
-      gm_lds_at_least((const void*)k_lookup_v5<0>, lds) != hipSuccess) return 0;
-  // (the half-size shapes: two workgroups a CU.  For the colour-space shape that leaves 16 KB of a CU's LDS, so the colour-space pass 2 runs beside it on the CUs the lookup
-  // has not filled yet or has left already rather than on all of them -- but the lookup itself takes 7.1 instead of 11.5 ms per launch (66 k reads on average), and since pass 2 takes eight
-  // windows a wave the step is shorter that way: 190 -> 179 ms per 1 M 50-colour reads, tools/k5_shape_cfg4.sh; with the four-window pass 2 of round 3 it made no difference)
-  int grid = std::min(2 * n_reads, (half || small_shape) ? 2 * K->cus : K->cus);
-  if (const char* e = gm_tune("GM_K5_GRID")) grid = std::max(1, std::min(2 * n_reads, atoi(e)));
+      gm_lds_at_least((const void*)k_lookup_v5<0>, sh.lds) != hipSuccess) return 0;
   K5Args a;
-  a.reads = d_reads; a.n_reads = n_reads; a.read_len = read_len; a.read_words = read_words; a.max_n_kmers = max_n_kmers; a.NL = NL;
-  a.lsw = lsw; a.ltw = ltw; a.cand_cap = cand_cap; a.hbits = hbits; a.cand_limit = cand_limit; a.xrec = xrec; a.rounds = rounds; a.round_regs = round_regs;
-  a.out = d_out; a.out_cnt = d_out_cnt; a.out_cap = out_cap; a.surv_cnt = d_surv_cnt; a.prune = prune; a.D = D; a.e_max = e_max;
-  a.heavy_list = d_heavy_list; a.heavy_cnt = d_heavy_cnt; a.heavy_cap = heavy_cap; a.stats = d_stats;
+  a.reads = c.reads; a.n_reads = c.n_reads; a.read_len = c.read_len; a.read_words = c.read_words; a.max_n_kmers = c.g.max_n_kmers; a.NL = c.g.NL;
+  a.lsw = sh.lsw; a.ltw = sh.ltw; a.cand_cap = sh.cand_cap; a.hbits = sh.hbits; a.cand_limit = sh.cand_limit; a.xrec = sh.xrec; a.rounds = sh.rounds; a.round_regs = sh.round_regs;
+  a.out = d_out; a.out_cnt = d_out_cnt; a.out_cap = out_cap; a.surv_cnt = c.surv_cnt; a.prune = sh.prune ? 1 : 0; a.D = sh.D; a.e_max = sh.e_max;
+  a.heavy_list = c.heavy_list; a.heavy_cnt = c.heavy_cnt; a.heavy_cap = c.heavy_cap; a.stats = c.stats;
   a.fb_list = K->k5_fb; a.fb_cnt = fb_cnt_p; a.fb_cap = fb_cap;
-  a.raw_out = prune ? d_raw : nullptr; a.raw_cap = raw_cap; a.surv_seg = d_surv_seg; a.n_slabs = ix.n_slabs; a.pl_list = K->k5_pl; a.pl_cnt = pl_cnt_p; a.pl_cap = fb_cap;
-  a.spill = nullptr; a.spill_cap = cand_cap;
-  a.wlist = 0x7FFFFFFF;
-  if (const char* e = gm_tune("GM_K5_WLIST")) a.wlist = std::max(0, atoi(e));
-  if (rounds > 1) {
-    const size_t need = (size_t)grid * (size_t)(rounds - 1) * (size_t)cand_cap;
+  // (the raw rows, their stride and the survivors-per-slab rows are read only with the prune rules)
+  a.raw_out = sh.prune ? c.surv : nullptr; a.raw_cap = c.scap; a.surv_seg = c.surv_seg; a.n_slabs = c.ix.n_slabs; a.pl_list = K->k5_pl; a.pl_cnt = pl_cnt_p; a.pl_cap = fb_cap;
+  a.spill = nullptr; a.spill_cap = sh.cand_cap;
+  a.wlist = wlist;
+  if (sh.rounds > 1) {
+    const size_t need = (size_t)sh.grid * (size_t)(sh.rounds - 1) * (size_t)sh.cand_cap;
     if (need > K->k5_spill_n) {
       if (K->k5_spill) { (void)hipStreamSynchronize(stream); (void)hipFree(K->k5_spill); K->k5_spill = nullptr; K->k5_spill_n = 0; }
       if (hipMalloc(&K->k5_spill, need * sizeof(uint2)) != hipSuccess) return 0;
@@ -355,19 +269,19 @@ int gm_lookup5_launch(const GmIndexDev& ix, const uint32_t* d_reads, int n_reads
     }
     a.spill = K->k5_spill;
   }
-  const bool use_flags = K->start_flags && grid <= K->flag_cap;
-  K->flag_grid = use_flags ? grid : 0;
+  const bool use_flags = K->start_flags && sh.grid <= K->flag_cap;
+  K->flag_grid = use_flags ? sh.grid : 0;
   a.start_flags = use_flags ? K->start_flags : nullptr; a.start_epoch = K->epoch;
-  K->rounds = rounds; K->half = half;
-  if (half) {
+  const dim3 grid(sh.grid), threads(sh.threads);
+  if (sh.half) {
 #ifdef GM_TUNING
-    if (half == 2) hipLaunchKernelGGL(k_lookup_v5_half_plain, dim3(grid), dim3(threads), lds, stream, ix, a); else
+    if (sh.half == 2) hipLaunchKernelGGL(k_lookup_v5_half_plain, grid, threads, sh.lds, stream, c.ix, a); else
 #endif
-    hipLaunchKernelGGL(k_lookup_v5_half, dim3(grid), dim3(threads), lds, stream, ix, a);
-  } else if (rounds > 1) hipLaunchKernelGGL(k_lookup_v5_rounds, dim3(grid), dim3(threads), lds, stream, ix, a);
-  else if (lsw == 15) hipLaunchKernelGGL((k_lookup_v5<15>), dim3(grid), dim3(threads), lds, stream, ix, a);
-  else if (lsw == 14) hipLaunchKernelGGL((k_lookup_v5<14>), dim3(grid), dim3(threads), lds, stream, ix, a);
-  else hipLaunchKernelGGL((k_lookup_v5<0>), dim3(grid), dim3(threads), lds, stream, ix, a);
+    hipLaunchKernelGGL(k_lookup_v5_half, grid, threads, sh.lds, stream, c.ix, a);
+  } else if (sh.rounds > 1) hipLaunchKernelGGL(k_lookup_v5_rounds, grid, threads, sh.lds, stream, c.ix, a);
+  else if (sh.lsw == 15) hipLaunchKernelGGL((k_lookup_v5<15>), grid, threads, sh.lds, stream, c.ix, a);
+  else if (sh.lsw == 14) hipLaunchKernelGGL((k_lookup_v5<14>), grid, threads, sh.lds, stream, c.ix, a);
+  else hipLaunchKernelGGL((k_lookup_v5<0>), grid, threads, sh.lds, stream, c.ix, a);
   if (hipGetLastError() != hipSuccess) return GM_E_NODEVICE;
   return 1;
 }

@@ -242,6 +242,11 @@ KERNEL_VARIANTS = [
     {"GM_P1_EARLY": "0"},                                    # pass 1 without the early stop of windows that cannot reach the threshold
     {"GM_P2_G": "8"},                                        # pass 2 with eight windows a wave and int16_t carry rows (the default in letter space: four, int)
 ]
+# What gm_last_lookup_kernel() names for each entry above, in their order, on both fixtures of the test below (2 Mbp and 1 Mbp: one slab with buckets unless the
+# entry says otherwise): recorded from the library as it was before the choice moved into k1_plan (gm_lookup_plan.h), so that the plan keeps the chain's choice.
+VARIANT_KERNELS = ["k_lookup_v3", "k_lookup_v3"] + ["k_lookup_v4"] * 5 + ["k_lookup_v3", "k_lookup_v4", "k_lookup"] + ["k_lookup_bkt"] * 4 + ["k_lookup_v5"] * 8 + \
+                  ["k_lookup_v5_rounds"] * 4 + ["k_lookup_v5_half"] * 5 + ["k_lookup_bkt"] * 2
+assert len(VARIANT_KERNELS) == len(KERNEL_VARIANTS)
 
 
 @pytest.mark.parametrize("env", KERNEL_VARIANTS, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
@@ -263,9 +268,9 @@ def test_kernel_variants_match_reference_golden(gm, name, env):
         for k, v in old.items():
             if v is None: os.environ.pop(k, None)
             else: os.environ[k] = v
+    print("lookup kernel: %s" % kern)
     assert got == sam, (_first_diff(got, sam), st)
-    want_kern = ("k_lookup_v5_half" if "GM_K5_HALF" in env else "k_lookup_v5_rounds" if "GM_K5_ROUNDS" in env else "k_lookup_v5") if "GM_K1_V5" in env else ("k_lookup_v4" if "GM_K1_V4" in env else None)
-    assert want_kern is None or kern == want_kern, kern
+    assert kern == VARIANT_KERNELS[KERNEL_VARIANTS.index(env)], kern
 
 
 @pytest.mark.parametrize("tag", sorted(oa.OPTION_CASES))

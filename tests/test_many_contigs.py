@@ -332,6 +332,9 @@ def test_paired_sam_matches_reference_golden(gm, run):
 VARIANTS = [{"GM_SCAP": "256", "GM_SCAP2": "64"},                        # the heavy tier: the contig search in global memory, the exact path
             {"GM_NO_PRUNE": "1"}, {"GM_SLAB_BITS": "18", "GM_K1_V5": "1"}, {"GM_NO_BUCKETS": "1"},
             {"GM_NO_BUCKETS": "1", "GM_K1_V5": "1"}]                     # (split_60bp is one slab of 2^18 bases and keeps its buckets: only this entry runs k_lookup_v5 on it)
+# what gm_last_lookup_kernel() names after the unpaired run of each entry, in their order (recorded before the choice moved into k1_plan, gm_lookup_plan.h)
+VARIANT_KERNELS = {"split_60bp": ["k_lookup_bkt", "k_lookup_bkt", "k_lookup_bkt", "k_lookup_v3", "k_lookup_v5"],
+                   "contigs_65536": ["k_lookup_bkt", "k_lookup_bkt", "k_lookup_v5", "k_lookup_v3", "k_lookup_v5"]}
 
 
 @pytest.mark.gpu
@@ -345,9 +348,10 @@ def test_kernel_variants_match_reference_golden(gm, name, env):
     with env_set(**env):
         got_hdr, got, st = map_unpaired(gm, (name, None))
         kern = gm.lib().gm_last_lookup_kernel().decode()
+    print("lookup kernel: %s" % kern)
     assert got_hdr == hdr and got == want, (_first_diff(got, want), st)
     if "GM_SCAP" in env: assert st["exact_order_reads"] >= 300, st          # (most read-strands leave the small LDS tier and take the exact path: 441 and 378; none by default)
-    if "GM_K1_V5" in env: assert kern == ("k_lookup_bkt" if name == "split_60bp" and "GM_NO_BUCKETS" not in env else "k_lookup_v5"), kern
+    assert kern == VARIANT_KERNELS[name][VARIANTS.index(env)], kern
     if name == "contigs_65536":
         with env_set(**env):
             _, got, st = map_paired(gm, (name, "pairs"))
