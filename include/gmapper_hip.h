@@ -129,6 +129,13 @@ void gm_params_default_cs(gm_params_t *p);     /* colour-space defaults (gmapper
  * (ref: gmapper/seeds.c:9-43); n_seeds == 0 selects the binary's default 3 seeds of weight 12
  * (ref: gmapper-defaults.h:212-227).  The index is built on the device (histogram-free radix
  * sort of (k-mer, position) pairs) and stays resident in HBM.
+ * Limits of a seed set: a span of 32 or less (the k-mer key is gathered through a 64-bit mask, two bits a
+ * position), a weight of 14 or less without hash_seeds (any weight with it), at most GM_MAX_SEEDS = 16 seeds,
+ * only '0' and '1', at least one '1'.  A set beyond a limit is refused by gm_index_build, gm_index_build_fasta
+ * and gm_index_load with GM_E_ARG; gm_last_error() names the seed and the limit.  Open against the reference:
+ * it accepts spans up to 64 (MAX_SEED_SPAN, ref: gmapper-definitions.h) -- spans of 33 to 64 are refused
+ * here, not mapped.  Held to the reference's output up to span 32, weight 14 and 16 seeds
+ * (tests/test_seed_sets.py).
  * ------------------------------------------------------------------------------------------- */
 typedef struct gm_index gm_index_t;
 /* The most contigs an index holds.  A window carries its contig number in 16 bits (the anchor kernel's aux word and window sort key, the hit record) where the

@@ -104,6 +104,7 @@ struct Params {
   bool Fflag = true, Cflag = true;  // -F / -C: positive / negative strand only (gmapper.c:1979-1992,2444-2451); both in paired mode
   int max_alignments = 0;
   bool sam_unaligned = false;
+  bool extra_sam_fields = false;  // --extra-sam-fields: ZM ZR ZV ZH ZE behind every mapped record (output.c:743-756)
   int longest_read_len = 1000;
   double score_alpha = 0, score_beta = 0;
   std::vector<Seed> seeds;
@@ -1594,6 +1595,35 @@ struct Mapper {
     if (pr_err > .99999999) return 0; else if (pr_err < 1E-25) return 250;
     return (int)(-10.0 * log(pr_err) / log(10.0));
   }
+  // alignment_edit_string (common/output.c:60-121): runs of matches as numbers, a mismatch as the read's letter, (letters) for a gap in the reference, '-' for a gap
+  // in the read, 'x' before a position that carries a crossover (a lower-case read letter)
+  static std::string edit_string(const std::string& db, const std::string& qr) {
+    std::string e; int consec = 0; bool refgap = false; const size_t len = db.size();
+    for (size_t i = 0; i <= len; i++) {
+      if (i != len && db[i] == qr[i] && db[i] != '-') { consec++; continue; }
+      if (refgap && (consec != 0 || db[i] != '-')) { e += ')'; refgap = false; }      // (db[len]: the terminator, as in the reference)
+      if (consec != 0) { e += std::to_string(consec); consec = 0; }
+      if (i == len) break;
+      const char up = (char)toupper((unsigned char)qr[i]); const bool low = islower((unsigned char)qr[i]) != 0;
+      if (db[i] == '-') { if (low) e += 'x'; if (!refgap) e += '('; e += up; refgap = true; continue; }
+      if (qr[i] == '-') e += '-';
+      else if (db[i] == up) { e += 'x'; consec++; }
+      else if (low) { e += 'x'; e += up; }
+      else e += qr[i];
+    }
+    return e;
+  }
+  // reverse_alignment_edit_string (gmapper/output.c:83-122): numbers keep their digits' order, brackets swap, A C G T are complemented.  Any other letter stops the
+  // reference (assert(0)); none of the committed goldens holds one.
+  static std::string reverse_edit_string(const std::string& e) {
+    const int n = (int)e.size(); std::string r(n, ' '); int i = 0;
+    while (i < n) {
+      const char c = e[n - 1 - i];
+      if (isdigit((unsigned char)c)) { int j = i + 1; while (j < n && isdigit((unsigned char)e[n - 1 - j])) j++; j--; memcpy(&r[i], &e[n - 1 - j], (size_t)(j - i + 1)); i = j + 1; continue; }
+      r[i++] = c == ')' ? '(' : c == '(' ? ')' : c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
+    }
+    return r;
+  }
   static int double_to_neglog(double x) { return (int)((double)1000 * -log(x)); }  // util.h:297-301
 
   void hit_output(const Read& re, const Hit* rh, std::string& out) const {
@@ -1669,6 +1699,11 @@ struct Mapper {
       if (P.Qflag) { out += "\tCQ:Z:"; out += re.qual; }
       out += "\tCS:Z:"; out += re.seq;
       snprintf(buf, sizeof buf, "\tCM:i:%d\tXX:Z:", s.crossovers); out += buf; out += s.qralign;
+    }
+    if (P.extra_sam_fields) {                    // output.c:743-756
+      std::string e = edit_string(s.dbalign, s.qralign);
+      if (reverse_strand) e = reverse_edit_string(e);
+      snprintf(buf, sizeof buf, "\tZM:i:%d\tZR:i:%d\tZV:i:%d\tZH:i:%d\tZE:Z:", rh->matches, rh->score_window_gen, rh->score_vector, s.score); out += buf; out += e;
     }
     out += "\n";
   }

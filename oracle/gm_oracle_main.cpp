@@ -298,7 +298,7 @@ int gmo_sw_full_cs_p(const int* sc, const uint32_t* genome_ls, int goff, int gle
 
 // opts = "key=value;key=value": the reference's command-line options by their long names (gmapper.c:1040-1140):
 // match mismatch open-r ext-r open-q ext-q match-window cmw-overlap cmw-threshold vec-threshold full-threshold
-// cmw-mode report anchor-width cutoff strata max-alignments seeds (comma separated 0/1 strings)
+// cmw-mode report anchor-width cutoff strata max-alignments extra-sam-fields hash-spaced-kmers seeds (comma separated 0/1 strings)
 static void apply_opts(Params& P, const char* opts) {
   if (!opts) return;
   std::string s(opts); size_t i = 0;
@@ -331,6 +331,7 @@ static void apply_opts(Params& P, const char* opts) {
     else if (k == "local") { P.Gflag = d == 0; if (!P.Gflag) P.compute_mapping_qualities = false; }   // --local (gmapper.c:2303-2305,2325-2328)
     else if (k == "ungapped") { if (d != 0) { P.gapless = true; P.anchor_width = 0; P.a_gap_open_score = -255; P.b_gap_open_score = -255; P.hash_filter_calls = false; } }   // -U (gmapper.c:2057-2062)
     else if (k == "hash-spaced-kmers") P.Hflag = d != 0;     // -H
+    else if (k == "extra-sam-fields") P.extra_sam_fields = d != 0;
     else if (k == "crossover") P.crossover_score = (int)d; else if (k == "indel-taboo-len") P.indel_taboo_len = (int)d;
     else if (k == "seeds") {
       P.seeds.clear(); P.max_seed_span = 0; P.min_seed_span = 64;

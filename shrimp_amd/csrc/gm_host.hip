@@ -111,17 +111,24 @@ GmIndexDev GmIndexHost::dev_view() const {
   return d;
 }
 
-static int add_seed(GmIndexHost* ix, const char* s) {   // add_spaced_seed, ref: gmapper/seeds.c:9-43
-  if (ix->n_seeds >= GM_MAX_SEEDS) return GM_E_ARG;
-  GmSeedHost& sd = ix->seeds[ix->n_seeds];
-  sd.mask = 0; sd.span = (int)strlen(s); sd.weight = 0; sd.text = s;
-  if (sd.span < 1 || sd.span > 32) return GM_E_ARG;
-  for (int i = 0; i < sd.span; i++) {
-    if (s[i] != '0' && s[i] != '1') return GM_E_ARG;
-    sd.mask = (sd.mask << 1) | (uint64_t)(s[i] == '1'); sd.weight += (s[i] == '1');
+// add_spaced_seed, ref: gmapper/seeds.c:9-43.  A refusal names the seed and the limit it broke in gm_last_error() (the limits: include/gmapper_hip.h, beside gm_index_build).
+static int add_seed(GmIndexHost* ix, const char* s) {
+  if (!s) { gm_set_error("seed %d: no seed string", ix->n_seeds); return GM_E_ARG; }
+  const size_t len = strlen(s);
+  if (ix->n_seeds >= GM_MAX_SEEDS) { gm_set_error("seed \"%.80s\": more than %d seeds (GM_MAX_SEEDS)", s, GM_MAX_SEEDS); return GM_E_ARG; }
+  if (len < 1) { gm_set_error("seed %d: an empty seed", ix->n_seeds); return GM_E_ARG; }
+  for (size_t i = 0; i < len; i++)
+    if (s[i] != '0' && s[i] != '1') { gm_set_error("seed \"%.80s\": character %zu is neither '0' nor '1'", s, i); return GM_E_ARG; }
+  if (len > 32) { gm_set_error("seed \"%.80s\": span %zu, the limit is 32 (the k-mer key is gathered through a 64-bit mask)", s, len); return GM_E_ARG; }
+  GmSeedHost sd = ix->seeds[ix->n_seeds];
+  sd.mask = 0; sd.span = (int)len; sd.weight = 0; sd.text = s;
+  for (int i = 0; i < sd.span; i++) { sd.mask = (sd.mask << 1) | (uint64_t)(s[i] == '1'); sd.weight += (s[i] == '1'); }
+  if (sd.weight < 1) { gm_set_error("seed \"%s\": weight 0, a seed needs a 1", s); return GM_E_ARG; }
+  if (!ix->params.hash_seeds && sd.weight > 14) {   // MAX_SEED_WEIGHT, ref: gmapper-definitions.h:50, seeds.c:132-136
+    gm_set_error("seed \"%s\": weight %d, the limit is 14 without hash_seeds (-H)", s, sd.weight); return GM_E_ARG;
   }
-  if (sd.weight < 1 || (!ix->params.hash_seeds && sd.weight > 14)) return GM_E_ARG;   // MAX_SEED_WEIGHT, ref: gmapper-definitions.h:50, seeds.c:132-136
   sd.kbits = ix->params.hash_seeds ? 2 * GM_HASH_TABLE_POWER : 2 * sd.weight;
+  ix->seeds[ix->n_seeds] = sd;
   ix->max_seed_span = std::max(ix->max_seed_span, sd.span);
   ix->min_seed_span = std::min(ix->min_seed_span, sd.span);
   ix->n_seeds++;
@@ -193,11 +200,11 @@ static int index_prepare(gm_index* ix, int n_contigs, const uint32_t* const* con
 
 extern "C" void gm_index_free(gm_index_t* ix);
 static int index_seeds(gm_index* ix, int n_seeds, const char* const* seeds) {
-  int rc = GM_OK;
-  if (n_seeds == 0) {   // load_default_seeds(0), letter space: ref gmapper-defaults.h:212-227
-    rc |= add_seed(ix, "11110111101111"); rc |= add_seed(ix, "1111011100100001111"); rc |= add_seed(ix, "1111000011001101111");
-  } else for (int i = 0; i < n_seeds; i++) rc |= add_seed(ix, seeds[i]);
-  return rc;
+  static const char* const DEFAULTS[3] = {"11110111101111", "1111011100100001111", "1111000011001101111"};   // load_default_seeds(0), letter space: ref gmapper-defaults.h:212-227
+  if (n_seeds < 0 || (n_seeds > 0 && !seeds)) { gm_set_error("%d seeds and no seed strings", n_seeds); return GM_E_ARG; }
+  if (n_seeds == 0) { n_seeds = 3; seeds = DEFAULTS; }
+  for (int i = 0; i < n_seeds; i++) { const int rc = add_seed(ix, seeds[i]); if (rc != GM_OK) return rc; }      // (the first refusal's text stays in gm_last_error())
+  return GM_OK;
 }
 extern "C" int gm_index_build(gm_index_t** out, int device, int n_contigs, const uint32_t* const* contigs,
                               const uint32_t* contig_len, const char* const* contig_names,
@@ -210,7 +217,7 @@ extern "C" int gm_index_build(gm_index_t** out, int device, int n_contigs, const
   ix->device = device;
   if (params) ix->params = *params; else gm_params_default(&ix->params);
   int rc = index_seeds(ix, n_seeds, seeds);
-  if (rc != GM_OK) { delete ix; gm_set_error("invalid spaced seed"); return GM_E_ARG; }
+  if (rc != GM_OK) { delete ix; return rc; }
   rc = index_prepare(ix, n_contigs, contigs, contig_len, contig_names);
   if (rc != GM_OK) { gm_index_free(ix); return rc; }
   hipStream_t stream; GM_HIP(hipStreamCreate(&stream));
@@ -232,7 +239,7 @@ extern "C" int gm_index_build_fasta(gm_index_t** out, int device, int n_files, c
   ix->device = device;
   if (params) ix->params = *params; else gm_params_default(&ix->params);
   int rc = index_seeds(ix, n_seeds, seeds);
-  if (rc != GM_OK) { delete ix; gm_set_error("invalid spaced seed"); return GM_E_ARG; }
+  if (rc != GM_OK) { delete ix; return rc; }
   GmFastaGenome G;
   rc = gm_fasta_to_device(n_files, paths, &G);
   if (rc != GM_OK) { delete ix; return rc; }

@@ -132,10 +132,16 @@ extern "C" int gm_index_load(gm_index_t** out, int device, const char* prefix, c
     if (!fp) break;
     struct { uint64_t mask; int32_t span, weight; } st;
     uint32_t m2 = 0, h2 = 0;
-    ok = gz_get(fp, &m2, 4) && gz_get(fp, &h2, 4) && gz_get(fp, &st, 16) && m2 == want_mode && h2 == want_h && st.span >= 1 && st.span <= 32;
+    ok = gz_get(fp, &m2, 4) && gz_get(fp, &h2, 4) && gz_get(fp, &st, 16) && m2 == want_mode && h2 == want_h && st.span >= 1;
+    if (ok && st.span > 32) {   // (the reference writes spans up to 64; its mask does not say what lies above bit 63, so the seed is named by its number)
+      gzclose(fp); delete ix; gm_set_error("%s: seed %d: span %d, the limit is 32 (the k-mer key is gathered through a 64-bit mask)", sname.c_str(), sn, (int)st.span); return GM_E_ARG;
+    }
     std::string text;
     if (ok) for (int i = st.span - 1; i >= 0; i--) text.push_back(((st.mask >> i) & 1) ? '1' : '0');   // first character = highest bit (ref: seeds.c:9-43)
-    ok = ok && add_seed(ix, text.c_str()) == GM_OK && ix->seeds[ix->n_seeds - 1].weight == st.weight;
+    if (ok && add_seed(ix, text.c_str()) != GM_OK) {      // weight above 14 without -H: the limit's own text, behind the file's name
+      const std::string why = gm_last_error(); gzclose(fp); delete ix; gm_set_error("%s: %s", sname.c_str(), why.c_str()); return GM_E_ARG;
+    }
+    ok = ok && ix->seeds[ix->n_seeds - 1].weight == st.weight;
     SeedFile f;
     if (ok) {
       const uint64_t K = 1ull << ix->seeds[ix->n_seeds - 1].kbits;     // capacity, ref: genome.c:141
@@ -147,6 +153,8 @@ extern "C" int gm_index_load(gm_index_t** out, int device, const char* prefix, c
     if (!ok) { delete ix; gm_set_error("%s: truncated or not a seed file of the requested mode", sname.c_str()); return GM_E_ARG; }
     sf.push_back(std::move(f));
   }
+  { const std::string sname = std::string(prefix) + ".seed." + std::to_string(GM_MAX_SEEDS);
+    if ((fp = gzopen(sname.c_str(), "rb"))) { gzclose(fp); delete ix; gm_set_error("%s: more than %d seeds (GM_MAX_SEEDS)", sname.c_str(), GM_MAX_SEEDS); return GM_E_ARG; } }
   if (sf.empty()) { delete ix; gm_set_error("%s.seed.0 not found", prefix); return GM_E_ARG; }
   std::vector<const uint32_t*> cptr(nc); std::vector<const char*> nptr(nc);
   for (uint32_t c = 0; c < nc; c++) { cptr[c] = fwd[c].data(); nptr[c] = names[c].c_str(); }

@@ -17,7 +17,14 @@ struct Row {
   const char* what; double len; int colour, hflag, region_bits, read_len, n_reads, fuse, mode;      // mode: 1 .. 7 the mate-pair mode, 8 no region counts
   const char* env;                                                                                   // knobs of the tuning build, NAME=value,...
   const char* kernel; const char* shape; int redo_mp;                                               // what gm_last_lookup_kernel names, the shape, MP of the heavy tier's re-run
+  const char* seeds;                                                                                 // a seed set of SEED_SETS below, comma separated strings, or null: the three defaults
 };
+// the seed sets of tests/oracle_api.py SEED_SETS that have rows here
+#define SEEDS_REF_W16H "111111101110111111,1111100101101101011111,11110011001010100011011111,111101001100000100110011010111"
+#define SEEDS_ONE "11110111101111"
+#define SEEDS_SIXTEEN "110111111111,1010111111111,11101010111111,1110011011101011,11110110011100101,111010110011010011,11011010011110100001,100001011110010011101," \
+                      "1100100011110001011001,111010011101000010000011,1010100011101000000110011,11100100000100011110100001,1001000010101011010000010101," \
+                      "10000001100001000000011111011,110001100111000001000000001011,10001001100001010010001010010001"
 static const Row ROWS[] = {
   {"100-base reads on 3 Gbp: v5, full shape, one round, prune rules fused", 3000000000, 0, 0, 11, 100, 131072, 1, 0, "", "k_lookup_v5", "v5 lsw=15 ltw=12 hbits=13 cand_cap=5456 cand_limit=5448 xrec=64 threads=1024 half=0 small=0 rounds=1 round_regs=1464844 grid=256 lds=156056 prune=1 D=140 e_max=35", 0},
   {"the same without a fuse request", 3000000000, 0, 0, 11, 100, 131072, 0, 0, "", "k_lookup_v5", "v5 lsw=15 ltw=12 hbits=13 cand_cap=5456 cand_limit=5448 xrec=64 threads=1024 half=0 small=0 rounds=1 round_regs=1464844 grid=256 lds=156056 prune=0 D=100 e_max=-1", 0},
@@ -61,28 +68,52 @@ static const Row ROWS[] = {
   {"mate-pair mode 4", 3000000000, 0, 0, 11, 150, 4096, 0, 4, "", "k_lookup", "sweep mp=4 threads=448 lds=141120", 4},
   {"mate-pair mode 5", 3000000000, 0, 0, 11, 150, 4096, 0, 5, "", "k_lookup", "sweep mp=5 threads=448 lds=141120", 5},
   {"mate-pair mode 7 runs as 2", 3000000000, 0, 0, 11, 150, 4096, 0, 7, "", "k_lookup", "sweep mp=2 threads=448 lds=141120", 0},
-  {"mate-pair mode 2, 60-base reads on 2 Mbp: at least 256 threads", 2000000, 0, 0, 11, 60, 4096, 0, 2, "", "k_lookup", "sweep mp=2 threads=256 lds=69248", 2},
+  {"mate-pair mode 2, 60-base reads on 2 Mbp: at least 256 threads", 2000000, 0, 0, 11, 60, 4096, 0, 2, "", "k_lookup", "sweep mp=2 threads=256 lds=69248", 2},  // Other seed sets (tests/oracle_api.py SEED_SETS), recorded from the plan as it stood when tests/test_seed_sets.py was written and read against gm_lookup_plan.h:
+  // NL = seeds x (read length - shortest span + 1).  sixteen: no bucket kernel (NL > 512); on 3 Gbp v5 would need more than four rounds and declines, at 70 bases v4
+  // takes over, at 100 bases v4's LDS does not fit and the automatic cutoff (71 525) is past v3's 65 535: the slab sweep.
+  {"the reference's weight-16 -H set (spans 18 to 30), 100-base reads, a bucket-sized genome", 2000000, 0, 1, 11, 100, 4096, 1, 0, "", "k_lookup_bkt", "bkt persistent=1 threads=384 lds=368 lds_p=480", 0, SEEDS_REF_W16H},
+  {"the reference's weight-16 -H set (spans 18 to 30), 100-base reads, 2 Mbp in 8 slabs", 2000000, 0, 1, 11, 100, 4096, 1, 0, "GM_SLAB_BITS=18", "k_lookup_v3", "v3 threads=768 lds=20752", 0, SEEDS_REF_W16H},
+  {"the reference's weight-16 -H set (spans 18 to 30), 100-base reads, 3 Gbp", 3000000000, 0, 1, 11, 100, 4096, 1, 0, "", "k_lookup_v5_rounds", "v5 lsw=15 ltw=12 hbits=13 cand_cap=5456 cand_limit=5448 xrec=64 threads=1024 half=0 small=0 rounds=2 round_regs=732422 grid=256 lds=157760 prune=1 D=140 e_max=35", 0, SEEDS_REF_W16H},
+  {"sixteen seeds, 70-base reads: 944 lists, a bucket-sized genome", 2000000, 0, 0, 11, 70, 4096, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=19216", 0, SEEDS_SIXTEEN},
+  {"sixteen seeds, 70-base reads: 944 lists, 2 Mbp in 8 slabs", 2000000, 0, 0, 11, 70, 4096, 1, 0, "GM_SLAB_BITS=18", "k_lookup_v3", "v3 threads=768 lds=58672", 0, SEEDS_SIXTEEN},
+  {"sixteen seeds, 70-base reads: 944 lists, 3 Gbp", 3000000000, 0, 0, 11, 70, 4096, 1, 0, "", "k_lookup_v4", "v4 tab_bits=19 cbits=29 SC=6 wcap=4096 bin_cap=4096 threads=1024 grid=256 lds=158272", 0, SEEDS_SIXTEEN},
+  {"sixteen seeds, 100-base reads: 1 424 lists, more than a workgroup has threads, a bucket-sized genome", 2000000, 0, 0, 11, 100, 4096, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=28848", 0, SEEDS_SIXTEEN},
+  {"sixteen seeds, 100-base reads: 1 424 lists, more than a workgroup has threads, 2 Mbp in 8 slabs", 2000000, 0, 0, 11, 100, 4096, 1, 0, "GM_SLAB_BITS=18", "k_lookup_v3", "v3 threads=768 lds=88464", 0, SEEDS_SIXTEEN},
+  {"sixteen seeds, 100-base reads: 1 424 lists, more than a workgroup has threads, 3 Gbp", 3000000000, 0, 0, 11, 100, 4096, 1, 0, "", "k_lookup", "sweep mp=0 threads=1024 lds=99840", 0, SEEDS_SIXTEEN},
+  {"one seed, 100-base reads: 87 lists, a bucket-sized genome", 2000000, 0, 0, 11, 100, 4096, 1, 0, "", "k_lookup_bkt", "bkt persistent=1 threads=128 lds=368 lds_p=480", 0, SEEDS_ONE},
+  {"one seed, 100-base reads: 87 lists, 2 Mbp in 8 slabs", 2000000, 0, 0, 11, 100, 4096, 1, 0, "GM_SLAB_BITS=18", "k_lookup_v3", "v3 threads=768 lds=5568", 0, SEEDS_ONE},
+  {"one seed, 100-base reads: 87 lists, 3 Gbp", 3000000000, 0, 0, 11, 100, 4096, 1, 0, "", "k_lookup_v5", "v5 lsw=15 ltw=12 hbits=13 cand_cap=5456 cand_limit=5448 xrec=64 threads=1024 half=0 small=0 rounds=1 round_regs=1464844 grid=256 lds=151880 prune=1 D=140 e_max=35", 0, SEEDS_ONE},
+  {"default seeds, 183-base reads on a bucket-sized genome: 510 lists (3 x 170), the last length with the bucket kernel", 2000000, 0, 0, 11, 183, 4096, 1, 0, "", "k_lookup_bkt", "bkt persistent=1 threads=512 lds=448 lds_p=640", 0, nullptr},
+  {"default seeds, 184-base reads on a bucket-sized genome: 513 lists: no bucket kernel", 2000000, 0, 0, 11, 184, 4096, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=10704", 0, nullptr},
+  {"default seeds, 187-base reads on a bucket-sized genome: 522 lists", 2000000, 0, 0, 11, 187, 4096, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=10896", 0, nullptr},
+  {"default seeds, 188-base reads on a bucket-sized genome: 525 lists", 2000000, 0, 0, 11, 188, 4096, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=10960", 0, nullptr},
 };
 
 static std::map<std::string, std::string> g_env;
 static const char* env_get(const char* name) { auto it = g_env.find(name); return it == g_env.end() ? nullptr : it->second.c_str(); }
 
 static K1PlanIn plan_in(const Row& r, const K1Tune& t) {
-  static const char* SEEDS[3] = {"11110111101111", "1111011100100001111", "1111000011001101111"};
+  const std::string set = r.seeds && *r.seeds ? r.seeds : "11110111101111,1111011100100001111,1111000011001101111";
   K1PlanIn in = K1PlanIn();
   in.total_len = (uint64_t)r.len; in.colour = r.colour; in.hflag = r.hflag; in.region_bits = r.region_bits; in.region_overlap = 50;
-  in.n_seeds = 3; in.min_seed_span = 64;
-  for (int i = 0; i < 3; i++) {
-    int w = 0; for (const char* c = SEEDS[i]; *c; c++) w += *c == '1';
-    in.seed[i].span = (int)strlen(SEEDS[i]); in.seed[i].weight = w; in.seed[i].n_pos = (uint32_t)(r.len - in.seed[i].span + 1);
-    in.min_seed_span = std::min(in.min_seed_span, in.seed[i].span);
+  in.n_seeds = 0; in.min_seed_span = 64;
+  int max_weight = 0;
+  for (size_t a = 0; a < set.size() && in.n_seeds < K1P_MAX_SEEDS;) {
+    size_t e = set.find(',', a); if (e == std::string::npos) e = set.size();
+    const std::string sd = set.substr(a, e - a); a = e + 1;
+    int w = 0; for (char c : sd) w += c == '1';
+    const int i = in.n_seeds++;
+    in.seed[i].span = (int)sd.size(); in.seed[i].weight = w; in.seed[i].n_pos = (uint32_t)(r.len - in.seed[i].span + 1);
+    in.min_seed_span = std::min(in.min_seed_span, in.seed[i].span); max_weight = std::max(max_weight, w);
   }
-  in.list_cutoff = std::max<uint32_t>(1000u, (uint32_t)((100ull * in.total_len) >> 24));
+  // the automatic cutoff and the lists of a seed: 4^weight, 4^12 with -H (index_tables, add_seed of gm_host.hip)
+  const int cut_bits = 2 * (r.hflag ? K1P_HASH_TABLE_POWER : max_weight), list_bits = 2 * (r.hflag ? K1P_HASH_TABLE_POWER : in.seed[0].weight);
+  in.list_cutoff = std::max<uint32_t>(1000u, (uint32_t)((100ull * in.total_len) >> cut_bits));
   int bits = 12; while ((1ull << bits) < in.total_len) bits++;
   in.slab_bits = std::min(bits, 29);
   if (const char* e = env_get("GM_SLAB_BITS")) in.slab_bits = std::max(r.region_bits + 2, std::min(31, atoi(e)));
   in.n_slabs = std::max(1, (int)((in.total_len + (1ull << in.slab_bits) - 1) >> in.slab_bits));
-  in.has_buckets = k1_buckets_allowed(in.n_slabs, t) && (double)in.seed[0].n_pos / (double)(1 << 24) <= 12.0;
+  in.has_buckets = k1_buckets_allowed(in.n_slabs, t) && (double)in.seed[0].n_pos / (double)(1ull << list_bits) <= 12.0;
   in.has_strips = k1_strips_wanted(in.n_slabs, in.region_bits, t);
   in.no_region_counts = r.mode == 8; in.mp_mode = r.mode < 8 ? r.mode : 0;
   in.n_reads = r.n_reads; in.read_len = r.read_len;
@@ -108,15 +139,33 @@ static std::string shape_of(const K1Plan& p, K1Variant v) {
   return b;
 }
 
-int main() {
+static void read_env(const char* env) {
+  g_env.clear();
+  for (std::string e = env; !e.empty();) {
+    const size_t q = e.find(','); const std::string kv = e.substr(0, q); const size_t eq = kv.find('=');
+    g_env[kv.substr(0, eq)] = kv.substr(eq + 1);
+    e = q == std::string::npos ? "" : e.substr(q + 1);
+  }
+}
+
+// query <bases> <colour> <hflag> <read_len> <n_reads> <mode> <NAME=value;...|-> <seeds,...>: the kernel the plan names for one shape, for the tests that hold
+// gm_last_lookup_kernel() to it (tests/test_seed_sets.py)
+static int query(char** a) {
+  std::string env = a[6]; if (env == "-") env = ""; for (char& c : env) if (c == ';') c = ',';
+  read_env(env.c_str());
+  const Row r = {"query", atof(a[0]), atoi(a[1]), atoi(a[2]), 11, atoi(a[3]), atoi(a[4]), 1, atoi(a[5]), "", "", "", 0, a[7]};
+  const K1Tune t = k1_tune_read(env_get);
+  const K1PlanIn in = plan_in(r, t);
+  const K1Plan p = k1_plan(in, t);
+  printf("%s | %s | NL=%d slabs=%d\n", p.n ? k1_variant_name(p, p.order[0]) : "", p.n ? shape_of(p, p.order[0]).c_str() : "", p.g.NL, in.n_slabs);
+  return p.n ? 0 : 1;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 10 && !strcmp(argv[1], "query")) return query(argv + 2);
   int bad = 0, n = 0;
   for (const Row& r : ROWS) {
-    g_env.clear();
-    for (std::string e = r.env; !e.empty();) {
-      const size_t q = e.find(','); const std::string kv = e.substr(0, q); const size_t eq = kv.find('=');
-      g_env[kv.substr(0, eq)] = kv.substr(eq + 1);
-      e = q == std::string::npos ? "" : e.substr(q + 1);
-    }
+    read_env(r.env);
     const K1Tune t = k1_tune_read(env_get);
     const K1PlanIn in = plan_in(r, t);
     const K1Plan p = k1_plan(in, t);

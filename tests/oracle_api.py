@@ -394,6 +394,59 @@ SAM_TAIL_CASES = {
 }
 
 
+# Seed sets beyond the ones the option cases use (tools/make_golden.py --seeds-only, tests/test_seed_sets.py): name -> (seed strings, -H).
+# ref_*: the four non-default rows of the reference's table of default seeds by weight (gmapper-defaults.h:216-227; weights 16 and 18 are the ones its README gives
+# for long reads with -H: spans up to 30, four words of eight positions under the hashed key).  The rest: the library's limits (span 32, weight 14 without -H,
+# 16 seeds) and the shapes next to them, drawn once and fixed here.
+SEED_SETS = {
+    "ref_w10": (["111110011111", "111100110001111", "111100100100100111", "111001000100001001111"], False),
+    "ref_w11": (["1111001111111", "1111100110001111", "11110010010001001111", "11100110010000100100111"], False),
+    "ref_w16H": (["111111101110111111", "1111100101101101011111", "11110011001010100011011111", "111101001100000100110011010111"], True),
+    "ref_w18H": (["11111011111110111111", "11110111011010111011111", "11111100110101101001011111", "11111010101100100010011101111"], True),
+    "span32": (["10000000001000000010001111101111"], False),                                    # weight 12: every bit of the 64-bit mask in use
+    "span32H": (["11101101110010000101100011101001"], True),                                   # weight 17
+    "span32_14": (["10000000001000000010001111101111", "11110111101111"], False),              # mixed spans share one max_seed_span
+    "span31_25H": (["1010011011100100111110111111001", "1001111111110010010100011"], True),    # weights 20 and 15
+    "one": (["11110111101111"], False),                                                        # the default's first seed alone
+    "sixteen": (["110111111111", "1010111111111", "11101010111111", "1110011011101011", "11110110011100101", "111010110011010011", "11011010011110100001",
+                 "100001011110010011101", "1100100011110001011001", "111010011101000010000011", "1010100011101000000110011", "11100100000100011110100001",
+                 "1001000010101011010000010101", "10000001100001000000011111011", "110001100111000001000000001011", "10001001100001010010001010010001"], False),   # GM_MAX_SEEDS, weight 11, spans 12 .. 32
+    "w13": (["11101111111100011", "1110110000111001100111"], False),
+    "w14": (["10111111101011000111"], False),                                                  # MAX_SEED_WEIGHT: 4^14 lists
+    "contiguous": (["111111111111"], False),
+}
+# the runs of every set: tag suffix -> (input golden, reads taken from its front (None: all), colour space, -n 1)
+SEED_RUNS = {
+    "": ("stress_100bp_unal", None, False, False),
+    "_n1": ("n1_noisy_70bp", 1500, False, True),
+    "_def": ("n1_noisy_70bp", 1500, False, False),
+    "_cs": ("stress_cs_60col_unal", 600, True, False),
+}
+SEED_RUNS_NO_EXTRA = ("",)                          # the reference does not return from --extra-sam-fields on stress_100bp_unal (an N in a reversed edit string): stored without them
+SEED_RUNS_W14 = ("", "_def")                       # w14 runs on the two default-mode letter-space inputs only
+# the index fixtures of the seed sets (tests/golden/<name>/, tools/make_golden.py seed_index_cases): name -> (seed strings, -H)
+SEED_INDEX_CASES = {
+    "idxfix_h30": (SEED_SETS["ref_w16H"][0], True),                                            # four mask words in the reference's -S files
+    "idxfix_s32": (["10101000010010000010000010000001", "110110111"], False),                 # span 32 at weight 8 (4^8 lists keep the files small)
+}
+
+
+def seed_runs(name):
+    return [r for r in SEED_RUNS if name != "w14" or r in SEED_RUNS_W14]
+
+
+def seed_oracle_opts(seeds, hashed, colour=False, n1=False):
+    """the oracle's option string of a seed set"""
+    return ("colour=1;" if colour else "") + ("hash-spaced-kmers=1;" if hashed else "") + ("cmw-mode=1;" if n1 else "") + "seeds=" + ",".join(seeds)
+
+
+def load_seed_sam(name, run):
+    """the reference's records (no header, no @PG) of seed set `name` on run `run` of SEED_RUNS, written with --extra-sam-fields --sam-unaligned"""
+    base = SEED_RUNS[run][0]
+    tag = {"": "", "_n1": "_n1", "_def": "", "_cs": ""}[run]
+    return load_option_sam(base, "seeds_%s%s" % (name, tag))
+
+
 def load_option_sam(base, tag):
     with gzip.open(os.path.join(ROOT, "tests", "golden", "%s@%s.sam.gz" % (base, tag)), "rb") as f:
         return f.read()

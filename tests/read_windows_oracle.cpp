@@ -19,11 +19,21 @@ std::string code_seq_cs(const uint8_t* c, int L) { std::string s(L, '.'); if (L)
 extern "C" {
 
 // the binary's defaults (letter space, or gmapper-cs with colour != 0) with the given match mode, automatic list cutoff
+void* rwo_create_opts(int n_contigs, const uint8_t* const* codes, const uint64_t* lens, int colour, int match_mode, int hash_seeds, int n_seeds, const char* const* seeds);
 void* rwo_create(int n_contigs, const uint8_t* const* codes, const uint64_t* lens, int colour, int match_mode) {
+  return rwo_create_opts(n_contigs, codes, lens, colour, match_mode, 0, 0, nullptr);
+}
+// ... with a seed set of its own (n_seeds == 0: the defaults) and -H (hash_seeds != 0), as oracle/gm_oracle_main.cpp's "seeds=" and "hash-spaced-kmers=" options set them
+void* rwo_create_opts(int n_contigs, const uint8_t* const* codes, const uint64_t* lens, int colour, int match_mode, int hash_seeds, int n_seeds, const char* const* seeds) {
   Session* S = new Session();
   load_default_seeds(S->M.P); derive_score_probs(S->M.P);
   if (colour) set_colour_space(S->M.P);
   S->M.P.match_mode = match_mode;
+  S->M.P.Hflag = hash_seeds != 0;
+  if (n_seeds > 0) {
+    S->M.P.seeds.clear(); S->M.P.max_seed_span = 0; S->M.P.min_seed_span = 64;
+    for (int i = 0; i < n_seeds; i++) add_spaced_seed(S->M.P, seeds[i]);
+  }
   S->G.colour = S->M.P.colour;
   for (int c = 0; c < n_contigs; c++) {
     char nm[64]; snprintf(nm, sizeof nm, "contig%d", c + 1);

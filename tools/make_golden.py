@@ -379,13 +379,24 @@ def index_cases():
     _index_case("idxfix_h", "1111011101111011,11011101101110111011", ["-H"])
 
 
-def _index_case(dirname, seeds, extra):
-    import shutil
+def index_genome(short_and_n=False):
+    """chrA / chrB of the index fixtures; short_and_n: + chrC / chrD / chrE of 31, 32 and 33 bases (a span-32 seed has no k-mer, one, two) and four single Ns: on
+    chrA's second and last-but-one base (its first and last span-32 k-mer hold them under a 0 of the mask 1010...01 and nowhere else) and on chrB's first and last
+    base (under the first and the last 1)"""
     rng = np.random.default_rng(5)
     c1 = rng.integers(0, 4, 12000, dtype=np.uint8); c1[3000:3040] = 15; c1[7000:7003] = [5, 6, 14]
     c2 = rng.integers(0, 4, 7003, dtype=np.uint8)
-    contigs = [c1, c2]; names = [b"chrA", b"chrB"]
-    reads, _ = synth.make_reads(contigs, 400, 50, 91)
+    if not short_and_n: return [c1, c2], [b"chrA", b"chrB"]
+    short = [rng.integers(0, 4, n, dtype=np.uint8) for n in (31, 32, 33)]
+    c1[1] = 15; c1[-2] = 15; c2[0] = 15; c2[-1] = 15
+    return [c1, c2] + short, [b"chrA", b"chrB", b"chrC", b"chrD", b"chrE"]
+
+
+def _index_case(dirname, seeds, extra, genome=None):
+    import shutil
+    contigs, names = genome if genome is not None else index_genome()
+    c1, c2 = contigs[:2]
+    reads, _ = synth.make_reads([c1, c2], 400, 50, 91)
     d = os.path.join(OUT, dirname); shutil.rmtree(d, ignore_errors=True); os.makedirs(d)
     with tempfile.TemporaryDirectory() as t:
         g = os.path.join(t, "g.fa"); r = os.path.join(t, "r.fa")
@@ -394,10 +405,78 @@ def _index_case(dirname, seeds, extra):
         subprocess.run([REF, *extra, "-s", seeds, "-S", os.path.join(d, "idx"), g], capture_output=True, check=True)
         p = subprocess.run([REF, "-N", "2", "-L", os.path.join(d, "idx"), r], capture_output=True, check=True)
         body = b"".join(l + b"\n" for l in p.stdout.split(b"\n") if l and not l.startswith(b"@PG"))
-    np.savez_compressed(os.path.join(d, "inputs.npz"), contig0=c1, contig1=c2, reads=reads, seeds=np.array(seeds), contig_names=np.array(names))
-    with gzip.open(os.path.join(d, "from_index.sam.gz"), "wb", compresslevel=9) as f:
-        f.write(body)
+    _npz_fixed(os.path.join(d, "inputs.npz"), **{"contig%d" % i: c for i, c in enumerate(contigs)}, reads=reads, seeds=np.array(seeds), contig_names=np.array(names))
+    _gz_fixed(os.path.join(d, "from_index.sam.gz"), body)
     print(dirname + ": %d SAM records from the reference's -L run; files:" % sum(1 for l in body.split(b"\n") if l and not l.startswith(b"@")), sorted(os.listdir(d)))
+
+
+def _gz_fixed(path, data):
+    """gzip without the time stamp: the same bytes on every run"""
+    with open(path, "wb") as raw:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=raw, compresslevel=9, mtime=0) as f: f.write(data)
+
+
+def _npz_fixed(path, **arrays):
+    """np.savez_compressed with the members' time stamps fixed"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, a in arrays.items():
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)); info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, "w") as f: np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+def seeds_cases():
+    """--seeds-only: the seed sets of tests/oracle_api.py SEED_SETS through the reference on committed inputs (SEED_RUNS), with --extra-sam-fields --sam-unaligned:
+    the match count of a window (ZM) sees a seed's lists go missing where the SAM's other fields do not.  Only the records are stored, without the header.
+    Then the two index fixtures of SEED_INDEX_CASES."""
+    from tests import oracle_api as oa
+    import shutil
+    total = 0
+    inputs = {}
+    for run, (base, n, cs, n1) in oa.SEED_RUNS.items():
+        if base not in inputs:
+            z = np.load(os.path.join(OUT, base + ".npz"))
+            inputs[base] = ([z["contig%d" % i] for i in range(sum(1 for f in z.files if f.startswith("contig") and f[6:].isdigit()))], z["reads"])
+    for name, (seeds, hashed) in oa.SEED_SETS.items():
+        for run in oa.seed_runs(name):
+            base, n, cs, n1 = oa.SEED_RUNS[run]
+            contigs, reads = inputs[base]; reads = reads[:n] if n else reads
+            with tempfile.TemporaryDirectory() as d:
+                g = os.path.join(d, "g.fa"); r = os.path.join(d, "r.csfasta" if cs else "r.fa")
+                write_fa_codes(g, [b"contig%d" % (i + 1) for i in range(len(contigs))], contigs)
+                if cs: synth.write_csfasta_reads(r, reads)
+                else: write_fa_codes(r, [b"r%d" % i for i in range(len(reads))], list(reads))
+                # The reference does not return from --extra-sam-fields when a record on the negative strand has an N in its edit string (reverse_alignment_edit_string,
+                # gmapper/output.c:83-122, knows A C G T only and spins): stress_100bp_unal has such reads and is stored without the extra fields (SEED_RUNS_NO_EXTRA).
+                # Every run has a time limit, so that another such input ends the generator instead of hanging it.
+                cmd = ["timeout", "-k", "5", "120", os.path.join(ROOT, "oracle", "_ref", "gmapper-cs" if cs else "gmapper-ls"), "-N", "4", "-s", ",".join(seeds),
+                       *(["-H"] if hashed else []), *(["-n", "1"] if n1 else []), *([] if run in oa.SEED_RUNS_NO_EXTRA else ["--extra-sam-fields"]), "--sam-unaligned", r, g]
+                p = subprocess.run(cmd, capture_output=True)
+                assert p.returncode == 0, (name, run, p.returncode, p.stderr[-2000:])
+            body = b"".join(l + b"\n" for l in p.stdout.split(b"\n") if l and not l.startswith(b"@"))
+            path = os.path.join(OUT, "%s@seeds_%s%s.sam.gz" % (base, name, "_n1" if n1 else ""))
+            _gz_fixed(path, body)
+            recs = [l.split(b"\t", 3) for l in body.split(b"\n") if l]
+            mapped = [t for t in recs if not int(t[1]) & 4]
+            size = os.path.getsize(path); total += size
+            assert size <= 734_000, (path, size)
+            print("%s@seeds_%s%s: %d reads -> %d records, %d mapped, %d reads mapped, %d bytes" % (base, name, "_n1" if n1 else "", len(reads), len(recs), len(mapped),
+                                                                                                  len({t[0] for t in mapped}), size))
+    print("seed-set goldens: %d bytes" % total)
+    seed_index_cases()
+
+
+def seed_index_cases():
+    from tests import oracle_api as oa
+    for name, (seeds, hashed) in oa.SEED_INDEX_CASES.items():
+        _index_case(name, ",".join(seeds), ["-H"] if hashed else [], genome=index_genome(short_and_n=True))
+        d = os.path.join(OUT, name)
+        for f in sorted(os.listdir(d)):      # the reference stamps its gzip files with the time: re-pack them so that a second run gives the same bytes
+            if f.startswith("idx."):
+                with gzip.open(os.path.join(d, f), "rb") as h: data = h.read()
+                _gz_fixed(os.path.join(d, f), data)
+            assert os.path.getsize(os.path.join(d, f)) <= 734_000, (name, f)
+        print(name + ":", {f: os.path.getsize(os.path.join(d, f)) for f in sorted(os.listdir(d))})
 
 
 def local_kat_cases():
@@ -1475,7 +1554,9 @@ def contigs_cases():
 
 
 if __name__ == "__main__":
-    if "--contigs-only" in sys.argv:
+    if "--seeds-only" in sys.argv:
+        os.makedirs(OUT, exist_ok=True); seeds_cases()
+    elif "--contigs-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); contigs_cases()
     elif "--pair-edges-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); pair_edges_cases()
