@@ -878,6 +878,58 @@ typedef struct gm_sam_input {
 int gm_sam_input_size(void);             /* sizeof(gm_sam_input_t), for the Python mirror */
 int gm_sam_records(gm_session_t *s, const gm_sam_input_t *in, char **sam, size_t *sam_len, uint64_t *read_off /* n_reads + 1, caller's */);
 
+/* gm_read_mappings: pass 2 as a seam -- packed reads to the arrays gm_sam_input_t takes, in one call.  The back half of the unpaired chain (the second vector score, the
+ * full alignment, gm_select_pass2, the text of the mappings) behind gm_read_hits' front, on arrays that stay on the device: a caller who wants a chunk's mappings as
+ * arrays (contig, strand, position, MAPQ, AS, CIGAR) makes this one call instead of gm_read_hits, a gather of a read per hit, gm_sw_vector_batch_ix,
+ * gm_sw_full_ls_batch_ix, gm_select_pass2 and gm_sw_full_batch_text_ix with host code in between.  Letter space, unpaired (see gm_read_windows); the mapping entries do
+ * not use it and print what they printed.
+ * The rule it applies per hit is hit_run_full_sw's (ref: gmapper/mapping.c:332-402), letter space:
+ *   thresh  = (int)abs_or_pct(sw_full_threshold, score_max): -sw_full_threshold for a negative (absolute) threshold, else score_max * (sw_full_threshold / 100.0) as
+ *             doubles, truncated (ref: common/util.h:53) -- evaluated by the host in that very expression, once per possible score_max of the call;
+ *   window  = (cn, gen_st, g_off, w_len) of the hit, resolved on the index as the _ix seams resolve it; the anchor box is the hit's; the read is the read as given;
+ *   sv      = sw_vector of that window and read (:386-388), also in an `ungapped` session (:386-394); this is ZV;
+ *   sv >= thresh: sw_full_ls(window, read, threshscore = thresh, maxscore = sv, revcmpl = gen_st && tiebreak_rev, the box, local_alignment) (:391-394): the hit's record,
+ *             exactly gm_sw_full_ls_batch_ix's -- genome_start counted on the strand's contig; score 0: rmapped = gmapped = 1, genome_start = g_off;
+ *   sv <  thresh: the record the reference leaves (calloc and score = 0, :365,396-398): every field 0, status 0, n_ops 0.
+ * Then gm_select_pass2's rules on those records (its doubles through the host's libm by the same functions: what comes down for that step is score, rmapped and
+ * score_max of every hit, not the hits), and gm_sw_full_batch_text_ix's CIGAR -- with extra_sam_fields also the edit string -- with reverse = gen_st and clip 'S' for
+ * the hits that ARE mappings; every other hit has an empty slice.  Under the session's gm_params_t: global and local_alignment, ungapped, tiebreak_rev, match_mode 1 / 2,
+ * hash_filter_calls, no_mapping_qualities, single_best_mapping, strata, max_alignments, num_outputs, any score set the session accepts.
+ * Per sub-batch of the session: the front of gm_read_hits unchanged (heavy tier, counter read, capacity growth, scan, scatter, scores, selection, emit); a kernel that
+ * makes the pass-2 items from the device hits, naming a hit's read by its ROW of the sub-batch's reads (no copy of a read per hit is made anywhere); the second vector
+ * score; a compaction of the hits with sv >= thresh into the full-alignment work list, in hit order, by wave ballots and prefix sums (no atomics: nothing depends on
+ * timing); the full alignment of that list only; the records; the selection; the text of the selected.  A fixed number of allocations, copies and launches a
+ * sub-batch; device memory under one owner; the call takes its turn on the device like gm_read_hits and leaves the session ready for any other call.
+ * Result: ONE struct, released by ONE call, gm_read_mappings_free (which frees the buffers and zeroes the struct; the struct itself is the caller's).  Indices and
+ * offsets are the call's, not the sub-batch's.  The four offset arrays are always there (n_reads + 1 / n_hits + 1 entries); an array of records or bytes is NULL when it
+ * would be empty.
+ *   hits, hit_off[n_reads + 1]    as gm_read_hits returns them;
+ *   score_vector[n_hits]          sv, the second vector score (ZV);  recs[n_hits]: see above; recs[i].ops_off / n_ops point into `ops`, whether or not it was asked for;
+ *   maps, map_off[n_reads + 1]    as gm_select_pass2 returns them (hit: the index in hits / recs);
+ *   cigar, cigar_off[n_hits + 1]  and, when has_edit (the session's extra_sam_fields), edit, edit_off[n_hits + 1]: as gm_sam_input_t takes them;
+ *   ops, ops_len                  want_ops != 0 only: the edit operations of all records, compacted in hit order (else NULL, and ops_len is still their total).
+ * stats (or NULL): as gm_read_hits fills it, and full_calls / full_cells: the hits that were aligned and their window x read cells.
+ * Refusals, on the host before anything is uploaded, the session usable afterwards: s or out NULL: GM_E_ARG; a colour-space session: GM_E_ARG (colour space needs
+ * post_sw and its host re-dos between the full alignment and the selection: use the chain of seams, gm_read_hits -> gm_sw_full_cs_batch_ix -> gm_post_sw_batch_ix ->
+ * gm_select_pass2 -> gm_sw_full_batch_text_ix); the read arguments as gm_read_hits (GM_E_ARG, GM_E_RANGE); num_tmp_outputs > 64: GM_E_RANGE; a read length whose
+ * windows do not fit the full-alignment kernel's LDS beside the read (the admission test of gm_sw_full_ls_batch): GM_E_RANGE.  A session has no pair mode of its own
+ * (see gm_read_windows), so there is no paired session to refuse.  n_reads <= 0: GM_OK, no hits.  After any failure *out holds nothing to free. */
+typedef struct gm_read_mappings {
+  int32_t  n_reads, has_edit;
+  uint64_t n_hits, n_maps, cigar_len, edit_len, ops_len;
+  gm_pass1_hit_t   *hits;  uint64_t *hit_off;
+  int32_t          *score_vector;
+  gm_sw_full_rec_t *recs;
+  gm_mapping_t     *maps;  uint64_t *map_off;
+  char *cigar; uint64_t *cigar_off;
+  char *edit;  uint64_t *edit_off;
+  uint8_t *ops;
+} gm_read_mappings_t;
+int  gm_read_mappings_size(void);        /* sizeof(gm_read_mappings_t), for the Python mirror */
+int  gm_read_mappings(gm_session_t *s, int n_reads, int read_len, const uint32_t *reads_packed, const uint8_t *initbp, int want_ops,
+                      gm_read_mappings_t *out, gm_map_stats_t *stats);
+void gm_read_mappings_free(gm_read_mappings_t *out);
+
 /* time of the dominant kernel (seed lookup) during the last gm_map_* call, from HIP events on the
  * session's own stream, and the algorithmic bytes it moved */
 int gm_last_lookup_timing(gm_session_t *s, double *ms, uint64_t *alg_bytes, int *launches);

@@ -2085,3 +2085,4 @@ extern "C" int gm_debug_tophits_cs(gm_session_t* s, int n_reads, int n_colours, 
 #include "gm_host_seams.inc"
 #include "gm_host_seams_ix.inc"
 #include "gm_host_text.inc"
+#include "gm_host_pass2.inc"

@@ -157,21 +157,28 @@ extern "C" int gm_select_pass1_f1(gm_session_t* s, int n_reads, int read_len, co
   return GM_OK;
 }
 
-extern "C" int gm_read_hits(gm_session_t* s, int n_reads, int read_len, const uint32_t* reads_packed, const uint8_t* initbp, gm_pass1_hit_t** hits, uint64_t* n_hits,
-                            uint64_t* hit_off, gm_read_window_t** wins, uint64_t* n_wins, uint64_t* off, int** scores, gm_map_stats_t* stats) {
-  if (!s || !hits || !n_hits || !hit_off) { gm_set_error("gm_read_hits: bad arguments"); return GM_E_ARG; }
+// One sub-batch of read_hits_impl while its hits are still on the device: reads [base, base + n) of the call are rows 0 .. n of D->d_reads, their nh hits d_hits (and
+// h_hits, the same records on the host) with the offsets hit_off[n + 1], all counted within the sub-batch but for the records' own `read` (the call's); hits_before:
+// the hits of the sub-batches before it.  gm_read_mappings runs pass 2 from here; a non-zero return ends the call with that code.
+struct Pass1Batch { int base, n; DevSet* D; const gm_pass1_hit_t* d_hits; const gm_pass1_hit_t* h_hits; uint64_t nh, hits_before; const uint64_t* hit_off; };
+typedef int (*pass1_batch_fn)(void* ctx, const Pass1Batch& b);
+
+// gm_read_hits (who names the entry in messages; after: null there)
+static int read_hits_impl(const char* who, gm_session_t* s, int n_reads, int read_len, const uint32_t* reads_packed, const uint8_t* initbp, gm_pass1_hit_t** hits, uint64_t* n_hits,
+                          uint64_t* hit_off, gm_read_window_t** wins, uint64_t* n_wins, uint64_t* off, int** scores, gm_map_stats_t* stats, pass1_batch_fn after, void* after_ctx) {
+  if (!s || !hits || !n_hits || !hit_off) { gm_set_error("%s: bad arguments", who); return GM_E_ARG; }
   const int n_opt = (wins ? 1 : 0) + (n_wins ? 1 : 0) + (off ? 1 : 0) + (scores ? 1 : 0);
-  if (n_opt != 0 && n_opt != 4) { gm_set_error("gm_read_hits: wins, n_wins, off and scores are given together or not at all (%d of the four are)", n_opt); return GM_E_ARG; }
+  if (n_opt != 0 && n_opt != 4) { gm_set_error("%s: wins, n_wins, off and scores are given together or not at all (%d of the four are)", who, n_opt); return GM_E_ARG; }
   const bool want = n_opt == 4;
   *hits = nullptr; *n_hits = 0; hit_off[0] = 0;
   if (want) { *wins = nullptr; *n_wins = 0; off[0] = 0; *scores = nullptr; }
   if (stats) memset(stats, 0, sizeof *stats);
   if (n_reads <= 0) return GM_OK;
-  if (int rc = pass1_reads_check("gm_read_hits", s, n_reads, read_len, reads_packed, initbp)) return rc;
-  if (int rc = pass1_k_check("gm_read_hits", s)) return rc;
+  if (int rc = pass1_reads_check(who, s, n_reads, read_len, reads_packed, initbp)) return rc;
+  if (int rc = pass1_k_check(who, s)) return rc;
   const int W = window_len_of(s->P, read_len);
   const bool cs = s->P.colour_space != 0, cache = s->P.hash_filter_calls != 0;
-  if (gm_score_windows_lds(cs, read_len, W) > GM_SCORE_WIN_LDS_LIMIT) { gm_set_error("gm_read_hits: windows of %d positions beside reads of %d are beyond the scoring kernel's LDS", W, read_len); return GM_E_RANGE; }
+  if (gm_score_windows_lds(cs, read_len, W) > GM_SCORE_WIN_LDS_LIMIT) { gm_set_error("%s: windows of %d positions beside reads of %d are beyond the scoring kernel's LDS", who, W, read_len); return GM_E_RANGE; }
   GmDevTurn dev_turn(s);     // (admitted like the mapping entries)
   GM_HIP(hipSetDevice(s->ix->device));
   DevSet& D = s->set[0];
@@ -219,7 +226,7 @@ extern "C" int gm_read_hits(gm_session_t* s, int n_reads, int read_len, const ui
     unsigned long long t = 0;
     GM_HIP(hipMemcpyAsync(&t, d_off + n_rs, 8, hipMemcpyDeviceToHost, q));
     GM_HIP(hipStreamSynchronize(q));
-    if (total + t >= (1ull << 31)) { gm_set_error("gm_read_hits: %llu windows (a hit names its window in 31 bits)", (unsigned long long)(total + t)); return GM_E_RANGE; }
+    if (total + t >= (1ull << 31)) { gm_set_error("%s: %llu windows (a hit names its window in 31 bits)", who, (unsigned long long)(total + t)); return GM_E_RANGE; }
     if (t > out_cap || !d_out) {
       mem.drop(d_out); mem.drop(d_scores); mem.drop(d_slots); out_cap = std::max<size_t>((size_t)t, 1);
       GM_HIP(mem.get(&d_out, out_cap * sizeof(gm_read_window_t))); GM_HIP(mem.get(&d_scores, out_cap * 4));
@@ -233,11 +240,11 @@ extern "C" int gm_read_hits(gm_session_t* s, int n_reads, int read_len, const ui
     gm_pass1_hit_t* d_hits = nullptr; uint64_t nh = 0, byp = 0;
     {
       GmDevMem sel;                    // the selection's scratch and records of this sub-batch
-      rc = pass1_select_device("gm_read_hits", s, sel, n, read_len, d_out, t, d_off, d_scores, d_slots, hho.data(), &d_hits, &nh, &byp); if (rc) return rc;
+      rc = pass1_select_device(who, s, sel, n, read_len, d_out, t, d_off, d_scores, d_slots, hho.data(), &d_hits, &nh, &byp); if (rc) return rc;
       if (total_hits + nh > hits_cap) {
         const size_t cap = std::max<size_t>((size_t)(total_hits + nh), hits_cap + hits_cap / 2);
         gm_pass1_hit_t* p = mem.host(cap * sizeof(gm_pass1_hit_t), false, h_hits);
-        if (!p) { gm_set_error("gm_read_hits: out of memory at %zu hits", cap); return GM_E_NOMEM; }
+        if (!p) { gm_set_error("%s: out of memory at %zu hits", who, cap); return GM_E_NOMEM; }
         h_hits = p; hits_cap = cap;
       }
       if (nh) GM_HIP(hipMemcpyAsync(h_hits + total_hits, d_hits, (size_t)nh * sizeof(gm_pass1_hit_t), hipMemcpyDeviceToHost, q));
@@ -245,10 +252,10 @@ extern "C" int gm_read_hits(gm_session_t* s, int n_reads, int read_len, const ui
         if (total + t > h_cap) {
           const size_t cap = std::max<size_t>((size_t)(total + t), h_cap + h_cap / 2);
           gm_read_window_t* p = mem.host(cap * sizeof(gm_read_window_t), false, h);
-          if (!p) { gm_set_error("gm_read_hits: out of memory at %zu windows", cap); return GM_E_NOMEM; }
+          if (!p) { gm_set_error("%s: out of memory at %zu windows", who, cap); return GM_E_NOMEM; }
           h = p;
           int* ps = mem.host(cap * sizeof(int), false, h_sc);
-          if (!ps) { gm_set_error("gm_read_hits: out of memory at %zu windows", cap); return GM_E_NOMEM; }
+          if (!ps) { gm_set_error("%s: out of memory at %zu windows", who, cap); return GM_E_NOMEM; }
           h_sc = ps; h_cap = cap;
         }
         hoff.resize((size_t)n_rs + 1);
@@ -260,6 +267,10 @@ extern "C" int gm_read_hits(gm_session_t* s, int n_reads, int read_len, const ui
       }
       if (stats) GM_HIP(hipMemcpyAsync(hraw.data(), d_stats, hraw.size() * 8, hipMemcpyDeviceToHost, q));      // again: the scoring kernel's counters
       GM_HIP(hipStreamSynchronize(q));
+      if (after) {
+        Pass1Batch pb; pb.base = base; pb.n = n; pb.D = &D; pb.d_hits = d_hits; pb.h_hits = h_hits + total_hits; pb.nh = nh; pb.hits_before = total_hits; pb.hit_off = hho.data();
+        rc = after(after_ctx, pb); if (rc) return rc;
+      }
     }
     for (uint64_t k = 0; k < nh; k++) h_hits[total_hits + k].win += (int32_t)total;      // window indices and offsets are the call's, not the sub-batch's
     for (int r = 0; r <= n; r++) hit_off[(size_t)base + r] = total_hits + hho[r];
@@ -283,4 +294,8 @@ extern "C" int gm_read_hits(gm_session_t* s, int n_reads, int read_len, const ui
     *n_wins = total;
   }
   return GM_OK;
+}
+extern "C" int gm_read_hits(gm_session_t* s, int n_reads, int read_len, const uint32_t* reads_packed, const uint8_t* initbp, gm_pass1_hit_t** hits, uint64_t* n_hits,
+                            uint64_t* hit_off, gm_read_window_t** wins, uint64_t* n_wins, uint64_t* off, int** scores, gm_map_stats_t* stats) {
+  return read_hits_impl("gm_read_hits", s, n_reads, read_len, reads_packed, initbp, hits, n_hits, hit_off, wins, n_wins, off, scores, stats, nullptr, nullptr);
 }

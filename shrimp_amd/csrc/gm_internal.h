@@ -276,6 +276,8 @@ int gm_launch_sw_vector_batch_cs(const GmScoreDev& sc, int n, const uint32_t* d_
 // flags: 1 = anchor box given (else the threshold band), 2 = revcmpl, 4 = the window is read on strand 1 (backwards and complemented; goff is then the global position of
 // its lowest forward base), 8 = its contig is RNA (both 0 on caller bitfields); initbp: colour space only, the primer letter | GM_SEAM_RNA; idx: the caller's item
 // (row of reads[] and of the crossover rows, slot of out[]); ops_off / ops_cap: the item's segment of the device ops buffer.
+// By-row form (letter space, gm_read_mappings: k_sw_vector_items and k_sw_full_batch<.., true, true>): the read is row `initbp` of reads[] -- a field letter space never
+// read -- and idx is the slot of out[] alone, so that the items of many hits name one copy of their read.
 struct GmFullItem { long long goff, ax, ay; unsigned long long ops_off; int glen, rlen, alen, awidth, thresh, maxscore, flags, initbp, ops_cap, idx; };
 // v[0..10] = score read_start rmapped genome_start (window-relative) gmapped matches mismatches insertions deletions crossovers n_ops
 struct GmFullOut { int v[12]; };
@@ -284,7 +286,28 @@ size_t gm_sw_full_batch_lds(int max_g, int max_r);
 size_t gm_sw_full_cs_batch_lds(int max_g, int max_r);
 // items[first .. first + n) by `grid` waves; wave b owns back-pointer scratch d_back + b * back_stride (bytes; colour space: uint32 words)
 int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
-                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream, int ix = 0);
+                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream, int ix = 0,
+                            int by_row = 0);      // by_row (with ix): the by-row form of GmFullItem
+
+// Pass 2 as a seam (gm_read_mappings, gm_host_pass2.inc): the rule of hit_run_full_sw on hits that stay on the device.
+//   gm_launch_p2_items (gm_pass2.hip): d_items[i] = the by-row pass-2 item of d_hits[i]; d_thresh_tab[m] = (int)abs_or_pct(sw_full_threshold, m * match) for m = 0 ..
+//                        read_len, made on the host; every item gets ops_cap bytes of operations; d_thresh[i] = the item's thresh again, dense.
+//   gm_launch_sw_vector_items (gm_sw.hip): d_scores[i] = sw_vector of item i's window (strand and RNA bits as the _ix kernels read them) against row d_items[i].initbp of
+//                        d_reads: the second vector score, on the turned hit (ref: mapping.c:386-388).
+//   gm_launch_p2_compact: d_work[0 .. *d_n_work) = the items with d_sv[i] >= d_thresh[i] in item order, maxscore = d_sv[i], ops_off = k * ops_cap; d_pos_of[i] = k, or
+//                        -1 (two launches: the places, then the copies).
+//   gm_launch_p2_records: d_recs[i] / d_p2in[i] from d_out[i] (the full kernel's, slot = hit) for a hit of the work list, the zero record for any other.
+//   gm_launch_p2_sel_items: k_sel_pass2's items from the records, the hits and the host's answers.
+struct GmP2In { int32_t score, rmapped, score_max; };        // what the host's double functions read of a hit
+struct GmP2Host { int32_t score_full, key, keep; };          // what they answer
+int gm_launch_p2_items(int n, const gm_pass1_hit_t* d_hits, int read_base, int read_len, const uint32_t* d_contig_off, const uint8_t* d_contig_rna, const int* d_thresh_tab,
+                       int tiebreak_rev, int ops_cap, GmFullItem* d_items, int* d_thresh, hipStream_t stream);
+int gm_launch_sw_vector_items(const GmScoreDev& sc, int n, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words, int max_g, int max_r,
+                              int* d_scores, hipStream_t stream);
+int gm_launch_p2_compact(int n, const GmFullItem* d_items, const int* d_thresh, const int* d_sv, GmFullItem* d_work, int* d_pos_of, uint32_t* d_n_work, hipStream_t stream);
+int gm_launch_p2_records(int n, const gm_pass1_hit_t* d_hits, const int* d_pos_of, const GmFullOut* d_out, int ops_cap, gm_sw_full_rec_t* d_recs, GmP2In* d_p2in,
+                         hipStream_t stream);
+int gm_launch_p2_sel_items(int n, const gm_pass1_hit_t* d_hits, const gm_sw_full_rec_t* d_recs, const GmP2Host* d_ans, GmSel2Item* d_items, hipStream_t stream);
 int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
                                int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
                                uint8_t* d_ops, int local, hipStream_t stream, int ix = 0);      // ix: the items carry strand / RNA bits (gm_sw_full_cs_batch_ix)

@@ -1172,8 +1172,8 @@ k_sw_vector_batch(GmScoreDev sc, int n, const uint32_t* __restrict__ genome, con
 // are agent-scope atomic loads (no stale line of an earlier item in the vector cache); an item's stores precede its walk by a barrier, and the next
 // item's stores follow the walk in program order of the same wave.
 // ---------------------------------------------------------------------------------------------
-template <bool LOCAL, bool IX = false>      // IX: gm_sw_full_ls_batch_ix -- the strand / RNA bits of GmFullItem.flags are read (an instantiation of its own)
-__global__ void __launch_bounds__(GM_WAVE)
+template <bool LOCAL, bool IX = false, bool BYROW = false>      // IX: gm_sw_full_ls_batch_ix -- the strand / RNA bits of GmFullItem.flags are read (an instantiation of its own);
+__global__ void __launch_bounds__(GM_WAVE)                      // BYROW: gm_read_mappings -- the read is row it.initbp of reads[], it.idx only the slot of out[] (likewise)
 k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ items, const uint32_t* __restrict__ genome, const uint32_t* __restrict__ reads,
                 int read_words, int max_g, int max_r, uint8_t* __restrict__ back_pool, size_t back_stride, GmFullOut* __restrict__ out, uint8_t* __restrict__ ops_all) {
   extern __shared__ __align__(16) uint8_t sm[];
@@ -1186,7 +1186,7 @@ k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ 
     const GmFullItem it = items[first + k];
     const int glen = __builtin_amdgcn_readfirstlane(it.glen), rlen = __builtin_amdgcn_readfirstlane(it.rlen), flags = __builtin_amdgcn_readfirstlane(it.flags);
     __syncthreads();                                                              // lane 0 may still read the previous item's db / qr
-    load_read(reads + (size_t)it.idx * read_words, rlen, false, qr, lane);
+    load_read(reads + (size_t)(BYROW ? it.initbp : it.idx) * read_words, rlen, false, qr, lane);
     load_window(genome, (uint64_t)it.goff, glen, IX && (flags & 4) != 0, db, lane, IX && (flags & 8) != 0);
     __syncthreads();
     const bool has_anchor = (flags & 1) != 0, revcmpl = (flags & 2) != 0;
@@ -1213,15 +1213,17 @@ k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ 
 
 size_t gm_sw_full_batch_lds(int max_g, int max_r) { return ((max_r + 15) & ~15) + ((max_g + 15) & ~15) + (size_t)max_g * 12 + 64; }
 int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
-                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream, int ix) {
+                            int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream, int ix, int by_row) {
   if (n == 0) return GM_OK;
   const size_t lds = gm_sw_full_batch_lds(max_g, max_r);
   if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("sw_full_ls batch: window of %d does not fit LDS", max_g); return GM_E_ARG; }
-#define GM_SWF_LAUNCH(LOC, IX) do { \
-    GM_HIP(gm_lds_at_least((const void*)k_sw_full_batch<LOC, IX>, lds)); \
-    hipLaunchKernelGGL((k_sw_full_batch<LOC, IX>), dim3(grid), dim3(GM_WAVE), lds, stream, sc, first, n, d_items, d_genome, d_reads, read_words, max_g, max_r, d_back, back_stride, \
+  if (by_row && !ix) { gm_set_error("sw_full_ls batch: the by-row items are items on the index"); return GM_E_ARG; }
+#define GM_SWF_LAUNCH(LOC, ...) do { \
+    GM_HIP(gm_lds_at_least((const void*)k_sw_full_batch<LOC, __VA_ARGS__>, lds)); \
+    hipLaunchKernelGGL((k_sw_full_batch<LOC, __VA_ARGS__>), dim3(grid), dim3(GM_WAVE), lds, stream, sc, first, n, d_items, d_genome, d_reads, read_words, max_g, max_r, d_back, back_stride, \
                        d_out, d_ops); } while (0)
-  if (local) { if (ix) GM_SWF_LAUNCH(true, true); else GM_SWF_LAUNCH(true, false); }
+  if (by_row) { if (local) GM_SWF_LAUNCH(true, true, true); else GM_SWF_LAUNCH(false, true, true); }
+  else if (local) { if (ix) GM_SWF_LAUNCH(true, true); else GM_SWF_LAUNCH(true, false); }
   else { if (ix) GM_SWF_LAUNCH(false, true); else GM_SWF_LAUNCH(false, false); }
 #undef GM_SWF_LAUNCH
   GM_HIP(hipGetLastError());
@@ -2313,6 +2315,39 @@ int gm_launch_sw_vector_batch_ix(const GmIndexDev& ix, const GmScoreDev& sc, int
                                    d_scores, 0, nullptr);
   else hipLaunchKernelGGL(k_sw_vector_batch_ix<false>, dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, n, d_wins, d_reads, read_words, d_rlen, d_initbp, max_g, max_r,
                           d_scores, early_thr, d_stopped);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// gm_read_mappings: the second vector score of every pass-1 hit, on the turned hit (ref: mapping.c:386-388) -- k_sw_vector_batch_ix's letter-space routine over the by-row
+// pass-2 items (GmFullItem): the window by its global forward offset and strand / RNA bits as k_sw_full_batch<.., true> reads it, the read by the item's row of the
+// sub-batch's reads.  No copy of a read per hit exists anywhere.
+__global__ void __launch_bounds__(GM_WAVE)
+k_sw_vector_items(GmScoreDev sc, int n, const GmFullItem* __restrict__ items, const uint32_t* __restrict__ genome, const uint32_t* __restrict__ reads, int read_words,
+                  int max_g, int max_r, int* __restrict__ scores) {
+  extern __shared__ __align__(16) uint8_t sm[];
+  const int lane = threadIdx.x;
+  uint8_t* qr = sm;
+  uint8_t* db = sm + ((max_r + 15) & ~15);
+  int16_t* carry = (int16_t*)(db + ((max_g + 15) & ~15));
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const GmFullItem* it = items + i;
+    const int glen = __builtin_amdgcn_readfirstlane(it->glen), rl = __builtin_amdgcn_readfirstlane(it->rlen), flags = __builtin_amdgcn_readfirstlane(it->flags);
+    const int row = __builtin_amdgcn_readfirstlane(it->initbp);
+    __syncthreads();
+    load_read(reads + (size_t)row * read_words, rl, false, qr, lane);
+    load_window(genome, (uint64_t)it->goff, glen, (flags & 4) != 0, db, lane, (flags & 8) != 0);
+    __syncthreads();
+    const int s = sw_vector_wave(db, glen, qr, rl, sc, carry, lane);
+    if (lane == 0) scores[i] = s;
+  }
+}
+int gm_launch_sw_vector_items(const GmScoreDev& sc, int n, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words, int max_g, int max_r,
+                              int* d_scores, hipStream_t stream) {
+  if (n == 0) return GM_OK;
+  const size_t lds = gm_score_windows_lds(0, max_r, max_g);      // (the layout of k_sw_vector_batch_ix: the read, the window, the carry rows)
+  if (lds > GM_SCORE_WIN_LDS_LIMIT) { gm_set_error("gm_launch_sw_vector_items: %zu bytes of LDS a wave", lds); return GM_E_RANGE; }
+  hipLaunchKernelGGL(k_sw_vector_items, dim3(std::min(n, 256 * 16)), dim3(GM_WAVE), lds, stream, sc, n, d_items, d_genome, d_reads, read_words, max_g, max_r, d_scores);
   GM_HIP(hipGetLastError());
   return GM_OK;
 }

@@ -141,12 +141,60 @@ class SAM_INPUT(C.Structure):       # gm_sam_input_t: what gm_sam_records takes 
                 ("map_off", C.c_void_p)]
 
 
+class ReadMappingsResult(C.Structure):   # gm_read_mappings_t: what gm_read_mappings fills (checked against gm_read_mappings_size())
+    _fields_ = [("n_reads", C.c_int32), ("has_edit", C.c_int32), ("n_hits", C.c_uint64), ("n_maps", C.c_uint64), ("cigar_len", C.c_uint64), ("edit_len", C.c_uint64),
+                ("ops_len", C.c_uint64), ("hits", C.c_void_p), ("hit_off", C.c_void_p), ("score_vector", C.c_void_p), ("recs", C.c_void_p), ("maps", C.c_void_p),
+                ("map_off", C.c_void_p), ("cigar", C.c_void_p), ("cigar_off", C.c_void_p), ("edit", C.c_void_p), ("edit_off", C.c_void_p), ("ops", C.c_void_p)]
+
+
 SW_FULL_REC_DTYPE = np.dtype(SwFullRec)      # the structured numpy view of an array of them
 POST_REC_DTYPE = np.dtype(PostRec)
 ANCHOR_DTYPE = np.dtype(Anchor)
 READ_WINDOW_DTYPE = np.dtype(ReadWindow)
 PASS1_HIT_DTYPE = np.dtype(Pass1Hit)
 MAPPING_DTYPE = np.dtype(Mapping)
+# one row of ReadMappings.table(): a mapping as a SAM record states it
+MAPPING_TABLE_DTYPE = np.dtype([("read", np.int32), ("contig", np.int32), ("strand", np.int32), ("pos", np.uint32), ("mapq", np.int32), ("as", np.int32), ("nm", np.int32),
+                                ("hit", np.int32)])
+
+
+def mapping_positions(hits, recs, contig_len, hit_index):
+    """POS of the mappings on the hits `hit_index`, as gm_sam_records prints it (ref: gmapper/output.c:626-634): forward strand genome_start + 1; strand 1
+    (contig_len - genome_start) - (rmapped - 1 - deletions + insertions); the low 32 bits, unsigned.  numpy only, no loop."""
+    k = np.asarray(hit_index, dtype=np.int64)
+    h, r = hits[k], recs[k]
+    gs = r["genome_start"].astype(np.int64)
+    fw = gs + 1
+    rv = (np.asarray(contig_len, dtype=np.int64)[h["cn"]] - gs) - (r["rmapped"].astype(np.int64) - 1 - r["deletions"] + r["insertions"])
+    return (np.where(h["gen_st"] == 0, fw, rv) & 0xFFFFFFFF).astype(np.uint32)
+
+
+class ReadMappings:
+    """What Session.read_mappings returns: the arrays of gm_read_mappings_t as numpy arrays of the existing dtypes.
+    hits (PASS1_HIT_DTYPE), hit_off; score_vector (ZV of every hit); recs (SW_FULL_REC_DTYPE); maps (MAPPING_DTYPE), map_off; cigar_buf / cigar_off and, where the
+    session prints them, edit_buf / edit_off; ops (want_ops only, else None).  cigar(i) / edit(i): the text of hit i (empty for a hit that is no mapping).  The object
+    goes into Session.sam_records in place of its first array."""
+    def __init__(self, hits, hit_off, score_vector, recs, maps, map_off, cigar_buf, cigar_off, edit_buf, edit_off, ops, contig_len):
+        self.hits, self.hit_off, self.score_vector, self.recs, self.maps, self.map_off = hits, hit_off, score_vector, recs, maps, map_off
+        self.cigar_buf, self.cigar_off, self.edit_buf, self.edit_off, self.ops, self.contig_len = cigar_buf, cigar_off, edit_buf, edit_off, ops, contig_len
+
+    def cigar(self, i): return self.cigar_buf[int(self.cigar_off[i]):int(self.cigar_off[i + 1])]
+
+    def edit(self, i):
+        if self.edit_off is None: raise GmError("read_mappings: the session prints no edit strings (extra_sam_fields)")
+        return self.edit_buf[int(self.edit_off[i]):int(self.edit_off[i + 1])]
+
+    def table(self):
+        """One MAPPING_TABLE_DTYPE row per mapping, in maps order: read, contig, strand, POS (1-based, as SAM prints it), MAPQ, AS, NM, hit"""
+        m = self.maps; k = m["hit"].astype(np.int64)
+        t = np.zeros(len(m), dtype=MAPPING_TABLE_DTYPE)
+        if not len(m): return t
+        h, r = self.hits[k], self.recs[k]
+        t["read"], t["contig"], t["strand"], t["hit"] = m["read"], h["cn"], h["gen_st"], m["hit"]
+        t["pos"] = mapping_positions(self.hits, self.recs, self.contig_len, k)
+        t["mapq"], t["as"] = m["mqv"], m["score_full"]
+        t["nm"] = r["mismatches"] + r["deletions"] + r["insertions"]
+        return t
 
 
 # every entry point include/gmapper_hip.h declares
@@ -161,7 +209,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_index_genome_is_rna", "gm_index_get_windows", "gm_sw_vector_batch_ix", "gm_sw_vector_batch_bounded_ix", "gm_sw_gapless_batch_ix", "gm_sw_full_ls_batch_ix", "gm_sw_full_cs_batch_ix",
            "gm_post_sw_batch_ix", "gm_sw_full_batch_text", "gm_sw_full_batch_text_ix",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits", "gm_debug_tophits_cs",
-           "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size", "gm_score_windows", "gm_select_pass1_f1", "gm_read_hits", "gm_sam_records", "gm_sam_input_size",
+           "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size", "gm_score_windows", "gm_select_pass1_f1", "gm_read_hits", "gm_sam_records", "gm_sam_input_size", "gm_read_mappings", "gm_read_mappings_free", "gm_read_mappings_size",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
 
@@ -283,6 +331,11 @@ def lib():
     L.gm_sam_records.argtypes = [vp, C.POINTER(SAM_INPUT), C.POINTER(vp), C.POINTER(C.c_size_t), u64p]
     if L.gm_sam_input_size() != C.sizeof(SAM_INPUT):
         raise GmError("gm_sam_input_t is %d bytes in the library, %d in SAM_INPUT" % (L.gm_sam_input_size(), C.sizeof(SAM_INPUT)))
+    L.gm_read_mappings_size.argtypes = []; L.gm_read_mappings_size.restype = C.c_int
+    L.gm_read_mappings.argtypes = [vp, C.c_int, C.c_int, u32p, u8p, C.c_int, C.POINTER(ReadMappingsResult), C.POINTER(MapStats)]
+    L.gm_read_mappings_free.argtypes = [C.POINTER(ReadMappingsResult)]; L.gm_read_mappings_free.restype = None
+    if L.gm_read_mappings_size() != C.sizeof(ReadMappingsResult):
+        raise GmError("gm_read_mappings_t is %d bytes in the library, %d in ReadMappingsResult" % (L.gm_read_mappings_size(), C.sizeof(ReadMappingsResult)))
     _lib = L
     return L
 
@@ -948,6 +1001,29 @@ class Session:
         if sout.value: L.gm_free(sout)
         return hits, hit_off, wins, off, scores
 
+    def read_mappings(self, reads_codes, want_ops=False):
+        """Reads to mappings in one call (gm_read_mappings: read_hits, then per hit the second vector score, the full alignment at or above the threshold, select_pass2
+        and the text of the mappings, on arrays that stay on the device): -> ReadMappings.  Letter space, unpaired.  want_ops: the edit operations of the records come
+        down too.  The stage counters of the call are left in self.stats."""
+        n, Lr, packed, _ = self._reads_args("read_mappings", reads_codes, None)
+        L = lib(); R = ReadMappingsResult(); st = MapStats()
+        _check(L.gm_read_mappings(self.h, n, Lr, packed.ctypes.data_as(C.POINTER(C.c_uint32)), None, 1 if want_ops else 0, C.byref(R), C.byref(st)), "gm_read_mappings")
+        try:
+            def take(p, count, dtype):
+                a = np.zeros(count, dtype=dtype)
+                if count and p: C.memmove(a.ctypes.data, p, count * a.dtype.itemsize)
+                return a
+            nh, nm = int(R.n_hits), int(R.n_maps)
+            res = ReadMappings(take(R.hits, nh, PASS1_HIT_DTYPE), take(R.hit_off, n + 1, np.uint64), take(R.score_vector, nh, np.int32), take(R.recs, nh, SW_FULL_REC_DTYPE),
+                               take(R.maps, nm, MAPPING_DTYPE), take(R.map_off, n + 1, np.uint64),
+                               C.string_at(R.cigar, int(R.cigar_len)) if R.cigar else b"", take(R.cigar_off, nh + 1, np.uint64),
+                               (C.string_at(R.edit, int(R.edit_len)) if R.edit else b"") if R.has_edit else None, take(R.edit_off, nh + 1, np.uint64) if R.has_edit else None,
+                               take(R.ops, int(R.ops_len), np.uint8) if want_ops else None, self.index.contig_lengths())
+        finally:
+            L.gm_read_mappings_free(C.byref(R))
+        self.stats = st.as_dict(); self._windows_read_len = Lr
+        return res
+
     def select_pass2(self, hits, hit_off, recs, post=None):
         """Pass 2's selection and the mapping qualities (gm_select_pass2) over the records of ONE full batch call on the hits of select_pass1: -> (maps, map_off).
         maps: structured array of MAPPING_DTYPE in the reference's output order, read r's at maps[map_off[r]:map_off[r + 1]]; post: the POST_REC_DTYPE answers of
@@ -971,7 +1047,7 @@ class Session:
         if out.value: L.gm_free(out)
         return maps, map_off
 
-    def sam_records(self, reads_codes, hits, recs, maps, map_off, cigar, *, initbp=None, names=None, seqs=None, quals=None, qual_delta=33, score_vector=None, post=None,
+    def sam_records(self, reads_codes, hits, recs=None, maps=None, map_off=None, cigar=None, *, initbp=None, names=None, seqs=None, quals=None, qual_delta=33, score_vector=None, post=None,
                     post_quals=None, qralign=None, edit=None):
         """The SAM text of a chunk's mappings (gm_sam_records): -> (bytes, read_off), read r's records at bytes[read_off[r]:read_off[r + 1]].
         reads_codes: [n, L] uint8 codes (colour space: the colours, with initbp); hits / recs / maps / map_off: select_pass1's hits, the records of the ONE full batch
@@ -979,6 +1055,12 @@ class Session:
         (buffer, offsets) pair; qralign / post_quals: what post_sw_batch returned (the text call's qralign where there is no post_sw), or the whole buffers; names /
         seqs / quals: None or one bytes a read; score_vector: ZV of every hit (None: hits["score_vector"]).  The rules: include/gmapper_hip.h."""
         from .synth import pack_reads
+        if isinstance(hits, ReadMappings):                                   # read_mappings' answer: its arrays, ZV = its second vector score
+            rm = hits
+            hits, recs, maps, map_off, cigar = rm.hits, rm.recs, rm.maps, rm.map_off, (rm.cigar_buf, rm.cigar_off)
+            if score_vector is None: score_vector = rm.score_vector
+            if edit is None and rm.edit_off is not None: edit = (rm.edit_buf, rm.edit_off)
+        if recs is None or maps is None or map_off is None or cigar is None: raise GmError("sam_records: recs, maps, map_off and cigar are required beside plain hits")
         reads_codes = np.ascontiguousarray(reads_codes, dtype=np.uint8)
         if reads_codes.ndim != 2: raise GmError("sam_records: reads_codes is (n, read_len)")
         n, Lr = reads_codes.shape
