@@ -930,6 +930,66 @@ int  gm_read_mappings(gm_session_t *s, int n_reads, int read_len, const uint32_t
                       gm_read_mappings_t *out, gm_map_stats_t *stats);
 void gm_read_mappings_free(gm_read_mappings_t *out);
 
+/* gm_read_mappings_cs: colour-space pass 2 as a seam -- packed colour reads to the arrays gm_sam_input_t takes, in one call: gm_read_mappings for a colour-space
+ * session.  It stands for the chain gm_read_hits -> gm_sw_full_cs_batch_ix -> gm_post_sw_batch_ix -> the rounding-guard recipe of gm_select_pass2 -> gm_select_pass2
+ * again -> gm_sw_full_batch_text_ix, with its copy of a read per hit, its thread-local post_sw_setup, its host re-dos of by_host items and its re-do of flagged reads:
+ * a sub-batch's hits, records, operations and posteriors stay on the device from the front to the text.  Unpaired; the mapping entries do not use it.
+ * The rule per hit is hit_run_full_sw's for colour space (ref: gmapper/mapping.c:375-379) and hit_run_post_sw's (:1609-1625):
+ *   thresh  = (int)abs_or_pct(sw_full_threshold, score_max), evaluated by the host in that double expression, once per possible score_max of the call (as gm_read_mappings);
+ *   every hit, with no second vector score, no compaction and no second filter, goes through
+ *             sw_full_cs(window, read, initbp, threshscore = thresh, revcmpl = gen_st && tiebreak_rev, is_rna of the index, the hit's box, local_alignment, the read's
+ *             crossover row): the hit's record, exactly gm_sw_full_cs_batch_ix's (all zero where no alignment reaches thresh);
+ *   crossover row: without quals, or under ignore_qvs, the global crossover score; with quals the per-position row the mapping entry gm_map_reads_cs_fastq makes of the
+ *             read's QVs (ref: gmapper.c:532-544) -- one row a read goes up once per call, not one a hit;
+ *   score > 0 and mapping qualities on (neither local_alignment nor no_mapping_qualities): post_sw under the SESSION's constants (pr_xover => alpha => pr_mismatch, the gap
+ *             probabilities from the scores) and, with quals, the session's table of per-colour error rates.  The calling thread's post_sw_setup is neither read nor
+ *             disturbed.  score_full, pct_score_full and the threshold compare by the functions gm_select_pass2 calls: they are gm_select_pass2's rules.
+ * The rounding guard is applied INSIDE.  An item the kernel flags (a letter call or a base quality the last bits of exp / log could decide) is redone by the library's host
+ * routine: by_host = 1.  A read that comes out of the selection with flag bit 0 set (see gm_select_pass2) has its device posteriors redone by the host routine and the
+ * selection is run once more; after it every hit of such a read is by_host, so NO mapping of the result has flag bit 0 set.  A by_host = 0 posterior is within 1e-9 relative
+ * of the single seam's (see gm_post_sw_batch); a by_host = 1 posterior carries the single seam's bits.  stats->post_sw_host_redo counts both kinds of re-do.  The guard's
+ * tolerance is 1e-7; builds with the tuning knobs read GM_POST_GUARD_TOL, as the mapping entries do.
+ * quals: NULL, or one QV string of n_colours characters a read, '\n' separated, as gm_map_reads_cs_fastq takes them; qual_delta re-bases a character to its QV.
+ * Result: ONE struct, released by ONE call, gm_read_mappings_cs_free.  Every field of gm_read_mappings_t, with
+ *   score_vector[n_hits]          pass 1's score of the hit (ZV): colour space has no second vector call;
+ *   cigar / edit                  of the hits that ARE mappings, clip character 'H'; every other hit has an empty slice;
+ *   ops, ops_len                  want_ops != 0 only; ops_len and recs[].ops_off are compacted in hit order whether or not ops comes down;
+ * and what colour space adds to gm_sam_input_t:
+ *   post[n_hits]                  gm_post_rec_t per hit (qual_off into post_quals); NULL when the session has no post_sw (local_alignment or no_mapping_qualities);
+ *   post_quals, post_quals_len    the base qualities post_sw leaves, hit after hit (NULL / 0 without post_sw);
+ *   qralign                       ops_len bytes, hit i's slice at [recs[i].ops_off, + n_ops): with post_sw its re-called qralign for every hit with an alignment; without,
+ *                                 the qralign of the strings built from the operations for the hits that are mappings, zero bytes elsewhere.
+ * Per sub-batch a fixed number of allocations, copies and launches (one more selection launch when the guard fires, one post_sw launch: the reads of a call have one
+ * length); for the host re-dos only the flagged items' operations, genome stretches and reads are fetched.  Device memory under one owner; the call takes its turn on the
+ * device like gm_read_hits.
+ * Refusals, on the host before anything is uploaded, the session usable afterwards: s or out NULL: GM_E_ARG; a letter-space session: GM_E_ARG (use gm_read_mappings); the
+ * read arguments as gm_read_hits checks them, initbp required (GM_E_ARG, GM_E_RANGE); quals with fewer lines than reads or a line whose length is not n_colours: GM_E_ARG;
+ * quals under a crossover score whose doubled value does not fit 8 bits: GM_E_RANGE, the message of gm_map_reads_cs_fastq; num_tmp_outputs > 64: GM_E_RANGE; a read length
+ * whose windows do not fit the full-alignment kernel's LDS (gm_sw_full_cs_batch's admission test), or whose survivor capacity is beyond the LDS of the front's prune
+ * kernel on this index (the front would fail there in mid-call; on a small index this binds first, near 900 colours under the default seeds): GM_E_RANGE.  The column
+ * scratch of one post_sw thread holds 59 918 colours; the LDS tests admit no read of more than a few thousand, so that bound is subsumed by them (the entry still checks it).
+ * n_reads <= 0: GM_OK, no hits.  After any failure *out holds nothing to free. */
+typedef struct gm_read_mappings_cs {
+  int32_t  n_reads, has_edit;                  /* reads of the call; 1: edit / edit_off are there (the session's extra_sam_fields) */
+  uint64_t n_hits, n_maps, cigar_len, edit_len, ops_len;      /* entries of hits / recs / post, of maps; bytes of cigar, of edit, of ops and of qralign */
+  gm_pass1_hit_t   *hits;  uint64_t *hit_off;  /* as gm_read_hits returns them; hit_off[n_reads + 1] */
+  int32_t          *score_vector;              /* [n_hits] pass 1's score (ZV) */
+  gm_sw_full_rec_t *recs;                      /* [n_hits] sw_full_cs's records (ZH = score) */
+  gm_mapping_t     *maps;  uint64_t *map_off;  /* as gm_select_pass2 returns them; map_off[n_reads + 1] */
+  char *cigar; uint64_t *cigar_off;            /* cigar_off[n_hits + 1] */
+  char *edit;  uint64_t *edit_off;             /* has_edit: edit_off[n_hits + 1] */
+  uint8_t *ops;                                /* want_ops: ops_len bytes */
+  uint64_t post_quals_len;                     /* bytes of post_quals */
+  gm_post_rec_t *post;                         /* [n_hits], or NULL without post_sw */
+  char *post_quals;                            /* post_quals_len bytes */
+  char *qralign;                               /* ops_len bytes */
+} gm_read_mappings_cs_t;
+int  gm_read_mappings_cs_size(void);     /* sizeof(gm_read_mappings_cs_t), for the Python mirror */
+int  gm_read_mappings_cs(gm_session_t *s, int n_reads, int n_colours, const uint32_t *colours_packed, const uint8_t *initbp,
+                         const char *quals, int qual_delta,       /* NULL, or '\n' separated QV strings as gm_map_reads_cs_fastq takes them */
+                         int want_ops, gm_read_mappings_cs_t *out, gm_map_stats_t *stats);
+void gm_read_mappings_cs_free(gm_read_mappings_cs_t *out);
+
 /* time of the dominant kernel (seed lookup) during the last gm_map_* call, from HIP events on the
  * session's own stream, and the algorithmic bytes it moved */
 int gm_last_lookup_timing(gm_session_t *s, double *ms, uint64_t *alg_bytes, int *launches);

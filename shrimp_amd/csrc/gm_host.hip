@@ -654,6 +654,19 @@ static void choose_caps(gm_session* s, DevSet& D, int read_len, int pair_mode = 
   (void)max_n_kmers;
 }
 
+// log(1 - e(q)), log(e(q) / 3) for q = 0..250 with the host's libm: the per-colour error rates post_sw derives from quality values (ref: sw-post.c:486-491, pr_err_from_qv
+// util.h:285-293), for every QV the formula distinguishes -- the device kernels read the very doubles the host routine computes.  sanger: PHRED, else Solexa-style odds.
+static std::vector<double> cs_qv_table(bool sanger) {
+  std::vector<double> qt(2 * 251);
+  for (int q = 0; q <= 250; q++) {
+    double e = q <= 0 ? .99999999 : (q >= 250 ? 1E-25 : pow(10.0, -(double)q / 10.0));
+    if (!sanger) e /= (1 + e);
+    if (e > .75) e = .75;
+    qt[2 * q] = log(1 - e); qt[2 * q + 1] = log(e / 3.0);
+  }
+  return qt;
+}
+
 extern "C" void gm_session_free(gm_session_t* s);
 extern "C" int gm_session_create(gm_session_t** out, const gm_index_t* ix, const gm_params_t* params, int max_batch_reads) {
   if (!out || !ix) return GM_E_ARG;
@@ -683,12 +696,7 @@ extern "C" int gm_session_create(gm_session_t** out, const gm_index_t* ix, const
   if (s->P.colour_space && !getenv("GM_POST_SW_HOST")) {
     // The per-colour error rates post_sw derives from quality values (ref: sw-post.c:486-491, pr_err_from_qv util.h:285-293; Sanger QVs, the binary's default),
     // tabulated here with the host's libm for every QV the formula distinguishes: the device kernel reads the very doubles the host routine computes.
-    std::vector<double> qt(2 * 251);
-    for (int q = 0; q <= 250; q++) {
-      double e = q <= 0 ? .99999999 : (q >= 250 ? 1E-25 : pow(10.0, -(double)q / 10.0));
-      if (e > .75) e = .75;
-      qt[2 * q] = log(1 - e); qt[2 * q + 1] = log(e / 3.0);
-    }
+    const std::vector<double> qt = cs_qv_table(true);
     GM_HIP_S(hipMalloc(&s->d_qtab, qt.size() * 8));
     GM_HIP_S(hipMemcpy(s->d_qtab, qt.data(), qt.size() * 8, hipMemcpyHostToDevice));
   }
@@ -2086,3 +2094,4 @@ extern "C" int gm_debug_tophits_cs(gm_session_t* s, int n_reads, int n_colours, 
 #include "gm_host_seams_ix.inc"
 #include "gm_host_text.inc"
 #include "gm_host_pass2.inc"
+#include "gm_host_pass2_cs.inc"

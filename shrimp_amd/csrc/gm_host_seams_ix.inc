@@ -283,13 +283,7 @@ static int post_sw_batch_impl(int n, const gm_sw_full_rec_t* recs, const uint8_t
     std::vector<double> qt;
     if (use_qvs) {
       // the per-colour error rates of every QV the formula distinguishes, from the host's libm: the very doubles cs_post_sw computes (ref: sw-post.c:486-491)
-      qt.resize(2 * 251);
-      for (int q = 0; q <= 250; q++) {
-        double e = q <= 0 ? .99999999 : (q >= 250 ? 1E-25 : pow(10.0, -(double)q / 10.0));
-        if (!c.sanger) e /= (1 + e);
-        if (e > .75) e = .75;
-        qt[2 * q] = log(1 - e); qt[2 * q + 1] = log(e / 3.0);
-      }
+      qt = cs_qv_table(c.sanger);
       GM_HIP(mem.up(&dqv, qv.data(), qv.size(), 0, 16)); GM_HIP(mem.up(&dqt, qt.data(), qt.size(), 0));
       K.qv = dqv; K.qtab = dqt;
     }

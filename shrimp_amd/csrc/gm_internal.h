@@ -308,9 +308,30 @@ int gm_launch_p2_compact(int n, const GmFullItem* d_items, const int* d_thresh, 
 int gm_launch_p2_records(int n, const gm_pass1_hit_t* d_hits, const int* d_pos_of, const GmFullOut* d_out, int ops_cap, gm_sw_full_rec_t* d_recs, GmP2In* d_p2in,
                          hipStream_t stream);
 int gm_launch_p2_sel_items(int n, const gm_pass1_hit_t* d_hits, const gm_sw_full_rec_t* d_recs, const GmP2Host* d_ans, GmSel2Item* d_items, hipStream_t stream);
+// Colour-space pass 2 as a seam (gm_read_mappings_cs, gm_host_pass2_cs.inc): every hit goes through sw_full_cs, then post_sw, on arrays that stay on the device.
+// Colour-space by-row form of GmFullItem (k_sw_full_cs_batch<.., true, true>): initbp carries the primer letter | GM_SEAM_RNA, so the ROW of the sub-batch's reads -- and
+// of the crossover rows -- rides in maxscore, a field sw_full_cs never reads; idx is the slot of out[] alone.
+//   gm_launch_p2_items_cs: d_items[i] = that item of d_hits[i]: window, box, revcmpl and thresh as gm_launch_p2_items makes them, the primer letter of the read's row of
+//                        d_initbp_rows, ops_off = i * ops_cap (no compaction: every hit is aligned).
+//   gm_launch_p2_records_cs: d_recs[i] / d_p2in[i] from d_out[i]: the record gm_sw_full_cs_batch_ix leaves (all zero where there is no alignment); d_len[i] = the read
+//                        positions post_sw will take of it (rmapped where score > 0, else 0).
+//   gm_launch_p2_post_items: d_items[i] = k_post_sw_batch's item of hit i from its device record: operations, genome_start, read_start, len = rmapped, gbase / flags as
+//                        gm_post_sw_batch_ix sets them, idx = the ROW of the read (k_post_sw_batch reads idx for the read and its QV row only: its answer goes to the item's
+//                        own slot, so the existing <true> instantiation is the by-row form), qual_off = d_qoff[i], the exclusive scan of d_len (gm_launch_win_scan).  A hit
+//                        without alignment gets an empty item (n_ops = len = 0), which the kernel leaves after two loads.
+//   gm_launch_p2_move:   segment k: n bytes from d_src + seg.src to d_dst + seg.dst, a wave a segment.  The few items the host routine redoes: their operations come
+//                        down packed (bytes bounded by those items), their re-called qralign and base qualities go back to their places.
+struct GmP2Seg { unsigned long long src, dst; uint32_t len, pad; };
+int gm_launch_p2_items_cs(int n, const gm_pass1_hit_t* d_hits, int read_base, int read_len, const uint32_t* d_contig_off, const uint8_t* d_contig_rna, const int* d_thresh_tab,
+                          int tiebreak_rev, int ops_cap, const uint8_t* d_initbp_rows, int is_rna, GmFullItem* d_items, hipStream_t stream);
+int gm_launch_p2_records_cs(int n, const gm_pass1_hit_t* d_hits, const GmFullOut* d_out, int ops_cap, gm_sw_full_rec_t* d_recs, GmP2In* d_p2in, uint32_t* d_len, hipStream_t stream);
+int gm_launch_p2_post_items(int n, const gm_pass1_hit_t* d_hits, const gm_sw_full_rec_t* d_recs, const unsigned long long* d_qoff, int read_base, int read_len,
+                            const uint32_t* d_contig_off, const uint8_t* d_contig_rna, const uint8_t* d_initbp_rows, GmPostItem* d_items, hipStream_t stream);
+int gm_launch_p2_move(int n_segs, const GmP2Seg* d_segs, const uint8_t* d_src, uint8_t* d_dst, hipStream_t stream);
 int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
                                int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
-                               uint8_t* d_ops, int local, hipStream_t stream, int ix = 0);      // ix: the items carry strand / RNA bits (gm_sw_full_cs_batch_ix)
+                               uint8_t* d_ops, int local, hipStream_t stream, int ix = 0,      // ix: the items carry strand / RNA bits (gm_sw_full_cs_batch_ix)
+                               int by_row = 0);      // by_row (with ix): the colour-space by-row form of GmFullItem
 
 // Text of the alignments of an S2 batch call (gm_sw_full_batch_text[_ix], k_sw_text in gm_text.hip): one accepted record.  The host has checked it (swf_rec_check):
 // ops[ops_off .. + n_ops), the genome positions from genome_start and the read positions read_start .. of read `idx` lie inside what was uploaded; tail = the read

@@ -13,6 +13,12 @@
 //   k_p2_records   a lane a hit: the record of the hit as the batch entries leave it (genome_start counted on the strand's contig), the zero record for a hit under
 //                  the threshold (calloc + score = 0, ref: mapping.c:365,396-398), and the three integers the host's double functions read of it.
 //   k_p2_sel_items a lane a hit: k_sel_pass2's item from the record, the hit and the host's answer (score_full, key, the threshold compare).
+// Colour space (gm_read_mappings_cs, gm_host_pass2_cs.inc; ref: mapping.c:375-379, 1609-1625) has no second score and no work list -- every hit is aligned -- and post_sw
+// behind the alignment:
+//   k_p2_items_cs   a lane a hit: the item in its colour-space by-row form (the primer letter stays in initbp, the row rides in maxscore), hit i's operations at i * ops_cap.
+//   k_p2_records_cs a lane a hit: the record as gm_sw_full_cs_batch_ix leaves it, the host's three integers, the read positions post_sw takes (scanned by k_win_scan).
+//   k_p2_post_items a lane a hit: k_post_sw_batch's item from the device record, the read named by its row, qual_off from the scan.
+//   k_p2_move       a wave a segment: bytes between two device buffers by a list -- the flagged items' operations packed for the host, its re-called letters back.
 #include "gm_common.h"
 #include <algorithm>
 #include "gm_internal.h"
@@ -119,6 +125,112 @@ __global__ __launch_bounds__(256) void k_p2_sel_items(int n, const gm_pass1_hit_
   it.endkey = (int32_t)(-R->genome_start - R->rmapped + R->deletions - R->insertions);
   it.score_full = a.score_full; it.key = a.key; it.keep = a.keep;
   items[i] = it;
+}
+
+// ---- colour space (gm_read_mappings_cs): every hit is aligned, so there is no second score and no work list; post_sw follows on the device -----------------------
+// k_p2_items_cs: k_p2_items with the colour-space by-row form of the item -- the primer letter (| GM_SEAM_RNA) in initbp, the read's row in maxscore, hit i's operations
+// at i * ops_cap.
+__global__ __launch_bounds__(256) void k_p2_items_cs(int n, const gm_pass1_hit_t* __restrict__ hits, int read_base, int read_len, const uint32_t* __restrict__ contig_off,
+                                                     const uint8_t* __restrict__ contig_rna, const int* __restrict__ thresh_tab, int tiebreak_rev, int ops_cap,
+                                                     const uint8_t* __restrict__ initbp_rows, int is_rna, GmFullItem* __restrict__ items) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint4* h = (const uint4*)(hits + i);
+  const uint4 a = h[0], b = h[1], d = h[3];                                // read st win cn | gen_st g_off w_len score_vector | ... | ax ay alen awidth
+  const int cn = (int)a.w, gen_st = (int)b.x, w_len = (int)b.z, row = (int)a.x - read_base;
+  const uint32_t c0 = contig_off[cn], clen = contig_off[cn + 1] - c0;
+  const uint32_t foff = gen_st ? clen - b.y - (uint32_t)w_len : b.y;
+  GmFullItem it;
+  it.goff = (long long)c0 + (long long)foff; it.glen = w_len; it.rlen = read_len;
+  const bool has_anchor = (int)d.z > 0;
+  it.ax = has_anchor ? (long long)(int)d.x : 0; it.ay = has_anchor ? (long long)(int)d.y : 0;
+  it.alen = has_anchor ? (int)d.z : 1; it.awidth = has_anchor ? (int)d.w : 1;
+  it.thresh = thresh_tab[min(read_len, w_len)]; it.maxscore = row;
+  it.flags = (has_anchor ? 1 : 0) | ((gen_st && tiebreak_rev) ? 2 : 0) | (gen_st ? 4 : 0) | ((contig_rna && contig_rna[cn]) ? 8 : 0);
+  it.initbp = (int)initbp_rows[row] | (is_rna ? GM_SEAM_RNA : 0);
+  it.ops_cap = ops_cap; it.ops_off = (unsigned long long)i * (unsigned long long)ops_cap; it.idx = i;
+  items[i] = it;
+}
+
+// k_p2_records_cs: the record of a hit as gm_sw_full_cs_batch_ix leaves it -- all zero where sw_full_cs found no alignment at or above thresh -- the three integers of
+// the host's double functions, and the read positions post_sw takes of it
+__global__ __launch_bounds__(256) void k_p2_records_cs(int n, const gm_pass1_hit_t* __restrict__ hits, const GmFullOut* __restrict__ out, int ops_cap,
+                                                       gm_sw_full_rec_t* __restrict__ recs, GmP2In* __restrict__ p2in, uint32_t* __restrict__ len) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const gm_pass1_hit_t* h = hits + i;
+  gm_sw_full_rec_t R;
+  R.score = 0; R.read_start = 0; R.rmapped = 0; R.gmapped = 0; R.matches = 0; R.mismatches = 0; R.insertions = 0; R.deletions = 0; R.crossovers = 0; R.status = 0;
+  R.genome_start = 0; R.ops_off = 0; R.n_ops = 0;
+  const GmFullOut o = out[i];
+  if (o.v[0] > 0) {
+    R.score = o.v[0]; R.read_start = o.v[1]; R.rmapped = o.v[2]; R.genome_start = (int64_t)h->g_off + o.v[3]; R.gmapped = o.v[4];
+    R.matches = o.v[5]; R.mismatches = o.v[6]; R.insertions = o.v[7]; R.deletions = o.v[8]; R.crossovers = o.v[9];
+    R.n_ops = (uint32_t)min(o.v[10], ops_cap); R.ops_off = (unsigned long long)i * (unsigned long long)ops_cap;
+  }
+  ((uint32_t*)&R)[15] = 0;                                                 // (the padding behind n_ops)
+  uint4* dst = (uint4*)(recs + i); const uint4* src = (const uint4*)&R;
+  dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
+  GmP2In q; q.score = R.score; q.rmapped = R.rmapped; q.score_max = h->score_max;
+  p2in[i] = q;
+  len[i] = R.score > 0 ? (uint32_t)max(R.rmapped, 0) : 0u;
+}
+
+// k_p2_post_items: post_sw's item of a hit from its device record (the host has checked the records against their windows before this is launched)
+__global__ __launch_bounds__(256) void k_p2_post_items(int n, const gm_pass1_hit_t* __restrict__ hits, const gm_sw_full_rec_t* __restrict__ recs,
+                                                       const unsigned long long* __restrict__ qoff, int read_base, int read_len, const uint32_t* __restrict__ contig_off,
+                                                       const uint8_t* __restrict__ contig_rna, const uint8_t* __restrict__ initbp_rows, GmPostItem* __restrict__ items) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const gm_pass1_hit_t* h = hits + i; const gm_sw_full_rec_t* R = recs + i;
+  const int row = h->read - read_base, cn = h->cn, gen_st = h->gen_st;
+  const uint32_t c0 = contig_off[cn], clen = contig_off[cn + 1] - c0;
+  GmPostItem it;
+  it.ops_off = 0; it.qual_off = qoff[i]; it.genome_start = 0; it.n_ops = 0; it.read_start = 0; it.len = 0;
+  it.gbase = (long long)c0 + (gen_st ? (long long)clen - 1 : 0);
+  it.rlen = read_len; it.initbp = (int)initbp_rows[row]; it.idx = row;
+  it.flags = (gen_st ? 1 : 0) | ((contig_rna && contig_rna[cn]) ? 2 : 0);
+  if (R->score > 0) { it.ops_off = R->ops_off; it.n_ops = R->n_ops; it.genome_start = R->genome_start; it.read_start = R->read_start; it.len = R->rmapped; }
+  items[i] = it;
+}
+
+// k_p2_move: a wave a segment, a byte a lane and step
+__global__ __launch_bounds__(GM_WAVE) void k_p2_move(int n_segs, const GmP2Seg* __restrict__ segs, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
+  for (int k = blockIdx.x; k < n_segs; k += gridDim.x) {
+    const GmP2Seg s = segs[k];
+    for (uint32_t j = threadIdx.x; j < s.len; j += GM_WAVE) dst[s.dst + j] = src[s.src + j];
+  }
+}
+
+int gm_launch_p2_items_cs(int n, const gm_pass1_hit_t* d_hits, int read_base, int read_len, const uint32_t* d_contig_off, const uint8_t* d_contig_rna, const int* d_thresh_tab,
+                          int tiebreak_rev, int ops_cap, const uint8_t* d_initbp_rows, int is_rna, GmFullItem* d_items, hipStream_t stream) {
+  if (n <= 0) return GM_OK;
+  hipLaunchKernelGGL(k_p2_items_cs, dim3((n + 255) / 256), dim3(256), 0, stream, n, d_hits, read_base, read_len, d_contig_off, d_contig_rna, d_thresh_tab, tiebreak_rev, ops_cap,
+                     d_initbp_rows, is_rna, d_items);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_launch_p2_records_cs(int n, const gm_pass1_hit_t* d_hits, const GmFullOut* d_out, int ops_cap, gm_sw_full_rec_t* d_recs, GmP2In* d_p2in, uint32_t* d_len, hipStream_t stream) {
+  if (n <= 0) return GM_OK;
+  hipLaunchKernelGGL(k_p2_records_cs, dim3((n + 255) / 256), dim3(256), 0, stream, n, d_hits, d_out, ops_cap, d_recs, d_p2in, d_len);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_launch_p2_post_items(int n, const gm_pass1_hit_t* d_hits, const gm_sw_full_rec_t* d_recs, const unsigned long long* d_qoff, int read_base, int read_len,
+                            const uint32_t* d_contig_off, const uint8_t* d_contig_rna, const uint8_t* d_initbp_rows, GmPostItem* d_items, hipStream_t stream) {
+  if (n <= 0) return GM_OK;
+  hipLaunchKernelGGL(k_p2_post_items, dim3((n + 255) / 256), dim3(256), 0, stream, n, d_hits, d_recs, d_qoff, read_base, read_len, d_contig_off, d_contig_rna, d_initbp_rows, d_items);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+int gm_launch_p2_move(int n_segs, const GmP2Seg* d_segs, const uint8_t* d_src, uint8_t* d_dst, hipStream_t stream) {
+  if (n_segs <= 0) return GM_OK;
+  hipLaunchKernelGGL(k_p2_move, dim3(std::min(n_segs, 4096)), dim3(GM_WAVE), 0, stream, n_segs, d_segs, d_src, d_dst);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
 }
 
 int gm_launch_p2_items(int n, const gm_pass1_hit_t* d_hits, int read_base, int read_len, const uint32_t* d_contig_off, const uint8_t* d_contig_rna, const int* d_thresh_tab,

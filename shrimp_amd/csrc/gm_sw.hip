@@ -2168,8 +2168,9 @@ int gm_launch_sw_vector_batch_cs(const GmScoreDev& sc, int n, const uint32_t* d_
 // reference takes a cell outside the band for "back == 0", the walk asks the band box (cs_walk's code_at returns 0 outside it, in k_pass2_cs / k_pass2_cs_g4
 // on their reused scratch too): every cell inside the band is written by the current item before the walk, and no word outside it is ever read.
 // ---------------------------------------------------------------------------------------------
-template <bool LOCAL, bool IX = false>                // IX: gm_sw_full_cs_batch_ix -- the strand / RNA bits of GmFullItem.flags are read (an instantiation of its own: the host-bitfield
+template <bool LOCAL, bool IX = false, bool BYROW = false>      // IX: gm_sw_full_cs_batch_ix -- the strand / RNA bits of GmFullItem.flags are read (an instantiation of its own: the host-bitfield
 __global__ void __launch_bounds__(GM_WAVE)          // entry's code stays what it was).  (one wave per SIMD: with a second one the four local-mode variants spill 100+ bytes a lane)
+                                                    // BYROW (gm_read_mappings_cs): the read and its crossover row are row `maxscore` of reads[] / xrows[], idx is the slot of out[] alone
 k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ items, const uint32_t* __restrict__ genome_ls, const uint32_t* __restrict__ reads,
                    int read_words, int max_g, int max_r, const int8_t* __restrict__ xrows, int xstride, uint32_t* __restrict__ back_pool, size_t back_words,
                    GmFullOut* __restrict__ out, uint8_t* __restrict__ ops_all) {
@@ -2187,9 +2188,10 @@ k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ i
     const int ib = __builtin_amdgcn_readfirstlane(it.initbp);
     const bool is_rna = (ib & GM_SEAM_RNA) != 0, revcmpl = (flags & 2) != 0;
     const int initbp = ib & 0xff;
-    const int8_t* xrow = xrows ? xrows + (size_t)it.idx * xstride : nullptr;
+    const int row = BYROW ? __builtin_amdgcn_readfirstlane(it.maxscore) : it.idx;
+    const int8_t* xrow = xrows ? xrows + (size_t)row * xstride : nullptr;
     __syncthreads();                                  // lane 0 may still read the previous item's db / qr4
-    load_read(reads + (size_t)it.idx * read_words, rlen, false, rc, lane);
+    load_read(reads + (size_t)row * read_words, rlen, false, rc, lane);
     load_window(genome_ls, (uint64_t)it.goff, glen, IX && (flags & 4) != 0, db, lane, IX && (flags & 8) != 0);
     __syncthreads();
     if (lane < 4) cs_translate4(rc, rlen, initbp, is_rna, qr4, qstride, lane);
@@ -2222,18 +2224,20 @@ k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ i
 size_t gm_sw_full_cs_batch_lds(int max_g, int max_r) { return 5 * (size_t)((max_r + 15) & ~15) + ((max_g + 15) & ~15) + (size_t)max_g * 48 + 64; }
 int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
                                int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
-                               uint8_t* d_ops, int local, hipStream_t stream, int ix) {
+                               uint8_t* d_ops, int local, hipStream_t stream, int ix, int by_row) {
   if (n == 0) return GM_OK;
+  if (by_row && !ix) { gm_set_error("sw_full_cs batch: the by-row form is an index form"); return GM_E_ARG; }
   GmCsDev P; P.match = cs_params9[0]; P.mismatch = cs_params9[1]; P.xover = cs_params9[2]; P.a_go = cs_params9[3]; P.a_ge = cs_params9[4];
   P.b_go = cs_params9[5]; P.b_ge = cs_params9[6]; P.anchor_width = cs_params9[7]; P.taboo = cs_params9[8];
   const size_t lds = gm_sw_full_cs_batch_lds(max_g, max_r);
   if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("sw_full_cs batch: window of %d does not fit LDS", max_g); return GM_E_ARG; }      // (the host entry refuses such items one by one before it gets here)
-#define GM_SWF_CS_LAUNCH(LOC, IX) do { \
-    GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_batch<LOC, IX>, lds)); \
-    hipLaunchKernelGGL((k_sw_full_cs_batch<LOC, IX>), dim3(grid), dim3(GM_WAVE), lds, stream, P, first, n, d_items, d_genome_ls, d_reads, read_words, max_g, max_r, d_xrows, xstride, \
+#define GM_SWF_CS_LAUNCH(LOC, IX, ROW) do { \
+    GM_HIP(gm_lds_at_least((const void*)k_sw_full_cs_batch<LOC, IX, ROW>, lds)); \
+    hipLaunchKernelGGL((k_sw_full_cs_batch<LOC, IX, ROW>), dim3(grid), dim3(GM_WAVE), lds, stream, P, first, n, d_items, d_genome_ls, d_reads, read_words, max_g, max_r, d_xrows, xstride, \
                        d_back, back_words, d_out, d_ops); } while (0)
-  if (local) { if (ix) GM_SWF_CS_LAUNCH(true, true); else GM_SWF_CS_LAUNCH(true, false); }
-  else { if (ix) GM_SWF_CS_LAUNCH(false, true); else GM_SWF_CS_LAUNCH(false, false); }
+  if (by_row) { if (local) GM_SWF_CS_LAUNCH(true, true, true); else GM_SWF_CS_LAUNCH(false, true, true); }
+  else if (local) { if (ix) GM_SWF_CS_LAUNCH(true, true, false); else GM_SWF_CS_LAUNCH(true, false, false); }
+  else { if (ix) GM_SWF_CS_LAUNCH(false, true, false); else GM_SWF_CS_LAUNCH(false, false, false); }
 #undef GM_SWF_CS_LAUNCH
   GM_HIP(hipGetLastError());
   return GM_OK;

@@ -147,6 +147,10 @@ class ReadMappingsResult(C.Structure):   # gm_read_mappings_t: what gm_read_mapp
                 ("map_off", C.c_void_p), ("cigar", C.c_void_p), ("cigar_off", C.c_void_p), ("edit", C.c_void_p), ("edit_off", C.c_void_p), ("ops", C.c_void_p)]
 
 
+class ReadMappingsCsResult(C.Structure):   # gm_read_mappings_cs_t: ReadMappingsResult's fields, then what colour space adds (checked against gm_read_mappings_cs_size())
+    _fields_ = ReadMappingsResult._fields_ + [("post_quals_len", C.c_uint64), ("post", C.c_void_p), ("post_quals", C.c_void_p), ("qralign", C.c_void_p)]
+
+
 SW_FULL_REC_DTYPE = np.dtype(SwFullRec)      # the structured numpy view of an array of them
 POST_REC_DTYPE = np.dtype(PostRec)
 ANCHOR_DTYPE = np.dtype(Anchor)
@@ -156,6 +160,11 @@ MAPPING_DTYPE = np.dtype(Mapping)
 # one row of ReadMappings.table(): a mapping as a SAM record states it
 MAPPING_TABLE_DTYPE = np.dtype([("read", np.int32), ("contig", np.int32), ("strand", np.int32), ("pos", np.uint32), ("mapq", np.int32), ("as", np.int32), ("nm", np.int32),
                                 ("hit", np.int32)])
+
+
+def gm_mqv_on(p):
+    """a session under these parameters runs post_sw / prints mapping qualities (neither local_alignment nor no_mapping_qualities)"""
+    return not p.local_alignment and not p.no_mapping_qualities
 
 
 def mapping_positions(hits, recs, contig_len, hit_index):
@@ -197,6 +206,22 @@ class ReadMappings:
         return t
 
 
+class ReadMappingsCs(ReadMappings):
+    """What Session.read_mappings_cs returns: ReadMappings (score_vector: pass 1's score; clip "H") and what colour space adds -- post (POST_REC_DTYPE per hit, None
+    where the session has no post_sw), post_quals (bytes; post[i]'s slice at qual_off, qual_len) and qralign (bytes, hit i's slice at recs[i].ops_off, n_ops).
+    Session.sam_records picks the three from it."""
+    def __init__(self, *base, post, post_quals, qralign):
+        ReadMappings.__init__(self, *base)
+        self.post, self.post_quals, self.qralign = post, post_quals, qralign
+
+    def qralign_of(self, i):
+        a = int(self.recs["ops_off"][i]); return self.qralign[a:a + int(self.recs["n_ops"][i])]
+
+    def quals_of(self, i):
+        if self.post is None: return b""
+        a = int(self.post["qual_off"][i]); return self.post_quals[a:a + int(self.post["qual_len"][i])]
+
+
 # every entry point include/gmapper_hip.h declares
 EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", "gm_preprocess_read_text", "gm_map_pairs_cs_fastq", "gm_map_reads_file", "gm_merge_options_default", "gm_merge_sam", "gm_release_cache", "gm_map_pairs_cs", "gm_last_error", "gm_device_count", "gm_params_default", "gm_params_default_cs", "gm_index_build", "gm_index_build_fasta", "gm_index_n_contigs", "gm_index_contig", "gm_sam_header", "gm_index_build_timing", "gm_index_free", "gm_index_list_cutoff",
            "gm_index_save", "gm_index_load", "gm_index_bytes", "gm_index_n_slabs", "gm_index_has_buckets", "gm_index_get_list", "gm_index_device_array", "gm_index_meta", "gm_index_alloc_like",
@@ -210,6 +235,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_post_sw_batch_ix", "gm_sw_full_batch_text", "gm_sw_full_batch_text_ix",
            "gm_session_create", "gm_session_free", "gm_sequence_to_bitfield", "gm_map_reads_text", "gm_map_reads", "gm_map_reads_fastq", "gm_map_reads_cs", "gm_map_reads_cs_fastq", "gm_map_reads_device", "gm_free", "gm_debug_tophits", "gm_debug_tophits_cs",
            "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size", "gm_score_windows", "gm_select_pass1_f1", "gm_read_hits", "gm_sam_records", "gm_sam_input_size", "gm_read_mappings", "gm_read_mappings_free", "gm_read_mappings_size",
+           "gm_read_mappings_cs", "gm_read_mappings_cs_free", "gm_read_mappings_cs_size",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
 
@@ -336,6 +362,11 @@ def lib():
     L.gm_read_mappings_free.argtypes = [C.POINTER(ReadMappingsResult)]; L.gm_read_mappings_free.restype = None
     if L.gm_read_mappings_size() != C.sizeof(ReadMappingsResult):
         raise GmError("gm_read_mappings_t is %d bytes in the library, %d in ReadMappingsResult" % (L.gm_read_mappings_size(), C.sizeof(ReadMappingsResult)))
+    L.gm_read_mappings_cs_size.argtypes = []; L.gm_read_mappings_cs_size.restype = C.c_int
+    L.gm_read_mappings_cs.argtypes = [vp, C.c_int, C.c_int, u32p, u8p, C.c_char_p, C.c_int, C.c_int, C.POINTER(ReadMappingsCsResult), C.POINTER(MapStats)]
+    L.gm_read_mappings_cs_free.argtypes = [C.POINTER(ReadMappingsCsResult)]; L.gm_read_mappings_cs_free.restype = None
+    if L.gm_read_mappings_cs_size() != C.sizeof(ReadMappingsCsResult):
+        raise GmError("gm_read_mappings_cs_t is %d bytes in the library, %d in ReadMappingsCsResult" % (L.gm_read_mappings_cs_size(), C.sizeof(ReadMappingsCsResult)))
     _lib = L
     return L
 
@@ -1024,6 +1055,42 @@ class Session:
         self.stats = st.as_dict(); self._windows_read_len = Lr
         return res
 
+    def read_mappings_cs(self, reads_codes, initbp=None, quals=None, qual_delta=33, want_ops=False):
+        """Colour reads to mappings in one call (gm_read_mappings_cs: read_hits, then per hit sw_full_cs, post_sw under the session's constants with the host re-dos and
+        the rounding guard inside, select_pass2 and the text of the mappings with clip "H", on arrays that stay on the device): -> ReadMappingsCs.
+        reads_codes: [n, colours] with initbp, or (initbp None) [n, 1 + colours] with the primer letter code in column 0 as map_reads_cs takes them; quals: None or one
+        QV string (bytes, a character a colour) per read, as map_reads_cs_fastq takes them.  The stage counters of the call are left in self.stats."""
+        reads_codes = np.ascontiguousarray(reads_codes, dtype=np.uint8)
+        if initbp is None and reads_codes.ndim == 2 and reads_codes.shape[1] >= 1:
+            initbp = np.ascontiguousarray(reads_codes[:, 0]); reads_codes = np.ascontiguousarray(reads_codes[:, 1:])
+        n, Lr, packed, ib = self._reads_args("read_mappings_cs", reads_codes, initbp)
+        q = None
+        if quals is not None:
+            quals = [x if isinstance(x, bytes) else x.encode() for x in quals]
+            if len(quals) != n: raise GmError("read_mappings_cs: one QV string per read")
+            q = b"\n".join(quals)
+        L = lib(); R = ReadMappingsCsResult(); st = MapStats()
+        _check(L.gm_read_mappings_cs(self.h, n, Lr, packed.ctypes.data_as(C.POINTER(C.c_uint32)), None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_uint8)), q, int(qual_delta),
+                                     1 if want_ops else 0, C.byref(R), C.byref(st)), "gm_read_mappings_cs")
+        try:
+            def take(p, count, dtype):
+                a = np.zeros(count, dtype=dtype)
+                if count and p: C.memmove(a.ctypes.data, p, count * a.dtype.itemsize)
+                return a
+            nh, nm = int(R.n_hits), int(R.n_maps)
+            res = ReadMappingsCs(take(R.hits, nh, PASS1_HIT_DTYPE), take(R.hit_off, n + 1, np.uint64), take(R.score_vector, nh, np.int32), take(R.recs, nh, SW_FULL_REC_DTYPE),
+                                 take(R.maps, nm, MAPPING_DTYPE), take(R.map_off, n + 1, np.uint64),
+                                 C.string_at(R.cigar, int(R.cigar_len)) if R.cigar else b"", take(R.cigar_off, nh + 1, np.uint64),
+                                 (C.string_at(R.edit, int(R.edit_len)) if R.edit else b"") if R.has_edit else None, take(R.edit_off, nh + 1, np.uint64) if R.has_edit else None,
+                                 take(R.ops, int(R.ops_len), np.uint8) if want_ops else None, self.index.contig_lengths(),
+                                 post=take(R.post, nh, POST_REC_DTYPE) if gm_mqv_on(self.params) else None,
+                                 post_quals=C.string_at(R.post_quals, int(R.post_quals_len)) if R.post_quals else b"",
+                                 qralign=C.string_at(R.qralign, int(R.ops_len)) if R.qralign else b"")
+        finally:
+            L.gm_read_mappings_cs_free(C.byref(R))
+        self.stats = st.as_dict(); self._windows_read_len = Lr
+        return res
+
     def select_pass2(self, hits, hit_off, recs, post=None):
         """Pass 2's selection and the mapping qualities (gm_select_pass2) over the records of ONE full batch call on the hits of select_pass1: -> (maps, map_off).
         maps: structured array of MAPPING_DTYPE in the reference's output order, read r's at maps[map_off[r]:map_off[r + 1]]; post: the POST_REC_DTYPE answers of
@@ -1060,6 +1127,10 @@ class Session:
             hits, recs, maps, map_off, cigar = rm.hits, rm.recs, rm.maps, rm.map_off, (rm.cigar_buf, rm.cigar_off)
             if score_vector is None: score_vector = rm.score_vector
             if edit is None and rm.edit_off is not None: edit = (rm.edit_buf, rm.edit_off)
+            if isinstance(rm, ReadMappingsCs):                               # colour space: post_sw's answers and the read letters
+                if post is None: post = rm.post
+                if post_quals is None and rm.post is not None: post_quals = rm.post_quals
+                if qralign is None: qralign = rm.qralign
         if recs is None or maps is None or map_off is None or cigar is None: raise GmError("sam_records: recs, maps, map_off and cigar are required beside plain hits")
         reads_codes = np.ascontiguousarray(reads_codes, dtype=np.uint8)
         if reads_codes.ndim != 2: raise GmError("sam_records: reads_codes is (n, read_len)")
