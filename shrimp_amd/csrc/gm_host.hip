@@ -750,642 +750,8 @@ extern "C" void gm_session_free(gm_session_t* s) {
   delete s;
 }
 
-// ---- host finalisation --------------------------------------------------------------------------
-struct FHit {            // one pass-2 candidate on the host (read_hit + sw_full_results subset)
-  const GmFullRes* r; const uint8_t* ops;
-  int score_full, pass2_key; double pct_score_full; double posterior; int mqv; double z0, z1;
-  bool dev_post = false;          // colour space: posterior and re-called letters came from k_post_sw_cs (the host routine can still redo them)
-  double z2, z3, pr_top_random, insert_size_denom, pr_missed_mp;   // paired mode (ref: sw-full-common.h:30-44)
-  std::string db, qr, qual; int cs_match = 0, cs_mismatch = 0, cs_xover = 0;   // colour space: dbalign / qralign and the counts post_sw leaves (ref: sw-post.c:531-565)
-};
-
-static inline char* put_uint(char* p, unsigned long long v) {      // two digits per division (a 64-bit division is ~25 cycles; a record prints half a dozen numbers)
-  static const char D2[201] = "00010203040506070809101112131415161718192021222324252627282930313233343536373839404142434445464748495051525354555657585960616263646566676869707172737475767778798081828384858687888990919293949596979899";
-  if (v < 10) { *p++ = (char)('0' + v); return p; }
-  char tmp[24]; int n = 0;
-  if (v <= 0xFFFFFFFFull) { uint32_t w = (uint32_t)v; while (w >= 100) { const uint32_t r = w % 100; w /= 100; tmp[n++] = D2[2 * r + 1]; tmp[n++] = D2[2 * r]; } if (w >= 10) { tmp[n++] = D2[2 * w + 1]; tmp[n++] = D2[2 * w]; } else tmp[n++] = (char)('0' + w); }
-  else { while (v >= 100) { const unsigned r = (unsigned)(v % 100); v /= 100; tmp[n++] = D2[2 * r + 1]; tmp[n++] = D2[2 * r]; } if (v >= 10) { tmp[n++] = D2[2 * v + 1]; tmp[n++] = D2[2 * v]; } else tmp[n++] = (char)('0' + v); }
-  while (n) *p++ = tmp[--n];
-  return p;
-}
-static inline char* put_int(char* p, long long v) { if (v < 0) { *p++ = '-'; return put_uint(p, (unsigned long long)(-v)); } return put_uint(p, (unsigned long long)v); }
-static inline char* put_str(char* p, const char* s, size_t n) { memcpy(p, s, n); return p + n; }
-
-static int qv_from_pr_corr(double pr_corr) {   // ref: common/util.h:267-283
-  double pr_err = 1 - pr_corr;
-  if (pr_err > .99999999) return 0; else if (pr_err < 1E-25) return 250;
-  return (int)(-10.0 * log(pr_err) / log(10.0));
-}
-static int double_to_neglog(double x) { return (int)((double)1000 * -log(x)); }   // ref: common/util.h:297-301
-
-// The double expressions of hit_run_post_sw and compute_unpaired_mqv (ref: mapping.c:1609-1625, output.c:777-793), shared by the finalisation of the mapping entries
-// and by gm_select_pass2: one text, so both round through the host's libm alike.
-static inline double gm_ls_posterior(double a, double b, int score, int rmapped) { return pow(2.0, ((double)score - (double)rmapped * (2.0 * a + b)) / a); }
-static inline double gm_post_score_x(double a, double b, double posterior, int rmapped) { return a * log(posterior) / log(2.0) + (double)rmapped * (2.0 * a + b); }   // what rint() turns into AS
-static inline int gm_post_score(double a, double b, double posterior, int rmapped) { return (int)rint(gm_post_score_x(a, b, posterior, rmapped)); }
-static inline double gm_full_threshold(const gm_params_t& P, int score_max) { return P.sw_full_threshold < 0 ? -P.sw_full_threshold : score_max * (P.sw_full_threshold / 100.0); }   // ref: mapping.c:1661
-static inline int gm_unpaired_mqv(double posterior, double z1) { const int q = qv_from_pr_corr(posterior / z1); return q < 4 ? 0 : q; }
-// the rounding guard's distance tests (see Finalizer::guard_tol)
-static inline bool gm_near_rint(double x, double tol) { const double f = x - floor(x); return fabs(f - 0.5) < tol; }              // rint(): boundary at the half integers
-static inline bool gm_near_trunc(double x, double tol) { return fabs(x - rint(x)) < tol; }                                          // (int): boundary at the integers
-static inline bool gm_near_qv(double pr_corr, double tol) {                                                                         // qv_from_pr_corr, ref: common/util.h:267-283
-  const double pr_err = 1 - pr_corr;
-  if (fabs(pr_err - .99999999) < tol * 1e-2 || (pr_err > 0 && fabs(pr_err / 1E-25 - 1.0) < tol)) return true;
-  if (pr_err > .99999999 || pr_err < 1E-25) return false;
-  return gm_near_trunc(-10.0 * log(pr_err) / log(10.0), tol);
-}
-
-static int cmp_gen_start(const FHit* a, const FHit* b) {   // ref: mapping.c:1485-1494
-  if (a->r->cn != b->r->cn) return (int)a->r->cn - (int)b->r->cn;
-  if (a->r->gen_st != b->r->gen_st) return a->r->gen_st - b->r->gen_st;
-  return a->r->genome_start - b->r->genome_start;
-}
-static int cmp_gen_end(const FHit* a, const FHit* b) {     // ref: mapping.c:1496-1506
-  if (a->r->cn != b->r->cn) return (int)a->r->cn - (int)b->r->cn;
-  if (a->r->gen_st != b->r->gen_st) return a->r->gen_st - b->r->gen_st;
-  return (-a->r->genome_start - a->r->rmapped + a->r->n_del - a->r->n_ins) - (-b->r->genome_start - b->r->rmapped + b->r->n_del - b->r->n_ins);
-}
-// A stable sort of the handful of mappings a read has: insertion sort below 24 elements (the same order as any stable sort; std::stable_sort asks the allocator for a merge
-// buffer at every call -- three calls a read were a third of the finalisation's cycles), the library's merge sort above.
-template <class It, class Less> static inline void gm_small_stable_sort(It b, It e, Less less) {
-  const auto n = e - b;
-  if (n < 2) return;
-  if (n > 24) { std::stable_sort(b, e, less); return; }
-  for (It i = b + 1; i != e; ++i) {
-    auto x = *i; It j = i;
-    while (j != b && less(x, *(j - 1))) { *j = *(j - 1); --j; }
-    *j = x;
-  }
-}
-template <class Cmp>
-static void dedup_pass(std::vector<FHit*>& v, Cmp cmp) {     // ref: mapping.c:1552-1600 (glibc qsort == stable merge sort here)
-  if (v.size() < 2) return;
-  gm_small_stable_sort(v.begin(), v.end(), [&](const FHit* a, const FHit* b) { return cmp(a, b) < 0; });
-  size_t i = 0, k = 0, n = v.size();
-  while (i < n) {
-    int mx = v[i]->pass2_key; size_t mi = i, j = i + 1;
-    while (j < n && !cmp(v[i], v[j])) { if (v[j]->pass2_key > mx) { mx = v[j]->pass2_key; mi = j; } j++; }
-    if (mi != k) v[k] = v[mi];
-    k++; i = j;
-  }
-  v.resize(k);
-}
-
-static const char CODE2SEQ[17] = "ACGTNNNNNNNNNNNN";   // SEQ letter of an aligned read base (ref: output.c:485-533: non-ACGTN -> N)
-static inline char seq_from_text(char c) {          // ref: gmapper/output.c:326-351
-  switch (c) { case 'R': case 'Y': case 'S': case 'W': case 'K': case 'M': case 'B': case 'D': case 'H': case 'V': return 'N'; default: return c >= 'a' ? (char)(c - 32) : c; }
-}
-static inline char rc_char(char c) { switch (c) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return 'N'; } }
-
-// ---- colour space: post_sw (ref: common/sw-post.c:639-758) for reads without quality values -----------------------------------
-// A 16-state forward-backward over the aligned columns; state j = previous letter << 2 | letter.  The sums run in the reference's
-// order in doubles through the same libm calls, so posterior (-> Z0/Z1, MAPQ, AS) carries the same bits; what is hoisted out of
-// the reference's inner loops (node priors, exp() of the previous column, log() of a sum shared by four states) is computed from
-// identical operands, once instead of four or sixteen times.
-struct CsPostConsts {
-  double let_m, let_x, col_m[2], col_x[2];            // log(1 - e), log(e / 3) for the letter and the two colour error rates
-  double pr_del_open, pr_del_extend, pr_ins_open, pr_ins_extend;
-  bool sanger = true; int qoff = 0;                   // read QVs: PHRED (Sanger) or Solexa-style odds (ref: sw-post.c:489-491); offset of the first colour's QV in the string
-};
-static CsPostConsts cs_post_consts_from(double pr_snp, double pr_xover, double pr_del_open, double pr_del_extend, double pr_ins_open, double pr_ins_extend,
-                                        bool sanger, int qoff) {
-  CsPostConsts c; const double ce[2] = {pr_xover, .75};
-  c.let_m = log(1 - pr_snp); c.let_x = log(pr_snp / 3.0);
-  for (int k = 0; k < 2; k++) { c.col_m[k] = log(1 - ce[k]); c.col_x[k] = log(ce[k] / 3.0); }
-  c.pr_del_open = pr_del_open; c.pr_del_extend = pr_del_extend; c.pr_ins_open = pr_ins_open; c.pr_ins_extend = pr_ins_extend; c.sanger = sanger; c.qoff = qoff;
-  return c;
-}
-static CsPostConsts cs_post_consts(const gm_session* s) {
-  return cs_post_consts_from(s->pr_mismatch, s->P.pr_xover, s->pr_del_open, s->pr_del_extend, s->pr_ins_open, s->pr_ins_extend, true, 0);
-}
-// exp() of 16 state values of one column.  The 16 arguments take few distinct values (a state's prior has four possible values, the
-// transition terms depend on one letter only), and exp is a pure function: computing it once per distinct bit pattern gives the very same
-// doubles as 16 calls do.
-static inline void exp_neg16(const double* in, double* out) {
-  uint64_t seen[16]; double val[16]; int ns = 0;
-  for (int k = 0; k < 16; k++) {
-    uint64_t b; memcpy(&b, &in[k], 8);
-    int j = 0; while (j < ns && seen[j] != b) j++;
-    if (j == ns) { seen[ns] = b; val[ns] = exp(-1 * in[k]); ns++; }
-    out[k] = val[j];
-  }
-}
-
-static void cs_post_sw(const CsPostConsts& K, const uint32_t* rw, int init_bp, int read_start, FHit& h,
-                       const char* qual = nullptr, int qual_delta = 33, bool base_quals = false) {   // qual: the read's QV string (csfastq) or null; base_quals: h.qual even without it
-  struct Col { double prior[16], fw[16], bw[16], fs, bs; int col, base_call; };
-  std::string& db = h.db; std::string& qr = h.qr;
-  static thread_local std::vector<Col> colbuf;
-  if (colbuf.size() < db.size() + 1) colbuf.resize(db.size() + 1);
-  Col* cols = colbuf.data(); int len = 0;
-  auto colour = [&](int j) { return (int)((rw[j >> 3] >> ((j & 7) * 4)) & 0xf); };
-  {  // load_local_vectors, ref: sw-post.c:448-528
-    int start_run = 0, j, min_qv = 10000;
-    for (j = 0; j < read_start; j++) {
-      const int c = colour(j);
-      if (c == 15) { start_run = 15; min_qv = 0; j = read_start; break; }
-      start_run ^= c;
-      if (qual) min_qv = std::min(min_qv, (int)qual[K.qoff + j]);
-    }
-    for (size_t i = 0; i < db.size(); i++) {
-      if (qr[i] == '-') continue;
-      Col& c = cols[len];
-      int let = -2;                                     // -2: no letter emission (insertion); -1: a letter no state matches
-      if (db[i] != '-') switch (db[i]) { case 'A': case 'a': let = 0; break; case 'C': case 'c': let = 1; break; case 'G': case 'g': let = 2; break;
-                                         case 'T': case 't': let = 3; break; default: let = -1; }
-      const int cc = colour(j); int which;
-      if ((len == 0 && start_run == 15) || cc == 15) { c.col = 0; which = 1; } else { c.col = cc ^ (len == 0 ? start_run : 0); which = 0; }
-      double col_m = K.col_m[which], col_x = K.col_x[which];
-      if (qual && which == 0) {                         // the colour's own error rate, ref: sw-post.c:486-491 (use_sanger_qvs = true)
-        const int qv = (len == 0 ? std::min(min_qv, (int)qual[K.qoff + j]) : (int)qual[K.qoff + j]) - qual_delta;
-        double e = qv <= 0 ? .99999999 : (qv >= 250 ? 1E-25 : pow(10.0, -(double)qv / 10.0));
-        if (!K.sanger) e /= (1 + e);
-        if (e > .75) e = .75;
-        col_m = log(1 - e); col_x = log(e / 3.0);
-      }
-      c.base_call = -1;
-      switch (qr[i]) { case 'A': case 'a': c.base_call = 0; break; case 'C': case 'c': c.base_call = 1; break; case 'G': case 'g': c.base_call = 2; break;
-                       case 'T': case 't': c.base_call = 3; break; default: break; }
-      for (int st = 0; st < 16; st++) {                 // nodePrior, ref: sw-post.c:111-138
-        const int l = (st >> 2) & 3, r = st & 3; double val = 0;
-        if (let != -2) val = val - ((r == let) ? K.let_m : K.let_x);
-        val = val - (((l ^ r) == c.col) ? col_m : col_x);
-        c.prior[st] = val;
-      }
-      len++; j++;
-    }
-  }
-  if (len == 0) { h.posterior = 0; return; }
-  double total;
-  {  // do_forwards, ref: sw-post.c:317-360
-    Col& a = cols[0]; a.fs = 999999999;
-    for (int j = 0; j < 16; j++) { if (((j >> 2) & 3) == init_bp) { a.fw[j] = a.prior[j]; a.fs = (a.fs < a.fw[j]) ? a.fs : a.fw[j]; } else a.fw[j] = HUGE_VAL; }
-    for (int j = 0; j < 16; j++) a.fw[j] -= a.fs;
-    for (int i = 1; i < len; i++) {
-      Col& c = cols[i]; const Col& p = cols[i - 1];
-      double e[16], lg[4];
-      exp_neg16(p.fw, e);
-      for (int l = 0; l < 4; l++) { double sum = 0; for (int k = l; k < 16; k += 4) sum += e[k]; lg[l] = log(sum); }   // states k with right(k) == l, ascending
-      c.fs = 999999999;
-      for (int j = 0; j < 16; j++) { c.fw[j] = c.prior[j] - lg[(j >> 2) & 3]; c.fs = (c.fs < c.fw[j]) ? c.fs : c.fw[j]; }
-      for (int j = 0; j < 16; j++) c.fw[j] -= c.fs;
-      c.fs += p.fs;
-    }
-    double val = 0;
-    for (int j = 0; j < 16; j++) val += exp(-1 * (cols[len - 1].fw[j]));
-    total = -log(val) + cols[len - 1].fs;
-  }
-  {  // do_backwards, ref: sw-post.c:269-315
-    Col& z = cols[len - 1]; z.bs = 999999999;
-    for (int j = 0; j < 16; j++) { z.bw[j] = 0; z.bs = (z.bs < z.bw[j]) ? z.bs : z.bw[j]; }
-    for (int j = 0; j < 16; j++) z.bw[j] -= z.bs;
-    for (int i = len - 2; i >= 0; i--) {
-      Col& c = cols[i]; const Col& n = cols[i + 1];
-      double e[16], nl[4];
-      { double a[16]; for (int k = 0; k < 16; k++) a[k] = n.prior[k] + n.bw[k]; exp_neg16(a, e); }
-      for (int r = 0; r < 4; r++) { double sum = 0; for (int k = 4 * r; k < 4 * r + 4; k++) sum += e[k]; nl[r] = -log(sum); }     // states k with left(k) == r
-      c.bs = 999999999;
-      for (int j = 0; j < 16; j++) { c.bw[j] = nl[j & 3]; c.bs = (c.bs < c.bw[j]) ? c.bs : c.bw[j]; }
-      for (int j = 0; j < 16; j++) c.bw[j] -= c.bs;
-      c.bs += n.bs;
-    }
-  }
-  {  // post_traceback + fix_base_calls, ref: sw-post.c:183-212,531-565
-    int j = 0, prev_base = init_bp; h.cs_match = h.cs_mismatch = h.cs_xover = 0; h.qual.clear();
-    for (size_t i = 0; i < qr.size(); i++) {
-      if (qr[i] == '-') continue;
-      const Col& c = cols[j];
-      double post[4] = {0, 0, 0, 0};
-      { double a[16], ev[16]; for (int st = 0; st < 16; st++) a[st] = c.fw[st] + c.bw[st] + c.fs + c.bs - total; exp_neg16(a, ev);
-        for (int st = 0; st < 16; st++) post[st & 3] += ev[st]; }
-      int crt = 0; for (int b = 1; b < 4; b++) if (post[b] > post[crt]) crt = b;
-      if (qual || base_quals) {                         // get_base_qualities, ref: sw-post.c:568-586: of the letter sw_full_cs had called
-        int t = c.base_call >= 0 ? qv_from_pr_corr(post[c.base_call]) : 0;
-        if (t > 40) t = 40;
-        h.qual.push_back((char)(33 + t));
-      }
-      if ((prev_base ^ crt) == c.col) qr[i] = "ACGT"[crt]; else { qr[i] = "acgt"[crt]; h.cs_xover++; }
-      if (db[i] != '-') { if (toupper((unsigned char)db[i]) == toupper((unsigned char)qr[i])) h.cs_match++; else h.cs_mismatch++; }
-      prev_base = crt; j++;
-    }
-  }
-  {  // get_posterior, ref: sw-post.c:589-612
-    double res = exp(-total);
-    for (size_t i = 0; i < db.size(); i++) {
-      if (db[i] == '-') { res *= K.pr_ins_extend; if (i == 0 || db[i - 1] != '-') res *= K.pr_ins_open; }
-      else if (qr[i] == '-') { res *= K.pr_del_extend; if (i == 0 || qr[i - 1] != '-') res *= K.pr_del_open; }
-    }
-    h.posterior = res;
-  }
-}
-// dbalign / qralign of a colour-space alignment from the backtrace bytes and letter codes k_pass2_cs wrote (pretty_print, ref: sw-full-cs.c:945-1060)
-// recalled: the read letters and lower-case marks k_post_sw_cs left in the spare bits of the backtrace bytes (gm_post.hip) instead of sw_full_cs's own
-static void cs_alignment_strings(const uint8_t* bt, const uint8_t* codes, int n, std::string& db, std::string& qr, bool recalled = false) {
-  static const char L[17] = "ACGTUMRWSYKVHDBN";
-  db.clear(); qr.clear();
-  for (int t = 0; t < n; t++) {
-    const int type = bt[t] & 0x0f; const bool xov = recalled ? (bt[t] & 0x40) != 0 : (bt[t] & 0x80) != 0;
-    if (type == 1) { db.push_back(L[codes[t] >> 4]); qr.push_back('-'); continue; }
-    char q = recalled ? L[(bt[t] >> 4) & 3] : L[codes[t] & 15]; if (xov) q = (char)tolower((unsigned char)q);
-    if (type >= 2 && type <= 5) { db.push_back('-'); qr.push_back(q); continue; }
-    const char d = L[codes[t] >> 4];
-    if (q == 'n' || q == 'N') q = xov ? (char)tolower((unsigned char)d) : d;      // an unknown read letter is shown as the genome's
-    db.push_back(d); qr.push_back(q);
-  }
-}
-
-// -DGM_HOST_PROFILE (diagnostic builds): where the finalisation's cycles go -- rdtsc sums per stage over all worker threads, printed by gm_host_profile_dump()
-#ifdef GM_HOST_PROFILE
-#include <x86intrin.h>
-struct GmHpSlots { unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };
-static std::mutex g_hp_m; static std::vector<GmHpSlots*> g_hp_all;
-static GmHpSlots& gm_hp_mine() {      // per thread (the pool's threads live as long as the process): no shared counter is touched per read
-  static thread_local GmHpSlots* mine = nullptr;
-  if (!mine) { mine = new GmHpSlots(); std::lock_guard<std::mutex> lk(g_hp_m); g_hp_all.push_back(mine); }
-  return *mine;
-}
-struct GmHp { unsigned long long t; GmHpSlots& S; GmHp() : t(__rdtsc()), S(gm_hp_mine()) {} void lap(int k) { const unsigned long long n = __rdtsc(); S.v[k] += n - t; t = n; } };
-extern "C" void gm_host_profile_dump(void) {
-  static const char* nm[8] = {"post_sw / FHit build", "dedup + sort", "mapping qualities", "record text", "unaligned record", "reads (count)", "", ""};
-  unsigned long long g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  { std::lock_guard<std::mutex> lk(g_hp_m); for (GmHpSlots* s : g_hp_all) for (int k = 0; k < 8; k++) { g[k] += s->v[k]; s->v[k] = 0; } }
-  unsigned long long tot = 0; for (int k = 0; k < 5; k++) tot += g[k];
-  for (int k = 0; k < 6; k++) { fprintf(stderr, "[host profile] %-22s %14llu%s %5.1f %%\n", nm[k], g[k], k < 5 ? " cycles" : "       ", k < 5 ? 100.0 * g[k] / (tot ? tot : 1) : 0.0); }
-  if (g[5]) fprintf(stderr, "[host profile] %.0f cycles per read\n", (double)tot / (double)g[5]);
-}
-#define GM_HP_DECL GmHp hp_
-#define GM_HP(k) hp_.lap(k)
-#else
-#define GM_HP_DECL do { } while (0)
-#define GM_HP(k) do { } while (0)
-#endif
-struct Finalizer {
-  const gm_session* s; int read_len, read_words; const uint32_t* reads;   // host copy of the packed reads of this sub-batch
-  const char* const* name_ptr; const int* name_len; long name_base;
-  const uint8_t* initbp = nullptr; int ops_half = 0; CsPostConsts csk = CsPostConsts();
-  const GmFullRes* res_base = nullptr; const GmPostRes* post_base = nullptr;           // colour space: post_sw results of the device, parallel to the sub-batch's result records
-  const uint8_t* bq_base = nullptr;                                                    // ... and, for reads with QVs, the base qualities it computed (read_len bytes per result)
-  const char* const* seq_ptr = nullptr;                                                // text input: the read as it stood in the file (fields the reference prints from re->seq)
-  const char* const* qual_ptr = nullptr; int qual_delta = 33;                          // FASTQ input: QUAL string of every read of this sub-batch   // colour space: primer letters of this sub-batch, ops_stride / 2
-  const uint32_t* hgen = nullptr;                                                      // SHRiMP / pretty output: the packed genome on the host
-
-  // dbalign / qralign of a letter-space result from its op record ('M' both, 'I' genome only, 'D' read only), the genome and the read: what sw_full_ls
-  // hands to the output routines (ref: sw-full-ls.c pretty_print).  A reverse-strand result aligned the read to the reverse complement of the contig.
-  void ls_alignment_strings(const GmFullRes& r, const uint8_t* ops, int nops, const uint32_t* rw, std::string& db, std::string& qr) const {
-    static const char L[17] = "ACGTUMRWSYKVHDBN";
-    const gm_index* ix = s->ix; const uint64_t base = ix->contig_off[r.cn]; const int glen = (int)(ix->contig_off[r.cn + 1] - ix->contig_off[r.cn]);
-    auto gcode = [&](int j) -> int {
-      const uint64_t p = base + (uint64_t)(r.gen_st ? glen - 1 - j : j); int c = (int)((hgen[p >> 3] >> ((p & 7) * 4)) & 0xf);
-      if (r.gen_st) c = (int)((0xFBCDE56879A00123ull >> (c * 4)) & 0xf);                    // complement_base, ref: util.h:125-151
-      return c; };
-    db.clear(); qr.clear();
-    int gi = r.genome_start, ri = r.read_start;
-    for (int k = 0; k < nops; k++) {
-      const char op = (char)ops[k];
-      if (op == 'M') { db.push_back(L[gcode(gi++)]); qr.push_back(L[(rw[ri >> 3] >> ((ri & 7) * 4)) & 0xf]); ri++; }
-      else if (op == 'I') { db.push_back(L[gcode(gi++)]); qr.push_back('-'); }
-      else { db.push_back('-'); qr.push_back(L[(rw[ri >> 3] >> ((ri & 7) * 4)) & 0xf]); ri++; }
-    }
-  }
-  // ref: common/output.c:36-115
-  static void edit_string(const std::string& db, const std::string& qr, std::string& o) {
-    const int len = (int)db.size(); int consec = 0; bool refgap = false; char nb[16];
-    for (int i = 0; i <= len; i++) {
-      if (i != len && db[i] == qr[i] && db[i] != '-') { consec++; continue; }
-      if (refgap && (consec != 0 || (i == len ? '\0' : db[i]) != '-')) { o += ')'; refgap = false; }
-      if (consec != 0) { o.append(nb, snprintf(nb, sizeof nb, "%d", consec)); consec = 0; }
-      if (i == len) break;
-      if (db[i] == '-') { if (islower((unsigned char)qr[i])) o += 'x'; if (!refgap) o += '('; o += (char)toupper((unsigned char)qr[i]); refgap = true; continue; }
-      if (qr[i] == '-') o += '-';
-      else if (db[i] == toupper((unsigned char)qr[i])) { o += 'x'; consec++; }
-      else if (islower((unsigned char)qr[i])) { o += 'x'; o += (char)toupper((unsigned char)qr[i]); }
-      else o += qr[i];
-    }
-  }
-  // reverse_alignment_edit_string, ref: gmapper/output.c:83-122
-  static void reverse_edit_string(std::string& e) {
-    const int n = (int)e.size(); std::string r(e.size(), ' ');
-    for (int i = 0; i < n;) {
-      const char c = e[n - 1 - i];
-      if (isdigit((unsigned char)c)) { int j = i + 1; while (j < n && isdigit((unsigned char)e[n - 1 - j])) j++; j--; memcpy(&r[i], &e[n - 1 - j], (size_t)(j - i + 1)); i = j + 1; }
-      else { r[i] = c == ')' ? '(' : c == '(' ? ')' : c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; i++; }
-    }
-    e.swap(r);
-  }
-  // the optional tail of a SAM record and its newline (ref: output.c:452-465,729-761): R2:Z / X2:Z (--sam-r2), RG:Z (--read-group), --extra-sam-fields of a mapping
-  static void sam_tail(const gm_params_t& P, std::string& out, const std::string* mate_seq, const FHit* h, const std::string* db, const std::string* qr) {
-    if (mate_seq) { out += P.colour_space ? "\tX2:Z:" : "\tR2:Z:"; out += *mate_seq; }
-    if (P.read_group[0]) { out += "\tRG:Z:"; out.append(P.read_group, strnlen(P.read_group, sizeof P.read_group)); }
-    if (h && P.extra_sam_fields) {
-      char b[96]; const GmFullRes& r = *h->r;
-      out.append(b, (size_t)snprintf(b, sizeof b, "\tZM:i:%d\tZR:i:%d\tZV:i:%d\tZH:i:%d\tZE:Z:", r.matches, r.score_window_gen, r.score_vector, r.score));
-      std::string e; edit_string(*db, *qr, e);
-      if (r.gen_st == 1) reverse_edit_string(e);
-      out += e;
-    }
-    out += '\n';
-  }
-  // one mapping in the SHRiMP format, with the pretty rows when asked (ref: gmapper/output.c:270-296; common/output.c:280-352 output_normal, :118-262 output_pretty)
-  void emit_shrimp(const FHit& h, const char* nm, size_t nl, int rd, const uint32_t* rw, const std::string& db, const std::string& qr, std::string& out) const {
-    const gm_params_t& P = s->P; const gm_index* ix = s->ix; const GmFullRes& r = *h.r;
-    const bool rev = r.gen_st == 1, cs = P.colour_space != 0;
-    const uint32_t glen = (uint32_t)(ix->contig_off[r.cn + 1] - ix->contig_off[r.cn]);
-    const uint32_t gs = (uint32_t)r.genome_start, ge = gs + (uint32_t)r.gmapped - 1;
-    const uint32_t igs = rev ? glen - ge - 1 : gs, ige = rev ? glen - gs - 1 : ge;
-    char b[160];
-    out += '>'; out.append(nm, nl); out += '\t'; out += ix->names[r.cn]; out += '\t'; out += rev ? '-' : '+';
-    out.append(b, snprintf(b, sizeof b, "\t%u\t%u\t%d\t%d\t%d\t%d\t", igs + 1, ige + 1, r.read_start + 1, r.read_start + r.rmapped, read_len, h.score_full));
-    edit_string(db, qr, out); out += '\t';
-    std::string rstr;                                                                   // readtostr, ref: common/output.c:17-34
-    auto read_text = [&]() { static const char LS[17] = "ACGTUMRWSYKVHDBN", CS[17] = "0123!@#$%^&*?~;."; rstr.clear(); if (cs) rstr += LS[initbp[rd] & 15];
-      for (int i = 0; i < read_len; i++) { const int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; rstr += cs ? CS[c] : LS[c]; } };
-    if (P.print_read_seq) { read_text(); out += rstr; }
-    out += '\n';
-    if (P.output_format != 2) return;
-    static const char LS[17] = "ACGTUMRWSYKVHDBN";
-    const uint64_t base = ix->contig_off[r.cn];
-    auto fwd_letter = [&](uint32_t j) { const uint64_t p = base + j; return LS[(hgen[p >> 3] >> ((p & 7) * 4)) & 0xf]; };   // (the reference reads the forward contig here on either strand)
-    const uint32_t read_start = (uint32_t)r.read_start, read_end = (uint32_t)(r.read_start + r.rmapped - 1);
-    std::string gpre, gpost, lspre, lspost, mpre;
-    for (uint32_t j = 0; j < read_start; j++) { gpre += (gs + j > read_start) ? fwd_letter(gs - read_start + j) : '-'; lspre += '-'; mpre += ' '; }
-    if (read_end < (uint32_t)read_len - 1) for (uint32_t j = 0; j < (uint32_t)read_len - read_end - 1; j++) { gpost += (ge + 1 + j < glen) ? fwd_letter(ge + 1 + j) : '-'; lspost += '-'; }
-    out.append(b, snprintf(b, sizeof b, "G: %10lld    ", (long long)(rev ? ige + 1 : igs + 1))); out += gpre; out += db; out += gpost;
-    out.append(b, snprintf(b, sizeof b, "    %-10lld\n", (long long)(rev ? igs + 1 : ige + 1)));
-    out.append(b, snprintf(b, sizeof b, "%16s ", "")); out += mpre;
-    for (size_t j = 0; j < db.size(); j++) {
-      if (db[j] == qr[j] && db[j] != '-') out += '|';
-      else if (db[j] == toupper((unsigned char)qr[j])) out += 'X';
-      else if (islower((unsigned char)qr[j])) out += 'x';
-      else out += ' ';
-    }
-    out += '\n';
-    if (cs) { out.append(b, snprintf(b, sizeof b, "T: %10s    ", "")); out += lspre; out += qr; out += lspost; out += '\n'; }
-    else { out.append(b, snprintf(b, sizeof b, "R: %10u    ", read_start + 1)); out += lspre; out += qr; out += lspost; out.append(b, snprintf(b, sizeof b, "    %-10u\n", read_end + 1)); }
-    if (cs) {
-      out.append(b, snprintf(b, sizeof b, "R: %10u   ", read_start + 1));
-      read_text(); size_t k = 0; out += rstr[k++];
-      for (uint32_t j = 0; j < read_start; j++) out += rstr[k++];
-      for (size_t j = 0; k < rstr.size();) { if (j < qr.size() && qr[j] == '-') out += '-'; else out += rstr[k++]; if (j < qr.size()) j++; }
-      out.append(b, snprintf(b, sizeof b, "    %-10u\n", read_end + 1));
-    }
-    out += '\n';
-  }
-
-  // Rounding guard for results of the device's post_sw (gm_post.hip): its posterior differs from the host routine's in the last bits (ocml exp / log instead of
-  // glibc's), which matters only where a value is about to be rounded right at a boundary.  Every such conversion below -- rint() for AS, truncation for MAPQ
-  // (with its two cut-offs) and for the Z tags -- checks the distance to the boundary; within guard_tol (1e-7, five orders above the difference) the read's device
-  // results are redone by the host routine (same libm as the reference), so the bytes never hang on the device's last bits.
-  double guard_tol = 1e-7; std::atomic<uint64_t>* redo_ctr = nullptr;
-  bool near_rint(double x) const { return gm_near_rint(x, guard_tol); }
-  bool near_trunc(double x) const { return gm_near_trunc(x, guard_tol); }
-  bool near_qv(double pr_corr) const { return gm_near_qv(pr_corr, guard_tol); }
-  void redo_on_host(FHit& h) const {                    // sw_full_cs's own strings, then the host's post_sw (ref: sw-post.c:636-758), then the posterior score
-    const GmFullRes* r = h.r;
-    cs_alignment_strings(h.ops, h.ops + ops_half, std::min(r->n_ops, ops_half), h.db, h.qr);
-    cs_post_sw(csk, reads + (size_t)r->read_idx * read_words, (int)initbp[r->read_idx], r->read_start, h, qual_ptr ? qual_ptr[r->read_idx] : nullptr, qual_delta);
-    h.dev_post = false;
-    const double a = s->score_alpha, b = s->score_beta;
-    int ps = gm_post_score(a, b, h.posterior, r->rmapped);
-    if (ps < 0) ps = 0;
-    h.score_full = ps; h.pct_score_full = (1000 * 100 * ps) / r->score_max;
-    h.pass2_key = s->P.sw_full_threshold < 0 ? h.score_full : (int)h.pct_score_full;
-    if (redo_ctr) redo_ctr->fetch_add(1, std::memory_order_relaxed);
-  }
-  // hit_run_post_sw for one pass-2 result (ref: mapping.c:1609-1625)
-  void post_sw(FHit& h, const GmFullRes* r, const uint8_t* ops) const {
-    const gm_params_t& P = s->P;
-    h.r = r; h.ops = ops + (size_t)r->ops_off; h.mqv = 255; h.z0 = h.z1 = 0; h.posterior = 0; h.dev_post = false;
-    h.z2 = h.z3 = h.pr_top_random = h.insert_size_denom = h.pr_missed_mp = 0;
-    h.score_full = r->score;
-    h.pct_score_full = (1000 * 100 * h.score_full) / r->score_max;                 // ref: mapping.c:400-401
-    if (h.score_full > 0 && gm_mqv_on(P)) {                        // local mode / --no-mapping-qualities: no post_sw (ref: gmapper.c:2325-2328, mapping.c:1648)
-      const double a = s->score_alpha, b = s->score_beta;
-      if (P.colour_space) {
-        if (post_base && (!qual_ptr || bq_base) && post_base[r - res_base].valid == 1) {   // k_post_sw_cs ran: the op record carries the re-called letters in its spare bits
-          const GmPostRes& pr = post_base[r - res_base];
-          cs_alignment_strings(h.ops, h.ops + ops_half, std::min(r->n_ops, ops_half), h.db, h.qr, true);
-          h.posterior = pr.posterior; h.cs_match = pr.cs_match; h.cs_mismatch = pr.cs_mismatch; h.cs_xover = pr.cs_xover; h.qual.clear(); h.dev_post = true;
-          if (qual_ptr) {                                                // base qualities of the read positions the alignment covers, in alignment order
-            size_t nq = 0; for (char c : h.qr) nq += c != '-';
-            h.qual.assign((const char*)bq_base + (size_t)(r - res_base) * read_len, std::min(nq, (size_t)read_len));
-          }
-          if (near_rint(gm_post_score_x(a, b, h.posterior, r->rmapped))) { redo_on_host(h); return; }      // AS at a rounding boundary
-        } else {
-        cs_alignment_strings(h.ops, h.ops + ops_half, std::min(r->n_ops, ops_half), h.db, h.qr);
-        cs_post_sw(csk, reads + (size_t)r->read_idx * read_words, (int)initbp[r->read_idx], r->read_start, h,
-                   qual_ptr ? qual_ptr[r->read_idx] : nullptr, qual_delta);
-        }
-      }
-      int ps;
-      if (!P.colour_space) {
-        // letter space: posterior and score are functions of (score, mapped read length) alone -- a small per-thread table of the values libm gave for the pairs seen
-        // last (reads of one length that map with 0, 1, 2 mismatches share a handful of pairs) instead of a pow and a log per mapping; the same doubles, so the same bytes
-        struct Memo { int score, rmapped; double a, b, post; int ps; };
-        static thread_local Memo memo[256];                        // (zero-initialised: a == 0 matches no session)
-        Memo& m = memo[((unsigned)r->score * 31u + (unsigned)r->rmapped) & 255u];
-        if (m.score != r->score || m.rmapped != r->rmapped || m.a != a || m.b != b) {
-          m.score = r->score; m.rmapped = r->rmapped; m.a = a; m.b = b;
-          m.post = gm_ls_posterior(a, b, r->score, r->rmapped);
-          m.ps = gm_post_score(a, b, m.post, r->rmapped);
-        }
-        h.posterior = m.post; ps = m.ps;
-      } else
-      ps = gm_post_score(a, b, h.posterior, r->rmapped);
-      if (ps < 0) ps = 0;
-      h.score_full = ps; h.pct_score_full = (1000 * 100 * ps) / r->score_max;
-    }
-    else if (h.score_full > 0 && P.colour_space) {                 // colour space, local mode: no post_sw (mapping.c:1648): sw_full_cs's own strings and counts go out
-      cs_alignment_strings(h.ops, h.ops + ops_half, std::min(r->n_ops, ops_half), h.db, h.qr);
-      h.cs_match = r->n_match; h.cs_mismatch = r->n_mismatch; h.cs_xover = r->n_xover; h.qual.clear();
-    }
-    h.pass2_key = P.sw_full_threshold < 0 ? h.score_full : (int)h.pct_score_full;
-  }
-  // read_pass2's selection over the n pass-2 results of one read (ref: mapping.c:1628-1750): p2 = final hits in output order
-  void select_hits(const GmFullRes* res, const uint8_t* ops, int n, std::vector<FHit>& fh, std::vector<FHit*>& p2) const {
-    const gm_params_t& P = s->P;
-    GM_HP_DECL;
-    fh.clear(); p2.clear();
-    fh.resize(n);
-    for (int i = 0; i < n; i++) {
-      FHit& h = fh[i]; post_sw(h, &res[i], ops);
-      const double thr = gm_full_threshold(P, h.r->score_max);
-      if (h.score_full >= thr) p2.push_back(&h);                                   // ref: mapping.c:1661 (double compare)
-    }
-    GM_HP(0);
-    dedup_pass(p2, cmp_gen_start);
-    dedup_pass(p2, cmp_gen_end);
-    gm_small_stable_sort(p2.begin(), p2.end(), [](const FHit* a, const FHit* b) { return (b->pass2_key - a->pass2_key) < 0; });   // ref :1479-1482,1678
-    if ((int)p2.size() > P.num_outputs) p2.resize(P.num_outputs);
-    if (P.strata && !p2.empty()) { size_t i = 1; while (i < p2.size() && p2[0]->score_full == p2[i]->score_full) i++; p2.resize(i); }   // ref :1706-1712
-    if (P.max_alignments != 0 && (int)p2.size() > P.max_alignments) p2.clear();                                                        // ref :1713-1722
-    GM_HP(1);
-  }
-
-  // emits the SAM records of read `rd` (local index) into out; returns number of records
-  int finalize_read(int rd, const GmFullRes* res, const uint8_t* ops, int ops_stride, int n, std::string& out, std::vector<FHit>& fh, std::vector<FHit*>& p2) const {
-    const gm_params_t& P = s->P; const gm_index* ix = s->ix;
-    select_hits(res, ops, n, fh, p2);
-    GM_HP_DECL;
-#ifdef GM_HOST_PROFILE
-    hp_.S.v[5]++;
-#endif
-    const uint32_t* rw = reads + (size_t)rd * read_words;
-    char nbuf[32]; const char* nm; size_t nl;
-    if (name_ptr) { nm = name_ptr[rd]; nl = (size_t)name_len[rd]; }
-    else { nbuf[0] = 'r'; nl = (size_t)(put_int(nbuf + 1, (long long)(name_base + rd)) - nbuf); nm = nbuf; }
-    // room reserved per record (std::string::resize zero-fills it: a letter-space record writes SEQ + QUAL + fixed fields, a colour-space one also CQ / CS / XX)
-    const size_t need = 64 + nl + (P.colour_space ? 8 : 3) * (size_t)read_len + 320;
-    // colour space: the read as csfasta text, primer letter + colours ('.' for a skipped cycle), for the CS:Z tag (ref: output.c:451,730)
-    auto put_csfasta = [&](char* p) { if (seq_ptr) return put_str(p, seq_ptr[rd], (size_t)read_len + 1);     // verbatim, as the reference prints re->seq
-      *p++ = "ACGT"[initbp[rd] & 3]; for (int i = 0; i < read_len; i++) { int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; *p++ = (c < 4) ? (char)('0' + c) : '.'; } return p; };
-    if (p2.empty()) {
-      if (P.sam_unaligned) {                                                       // ref: output.c:411-466
-        size_t o = out.size(); out.resize(o + need); char* p = &out[o];
-        p = put_str(p, nm, nl); p = put_str(p, "\t4\t*\t0\t0\t*\t*\t0\t0\t", 17);
-        if (P.colour_space) {                                                        // ref: output.c:353-355,441-451
-          p = put_str(p, "*\t*\tCQ:Z:", 9);
-          if (qual_ptr) p = put_str(p, qual_ptr[rd], (size_t)read_len); else *p++ = '*';
-          p = put_str(p, "\tCS:Z:", 6); p = put_csfasta(p); out.resize(p - out.data()); sam_tail(P, out, nullptr, nullptr, nullptr, nullptr); return 1;
-        }
-        if (seq_ptr) for (int i = 0; i < read_len; i++) *p++ = seq_from_text(seq_ptr[rd][i]);
-        else for (int i = 0; i < read_len; i++) { int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; *p++ = "ACGTUMRWSYKVHDBN"[c]; }      // (the reference prints the file's own letters here: a U stays a U)
-        if (qual_ptr) { *p++ = '\t'; p = put_str(p, qual_ptr[rd], (size_t)read_len); }      // ref: output.c:419-421 (verbatim)
-        else p = put_str(p, "\t*", 2);
-        out.resize(p - out.data()); sam_tail(P, out, nullptr, nullptr, nullptr, nullptr);
-        GM_HP(4);
-        return 1;
-      }
-      return 0;
-    }
-    if (gm_mqv_on(P)) {                                                            // compute_unpaired_mqv, ref: output.c:777-793,975
-      for (int pass = 0; pass < 2; pass++) {
-        double z1 = 0.0;
-        for (auto* h : p2) z1 += h->posterior;
-        for (auto* h : p2) { h->z0 = h->posterior; h->z1 = z1; h->mqv = gm_unpaired_mqv(h->posterior, z1); }
-        // rounding guard (see post_sw above): MAPQ and the Z0 / Z1 tags of this read's records, when any posterior came from the device
-        bool dev = false, near = false;
-        for (auto* h : p2) dev = dev || h->dev_post;
-        if (pass || !dev) break;
-        near = near_trunc(1000.0 * -log(z1));
-        for (auto* h : p2) near = near || near_qv(h->posterior / z1) || near_trunc(1000.0 * -log(h->z0));
-        if (!near) break;
-        for (auto* h : p2) if (h->dev_post) redo_on_host(*h);
-      }
-      if (P.single_best_mapping) {                                                 // the first mapping with the highest quality, ref: output.c:977-984
-        size_t mx = 0;
-        for (size_t i = 1; i < p2.size(); i++) if (p2[i]->mqv > p2[mx]->mqv) mx = i;
-        FHit* best = p2[mx]; p2.assign(1, best);
-      }
-    }
-    GM_HP(2);
-    if (P.output_format) {                                                         // --shrimp-format / --pretty, ref: gmapper/output.c:270-296
-      std::string db, qr;
-      for (auto* h : p2) {
-        if (P.colour_space) emit_shrimp(*h, nm, nl, rd, rw, h->db, h->qr, out);
-        else { ls_alignment_strings(*h->r, h->ops, std::min(h->r->n_ops, ops_stride), rw, db, qr); emit_shrimp(*h, nm, nl, rd, rw, db, qr, out); }
-      }
-      return (int)p2.size();
-    }
-    for (auto* h : p2) {
-      const GmFullRes& r = *h->r;
-      // The record is assembled in a buffer on the stack and appended (its bound -- every CIGAR operation a run of its own -- is ~2 KB for a 250-byte record, and
-      // std::string::resize zero-fills what it adds); a record beyond the buffer grows the string in place as before.
-      const size_t bound = need + 12 * (size_t)r.n_ops + ix->names[r.cn].size();
-      char stage[4096]; const bool staged = bound <= sizeof stage;
-      if (!staged) { const size_t o = out.size(); out.resize(o + bound); }
-      char* p = staged ? stage : &out[out.size() - bound];
-      auto commit = [&](char* e) { if (staged) out.append(stage, (size_t)(e - stage)); else out.resize((size_t)(e - out.data())); };
-      const bool rev = r.gen_st == 1;
-      const int read_start = r.read_start + 1, read_end = read_start + r.rmapped - 1;
-      const int glen = (int)(ix->contig_off[r.cn + 1] - ix->contig_off[r.cn]);
-      p = put_str(p, nm, nl); *p++ = '\t';
-      p = put_int(p, rev ? 16 : 0); *p++ = '\t';
-      p = put_str(p, ix->names[r.cn].data(), ix->names[r.cn].size()); *p++ = '\t';
-      int genome_start;
-      if (!rev) genome_start = r.genome_start + 1;
-      else genome_start = (glen - r.genome_start) - (read_end - read_start - r.n_del + r.n_ins);   // ref: output.c:626-634
-      p = put_uint(p, (unsigned)genome_start); *p++ = '\t';
-      p = put_int(p, h->mqv); *p++ = '\t';
-      // CIGAR (make_cigar, ref: output.c:15-64): 'I' op = gap in the read -> D; 'D' op = gap in the genome -> I
-      struct Run { int len; char op; }; Run runs[GM_MAX_OPS]; int nr = 0;
-      const char clip = P.colour_space ? 'H' : 'S';                                 // ref: output.c:575-579
-      if (read_start > 1) runs[nr++] = {read_start - 1, clip};
-      if (P.colour_space) {
-        const int na = (int)h->qr.size();
-        for (int i = 0; i < na;) {
-          const char op = h->qr[i] == '-' ? 'D' : (h->db[i] == '-' ? 'I' : 'M'); int j = i;
-          while (j < na && (h->qr[j] == '-' ? 'D' : (h->db[j] == '-' ? 'I' : 'M')) == op) j++;
-          if (nr < GM_MAX_OPS - 1) runs[nr++] = {j - i, op};
-          i = j;
-        }
-      } else {
-      const int nops = std::min(r.n_ops, ops_stride);
-      for (int i = 0; i < nops;) {
-        const char op = (char)h->ops[i]; int j = i; while (j < nops && h->ops[j] == (uint8_t)op) j++;
-        if (nr < GM_MAX_OPS - 1) runs[nr++] = {j - i, op == 'M' ? 'M' : (op == 'I' ? 'D' : 'I')};
-        i = j;
-      }
-      }
-      if (read_end != read_len) runs[nr++] = {read_len - read_end, clip};
-      if (!rev) for (int i = 0; i < nr; i++) { p = put_uint(p, (unsigned)runs[i].len); *p++ = runs[i].op; }
-      else for (int i = nr - 1; i >= 0; i--) { p = put_uint(p, (unsigned)runs[i].len); *p++ = runs[i].op; }
-      p = put_str(p, "\t*\t0\t0\t", 7);
-      if (P.colour_space) {   // SEQ = the aligned letters post_sw called (ref: output.c:485-537), then the colour-space tags (:717-730)
-        auto up = [](char c) { if (c >= 'a') c -= 32; return (c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N') ? c : 'N'; };
-        const int na = (int)h->qr.size();
-        if (!rev) { for (int i = 0; i < na; i++) if (h->qr[i] != '-') *p++ = up(h->qr[i]); }
-        else for (int i = na - 1; i >= 0; i--) if (h->qr[i] != '-') *p++ = rc_char(up(h->qr[i]));
-        *p++ = '\t';
-        if (qual_ptr && !h->qual.empty()) {                                         // post_sw's base qualities, ref: output.c:613-621 (none in local mode: no post_sw there)
-          const int nq = (int)h->qual.size();
-          if (!rev) p = put_str(p, h->qual.data(), (size_t)nq); else for (int i = nq - 1; i >= 0; i--) *p++ = h->qual[i];
-        } else *p++ = '*';
-        p = put_str(p, "\tAS:i:", 6); p = put_int(p, h->score_full);
-        if (gm_mqv_on(P) && !P.all_contigs) {                                        // ref: output.c:691-696
-          p = put_str(p, "\tZ0:i:", 6); p = put_int(p, double_to_neglog(h->z0));
-          p = put_str(p, "\tZ1:i:", 6); p = put_int(p, double_to_neglog(h->z1));
-        }
-        p = put_str(p, "\tNM:i:", 6); p = put_int(p, h->cs_mismatch + r.n_del + r.n_ins);
-        if (qual_ptr) { p = put_str(p, "\tCQ:Z:", 6); p = put_str(p, qual_ptr[rd], (size_t)read_len); }   // ref: output.c:724-727
-        p = put_str(p, "\tCS:Z:", 6); p = put_csfasta(p);
-        p = put_str(p, "\tCM:i:", 6); p = put_int(p, h->cs_xover);
-        p = put_str(p, "\tXX:Z:", 6); p = put_str(p, h->qr.data(), h->qr.size());
-        commit(p); sam_tail(P, out, nullptr, h, &h->db, &h->qr);
-        continue;
-      }
-      // SEQ: read bases in input orientation (aligned part from qralign == the read's own letters), revcomp on '-'
-      // (text input: the clipped ends -- local mode only -- keep the file's letters, ref: output.c:326-351,482-533; on the reverse strand the reference's
-      // reverse() knows no 'X' / 'U' and exits there, those print as N here)
-      auto seq_at = [&](int i) -> char { const int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; return (seq_ptr && (i < read_start - 1 || i >= read_end)) ? seq_from_text(seq_ptr[rd][i]) : CODE2SEQ[c]; };
-      if (!seq_ptr || (read_start == 1 && read_end == read_len)) {                // every base from its code: eight to a word, the reverse strand through the complement's letters
-        static const char RC2SEQ[17] = "TGCANNNNNNNNNNNN";                         // rc_char(CODE2SEQ[c])
-        if (!rev) { for (int i = 0; i < read_len; i += 8) { uint32_t x = rw[i >> 3]; const int m = std::min(8, read_len - i); for (int k = 0; k < m; k++) { *p++ = CODE2SEQ[x & 15u]; x >>= 4; } } }
-        else { for (int i = read_len - 1; i >= 0;) { const uint32_t x = rw[i >> 3]; for (int k = i & 7; k >= 0; k--, i--) *p++ = RC2SEQ[(x >> (4 * k)) & 15u]; } }
-      } else {
-      if (!rev) for (int i = 0; i < read_len; i++) *p++ = seq_at(i);
-      else for (int i = read_len - 1; i >= 0; i--) { const char c = seq_at(i); *p++ = c == '.' ? '.' : rc_char(c); }
-      }
-      if (qual_ptr) {                                                              // ref: output.c:539-570
-        *p++ = '\t';
-        const char* q = qual_ptr[rd]; const int dq = 33 - qual_delta;
-        if (!rev) for (int i = 0; i < read_len; i++) *p++ = (char)(q[i] + dq);
-        else for (int i = read_len - 1; i >= 0; i--) *p++ = (char)(q[i] + dq);
-        p = put_str(p, "\tAS:i:", 6);
-      } else p = put_str(p, "\t*\tAS:i:", 8);
-      p = put_int(p, h->score_full);
-      if (gm_mqv_on(P) && !P.all_contigs) {                                        // ref: output.c:691-696
-        p = put_str(p, "\tZ0:i:", 6); p = put_int(p, double_to_neglog(h->z0));
-        p = put_str(p, "\tZ1:i:", 6); p = put_int(p, double_to_neglog(h->z1));
-      }
-      p = put_str(p, "\tNM:i:", 6); p = put_int(p, r.n_mismatch + r.n_del + r.n_ins);
-      commit(p);
-      if (P.extra_sam_fields) { std::string db, qr; ls_alignment_strings(r, h->ops, std::min(r.n_ops, ops_stride), rw, db, qr); sam_tail(P, out, nullptr, h, &db, &qr); }
-      else sam_tail(P, out, nullptr, nullptr, nullptr, nullptr);
-    }
-    GM_HP(3);
-    return (int)p2.size();
-  }
-};
+#include "gm_host_finalize.inc"
+#include "gm_host_records.inc"
 
 // Heavy tier of K2: the few read-strands whose survivors exceed the LDS tier (low-complexity reads,
 // repeats).  Sizes are known now, so every array is allocated exactly, the keys are re-emitted by K1
@@ -1849,12 +1215,11 @@ struct ReadRun : ReadCall {
     const int nchunks = (n + chunk - 1) / chunk;
     J->outs.assign(nchunks, std::string()); J->cm.assign(nchunks, 0); J->cr.assign(nchunks, 0);
     std::atomic<int> next(0);
-    Finalizer F{s, read_len, read_words, J->hreads, named ? nptr.data() + J->base : nullptr, named ? nlen.data() + J->base : nullptr, (long)J->base};
-    if (s->P.colour_space) { F.initbp = initbp + J->base; F.ops_half = ops_stride / 2; F.csk = cs_post_consts(s); if (J->hs->post_on) { F.res_base = J->hs->res; F.post_base = J->hs->post; if (J->hs->post_bq_on) F.bq_base = J->hs->post_bq; } }
+    HitScorer F; F.s = s; F.read_len = read_len; F.read_words = read_words;
+    if (s->P.colour_space) { F.reads = J->hreads; F.initbp = initbp + J->base; F.ops_half = ops_stride / 2; F.csk = cs_post_consts(s); if (J->hs->post_on) { F.res_base = J->hs->res; F.post_base = J->hs->post; if (J->hs->post_bq_on) F.bq_base = J->hs->post_bq; } }
     F.redo_ctr = &post_redo; if (guard_tol) F.guard_tol = atof(guard_tol);
     if (quals) { F.qual_ptr = qptr.data() + J->base; F.qual_delta = qual_delta; }
-    if (seq_text) F.seq_ptr = sptr.data() + J->base;
-    if (s->P.output_format || s->P.extra_sam_fields) F.hgen = s->h_genome.data();
+    const RecCtx C{s->P, s->ix->names, s->ix->contig_off, s->h_genome.data()};
     auto worker = [&]() {
       std::vector<FHit> fh; std::vector<FHit*> p2;
       for (;;) {
@@ -1863,7 +1228,11 @@ struct ReadRun : ReadCall {
         for (int rd = c * chunk; rd < std::min(n, (c + 1) * chunk); rd++) {
           const uint32_t cnt = J->hs->sel_cnt[rd], off = J->hs->sel_off[rd];
           const size_t before = o.size();
-          int k = F.finalize_read(rd, cnt ? &J->hs->res[off] : nullptr, J->hs->ops, ops_stride, (int)cnt, o, fh, p2);
+          const int g = J->base + rd;                           // the read's place in the call: its name ("r<g>" when the call gave none) and lines
+          char nbuf[32]; nbuf[0] = 'r';
+          const RecRead R{named ? nptr[g] : nbuf, named ? (size_t)nlen[g] : (size_t)(put_int(nbuf + 1, g) - nbuf), J->hreads + (size_t)rd * read_words, read_len,
+                          initbp ? (int)initbp[g] : -1, quals ? qptr[g] : nullptr, qual_delta, seq_text ? sptr[g] : nullptr, ops_stride};
+          int k = F.finalize_read(C, R, cnt ? &J->hs->res[off] : nullptr, J->hs->ops, (int)cnt, o, fh, p2);
           if (per_read_bytes) per_read_bytes[J->base + rd] = (uint32_t)(o.size() - before);
           if (!p2.empty()) J->cm[c]++;  J->cr[c] += k;
           if (!emit_sam) o.clear();

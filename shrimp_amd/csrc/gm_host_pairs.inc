@@ -1,7 +1,7 @@
 // gm_host_pairs.inc -- host side of paired mode; included by gm_host.hip (same translation unit, after map_impl).
 //   handle_readpair            ref: gmapper/mapping.c:2502-2636     readpair_pass2          ref: mapping.c:2181-2314
 //   readpair_save_final_hits   ref: mapping.c:2446-2499             compute_paired_mqv      ref: output.c:811-942
-//   readpair_output            ref: output.c:1070-1291              hit_output (paired)     ref: output.c:227-774
+//   readpair_output            ref: output.c:1070-1291              hit_output: sam_record with a mate (gm_host_records.inc)
 // Device work per sub-batch of pairs: K1/K2 per mate set, pair-up, pass 1 over paired windows, pair top-K,
 // pass 2 at half threshold; host: pair selection; device: the half-paired fall-back (pass 1 over all windows,
 // top-K, pass 2); host: selection, paired mapping qualities, SAM text.
@@ -20,17 +20,9 @@ struct PairCtx {
   const gm_session* s; gm_pair_opts_t O; int len[2], rwords[2]; double total_genome_size;
 };
 
-static void hit_ends(const gm_index* ix, const FHit* h, int* gstart, int* gend) {   // ref: mapping.c:414-441
-  const GmFullRes& r = *h->r;
-  const int read_start = r.read_start + 1, read_end = read_start + r.rmapped - 1;
-  const int glen = (int)(ix->contig_off[r.cn + 1] - ix->contig_off[r.cn]);
-  if (r.gen_st != 1) *gstart = r.genome_start + 1;
-  else *gstart = (glen - r.genome_start) - (read_end - read_start - r.n_del + r.n_ins);
-  *gend = *gstart + r.gmapped - 1;
-}
 static int get_insert_size(const gm_index* ix, const FHit* rh, const FHit* rh_mp) {    // ref: mapping.c:405-456
   if (rh->r->cn != rh_mp->r->cn) return 0;
-  int gs_mp, ge_mp, gs, ge; hit_ends(ix, rh_mp, &gs_mp, &ge_mp); hit_ends(ix, rh, &gs, &ge);
+  int gs_mp, ge_mp, gs, ge; hit_ends(ix->contig_off, rh_mp, &gs_mp, &ge_mp); hit_ends(ix->contig_off, rh, &gs, &ge);
   const int fivep = (rh->r->gen_st == 1) ? ge : gs - 1;
   const int fivep_mp = (rh_mp->r->gen_st == 1) ? ge_mp : gs_mp - 1;
   return fivep_mp - fivep;
@@ -183,137 +175,6 @@ static void compute_paired_mqv(const PairCtx& C, FHit* const HP[2], const PPair*
     }
 }
 
-// hit_output for one mate of a pair (ref: output.c:227-774); rh == nullptr: unmapped-mate line
-static void emit_pair_record(const PairCtx& C, std::string& out, const char* qn, size_t qnl, const uint32_t* rw, int read_len, int ops_stride,
-                             const FHit* rh, const FHit* rh_mp, bool first_in_pair, bool improper, const char* qual = nullptr, int qual_delta = 33, int initbp = -1,
-                             const std::string* mate_seq = nullptr) {
-  const gm_index* ix = C.s->ix;
-  const bool cs = C.s->P.colour_space != 0;                    // colour space (initbp = the read's primer letter): SEQ / clips / tags as in the unpaired records (ref: output.c:353-355,441-451,485-537,572-580,717-730)
-  auto put_csfasta = [&](char* p) { *p++ = "ACGT"[initbp & 3]; for (int i = 0; i < read_len; i++) { const int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; *p++ = (c < 4) ? (char)('0' + c) : '.'; } return p; };
-  const bool paired_alignment = (rh != nullptr && rh_mp != nullptr && !improper);
-  const bool query_unmapped = (rh == nullptr), mate_unmapped = (rh_mp == nullptr);
-  bool reverse_strand = false, reverse_strand_mp = false;
-  int genome_start_mp = 0, genome_end_mp = 0; unsigned mpos = 0;
-  const std::string* mrnm = nullptr;
-  if (!mate_unmapped) {
-    reverse_strand_mp = (rh_mp->r->gen_st == 1);
-    hit_ends(ix, rh_mp, &genome_start_mp, &genome_end_mp);
-    mpos = (unsigned)genome_start_mp; mrnm = &ix->names[rh_mp->r->cn];
-  }
-  const size_t n_ops = rh ? (size_t)rh->r->n_ops : 0;
-  const size_t need = qnl + 5 * (size_t)read_len + 12 * n_ops + 400 + (rh ? ix->names[rh->r->cn].size() : 0) + (mrnm ? mrnm->size() : 0);
-  // (staged on the stack and appended, as in the unpaired writer: the bound is several times the record and std::string::resize zero-fills it)
-  char stage[6144]; const bool staged = need <= sizeof stage;
-  if (!staged) { const size_t o = out.size(); out.resize(o + need); }
-  char* p = staged ? stage : &out[out.size() - need];
-  auto commit = [&](char* e) { if (staged) out.append(stage, (size_t)(e - stage)); else out.resize((size_t)(e - out.data())); };
-  p = put_str(p, qn, qnl); *p++ = '\t';
-  if (query_unmapped) {                                                               // ref: output.c:411-466
-    const int flags = 0x1 | 0x4 | (mate_unmapped ? 0x8 : 0) | (reverse_strand_mp ? 0x20 : 0) | (first_in_pair ? 0x40 : 0x80);
-    p = put_int(p, flags); p = put_str(p, "\t*\t0\t0\t*\t", 9);
-    if (mrnm) p = put_str(p, mrnm->data(), mrnm->size()); else *p++ = '*';
-    *p++ = '\t'; p = put_uint(p, mpos); p = put_str(p, "\t0\t", 3);
-    if (cs) {                                                                         // ref: output.c:441-451
-      p = put_str(p, "*\t*\tCQ:Z:", 9); if (qual) p = put_str(p, qual, (size_t)read_len); else *p++ = '*';
-      p = put_str(p, "\tCS:Z:", 6); p = put_csfasta(p); commit(p); Finalizer::sam_tail(C.s->P, out, mate_seq, nullptr, nullptr, nullptr); return; }
-    for (int i = 0; i < read_len; i++) { const int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; *p++ = (c < 4) ? "ACGT"[c] : (c == 4 ? 'U' : 'N'); }
-    if (qual) { *p++ = '\t'; p = put_str(p, qual, (size_t)read_len); }               // FASTQ input, verbatim (ref: output.c:419-421)
-    else p = put_str(p, "\t*", 2);
-    commit(p); Finalizer::sam_tail(C.s->P, out, mate_seq, nullptr, nullptr, nullptr);
-    return;
-  }
-  const GmFullRes& r = *rh->r;
-  reverse_strand = (r.gen_st == 1);
-  const int read_start = r.read_start + 1, read_end = read_start + r.rmapped - 1;
-  int genome_start, genome_end; hit_ends(ix, rh, &genome_start, &genome_end);
-  const int flags = 0x1 | (paired_alignment ? 0x2 : 0) | (mate_unmapped ? 0x8 : 0) | (reverse_strand ? 0x10 : 0) | (reverse_strand_mp ? 0x20 : 0) |
-                    (first_in_pair ? 0x40 : 0x80);
-  p = put_int(p, flags); *p++ = '\t';
-  p = put_str(p, ix->names[r.cn].data(), ix->names[r.cn].size()); *p++ = '\t';
-  p = put_uint(p, (unsigned)genome_start); *p++ = '\t';
-  p = put_int(p, rh->mqv); *p++ = '\t';
-  {  // CIGAR (make_cigar, ref: output.c:15-64)
-    struct Run { int len; char op; }; Run runs[GM_MAX_OPS]; int nr = 0;
-    const char clip = cs ? 'H' : 'S';
-    if (read_start > 1) runs[nr++] = {read_start - 1, clip};
-    if (cs) {
-      const int na = (int)rh->qr.size();
-      for (int i = 0; i < na;) {
-        const char op = rh->qr[i] == '-' ? 'D' : (rh->db[i] == '-' ? 'I' : 'M'); int j = i;
-        while (j < na && (rh->qr[j] == '-' ? 'D' : (rh->db[j] == '-' ? 'I' : 'M')) == op) j++;
-        if (nr < GM_MAX_OPS - 1) runs[nr++] = {j - i, op};
-        i = j;
-      }
-    } else {
-    const int nops = std::min(r.n_ops, ops_stride);
-    for (int i = 0; i < nops;) {
-      const char op = (char)rh->ops[i]; int j = i; while (j < nops && rh->ops[j] == (uint8_t)op) j++;
-      if (nr < GM_MAX_OPS - 1) runs[nr++] = {j - i, op == 'M' ? 'M' : (op == 'I' ? 'D' : 'I')};
-      i = j;
-    }
-    }
-    if (read_end != read_len) runs[nr++] = {read_len - read_end, clip};
-    if (!reverse_strand) for (int i = 0; i < nr; i++) { p = put_uint(p, (unsigned)runs[i].len); *p++ = runs[i].op; }
-    else for (int i = nr - 1; i >= 0; i--) { p = put_uint(p, (unsigned)runs[i].len); *p++ = runs[i].op; }
-  }
-  *p++ = '\t';
-  int isize = 0;
-  if (!mate_unmapped) {                                                               // ref: output.c:640-655
-    if (ix->names[r.cn] == *mrnm) {
-      *p++ = '=';
-      const int fivep = reverse_strand ? genome_end : genome_start - 1;
-      const int fivep_mp = reverse_strand_mp ? genome_end_mp : genome_start_mp - 1;
-      isize = fivep_mp - fivep;
-    } else p = put_str(p, mrnm->data(), mrnm->size());
-  } else *p++ = '*';
-  *p++ = '\t'; p = put_uint(p, mpos); *p++ = '\t'; p = put_int(p, isize); *p++ = '\t';
-  if (cs) {                                                    // the aligned letters post_sw called
-    auto up = [](char c) { if (c >= 'a') c -= 32; return (c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N') ? c : 'N'; };
-    const int na = (int)rh->qr.size();
-    if (!reverse_strand) { for (int i = 0; i < na; i++) if (rh->qr[i] != '-') *p++ = up(rh->qr[i]); }
-    else for (int i = na - 1; i >= 0; i--) if (rh->qr[i] != '-') *p++ = rc_char(up(rh->qr[i]));
-  } else
-  if (!reverse_strand) for (int i = 0; i < read_len; i++) { const int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; *p++ = CODE2SEQ[c]; }
-  else for (int i = read_len - 1; i >= 0; i--) { const int c = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; *p++ = rc_char(CODE2SEQ[c]); }
-  if (cs && qual && !rh->qual.empty()) {                                              // csfastq: post_sw's base qualities (ref: output.c:613-621); --local runs no post_sw: '*'
-    *p++ = '\t'; const int nq = (int)rh->qual.size();
-    if (!reverse_strand) p = put_str(p, rh->qual.data(), (size_t)nq); else for (int i = nq - 1; i >= 0; i--) *p++ = rh->qual[i];
-    p = put_str(p, "\tAS:i:", 6);
-  } else
-  if (qual && !cs) {                                                                  // FASTQ input: reversed with the read, re-based to PHRED+33 (ref: output.c:539-570)
-    *p++ = '\t'; const int dq = 33 - qual_delta;
-    if (!reverse_strand) for (int i = 0; i < read_len; i++) *p++ = (char)(qual[i] + dq);
-    else for (int i = read_len - 1; i >= 0; i--) *p++ = (char)(qual[i] + dq);
-    p = put_str(p, "\tAS:i:", 6);
-  } else p = put_str(p, "\t*\tAS:i:", 8);
-  p = put_int(p, rh->score_full);
-  if (!gm_mqv_on(C.s->P) || C.s->P.all_contigs) {}                                     // no Z tags without mapping qualities or with --all-contigs (ref: output.c:691)
-  else if (paired_alignment) {
-    p = put_str(p, "\tZ2:i:", 6); p = put_int(p, double_to_neglog(rh->z2));
-    p = put_str(p, "\tZ3:i:", 6); p = put_int(p, double_to_neglog(rh->z3));
-    p = put_str(p, "\tZ4:i:", 6); p = put_int(p, double_to_neglog(rh->pr_top_random));
-    p = put_str(p, "\tZ6:i:", 6); p = put_int(p, double_to_neglog(rh->insert_size_denom));
-  } else {
-    p = put_str(p, "\tZ0:i:", 6); p = put_int(p, double_to_neglog(rh->z0));
-    p = put_str(p, "\tZ1:i:", 6); p = put_int(p, double_to_neglog(rh->z1));
-    p = put_str(p, "\tZ4:i:", 6); p = put_int(p, double_to_neglog(rh->pr_top_random));
-    p = put_str(p, "\tZ5:i:", 6); p = put_int(p, double_to_neglog(rh->pr_missed_mp));
-  }
-  p = put_str(p, "\tNM:i:", 6); p = put_int(p, (cs ? rh->cs_mismatch : r.n_mismatch) + r.n_del + r.n_ins);
-  if (cs) {
-    if (qual) { p = put_str(p, "\tCQ:Z:", 6); p = put_str(p, qual, (size_t)read_len); }           // ref: output.c:724-727
-    p = put_str(p, "\tCS:Z:", 6); p = put_csfasta(p);
-    p = put_str(p, "\tCM:i:", 6); p = put_int(p, rh->cs_xover);
-    p = put_str(p, "\tXX:Z:", 6); p = put_str(p, rh->qr.data(), rh->qr.size());
-  }
-  commit(p);
-  if (C.s->P.extra_sam_fields && !cs) {
-    std::string db, qr; Finalizer F{C.s, read_len, (read_len + 7) / 8, nullptr, nullptr, nullptr, 0}; F.hgen = C.s->h_genome.data();
-    F.ls_alignment_strings(r, rh->ops, std::min(r.n_ops, ops_stride), rw, db, qr);
-    Finalizer::sam_tail(C.s->P, out, mate_seq, rh, &db, &qr);
-  } else Finalizer::sam_tail(C.s->P, out, mate_seq, rh, &rh->db, &rh->qr);
-}
-
 // K1 + K1b + K2 for one read set, nothing waits on the host: the heavy count goes to the pinned word *pin (the caller looks at it after the
 // front's event and runs the heavy tier then)
 static int stage_windows_async(gm_session* s, DevSet& D, const GmIndexDev& dv, int n, int read_len, unsigned long long* d_stats, uint32_t* pin,
@@ -442,7 +303,7 @@ struct PairCall {
 // the unpaired results in one of the session's two pinned sets (pinned: the copies run at link rate beside the kernels)
 struct PairOut {
   int base = 0, n = 0, chunk = 2048, nchunks = 0, NO = 1, ops_stride[2] = {0, 0};
-  Finalizer F[2];
+  HitScorer F[2];                                                // the mates' post_sw and unpaired selection
   GmPinVec<GmFullRes>* resP = nullptr; GmPinVec<uint8_t>* opsP = nullptr; GmPinVec<GmFullRes>* resU = nullptr; GmPinVec<uint8_t>* opsU = nullptr;
   std::vector<FHit> fhP[2]; std::vector<PPair> fpairs; std::vector<int> fcnt; std::vector<uint32_t> offP[2], cntU[2], offU[2];
 };
@@ -507,20 +368,19 @@ static uint64_t emit_pair(const PairCall& c, PairOut& b, int pr, std::string& o,
     if (i > 0 && (a[i - 1] == ':' || a[i - 1] == '/')) i--;
     qn = a; qnl = i;
   } else { qnl = (size_t)snprintf(qbuf, sizeof qbuf, "p%ld", gp); qn = qbuf; }
-  const uint32_t* rw[2]; const char* ql[2]; int ib[2];
-  for (int m = 0; m < 2; m++) { rw[m] = c.mates[m] + (size_t)gp * c.rwords[m]; ql[m] = c.quals ? c.qptr[m][gp] : nullptr; ib[m] = c.cs ? (int)c.initbp_in[m][gp] : -1; }
+  const RecCtx C{P, c.s->ix->names, c.s->ix->contig_off, c.s->h_genome.data()};
+  auto mate_view = [&](int m) { return RecRead{qn, qnl, c.mates[m] + (size_t)gp * c.rwords[m], c.len[m], c.cs ? (int)c.initbp_in[m][gp] : -1,
+                                               c.quals ? c.qptr[m][gp] : nullptr, c.qual_delta, nullptr, b.ops_stride[m]}; };
+  const RecRead R[2] = {mate_view(0), mate_view(1)};
   uint64_t k = 0;
   if (P.output_format) {
     // --shrimp-format / -P: one line (block) per mapped mate under the mate's own name, ">name" for the unmapped mate of a half-paired
     // mapping (ref: gmapper/output.c:270-296, hit_output called per mate by readpair_output :1070-1291)
-    std::string db, qr;
     auto one = [&](int m, const FHit* rh) {
-      const char* nm = qn; size_t nl = qnl;
-      if (c.named) { nm = c.nptr[m][gp]; nl = (size_t)c.nlen[m][gp]; }
-      if (!rh) { o += '>'; o.append(nm, nl); o += '\n'; return; }
-      const Finalizer& F = b.F[m];
-      if (c.cs) F.emit_shrimp(*rh, nm, nl, pr, rw[m], rh->db, rh->qr, o);
-      else { F.ls_alignment_strings(*rh->r, rh->ops, std::min(rh->r->n_ops, b.ops_stride[m]), rw[m], db, qr); F.emit_shrimp(*rh, nm, nl, pr, rw[m], db, qr, o); }
+      RecRead rd = R[m];
+      if (c.named) { rd.name = c.nptr[m][gp]; rd.name_len = (size_t)c.nlen[m][gp]; }
+      if (!rh) { o += '>'; o.append(rd.name, rd.name_len); o += '\n'; return; }
+      shrimp_record(C, rd, *rh, o);
     };
     for (int j = p.first2; j < p.last2; j++) { one(0, &HP[0][fp[j].h[0]]); one(1, &HP[1][fp[j].h[1]]); k += 2; }
     if (p.imp[0]) { one(0, p.imp[0]); one(1, p.imp[1]); k += 2; }
@@ -532,16 +392,16 @@ static uint64_t emit_pair(const PairCall& c, PairOut& b, int pr, std::string& o,
   std::string mseq[2]; const std::string* ms[2] = {nullptr, nullptr};
   if (P.sam_r2) {
     for (int m = 0; m < 2; m++) {
-      const int L = c.len[m];
-      if (c.cs) { mseq[m] += "ACGT"[ib[m] & 3]; for (int i = 0; i < L; i++) { const int cc = (rw[m][i >> 3] >> ((i & 7) * 4)) & 0xf; mseq[m] += (cc < 4) ? (char)('0' + cc) : '.'; } }
-      else for (int i = 0; i < L; i++) { const int cc = (rw[m][i >> 3] >> ((i & 7) * 4)) & 0xf; mseq[m] += (cc < 4) ? "ACGT"[cc] : (cc == 4 ? 'U' : 'N'); }
+      const int L = c.len[m]; const uint32_t* rw = R[m].words;
+      if (c.cs) { mseq[m] += "ACGT"[R[m].primer & 3]; for (int i = 0; i < L; i++) { const int cc = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; mseq[m] += (cc < 4) ? (char)('0' + cc) : '.'; } }
+      else for (int i = 0; i < L; i++) { const int cc = (rw[i >> 3] >> ((i & 7) * 4)) & 0xf; mseq[m] += (cc < 4) ? "ACGT"[cc] : (cc == 4 ? 'U' : 'N'); }
     }
     ms[0] = &mseq[1]; ms[1] = &mseq[0];                                        // (mate 1's records carry mate 2's sequence and the other way round)
   }
   // the two records of one line of the output: mate 0's mapping h0 and mate 1's h1 (null: that mate is unmapped)
   auto two = [&](const FHit* h0, const FHit* h1, bool improper) {
-    emit_pair_record(c.C, o, qn, qnl, rw[0], c.len[0], b.ops_stride[0], h0, h1, true, improper, ql[0], c.qual_delta, ib[0], ms[0]);
-    emit_pair_record(c.C, o, qn, qnl, rw[1], c.len[1], b.ops_stride[1], h1, h0, false, improper, ql[1], c.qual_delta, ib[1], ms[1]);
+    const RecMate of0{true, improper, h1, ms[0]}, of1{false, improper, h0, ms[1]};      // what mate 0's record says of mate 1, and the other way round
+    sam_record(C, R[0], h0, &of0, o); sam_record(C, R[1], h1, &of1, o);
     k += 2;
   };
   for (int j = p.first2; j < p.last2; j++) two(&HP[0][fp[j].h[0]], &HP[1][fp[j].h[1]], false);
@@ -828,11 +688,10 @@ struct PairRun : PairCall {
     b.NO = std::max(1, s->P.num_outputs);
     b.fpairs.resize((size_t)b.n * b.NO); b.fcnt.assign(b.n, 0);
     t.saved_chunks[0].resize(b.nchunks); t.saved_chunks[1].resize(b.nchunks);
-    for (int m = 0; m < 2; m++) b.F[m] = Finalizer{s, len[m], rwords[m], nullptr, nullptr, nullptr, 0};
-    if (s->P.output_format) b.F[0].hgen = b.F[1].hgen = s->h_genome.data();
+    for (int m = 0; m < 2; m++) { b.F[m] = HitScorer(); b.F[m].s = s; b.F[m].read_len = len[m]; b.F[m].read_words = rwords[m]; }
     if (cs) {   // post_sw needs the colours and the primer letter of each read (ref: sw-post.c:448-528)
       for (int m = 0; m < 2; m++) {
-        Finalizer& F = b.F[m];
+        HitScorer& F = b.F[m];
         F.reads = mates[m] + (size_t)b.base * rwords[m]; F.initbp = initbp_in[m] + b.base; F.ops_half = S[m]->ops_stride / 2; F.csk = cs_post_consts(s);
         if (quals) { F.qual_ptr = qptr[m].data() + b.base; F.qual_delta = qual_delta; }      // post_sw with the reads' QVs (ref: sw-post.c:486-491)
       }

@@ -93,7 +93,7 @@ extern "C" int gm_select_pass2(gm_session_t* s, int n_reads, const uint64_t* hit
   }
   for (int r = 0; r <= n_reads; r++) map_off[r] = 0;
   if (nh == 0) return GM_OK;
-  // hit_run_post_sw per hit (ref: mapping.c:1609-1625), as Finalizer::post_sw
+  // hit_run_post_sw per hit (ref: mapping.c:1609-1625), as HitScorer::post_sw (gm_host_finalize.inc)
   const double a = s->score_alpha, b = s->score_beta, tol = 1e-7;
   std::vector<GmSel2Item> items((size_t)nh);
   std::vector<double> posterior((size_t)nh, 0.0);

@@ -19,7 +19,7 @@
 // bits of the result's backtrace bytes -- letter in bits 4-5 of bt[t], lower-case flag in bit 6; the type nibble, sw_full_cs's crossover mark (bit 7) and
 // the letter codes stay as they were -- so that the host's cs_alignment_strings yields the final qralign directly AND the host routine can still redo
 // any result from sw_full_cs's own record.  The host does that whenever a value it is about to round (AS, MAPQ, the Z tags) lies within 1e-7 of its
-// rounding boundary (Finalizer::post_sw / finalize_read, gm_host.hip): there the last bits of exp / log would decide an output byte.
+// rounding boundary (HitScorer::post_sw / unpaired_mqv, gm_host_finalize.inc): there the last bits of exp / log would decide an output byte.
 #include "gm_common.h"
 #include "gm_internal.h"
 
