@@ -52,13 +52,15 @@ typedef struct gm_params {
   int match_score, mismatch_score;             /* ref: gmapper-defaults.h:45-46   (10, -15) */
   int a_gap_open_score, a_gap_extend_score;    /* ref: gmapper-defaults.h:47,49   (-33, -7)  gap along the genome */
   int b_gap_open_score, b_gap_extend_score;    /* ref: gmapper-defaults.h:48,50   (-33, -3)  gap along the read   */
-  double window_len;                           /* ref: gmapper-defaults.h:31  140.0 (%; negative = absolute) */
+  double window_len;                           /* ref: gmapper-defaults.h:31  140.0 (%; negative = absolute).  A window longer than pass 2 has LDS for beside the call's
+                                                  reads (3 140 columns beside 100 bases in letter space) is refused with GM_E_RANGE before anything is uploaded */
   double window_overlap;                       /* ref: gmapper-defaults.h:32   90.0 */
   double window_gen_threshold;                 /* ref: gmapper-defaults.h:62   55.0 */
   double sw_vect_threshold, sw_full_threshold; /* ref: gmapper-defaults.h:67-68; LS: vect := full (gmapper.c:2456-2458) */
   int match_mode;                              /* ref: gmapper-defaults.h:34    2 */
   int num_outputs, num_tmp_outputs;            /* ref: gmapper.h:53-55         10, 30 */
-  int anchor_width;                            /* ref: gmapper-defaults.h:36    8 */
+  int anchor_width;                            /* ref: gmapper-defaults.h:36    8; 0 .. 99, or -1: no anchor band -- the threshold band in every full alignment
+                                                  (sw-full-ls.c:175-192, sw-full-cs.c:285-301); anything else: GM_E_ARG, as the reference exits (gmapper.c:2014-2016) */
   int region_bits, region_overlap;             /* ref: gmapper-defaults.h:22-23 11, 50 */
   uint32_t list_cutoff;                        /* 0 = automatic (ref: gmapper.c:2811-2837) */
   int hash_filter_calls;                       /* ref: gmapper-defaults.h:17 true; 0 == -Z */

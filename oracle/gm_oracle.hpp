@@ -776,7 +776,13 @@ static inline void sw_full_cs(const CsParams& C, const uint32_t* genome_ls, llin
   };
   auto FROM_x = [](int mat, int dir) { return (int8_t)((dir << 2) | mat); };
   Anchor rectangle;
-  anchor_join(anchors, anchors_cnt, &rectangle); anchor_widen(&rectangle, C.anchor_width);      // :284-287
+  if (anchors != nullptr && C.anchor_width >= 0) { anchor_join(anchors, anchors_cnt, &rectangle); anchor_widen(&rectangle, C.anchor_width); }      // :285-287
+  else {                                                                 // :288-302: -a -1, or no box: the band the threshold allows
+    Anchor t[2];
+    t[0].x = 0; t[0].y = (lenb * C.match - threshscore) / C.match; t[0].length = 1; t[0].width = 1;
+    t[1].x = lena - 1; t[1].y = lenb - 1 - t[0].y; t[1].length = 1; t[1].width = 1;
+    anchor_join(t, 2, &rectangle);
+  }
   for (int j = 0; j < lena + 1; j++) init_cell(j, 1);                     // :266-268
   int score = 0, max_i = 0, max_j = 0, max_k = 0;
   for (int i = 0; i < lenb; i++) {

@@ -239,17 +239,17 @@ int gmo_sw_full_cs_xover(const uint32_t* genome_ls, int goff, int glen, const ui
 
 // ---- the same kernels with the scores as an argument (the _p family) -------------------------------------------------------------------
 // sc[] = match, mismatch, a_open, a_ext, b_open, b_ext, and in colour space crossover, indel_taboo_len behind them: penalties negative, as the reference's setups
-// take them (the P lines of tests/golden/sw_kat_scores.txt.gz / sw_kat_cs_scores.txt.gz in this order).  The colour-space vector filter's mismatch is
-// match + crossover (gmapper.c:2935).
+// take them (the P lines of tests/golden/sw_kat_scores.txt.gz / sw_kat_cs_scores.txt.gz in this order), and sc[8] = the setups' anchor_width (-1: the threshold band
+// whatever box is given).  The colour-space vector filter's mismatch is match + crossover (gmapper.c:2935).
 static Params params_of(const int* sc) {
   Params P = default_params();
   P.match_score = sc[0]; P.mismatch_score = sc[1];
-  P.a_gap_open_score = sc[2]; P.a_gap_extend_score = sc[3]; P.b_gap_open_score = sc[4]; P.b_gap_extend_score = sc[5];
+  P.a_gap_open_score = sc[2]; P.a_gap_extend_score = sc[3]; P.b_gap_open_score = sc[4]; P.b_gap_extend_score = sc[5]; P.anchor_width = sc[8];
   return P;
 }
 static CsParams cs_params_of(const int* sc) {
   CsParams C;
-  C.match = sc[0]; C.mismatch = sc[1]; C.a_go = -sc[2]; C.a_ge = -sc[3]; C.b_go = -sc[4]; C.b_ge = -sc[5]; C.xover = sc[6]; C.indel_taboo_len = sc[7];
+  C.match = sc[0]; C.mismatch = sc[1]; C.a_go = -sc[2]; C.a_ge = -sc[3]; C.b_go = -sc[4]; C.b_ge = -sc[5]; C.xover = sc[6]; C.indel_taboo_len = sc[7]; C.anchor_width = sc[8];
   return C;
 }
 // n windows in one call (OpenMP over the windows): window i is glen[i] positions from g_off[i] of `genome`, read i the row i of reads (read_words words each);

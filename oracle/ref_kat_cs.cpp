@@ -16,6 +16,11 @@
 //   P name dblen qrlen a_open a_ext b_open b_ext match mismatch crossover indel_taboo_len      (sw_full_cs_setup's arguments; the vector filter's mismatch is match + crossover)
 // and is followed by the C, S (both strands), L, X and Y (one strand each, Y on every other case) records of n cases, thresholds scaled by the set's match score
 // and the per-position crossover scores drawn in [2 * crossover, -1].
+// Second argument "anchors": default scores under the anchor widths -1 (the threshold band whatever the box), 0, 1, 9 and 99 -> tests/golden/sw_kat_cs_anchors.txt.gz.
+// Each width opens with
+//   P w<width> dblen qrlen a_open a_ext b_open b_ext match mismatch crossover indel_taboo_len anchor_width
+// and holds the S and L records (both strands) of the same n cases (the generator is re-seeded), with the boxes of oracle/ref_kat.cpp's mode "anchors": boxes that leave
+// the matrix on the left, on the right and at the bottom, boxes up to 12 wide, boxes on windows shorter than the read.
 // Otherwise scores are the binary's colour-space defaults (ref: gmapper-defaults.h:52-58): match 10, mismatch -24, crossover -20,
 // gaps -33/-7 (reference) -33/-3 (query); the vector filter's mismatch is match + crossover (ref: gmapper.c:2935).
 #include <cstdio>
@@ -50,16 +55,22 @@ int main(int argc, char** argv) {
   const bool xover = argc > 2 && !strcmp(argv[2], "xover");     // "X" / "Y" records only
   const bool rna = argc > 2 && !strcmp(argv[2], "rna");         // C, S and L records on an RNA genome with is_rna = true
   const bool score_mode = argc > 2 && !strcmp(argv[2], "scores");   // "P" lines, and C, S, L, X and Y records under each of SCORE_SETS
+  const bool anchor_mode = argc > 2 && !strcmp(argv[2], "anchors");   // "P" lines, and S and L records under each of ANCHOR_WIDTHS
+  static const int ANCHOR_WIDTHS[] = {-1, 0, 1, 9, 99};
   std::mt19937_64 rng(20260202), xrng(20261005);
-  const int n_sets = score_mode ? (int)(sizeof SCORE_SETS / sizeof SCORE_SETS[0]) : 1;
+  const int n_sets = score_mode ? (int)(sizeof SCORE_SETS / sizeof SCORE_SETS[0]) : anchor_mode ? (int)(sizeof ANCHOR_WIDTHS / sizeof ANCHOR_WIDTHS[0]) : 1;
   for (int si = 0; si < n_sets; si++) {
   const ScoreSet& S = score_mode ? SCORE_SETS[si] : DEFAULT_SET;
+  const int width = anchor_mode ? ANCHOR_WIDTHS[si] : 8;
+  if (anchor_mode) rng.seed(20260202);                // the same cases under every width
   sw_vector_setup(1400, 1000, S.a_go, S.a_ge, S.b_go, S.b_ge, S.match, S.match + S.xover, 1, true);
-  sw_full_cs_setup(1400, 1000, S.a_go, S.a_ge, S.b_go, S.b_ge, S.match, S.mismatch, S.xover, true, 8, S.taboo);
+  sw_full_cs_setup(1400, 1000, S.a_go, S.a_ge, S.b_go, S.b_ge, S.match, S.mismatch, S.xover, true, width, S.taboo);
+  if (anchor_mode) printf("P w%d 1400 1000 %d %d %d %d %d %d %d %d %d\n", width, S.a_go, S.a_ge, S.b_go, S.b_ge, S.match, S.mismatch, S.xover, S.taboo, width);
   if (score_mode) printf("P %s 1400 1000 %d %d %d %d %d %d %d %d\n", S.name, S.a_go, S.a_ge, S.b_go, S.b_ge, S.match, S.mismatch, S.xover, S.taboo);
   for (int t = 0; t < n; t++) {
     int rlen = 20 + rng() % 56;                        // 20..75 colours
     int kind = rng() % 8;
+    if (anchor_mode && t % 8 == 6) kind = 0;             // a window shorter than the read, together with a box
     int glen = (kind == 0) ? (int)(rlen - rng() % 6) : (int)(rlen * 1.4);
     if (glen < 8) glen = 8;
     int goff = 1 + rng() % 23;
@@ -91,10 +102,20 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < g.size(); i++) { put(gl, (int)i, g[i]); put(gc, (int)i, lstocs(i ? g[i - 1] : BASE_T, g[i], rna)); }   // ref: fasta.c:586-607
     for (int i = 0; i < rlen; i++) put(rb, i, rc[i]);
     int sv = sw_vector(gc.data(), goff, glen, rb.data(), rlen, gl.data(), initbp, rna);
-    if (!local && !xover) { printf("C %d %d %d %d ", goff, glen, rlen, initbp); dump(gc); printf(" "); dump(gl); printf(" "); dump(rb); printf(" %d\n", sv); }
+    if (!local && !xover && !anchor_mode) { printf("C %d %d %d %d ", goff, glen, rlen, initbp); dump(gc); printf(" "); dump(gl); printf(" "); dump(rb); printf(" %d\n", sv); }
     struct anchor a; memset(&a, 0, sizeof a);
     a.x = (start - goff) + (int)(rng() % 7) - 3; a.y = 0; a.length = 10 + rng() % (rlen > 16 ? rlen - 10 : 6); a.width = 1 + rng() % 4; a.weight = 2;
     if (rng() % 4 == 0) { a.y = rng() % 10; a.x += a.y; }
+    if (anchor_mode) {                                   // the boxes of oracle/ref_kat.cpp's mode "anchors"; d: the diagonal the read was copied from
+      const int d = start - goff, half = a.length / 2;
+      switch (t % 8) {
+        case 2: a.x = -(1 + (int)(rng() % 5)); a.y = 0; a.width = 6 + rng() % 7; break;                                        // x < 0
+        case 3: a.y = glen - d - half; if (a.y > rlen - 1) a.y = rlen - 1; if (a.y < 0) a.y = 0; a.x = d + a.y; break;          // x + length > glen
+        case 4: a.y = rlen - half; if (a.y < 0) a.y = 0; a.x = d + a.y; break;                                                  // y + length > rlen
+        case 5: a.width = (t % 16 == 5) ? 12 : 5 + rng() % 8; break;                                                            // up to 12 wide
+        default: break;
+      }
+    }
     int thresh = (rng() % 3 == 0) ? (int)(0.6 * rlen * S.match) : (int)(0.3 * rlen * S.match);
     if (xover || score_mode) {
       // per-position scores as the read loop derives them from quality values: most positions good (near the global -20 .. -40), some poor (-1 .. -8)
@@ -123,8 +144,8 @@ int main(int argc, char** argv) {
       }
       if (!score_mode) continue;
     }
-    for (int md = 0; md < (rna || score_mode ? 2 : 1); md++) for (int rv = 0; rv < 2; rv++) {
-      const bool loc = rna || score_mode ? md == 1 : local;
+    for (int md = 0; md < (rna || score_mode || anchor_mode ? 2 : 1); md++) for (int rv = 0; rv < 2; rv++) {
+      const bool loc = rna || score_mode || anchor_mode ? md == 1 : local;
       if (score_mode && loc && rv != (t & 1)) continue;                      // L records: one strand a case
       struct sw_full_results sfr; memset(&sfr, 0, sizeof sfr);
       sw_full_cs(gl.data(), goff, glen, rb.data(), rlen, initbp, thresh, &sfr, rv != 0, rna, &a, 1, loc ? 1 : 0, NULL);

@@ -118,7 +118,7 @@ struct GmScoreDev {
 struct GmHit {
   uint32_t g_off;        // contig-relative window start on the + strand (g_off_pos_strand)
   int32_t  ax, ay;       // anchor box relative to the window (ref: struct anchor x,y)
-  int32_t  alen, awidth; // anchor length / width
+  int32_t  alen, awidth; // anchor length / width.  With anchor_width < 0 pass 2 overwrites the box of every hit it aligns with its threshold band (gm_launch_pass2)
   int32_t  score_window_gen;
   int32_t  score_vector; // -1 = not scored
   int32_t  pct_score_vector;

@@ -561,6 +561,12 @@ static bool gm_fixed_lines(const char* text, size_t n, size_t want) {
   return ok;
 }
 
+// -a: 0 .. 99, or -1 for no anchor band at all -- the threshold band in every full alignment (gm_sw.hip threshold_box); the reference exits on anything else (gmapper.c:2014-2016)
+static int gm_check_anchor_width(const char* who, int anchor_width) {
+  if (anchor_width >= -1 && anchor_width <= 99) return GM_OK;
+  gm_set_error("%s: anchor_width %d outside [-1, 99] (ref: gmapper.c:2014-2016)", who, anchor_width); return GM_E_ARG;
+}
+
 static int window_len_of(const gm_params_t& P, int read_len) {   // ref: gmapper.c:530
   double w = P.window_len < 0 ? -P.window_len : read_len * (P.window_len / 100.0);
   return (int)(uint16_t)w;
@@ -676,6 +682,7 @@ extern "C" int gm_session_create(gm_session_t** out, const gm_index_t* ix, const
   // (the parameters are checked before anything is allocated; every failure further down goes through gm_session_free, which releases what exists by then)
   if (s->P.strand_only < 0 || s->P.strand_only > 2) { delete s; gm_set_error("strand_only %d: 0 (both), 1 (-F) or 2 (-C)", params ? params->strand_only : 0); return GM_E_ARG; }
   if (s->P.match_mode != 1 && s->P.match_mode != 2) { delete s; gm_set_error("match_mode %d: 1 or 2 (ref: gmapper.c:2624; 3 and 4 are paired-mode settings with mate-pair region counts)", s->P.match_mode); return GM_E_ARG; }
+  if (gm_check_anchor_width("gm_session_create", s->P.anchor_width)) { delete s; return GM_E_ARG; }
   if (s->P.ungapped && !s->P.local_alignment) { delete s; gm_set_error("ungapped mode needs local alignment (ref: gmapper.c:2330-2333)"); return GM_E_ARG; }
   if ((s->P.colour_space != 0) != (ix->params.colour_space != 0)) { delete s; gm_set_error("session and index disagree on colour space"); return GM_E_ARG; }
   s->sc = make_score(s->P);
@@ -1084,6 +1091,10 @@ static int ensure_host_genome(gm_session* s) {
 }
 static int check_read_len(const gm_session* s, int read_len) {
   if (read_len > s->P.longest_read_len || read_len >= 32768 / std::max(1, s->P.match_score)) { gm_set_error("read length %d out of range (ref: sw-vector.c:393-398)", read_len); return GM_E_RANGE; }
+  // the window of these reads (window_len_of, before its cut to 16 bits) against what pass 2 can take: nothing is uploaded for a window beyond it
+  const double w = s->P.window_len < 0 ? -s->P.window_len : read_len * (s->P.window_len / 100.0);
+  const int w_max = gm_pass2_max_window(s->P.colour_space ? 1 : 0, s->P.local_alignment ? 1 : 0, read_len);
+  if (w > (double)w_max) { gm_set_error("window length %.0f for reads of %d: beyond the %d columns pass 2 has LDS for", w, read_len, w_max); return GM_E_RANGE; }
   return GM_OK;
 }
 

@@ -128,6 +128,7 @@ static const char LSTRANS[17] = "ACGTUMRWSYKVHDBN";   // base_translate, ref: co
 extern "C" int sw_full_ls_setup(int dblen, int qrlen, int a_gap_open, int a_gap_ext, int b_gap_open, int b_gap_ext,
                                 int match, int mismatch, bool reset_stats, int anchor_width) {
   if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
+  if (const int rc = gm_check_anchor_width("sw_full_ls_setup", anchor_width)) return rc;
   gm_params_t P; gm_params_default(&P);
   P.match_score = match; P.mismatch_score = mismatch; P.a_gap_open_score = a_gap_open; P.a_gap_extend_score = a_gap_ext;
   P.b_gap_open_score = b_gap_open; P.b_gap_extend_score = b_gap_ext; P.anchor_width = anchor_width;
@@ -201,6 +202,7 @@ extern "C" int sw_full_cs_setup(int dblen, int qrlen, int a_gap_open, int a_gap_
                                 int match, int mismatch, int global_xover_penalty, bool reset_stats, int anchor_width, int indel_taboo_len) {
   if (reset_stats) { g_sc.invocs = g_sc.cells = 0; g_sc.secs = 0; }
   if (gm_device_count() < 1) { gm_set_error("no HIP device"); return GM_E_NODEVICE; }
+  if (const int rc = gm_check_anchor_width("sw_full_cs_setup", anchor_width)) return rc;
   const int p[9] = {match, mismatch, global_xover_penalty, -a_gap_open, -a_gap_ext, -b_gap_open, -b_gap_ext, anchor_width, indel_taboo_len};
   memcpy(g_sc.p, p, sizeof p); g_sc.dblen = dblen; g_sc.qrlen = qrlen; g_sc.init = true;
   return 0;
@@ -219,9 +221,9 @@ extern "C" void sw_full_cs(uint32_t* genome_ls, int goff, int glen, uint32_t* re
   auto fail = [&](const char* why) { gm_set_error("sw_full_cs: %s", why); fprintf(stderr, "gmapper_hip: sw_full_cs refused: %s\n", why); sfr->score = 0; sfr->dbalign = nullptr; sfr->qralign = nullptr; };
   // ... and where the batch body or a launcher has refused, its reason stands as it is ("sw_full_cs: item 0 refused: ...", or what the failing call left)
   auto refused = [&] { fprintf(stderr, "gmapper_hip: %s\n", gm_last_error()); sfr->score = 0; sfr->dbalign = nullptr; sfr->qralign = nullptr; };
-  if (anchors == nullptr || anchors_cnt != 1 || glen > g_sc.dblen || rlen > g_sc.qrlen || glen < 1 || rlen < 1 ||
-      initbp < 0 || initbp > 3 || g_sc.p[7] < 0) {
-    fail("only one anchor box (gmapper's call, ref: mapping.c:375-379) is implemented"); return;
+  if ((anchors == nullptr ? g_sc.p[7] >= 0 : anchors_cnt != 1) || glen > g_sc.dblen || rlen > g_sc.qrlen || glen < 1 || rlen < 1 ||
+      initbp < 0 || initbp > 3) {
+    fail("only one anchor box (gmapper's call, ref: mapping.c:375-379) is implemented -- or none under anchor_width -1, the threshold band"); return;
   }
   // crossover_score: one score per read position (from the QVs, ref: gmapper.c:532-544 -- clamped there to [2 * global, -1]); the kernels keep a row of them in 8 bits,
   // and the batch body refuses a score outside them as this seam always has (a window that does not fit LDS likewise: same formula, same limit)

@@ -111,7 +111,7 @@ static int sw_full_batch_impl(bool colour, int n, const uint32_t* genome, uint64
     if (glen[i] > dblen || rlen[i] > qrlen) { refuse(GM_E_ARG, "window / read longer than the setup sizes"); continue; }
     const bool has_anchor = anchors && (seam || anchors[i].length > 0);
     if (colour) {
-      if (!has_anchor || g_sc.p[7] < 0) { refuse(GM_E_ARG, "colour space needs one anchor box (gmapper's call, ref: mapping.c:375-379)"); continue; }
+      if (!has_anchor && g_sc.p[7] >= 0) { refuse(GM_E_ARG, "colour space needs one anchor box (gmapper's call, ref: mapping.c:375-379)"); continue; }      // (anchor_width -1: the threshold band, box or none)
       if (initbp[i] > 3) { refuse(GM_E_ARG, "initbp outside 0..3"); continue; }
       if (gm_sw_full_cs_batch_lds(glen[i], call_max_r) > GM_SWF_LDS_LIMIT) { refuse(GM_E_ARG, "the window does not fit LDS (48 bytes a column) beside the call's longest read"); continue; }
       if (xover) {

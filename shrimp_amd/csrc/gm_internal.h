@@ -196,12 +196,20 @@ int gm_launch_select(const GmScoreDev& sc, int n_reads, int read_len, const GmHi
                      const uint32_t* d_hit_cnt, int hcap, int32_t* d_sel, uint32_t* d_sel_cnt, uint32_t* d_sel_off,
                      uint32_t* d_work, uint32_t* d_n_work, hipStream_t stream, const uint8_t* d_saved = nullptr);
 int gm_launch_build_work(int n_reads, const uint32_t* d_sel_cnt, uint32_t* d_sel_off, uint32_t* d_work, uint32_t* d_n_work, hipStream_t stream);
+// anchor_width < 0 (no anchor band): both pass-2 launchers first OVERWRITE the anchor boxes of the selected hits in d_hits with the band the launch's threshold allows
+// (k_threshold_box_hits, gm_sw.hip) -- after such a launch d_hits no longer holds what window generation found for them.  Nothing reads the boxes behind pass 2.
 int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                     int window_len, GmHit* d_hits, const uint16_t* d_perm, int hcap, const int32_t* d_sel, const uint32_t* d_sel_cnt,
                     const uint32_t* d_work, const uint32_t* d_n_work, GmFullRes* d_res, uint8_t* d_ops, int ops_stride,
                     uint8_t* d_back, size_t back_stride, int grid, unsigned long long* d_stats, hipStream_t stream,
                     const int32_t* d_sel_sidx = nullptr, int input_strand = 0, int write_back = 0,
                     uint32_t* d_order = nullptr, uint32_t* d_cls_cnt = nullptr);        // the work items listed by kind (as many words as d_work), four counter words; without them: the one-window kernel
+
+// The longest window pass 2 takes beside reads of read_len: what the kernel gm_launch_pass2 / gm_launch_pass2_cs choose fits into GM_SWF_LDS_LIMIT, and no more than the
+// 16 bits of GmHit.w_len.  gm_map_reads / gm_map_pairs refuse a longer window (GM_E_RANGE) before they upload anything.
+int gm_pass2_max_window(int colour, int local, int read_len);
+size_t gm_pass2_g4_lds(int ng, int read_len, int window_len);      // letter space, ng = 4 / 8 windows a wave
+size_t gm_pass2_cs_lds(int ng, int read_len, int window_len);      // colour space, ng = 1 / 4 / 8
 
 // colour-space pass 2 (sw_full_cs per selected window); ops_stride bytes per result: backtrace bytes, then (genome << 4 | read) codes
 // colour-space post_sw on the device (gm_post.hip): constants = CsPostConsts of gm_host.hip (logs taken on the host), one record per pass-2 result
@@ -224,7 +232,7 @@ int gm_launch_post_sw_batch(const GmCsPostDev& K, int first, int n, int threads,
                             const uint32_t* d_reads, int read_words, int qv_stride, int is_rna, GmPostRes* d_post, uint8_t* d_qralign, uint8_t* d_quals,
                             double* d_fw, uint32_t* d_info, hipStream_t stream, int ix = 0);      // ix: the items carry gbase / flags (gm_post_sw_batch_ix)
 int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs_params9, const uint32_t* d_reads, const uint8_t* d_initbp, int n_reads,
-                       int read_len, int read_words, int window_len, const GmHit* d_hits, int hcap, const int32_t* d_sel, const uint32_t* d_work,
+                       int read_len, int read_words, int window_len, GmHit* d_hits, int hcap, const int32_t* d_sel, const uint32_t* d_work,
                        const uint32_t* d_n_work, GmFullRes* d_res, uint8_t* d_ops, int ops_stride, uint32_t* d_back, size_t back_words, int grid,
                        unsigned long long* d_stats, hipStream_t stream, const int8_t* d_xover = nullptr,   // d_xover[n_reads][read_len]: per-position crossover scores (reads with QVs)
                        const int32_t* d_sel_sidx = nullptr,                                                // paired mode: sort index of every selected window
@@ -285,7 +293,7 @@ static const size_t GM_SWF_LDS_LIMIT = 160 * 1024;      // LDS of a CU: what one
 size_t gm_sw_full_batch_lds(int max_g, int max_r);
 size_t gm_sw_full_cs_batch_lds(int max_g, int max_r);
 // items[first .. first + n) by `grid` waves; wave b owns back-pointer scratch d_back + b * back_stride (bytes; colour space: uint32 words)
-int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
+int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
                             int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream, int ix = 0,
                             int by_row = 0);      // by_row (with ix): the by-row form of GmFullItem
 
@@ -328,7 +336,7 @@ int gm_launch_p2_records_cs(int n, const gm_pass1_hit_t* d_hits, const GmFullOut
 int gm_launch_p2_post_items(int n, const gm_pass1_hit_t* d_hits, const gm_sw_full_rec_t* d_recs, const unsigned long long* d_qoff, int read_base, int read_len,
                             const uint32_t* d_contig_off, const uint8_t* d_contig_rna, const uint8_t* d_initbp_rows, GmPostItem* d_items, hipStream_t stream);
 int gm_launch_p2_move(int n_segs, const GmP2Seg* d_segs, const uint8_t* d_src, uint8_t* d_dst, hipStream_t stream);
-int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
+int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
                                int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
                                uint8_t* d_ops, int local, hipStream_t stream, int ix = 0,      // ix: the items carry strand / RNA bits (gm_sw_full_cs_batch_ix)
                                int by_row = 0);      // by_row (with ix): the colour-space by-row form of GmFullItem

@@ -715,6 +715,41 @@ __device__ __forceinline__ void anchor_band(long long ax, long long ay, int alen
   *rx -= anchor_width / 2; *ry += anchor_width / 2; *rw += anchor_width;
 }
 
+// anchor_width < 0 (-a -1, "disabled", ref: gmapper.c:2014-2016): the reference takes the threshold band for every full alignment, whatever box it was handed
+// (sw-full-ls.c:175-192, sw-full-cs.c:285-301).  The alignment kernels are left as they are: at anchor_width 0 anchor_band hands its box through unchanged (2 ax is even,
+// so no corner is rounded, and nothing is widened), so the launchers below put the threshold band itself into the box of every window they are about to align and run
+// their kernels at width 0 -- one small launch, only when the width is negative.  For a hit the pass-2 kernels turn (p2_reverse_hit, `turned`) the box is stored turned:
+// the turn is its own inverse, so they arrive at the band.  The band is a function of the window, the read and the threshold alone: a hit that goes through pass 2 twice
+// (paired mode: the pairs at half the threshold, then the rescue) gets the band of each launch.
+__device__ __forceinline__ void threshold_box(int glen, int rlen, int match, int thresh, bool turned, long long* ax, long long* ay, int* alen, int* awidth) {
+  threshold_band(glen, rlen, match, thresh, ax, ay, alen, awidth);
+  if (turned) { *ax = -*ax + (glen - 1) - (*alen - 1) - (*awidth - 1); *ay = -*ay + (rlen - 1) - (*alen - 1) + (*awidth - 1); }      // anchor_reverse, ref: anchors.h:30-34
+}
+__global__ void __launch_bounds__(256) k_threshold_box_items(int first, int n, GmFullItem* __restrict__ items, int match) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  GmFullItem* it = items + first + k;
+  long long ax, ay; int alen, awidth;
+  threshold_box(it->glen, it->rlen, match, it->thresh, false, &ax, &ay, &alen, &awidth);
+  it->ax = ax; it->ay = ay; it->alen = alen; it->awidth = awidth; it->flags |= 1;
+}
+// ... and the same for the selected hits of a pass-2 work list; input_strand: the strand label the read is aligned on (colour space: cs_flip), a hit of the other one is turned
+__global__ void __launch_bounds__(256) k_threshold_box_hits(GmScoreDev sc, int read_len, GmHit* __restrict__ hits, int hcap, const int32_t* __restrict__ sel,
+                                                            const uint32_t* __restrict__ work, const uint32_t* __restrict__ n_work_p, int input_strand) {
+  const uint32_t n_work = *n_work_p;
+  for (uint32_t wi = blockIdx.x * 256u + threadIdx.x; wi < n_work; wi += gridDim.x * 256u) {
+    const uint32_t wk = work[wi];
+    const int rd = (int)(wk >> 6), id = sel[(size_t)rd * SEL_MAX + (wk & 63)];
+    const int st = id >> 16, hi = id & 0xFFFF;
+    GmHit* h = hits + ((size_t)rd * 2 + st) * hcap + hi;
+    const int w_len = h->w_len;
+    const int thresh = thr_of(sc.full_thr_frac, sc.full_abs, (read_len < w_len ? read_len : w_len) * sc.match);
+    long long ax, ay; int alen, awidth;
+    threshold_box(w_len, read_len, sc.match, thresh, st != input_strand, &ax, &ay, &alen, &awidth);
+    h->ax = (int32_t)ax; h->ay = (int32_t)ay; h->alen = alen; h->awidth = awidth;
+  }
+}
+
 // do_backtrace, ref: sw-full-ls.c:413-516 -- one lane walks from the cell full_sw_wave / full_sw_g4 returned (score > 0); the ops ('M' / 'I' / 'D') are emitted reversed, then
 // flipped; no counts all of them, ops[] holds the first ops_cap.  back: the walker's scratch, `stride` bytes a read row, read by agent-scope atomic loads.  BANDED: a cell
 // outside the band box is not believed, whatever byte lies there (see the comment above k_sw_full_batch; the pass-2 kernels ask in local mode only, where it is needed).
@@ -1212,9 +1247,14 @@ k_sw_full_batch(GmScoreDev sc, int first, int n, const GmFullItem* __restrict__ 
 }
 
 size_t gm_sw_full_batch_lds(int max_g, int max_r) { return ((max_r + 15) & ~15) + ((max_g + 15) & ~15) + (size_t)max_g * 12 + 64; }
-int gm_launch_sw_full_batch(const GmScoreDev& sc, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
+int gm_launch_sw_full_batch(const GmScoreDev& sc_in, int first, int n, int grid, GmFullItem* d_items, const uint32_t* d_genome, const uint32_t* d_reads, int read_words,
                             int max_g, int max_r, uint8_t* d_back, size_t back_stride, GmFullOut* d_out, uint8_t* d_ops, int local, hipStream_t stream, int ix, int by_row) {
   if (n == 0) return GM_OK;
+  GmScoreDev sc = sc_in;
+  if (sc.anchor_width < 0) {                                   // -a -1: the threshold band as every item's box (threshold_box)
+    hipLaunchKernelGGL(k_threshold_box_items, dim3((n + 255) / 256), dim3(256), 0, stream, first, n, d_items, sc.match);
+    sc.anchor_width = 0;
+  }
   const size_t lds = gm_sw_full_batch_lds(max_g, max_r);
   if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("sw_full_ls batch: window of %d does not fit LDS", max_g); return GM_E_ARG; }
   if (by_row && !ix) { gm_set_error("sw_full_ls batch: the by-row items are items on the index"); return GM_E_ARG; }
@@ -1277,12 +1317,22 @@ int gm_launch_build_work(int n_reads, const uint32_t* d_sel_cnt, uint32_t* d_sel
   return GM_OK;
 }
 
-int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
+// LDS of the letter-space pass-2 kernels of NG windows a wave (k_pass2_g4: NG = 4 with int carry rows, 8 with int16_t ones): reads, windows, three carry values a column
+size_t gm_pass2_g4_lds(int ng, int read_len, int window_len) {
+  const size_t r16 = (size_t)((read_len + 15) & ~15), w16 = (size_t)((window_len + 15) & ~15);
+  return ng * r16 + ng * w16 + ng * (size_t)window_len * 3 * (ng == 8 ? sizeof(int16_t) : sizeof(int)) + 64;
+}
+int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc_in, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                     int window_len, GmHit* d_hits, const uint16_t* d_perm, int hcap, const int32_t* d_sel, const uint32_t* d_sel_cnt,
                     const uint32_t* d_work, const uint32_t* d_n_work, GmFullRes* d_res, uint8_t* d_ops, int ops_stride,
                     uint8_t* d_back, size_t back_stride, int grid, unsigned long long* d_stats, hipStream_t stream,
                     const int32_t* d_sel_sidx, int input_strand, int write_back, uint32_t* d_order, uint32_t* d_cls_cnt) {
   if (n_reads == 0) return GM_OK;
+  GmScoreDev sc = sc_in;
+  if (sc.anchor_width < 0) {                                   // -a -1: the threshold band as every selected hit's box (threshold_box)
+    hipLaunchKernelGGL(k_threshold_box_hits, dim3(512), dim3(256), 0, stream, sc, read_len, d_hits, hcap, d_sel, d_work, d_n_work, input_strand);
+    sc.anchor_width = 0;
+  }
   const int p2_ablate = gm_tune("GM_P2_ABLATE") ? atoi(gm_tune("GM_P2_ABLATE")) : 0;
   const size_t lds = gm_sw_full_batch_lds(window_len, read_len);
 #define GM_P2_LAUNCH(LOC) hipLaunchKernelGGL((k_pass2<LOC>), dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, d_reads, n_reads, read_len, read_words, \
@@ -1295,19 +1345,18 @@ int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* 
   // a cell) takes eight.
   const bool g4 = !(gm_tune("GM_P2_G4") && atoi(gm_tune("GM_P2_G4")) == 0) && grid >= 8 && d_order && d_cls_cnt;
   if (g4) {
-    const size_t r16 = (size_t)((read_len + 15) & ~15), w16 = (size_t)((window_len + 15) & ~15);
     // no score on a path through the matrix lies further from 0 than `reach`: a path has at most read_len + window_len moves, and a move changes the score by a match, a
     // mismatch or a gap's opening + extension at most
     const int big = std::max(std::max(std::abs(sc.match), std::abs(sc.mismatch)), std::max(std::max(std::abs(sc.a_go) + std::abs(sc.a_ge), std::abs(sc.b_go) + std::abs(sc.b_ge)), 1));
     const long long reach = (long long)(read_len + window_len) * big;
-    const size_t lds8 = 8 * r16 + 8 * w16 + 8 * (size_t)window_len * 3 * sizeof(int16_t) + 64;
-    const size_t lds4 = 4 * r16 + 4 * w16 + 4 * (size_t)window_len * 3 * sizeof(int) + 64;
+    const size_t lds8 = gm_pass2_g4_lds(8, read_len, window_len), lds4 = gm_pass2_g4_lds(4, read_len, window_len);
 #ifdef GM_TUNING
     const bool g8 = reach < 16000 && lds8 <= 64 * 1024 && gm_tune("GM_P2_G") && atoi(gm_tune("GM_P2_G")) == 8;
 #else
     const bool g8 = false; (void)reach; (void)lds8;
 #endif
     const size_t ldsn = g8 ? lds8 : lds4;
+    if (ldsn > GM_SWF_LDS_LIMIT) { gm_set_error("pass 2: window of %d does not fit LDS (gm_pass2_max_window)", window_len); return GM_E_RANGE; }      // (the mapping calls refuse it before they upload anything)
     GM_HIP(gm_lds_at_least((const void*)k_pass2_g4<16, int, false>, ldsn)); GM_HIP(gm_lds_at_least((const void*)k_pass2_g4<16, int, true>, ldsn));
 #ifdef GM_TUNING
     GM_HIP(gm_lds_at_least((const void*)k_pass2_g4<8, int16_t, false>, ldsn)); GM_HIP(gm_lds_at_least((const void*)k_pass2_g4<8, int16_t, true>, ldsn));
@@ -2027,15 +2076,25 @@ k_pass2_cs_g4(GmIndexDev ix, GmScoreDev sc, GmCsDev P, const uint32_t* __restric
   if (lane == 0) { GS_ADD(stats, GS_FULL_CALLS, fcalls); GS_ADD(stats, GS_FULL_CELLS, fcells); }
 }
 
+// LDS of the colour-space pass-2 kernels: one window a wave (ng = 1, k_pass2_cs), or NG (k_pass2_cs_g4: 4 with int carry rows, 8 with int16_t ones) -- the colours and the
+// four translations of a read, the window, twelve carry values a column
+size_t gm_pass2_cs_lds(int ng, int read_len, int window_len) {
+  const size_t q16 = (size_t)((read_len + 15) & ~15), w16 = (size_t)((window_len + 15) & ~15);
+  return ng * 5 * q16 + ng * w16 + ng * (size_t)window_len * 12 * (ng == 8 ? sizeof(int16_t) : sizeof(int)) + 64;
+}
 int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs_params9, const uint32_t* d_reads, const uint8_t* d_initbp, int n_reads,
-                       int read_len, int read_words, int window_len, const GmHit* d_hits, int hcap, const int32_t* d_sel, const uint32_t* d_work,
+                       int read_len, int read_words, int window_len, GmHit* d_hits, int hcap, const int32_t* d_sel, const uint32_t* d_work,
                        const uint32_t* d_n_work, GmFullRes* d_res, uint8_t* d_ops, int ops_stride, uint32_t* d_back, size_t back_words, int grid,
                        unsigned long long* d_stats, hipStream_t stream, const int8_t* d_xover, const int32_t* d_sel_sidx, uint32_t* d_order, uint32_t* d_cls_cnt) {
   if (n_reads == 0) return GM_OK;
   GmCsDev P; P.match = cs_params9[0]; P.mismatch = cs_params9[1]; P.xover = cs_params9[2]; P.a_go = cs_params9[3]; P.a_ge = cs_params9[4];
   P.b_go = cs_params9[5]; P.b_ge = cs_params9[6]; P.anchor_width = cs_params9[7]; P.taboo = cs_params9[8];
-  const size_t lds = 5 * (size_t)((read_len + 15) & ~15) + ((window_len + 15) & ~15) + (size_t)window_len * 48 + 64;
-  if (lds > 160 * 1024) { gm_set_error("colour-space pass 2: window of %d does not fit LDS", window_len); return GM_E_ARG; }
+  if (P.anchor_width < 0) {                                    // -a -1: the threshold band as every selected hit's box (threshold_box)
+    hipLaunchKernelGGL(k_threshold_box_hits, dim3(512), dim3(256), 0, stream, sc, read_len, d_hits, hcap, d_sel, d_work, d_n_work, ix.cs_flip);
+    P.anchor_width = 0;
+  }
+  const size_t lds = gm_pass2_cs_lds(1, read_len, window_len);
+  if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("colour-space pass 2: window of %d does not fit LDS", window_len); return GM_E_ARG; }
   GM_HIP(gm_lds_at_least((const void*)k_pass2_cs<false>, lds)); GM_HIP(gm_lds_at_least((const void*)k_pass2_cs<true>, lds));
   // Four or eight windows per wave (k_pass2_cs_g4) unless GM_P2_G4=0 asks for the one-window kernel; a wave owns that many consecutive back-pointer scratches.
   // Eight (groups of 8 lanes: a stripe of 8 rows takes band width + 14 steps, against band width + 30 for 16 rows -- the chain north, west, north, ... through a band is two steps a
@@ -2043,18 +2102,16 @@ int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs
   // Local alignment (sc.local, ref: sw-full-cs.c:199-203,439-552) exists in these kernels only.
   const bool want_g4 = !(gm_tune("GM_P2_G4") && atoi(gm_tune("GM_P2_G4")) == 0) && grid >= 8;
   if (want_g4 || sc.local) {
-    const size_t q16 = (size_t)((read_len + 15) & ~15), w16 = (size_t)((window_len + 15) & ~15);
     // no score on a path through the matrix lies further from 0 than `reach`: a path has at most read_len + window_len moves, and a move changes the score by a match, a
     // mismatch or a gap's opening + extension, and by a crossover on top of any of the three (sw_full_cs charges one on the gap transitions too; per-position crossover
     // scores lie in [2 x crossover_score, -1], ref: gmapper.c:532-544; an int8 row), at most
     const int xmax = d_xover ? std::min(127, 2 * std::abs(P.xover)) : std::abs(P.xover);
     const int big = std::max(std::max(std::abs(P.match), std::abs(P.mismatch)), std::max(std::max(std::abs(P.a_go) + std::abs(P.a_ge), std::abs(P.b_go) + std::abs(P.b_ge)), 1)) + xmax;
     const long long reach = (long long)(read_len + window_len) * big;
-    const size_t lds8 = 8 * 5 * q16 + 8 * w16 + 8 * (size_t)window_len * 12 * sizeof(int16_t) + 64;
-    const size_t lds4 = 4 * 5 * q16 + 4 * w16 + 4 * (size_t)window_len * 12 * sizeof(int) + 64;
+    const size_t lds8 = gm_pass2_cs_lds(8, read_len, window_len), lds4 = gm_pass2_cs_lds(4, read_len, window_len);
     const bool g8 = reach < 16000 && lds8 <= 64 * 1024 && !(gm_tune("GM_P2_G") && atoi(gm_tune("GM_P2_G")) == 16);
     const size_t ldsn = g8 ? lds8 : lds4;
-    if (ldsn <= 160 * 1024 && grid >= 8) {
+    if (ldsn <= GM_SWF_LDS_LIMIT && grid >= 8) {
       for (const void* k : {(const void*)k_pass2_cs_g4<16, int, false, false>, (const void*)k_pass2_cs_g4<16, int, true, false>, (const void*)k_pass2_cs_g4<16, int, false, true>,
                             (const void*)k_pass2_cs_g4<16, int, true, true>, (const void*)k_pass2_cs_g4<8, int16_t, false, false>, (const void*)k_pass2_cs_g4<8, int16_t, true, false>,
                             (const void*)k_pass2_cs_g4<8, int16_t, false, true>, (const void*)k_pass2_cs_g4<8, int16_t, true, true>})
@@ -2082,6 +2139,16 @@ int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs
                      d_work, d_n_work, d_res, d_ops, ops_stride, d_back, back_words, window_len, d_stats, d_xover, d_sel_sidx);
   GM_HIP(hipGetLastError());
   return GM_OK;
+}
+
+// (by the launchers' own size functions.  Letter space: the four-window kernel, which every mapping call gets; colour space: the one-window kernel, which global alignment
+// falls back to when the four-window one does not fit, and the four-window one with int carry rows, which local alignment needs -- the eight-window shape, taken only
+// within 64 KB, fits wherever that one does)
+int gm_pass2_max_window(int colour, int local, int read_len) {
+  auto lds = [&](int W) -> size_t { return !colour ? gm_pass2_g4_lds(4, read_len, W) : gm_pass2_cs_lds(local ? 4 : 1, read_len, W); };
+  int lo = 0, hi = 65535;
+  while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (lds(mid) <= GM_SWF_LDS_LIMIT) lo = mid; else hi = mid - 1; }
+  return lo;
 }
 
 // S1's ungapped filter at the seam (ref: common/sw-gapless.c:57-117): call i scores the diagonal of its own genome bitfield (window i starts at word
@@ -2222,13 +2289,17 @@ k_sw_full_cs_batch(GmCsDev P, int first, int n, const GmFullItem* __restrict__ i
 }
 
 size_t gm_sw_full_cs_batch_lds(int max_g, int max_r) { return 5 * (size_t)((max_r + 15) & ~15) + ((max_g + 15) & ~15) + (size_t)max_g * 48 + 64; }
-int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, const GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
+int gm_launch_sw_full_cs_batch(const int* cs_params9, int first, int n, int grid, GmFullItem* d_items, const uint32_t* d_genome_ls, const uint32_t* d_reads,
                                int read_words, int max_g, int max_r, const int8_t* d_xrows, int xstride, uint32_t* d_back, size_t back_words, GmFullOut* d_out,
                                uint8_t* d_ops, int local, hipStream_t stream, int ix, int by_row) {
   if (n == 0) return GM_OK;
   if (by_row && !ix) { gm_set_error("sw_full_cs batch: the by-row form is an index form"); return GM_E_ARG; }
   GmCsDev P; P.match = cs_params9[0]; P.mismatch = cs_params9[1]; P.xover = cs_params9[2]; P.a_go = cs_params9[3]; P.a_ge = cs_params9[4];
   P.b_go = cs_params9[5]; P.b_ge = cs_params9[6]; P.anchor_width = cs_params9[7]; P.taboo = cs_params9[8];
+  if (P.anchor_width < 0) {                                    // -a -1: the threshold band as every item's box (threshold_box)
+    hipLaunchKernelGGL(k_threshold_box_items, dim3((n + 255) / 256), dim3(256), 0, stream, first, n, d_items, P.match);
+    P.anchor_width = 0;
+  }
   const size_t lds = gm_sw_full_cs_batch_lds(max_g, max_r);
   if (lds > GM_SWF_LDS_LIMIT) { gm_set_error("sw_full_cs batch: window of %d does not fit LDS", max_g); return GM_E_ARG; }      // (the host entry refuses such items one by one before it gets here)
 #define GM_SWF_CS_LAUNCH(LOC, IX, ROW) do { \

@@ -452,6 +452,112 @@ def load_option_sam(base, tag):
         return f.read()
 
 
+# Window and anchor-band geometry off the defaults (tools/make_golden.py --geometry-only, tests/test_window_geometry.py): -a anchor width (-1: no anchor band, the
+# threshold band in every full alignment), -w window length, -l window overlap, -r window generation threshold (a trailing % in the reference's options: of the read
+# length / the window / the best score; without it an absolute count -- a negative value in the oracle's options and in gm_params_t), -h / -v the full and the vector
+# threshold (letter space takes -h for both, gmapper.c), -z the list cutoff.  The inputs are committed ones, cut to their first GEOMETRY_READS reads or pairs; only the
+# reference's records are stored, as <input>@geo_<tag>.sam.gz.
+GEOMETRY_READS = {"stress_60bp": 1500, "stress_100bp_unal": 1500, "stress_cs_60col_unal": 600, "stress_pairs_2x100": 600, "pair_edges_opp-in": 378, "pair_edges_col-bw": 378}
+# (on the first 1 500 reads -h 437 moves 4 records only, on the whole input 6; -w 300% moves 2 records of the first 600 colour-space reads, 5 of the first 1 400)
+# -w 170 -l 30 moves the records of one pair among the first 600, of two among the first 900
+GEOMETRY_READS_OF = {"stress_60bp:h437abs": 3000, "stress_cs_60col_unal:w300": 1400, "stress_pairs_2x100:w170abs_l30abs": 900}
+GEOMETRY_UNAL = ("stress_100bp_unal", "stress_cs_60col_unal")      # inputs whose goldens are made with --sam-unaligned
+_W100 = (["-w", "100%"], "match-window=100", dict(window_len=100.0))
+_GEO_SETS = {      # what -> (the reference's options, the oracle's, gm_params_t fields; "pair_" fields go to gm_pair_opts_t)
+    "a-1": (["-a", "-1"], "anchor-width=-1", dict(anchor_width=-1)),
+    "a0": (["-a", "0"], "anchor-width=0", dict(anchor_width=0)),
+    "a1": (["-a", "1"], "anchor-width=1", dict(anchor_width=1)),
+    "a99": (["-a", "99"], "anchor-width=99", dict(anchor_width=99)),
+    "w100": _W100,
+    "w250": (["-w", "250%"], "match-window=250", dict(window_len=250.0)),
+    "w300": (["-w", "300%"], "match-window=300", dict(window_len=300.0)),
+    "w131abs": (["-w", "131"], "match-window=-131", dict(window_len=-131.0)),
+    "w61abs": (["-w", "61"], "match-window=-61", dict(window_len=-61.0)),
+    "w60abs": (["-w", "60"], "match-window=-60", dict(window_len=-60.0)),
+    "w50abs": (["-w", "50"], "match-window=-50", dict(window_len=-50.0)),                      # a window shorter than the read
+    "l20abs": (["-l", "20"], "cmw-overlap=-20", dict(window_overlap=-20.0)),
+    "l100": (["-l", "100%"], "cmw-overlap=100", dict(window_overlap=100.0)),
+    "l10": (["-l", "10%"], "cmw-overlap=10", dict(window_overlap=10.0)),
+    "r250abs": (["-r", "250"], "cmw-threshold=-250", dict(window_gen_threshold=-250.0)),
+    "r90": (["-r", "90%"], "cmw-threshold=90", dict(window_gen_threshold=90.0)),
+    "h437abs": (["-h", "437"], "full-threshold=-437;vec-threshold=-437", dict(sw_full_threshold=-437.0, sw_vect_threshold=-437.0)),
+    "z5": (["-z", "5"], "cutoff=5", dict(list_cutoff=5)),
+    "v40_h80": (["-v", "40%", "-h", "80%"], "vec-threshold=40;full-threshold=80", dict(sw_vect_threshold=40.0, sw_full_threshold=80.0)),
+    "local_a-1": (["--local", "-a", "-1"], "local=1;anchor-width=-1", dict(local_alignment=1, anchor_width=-1)),
+    "w100_a-1": (["-w", "100%", "-a", "-1"], "match-window=100;anchor-width=-1", dict(window_len=100.0, anchor_width=-1)),
+    "w100_n1": (["-w", "100%", "-n", "1"], "match-window=100;cmw-mode=1", dict(window_len=100.0, match_mode=1)),
+    "w170abs_l30abs": (["-w", "170", "-l", "30"], "match-window=-170;cmw-overlap=-30", dict(window_len=-170.0, window_overlap=-30.0)),
+    "w100_nhp": (["-w", "100%", "--no-half-paired"], "match-window=100;half-paired=0", dict(window_len=100.0, pair_half_paired=0)),
+    "w250_n3": (["-w", "250%", "-n", "3"], "match-window=250;mp-match-mode=3", dict(window_len=250.0, pair_match_mode=3)),
+}
+_GEO_ON = {
+    "stress_60bp": ["a-1", "a0", "a1", "a99", "w100", "w300", "w131abs", "w60abs", "w61abs", "w50abs", "l20abs", "l100", "l10", "r250abs", "r90", "h437abs", "z5",
+                    "local_a-1", "w100_a-1", "w100_n1"],
+    "stress_100bp_unal": ["a-1", "a0", "a1", "a99", "w100", "w300", "l20abs", "r90", "z5", "local_a-1"],      # w300: windows of 300 > 256 columns under one stripe
+    "stress_cs_60col_unal": ["a-1", "a0", "w100", "w300", "v40_h80", "local_a-1"],
+    "stress_pairs_2x100": ["w100", "w250", "a-1", "a0", "w170abs_l30abs", "w100_nhp", "w250_n3"],
+    "pair_edges_opp-in": ["w100"],      # mates of 40 and 60 bases: window_len - read_len is 0 for both, the four delta_g_off formulas of the mate ranges collapse
+    "pair_edges_col-bw": ["w100"],
+}
+# tag -> (input, the reference's options, the oracle's options, gm_params_t / pair_ fields)
+GEOMETRY_CASES = {"%s:%s" % (base, what): (base,) + _GEO_SETS[what] for base, whats in _GEO_ON.items() for what in whats}
+GEOMETRY_MIN_DISTANCE = 5      # records of a golden that are not in its input's default golden; and of -a -1 / -a 99 that are not in -a 0
+# ... but for colour space -a -1: there the threshold band and the default band of width 8 give the same records on this input, and its distance from -a 0 stands alone
+GEOMETRY_SAME_AS_DEFAULT = ("stress_cs_60col_unal:a-1",)
+
+
+def geometry_kind(base):
+    """'cs', 'pairs' or 'ls'"""
+    return "cs" if "_cs_" in base else ("pairs" if "pairs" in base or base.startswith("pair_") else "ls")
+
+
+def geometry_file(tag):
+    base, what = tag.split(":")
+    return "%s@geo_%s.sam.gz" % (base, what)
+
+
+def load_geometry_sam(tag):
+    """the reference's records (no header) of a geometry case"""
+    with gzip.open(os.path.join(ROOT, "tests", "golden", geometry_file(tag)), "rb") as f:
+        return f.read()
+
+
+def geometry_reads(tag):
+    """reads / pairs of its input a geometry case runs on, from the input's front"""
+    return GEOMETRY_READS_OF.get(tag, GEOMETRY_READS[tag.split(":")[0]])
+
+
+def geometry_default_records(base, n=None):
+    """the records of the input's default golden that belong to its first n (GEOMETRY_READS) reads / pairs, header dropped (the goldens are written in read order)"""
+    n = n or GEOMETRY_READS[base]
+    if geometry_kind(base) == "pairs":
+        g = load_golden_pairs(base); keep = {x[:-2] for x in g["names1"][:n]}; sam = g["sam"]      # (the mates' names without their /1, :1)
+    else:
+        keep = {b"r%d" % i for i in range(n)}; sam = load_golden(base)[2]
+    return b"".join(l + b"\n" for l in sam.split(b"\n") if l and not l.startswith(b"@") and l.split(b"\t", 1)[0] in keep)
+
+
+def sam_distance(body, other):
+    """records of `body` that are not records of `other`"""
+    have = set(other.split(b"\n"))
+    return sum(1 for l in body.split(b"\n") if l and l not in have)
+
+
+def load_kat_anchors(colour=False):
+    """the known answers of the full alignments at other anchor widths than 8 (oracle/ref_kat.cpp / ref_kat_cs.cpp, mode "anchors"): (name, setup, records) a width as
+    load_kat_scores gives them; the setup tuple ends with the width.  Letter space: F records (global, threshold 0), and G / L records in the L records' layout (global /
+    local at a threshold of half the read, with the box and without); colour space: S and L records."""
+    sets = []
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "sw_kat_cs_anchors.txt.gz" if colour else "sw_kat_anchors.txt.gz"), "rb" if colour else "rt") as f:
+        for line in f:
+            t = line.split()
+            if t[0] in ("P", b"P"): sets.append((t[1].decode() if colour else t[1], tuple(int(x) for x in t[2:]), []))
+            elif colour: sets[-1][2].append(_kat_cs_record(t))
+            elif t[0] == "G": sets[-1][2].append(("G",) + _kat_ls_record(["L"] + t[1:]))
+            else: sets[-1][2].append(_kat_ls_record(t))
+    return sets
+
+
 def load_kat_local():
     """sw_full_ls in local mode (Gflag off), with an anchor box and without, from the reference's own function (oracle/ref_kat.cpp local)"""
     with gzip.open(os.path.join(ROOT, "tests", "golden", "sw_kat_local.txt.gz"), "rt") as f:
@@ -495,10 +601,11 @@ def load_kat_scores(colour=False):
     return sets
 
 
-def score_array(setup):
-    """the _p entry points' score argument from a setup tuple of load_kat_scores: match, mismatch, a_open, a_ext, b_open, b_ext (, crossover, indel_taboo_len)"""
+def score_array(setup, anchor_width=8):
+    """the _p entry points' score argument from a setup tuple of load_kat_scores: match, mismatch, a_open, a_ext, b_open, b_ext (, crossover, indel_taboo_len), and
+    the anchor width behind them"""
     s = list(setup[2:])
-    return (C.c_int * 8)(*([s[4], s[5], s[0], s[1], s[2], s[3]] + (s[6:8] if len(s) > 6 else [0, 0])))
+    return (C.c_int * 9)(*([s[4], s[5], s[0], s[1], s[2], s[3]] + (s[6:8] if len(s) > 6 else [0, 0]) + [anchor_width]))
 
 
 # RNA fixtures (tools/make_golden.py rna_cases): tag -> (colour space?, genome file, read files, oracle options, pairing)

@@ -45,6 +45,8 @@ void* rwo_create_opts(int n_contigs, const uint8_t* const* codes, const uint64_t
   return S;
 }
 void rwo_destroy(void* s) { delete (Session*)s; }
+// window geometry as the options carry it: a percentage (of the read, of the window), or below zero an absolute count (-w, -l)
+void rwo_set_windows(void* s, double window_len, double window_overlap) { Session* S = (Session*)s; S->M.P.window_len = window_len; S->M.P.window_overlap = window_overlap; }
 
 // Every hit of both strands of every read, as the lists stand before pass 1: rows of 12 int64
 //   read st cn g_off w_len score_window_gen matches anchor.x anchor.y anchor.length anchor.width 0

@@ -10,6 +10,7 @@
 //   setup_v <colours 0|1> <mismatch> [a_open a_ext b_open b_ext match]      sw_vector_setup(1400, 1000, -33, -7, -33, -3, 10, mismatch, colours, true), or with the scores given
 //   setup_f_ls [a_open a_ext b_open b_ext match mismatch]                   sw_full_ls_setup(1400, 1000, -33, -7, -33, -3, 10, -15, true, 8), or with the scores given
 //   setup_f_cs [a_open a_ext b_open b_ext match mismatch crossover taboo]   sw_full_cs_setup(1400, 1000, -33, -7, -33, -3, 10, -24, -20, true, 8, 0), or with the scores given
+//   width <anchor_width>                      the anchor_width of the setup_f_ls / setup_f_cs requests that follow (8 until then; -1: the threshold band whatever the box)
 //   setup_g <match> <mismatch>                sw_gapless_setup
 //   setup_p <use_qvs> <6 doubles, %a>         post_sw_setup(2400, ..., use_qvs, true, 0, 33, true)
 //   V goff glen rlen <genome> <read>                                   -> V score
@@ -75,20 +76,22 @@ static void take(std::istringstream& in, int* v, int n, const std::string& line)
 }
 
 static bool g_is_rna = false;
+static int g_anchor_width = 8;
 int main() {
   std::string line;
   while (std::getline(std::cin, line)) {
     std::istringstream in(line); std::string op; in >> op;
     if (op == "rna") { int v; in >> v; g_is_rna = v != 0; }      // the is_rna argument of the calls that follow (sw_vector / sw_gapless / sw_full_cs)
+    else if (op == "width") in >> g_anchor_width;
     else if (op == "setup_v") {
       int col, mm, v[5] = {-33, -7, -33, -3, 10}; in >> col >> mm; take(in, v, 5, line);
       if (sw_vector_setup(1400, 1000, v[0], v[1], v[2], v[3], v[4], mm, col, true)) return 3;
     } else if (op == "setup_f_ls") {
       int v[6] = {-33, -7, -33, -3, 10, -15}; take(in, v, 6, line);
-      if (sw_full_ls_setup(1400, 1000, v[0], v[1], v[2], v[3], v[4], v[5], true, 8)) return 3;
+      if (sw_full_ls_setup(1400, 1000, v[0], v[1], v[2], v[3], v[4], v[5], true, g_anchor_width)) return 3;
     } else if (op == "setup_f_cs") {
       int v[8] = {-33, -7, -33, -3, 10, -24, -20, 0}; take(in, v, 8, line);
-      if (sw_full_cs_setup(1400, 1000, v[0], v[1], v[2], v[3], v[4], v[5], v[6], true, 8, v[7])) return 3;
+      if (sw_full_cs_setup(1400, 1000, v[0], v[1], v[2], v[3], v[4], v[5], v[6], true, g_anchor_width, v[7])) return 3;
     }
     else if (op == "setup_g") { int m, mm; in >> m >> mm; if (sw_gapless_setup(m, mm, true)) return 3; }
     else if (op == "setup_p") {

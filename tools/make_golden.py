@@ -1553,8 +1553,76 @@ def contigs_cases():
         assert os.path.getsize(os.path.join(OUT, f + ".npz")) <= 734_000, f
 
 
+def _geometry_ref_body(base, n, extra):
+    """the reference's records (no header line) on the first n reads / pairs of a committed input under the options `extra`"""
+    from tests import oracle_api as oa
+    kind = oa.geometry_kind(base)
+    z = np.load(os.path.join(OUT, base + ".npz"))
+    contigs = [z["contig%d" % i] for i in range(sum(1 for f in z.files if f.startswith("contig") and f[6:].isdigit()))]
+    with tempfile.TemporaryDirectory() as d:
+        g = os.path.join(d, "g.fa"); r = os.path.join(d, "r.csfasta" if kind == "cs" else "r.fa")
+        if kind == "pairs":
+            write_fa_codes(g, [bytes(x) for x in z["contig_names"]], contigs)
+            names = [bytes(x) for pair in zip(z["names1"][:n], z["names2"][:n]) for x in pair]
+            write_fa_codes(r, names, [q for pair in zip(list(z["mates1"][:n]), list(z["mates2"][:n])) for q in pair])
+            extra = ["-p", str(z["mode"]), "-I", "%d,%d" % tuple(int(x) for x in z["ins"]), *extra]
+        else:
+            write_fa_codes(g, [b"contig%d" % (i + 1) for i in range(len(contigs))], contigs)
+            if kind == "cs": synth.write_csfasta_reads(r, z["reads"][:n])
+            else: write_fa_codes(r, [b"r%d" % i for i in range(n)], list(z["reads"][:n]))
+        if base in oa.GEOMETRY_UNAL: extra = [*extra, "--sam-unaligned"]
+        cmd = ["timeout", "-k", "5", "300", os.path.join(ROOT, "oracle", "_ref", "gmapper-cs" if kind == "cs" else "gmapper-ls"), "-N", "4", *extra, r, g]
+        p = subprocess.run(cmd, capture_output=True)
+        assert p.returncode == 0, (base, extra, p.returncode, p.stderr[-2000:])
+    return b"".join(l + b"\n" for l in p.stdout.split(b"\n") if l and not l.startswith(b"@"))
+
+
+def geometry_cases():
+    """--geometry-only: the option sets of tests/oracle_api.py GEOMETRY_CASES through the reference on committed inputs.  Only the records are stored.  Prints, and asserts,
+    how far each golden lies from its input's default golden, and the -a -1 and -a 99 goldens from the -a 0 one (records of the one that are not in the other)."""
+    from tests import oracle_api as oa
+    total = 0; bodies = {}
+    for base, n in list(oa.GEOMETRY_READS.items()) + [(t.split(":")[0], n) for t, n in oa.GEOMETRY_READS_OF.items()]:
+        want = oa.geometry_default_records(base, n)
+        assert _geometry_ref_body(base, n, []) == want, "%s: the default golden's records of the first %d reads are not the reference's output on them" % (base, n)
+    for tag, (base, extra, _, _) in oa.GEOMETRY_CASES.items():
+        body = _geometry_ref_body(base, oa.geometry_reads(tag), extra)
+        path = os.path.join(OUT, oa.geometry_file(tag)); _gz_fixed(path, body); bodies[tag] = body
+        size = os.path.getsize(path); total += size
+        recs = body.count(b"\n"); mapped = sum(1 for l in body.split(b"\n") if l and not int(l.split(b"\t", 2)[1]) & 4)
+        dist = oa.sam_distance(body, oa.geometry_default_records(base, oa.geometry_reads(tag)))
+        print("%-36s %-28s %5d records, %5d mapped, %5d not in the default golden, %6d bytes" % (tag, " ".join(extra), recs, mapped, dist, size))
+        assert dist >= oa.GEOMETRY_MIN_DISTANCE or (tag in oa.GEOMETRY_SAME_AS_DEFAULT and dist == 0), (tag, dist)
+        assert size <= 130_000, (tag, size)
+    for tag, body in bodies.items():
+        base, what = tag.split(":")
+        if what in ("a-1", "a99"):
+            dist = oa.sam_distance(body, bodies[base + ":a0"])
+            print("%-36s %5d records not in %s:a0" % (tag, dist, base))
+            assert dist >= oa.GEOMETRY_MIN_DISTANCE, (tag, dist)
+    print("geometry goldens: %d files, %d bytes" % (len(bodies), total))
+
+
+def anchor_kat_cases():
+    """--anchor-kat-only: the known answers of sw_full_ls / sw_full_cs at the anchor widths -1, 0, 1, 9 and 99 (oracle/ref_kat.cpp, ref_kat_cs.cpp, mode "anchors")"""
+    for exe, name, n in (("ref_kat", "sw_kat_anchors", 90), ("ref_kat_cs", "sw_kat_cs_anchors", 120)):
+        kat = subprocess.run([os.path.join(ROOT, "oracle", "_ref", exe), str(n), "anchors"], capture_output=True, check=True).stdout
+        path = os.path.join(OUT, name + ".txt.gz"); _gz_fixed(path, kat)
+        assert os.path.getsize(path) < 400_000, "cut cases per width, not widths"
+        per = {}
+        for l in kat.split(b"\n"):
+            if not l: continue
+            if l[:1] == b"P": cur = l.split()[1].decode(); per[cur] = {}
+            else: per[cur][l[:1].decode()] = per[cur].get(l[:1].decode(), 0) + 1
+        print("%s: %d bytes;" % (name, os.path.getsize(path)), "; ".join("%s: %s" % (k, ", ".join("%d %s" % (c, t) for t, c in sorted(v.items()))) for k, v in per.items()))
+
+
 if __name__ == "__main__":
-    if "--seeds-only" in sys.argv:
+    if "--geometry-only" in sys.argv:
+        os.makedirs(OUT, exist_ok=True); geometry_cases()
+    elif "--anchor-kat-only" in sys.argv:
+        os.makedirs(OUT, exist_ok=True); anchor_kat_cases()
+    elif "--seeds-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); seeds_cases()
     elif "--contigs-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); contigs_cases()
