@@ -669,7 +669,7 @@ int gm_debug_tophits_cs(gm_session_t *s, int n_reads, int n_colours, const uint3
  *   like a mapping call and leaves the session ready for any other call.
  *   stats (or NULL): reads, lookups, list_entries, list_bytes, survivors, anchors, windows (== *n_wins), survivors_pruned, exact_order_reads, retries, ms_lookup,
  *   ms_anchors; every other field 0.
- *   Unpaired sessions only: a session has no pair mode of its own (pairing is an argument of gm_map_pairs*), so there is no paired form of this call, and the
+ *   Unpaired sessions only: a session has no pair mode of its own (pairing is an argument of gm_map_pairs*), so this call has no paired form (gm_pair_mappings is the one-call seam for pairs), and the
  *   mate-pair region counts of the paired option sets (-p) never apply here.
  * How a window feeds the _ix seams (cn, gen_st, g_off, glen), with contig_len the length of contig cn:
  *   read strand 0: (cn, 0, g_off, w_len) with the read as given;
@@ -915,7 +915,7 @@ int gm_sam_records(gm_session_t *s, const gm_sam_input_t *in, char **sam, size_t
  * post_sw and its host re-dos between the full alignment and the selection: use the chain of seams, gm_read_hits -> gm_sw_full_cs_batch_ix -> gm_post_sw_batch_ix ->
  * gm_select_pass2 -> gm_sw_full_batch_text_ix); the read arguments as gm_read_hits (GM_E_ARG, GM_E_RANGE); num_tmp_outputs > 64: GM_E_RANGE; a read length whose
  * windows do not fit the full-alignment kernel's LDS beside the read (the admission test of gm_sw_full_ls_batch): GM_E_RANGE.  A session has no pair mode of its own
- * (see gm_read_windows), so there is no paired session to refuse.  n_reads <= 0: GM_OK, no hits.  After any failure *out holds nothing to free. */
+ * (see gm_read_windows), so there is no paired session to refuse (pairs: gm_pair_mappings).  n_reads <= 0: GM_OK, no hits.  After any failure *out holds nothing to free. */
 typedef struct gm_read_mappings {
   int32_t  n_reads, has_edit;
   uint64_t n_hits, n_maps, cigar_len, edit_len, ops_len;
@@ -991,6 +991,82 @@ int  gm_read_mappings_cs(gm_session_t *s, int n_reads, int n_colours, const uint
                          const char *quals, int qual_delta,       /* NULL, or '\n' separated QV strings as gm_map_reads_cs_fastq takes them */
                          int want_ops, gm_read_mappings_cs_t *out, gm_map_stats_t *stats);
 void gm_read_mappings_cs_free(gm_read_mappings_cs_t *out);
+
+/* gm_pair_mappings: paired pass 2 as a seam -- a chunk of read pairs to mapping arrays in one call; the paired counterpart of gm_read_mappings.  A caller who wants the
+ * mappings of read pairs as data (to write BAM, filter by insert size, count, feed a variant caller) makes this call instead of gm_map_pairs and a SAM parser.  Letter
+ * space; all four pair modes; half_paired 1 and 0; match_mode 4 and 3.  The mapping entries gm_map_pairs* do not use it and print what they printed.
+ * The entry drives the call object of gm_map_pairs through its own stages and launches what gm_map_pairs launches: the front (lookup, the mate-pair region counts of
+ * --no-half-paired and -n 3, anchors), pair-up, pass 1 over the paired windows, the pair top-K, the full alignment of the windows of the selected pairs at half the
+ * threshold per mate (ref: gmapper.c:2677), the half-paired rescue (pass 1 over all windows with the windows of the final pairs saved, top-K, the full alignment at the
+ * full threshold; ref: mapping.c:2598-2625), with the same sub-batch walk, capacity growth, re-dos and buffer-set pairs.  Two things differ from gm_map_pairs.
+ *   The pair selection runs on the device, a wave a pair, a lane a candidate pair of the pair heap's list (at most 64), where gm_map_pairs runs a host loop.  Its rules
+ *   are readpair_pass2's (ref: mapping.c:2181-2314):
+ *     1. a candidate stays when both its windows were aligned (score_full != 0, :2243-2245) and score_full of mate 1 + score_full of mate 2 >= the pair threshold:
+ *        -sw_full_threshold for an absolute threshold, else (int)(sum of the two score_max * (sw_full_threshold / 100.0)) -- evaluated by the host in that double
+ *        expression, once per possible sum; the kernel reads the table (:2246-2262).  score_full is hit_run_post_sw's, from the host's libm as in gm_read_mappings.
+ *     2. readpair_remove_duplicate_hits (:2113-2175): four passes of readpair_push_dominant_single_hits (:2083-2110) -- mate 1 by (cn, gen_st, genome_start), mate 1 by
+ *        (cn, gen_st, -genome_start - rmapped + deletions - insertions), mate 2 by the first, mate 2 by the second.  A pass sorts the pairs stably by that key of that
+ *        mate's window; within every run of equal keys each pair takes the window of the run's FIRST maximum score_full for that mate, and compute_paired_hit
+ *        (:2053-2080) is evaluated again for it.
+ *     3. a stable sort by (sort_idx of mate 1's window, sort_idx of mate 2's window) -- the comparator of :2004-2050 -- and of every run of equal neighbours only the
+ *        first stays (removedups, common/util.c:1240-1255).
+ *     4. a stable sort by descending key: pct_score = (1000 * 100 * score) / score_max of the sums, or the score for an absolute threshold.
+ *     5. the cut to num_outputs, strata (the leading run of equal score), max_alignments (more than that many leaves none) (:2264-2284).
+ *   And instead of text the call returns arrays.  The mapping qualities are compute_paired_mqv's (ref: output.c:811-942) and the records named are plan_pair_output's
+ *   (ref: output.c:1086-1235, --single-best-mapping with the one improper pair of two unpaired winners included): the host functions gm_map_pairs prints through, called
+ *   on the same objects -- erf, log and pow go through the host's libm, and the reference's bytes hang on their last bits.
+ * Result: ONE struct, released by ONE call, gm_pair_mappings_free (frees the buffers and zeroes the struct; the struct itself is the caller's).  m = 0 / 1: mate 1 / 2.
+ * Offset arrays are always there (n_pairs + 1 / n_hits[m] + 1 entries); an array of records or bytes is NULL when it would be empty.
+ *   hits[m], hit_off[m][n_pairs + 1]   every window of mate m that went through the full alignment for the pair: the hits of the paired pass in the order of the pair
+ *                     heap's window list, then the hits of the half-paired rescue in its heap's array order.  gm_pass1_hit_t as gm_read_hits fills it, with read = the
+ *                     pair, score_vector / pct_score_vector = pass 2's second vector score (ZV), win = -1 and the anchor box 0 (the call has no window list to name).
+ *   hit_kind[m][i]    0: a hit of the paired pass; 1: a hit of the rescue.
+ *   recs[m][i]        the record as the pipeline's pass 2 leaves it; a window under its threshold -- half the threshold in the paired pass, the full one in the rescue
+ *                     -- has the zero record.  genome_start counts on strand gen_st of the contig; ops_off / n_ops point into ops[m] whether or not it was asked for.
+ *   pmaps, pmap_off[n_pairs + 1]   the paired mappings of each pair in the reference's output order, gm_pair_mapping_t below.
+ *   umaps[m], umap_off[m][n_pairs + 1]   the unpaired (half-paired) mappings of mate m in output order, gm_mapping_t: read = the pair, hit = the index in hits[m] /
+ *                     recs[m] (the call's, not the pair's), mqv from compute_paired_mqv's unpaired branch, z0 / z1 the Z0 / Z1 tags' values;
+ *   umap_z45[m]       two doubles a mapping of umaps[m]: the values of its Z4 (pr_top_random) and Z5 (pr_missed_mp) tags.
+ *                     In the SAM text a pair's records are: its paired mappings, then mate 1's unpaired ones (each with mate 2's unmapped record), then mate 2's.
+ *   cigar[m], cigar_off[m][n_hits[m] + 1]  and, when has_edit (the session's extra_sam_fields), edit[m], edit_off[m]: the text of every hit that some mapping names, clip
+ *                     character 'S', reverse = gen_st, made on the device over those hits only; every other hit has an empty slice.
+ *   ops[m], ops_len[m]   want_ops != 0 only: the edit operations of all records of mate m, compacted in hit order (else NULL; ops_len is still their total).
+ * stats (or NULL): as gm_map_pairs fills it; sam_records stays 0.
+ * Refusals, on the host before anything is uploaded, the session usable afterwards: s or out NULL, n_pairs < 0, a length < 1, a missing mate array: GM_E_ARG; a
+ * colour-space session, output_format 1 / 2, match_mode 2: GM_E_ARG with a message; num_tmp_outputs > 64: GM_E_RANGE (as gm_select_pass2); then every refusal of
+ * gm_map_pairs by the same functions with the same codes: pair_mode outside 1..4 and match_mode outside 2..4 GM_E_ARG, a read length out of range or a window beyond
+ * pass 2's LDS for either mate GM_E_RANGE.  n_pairs == 0: GM_OK, no hits.  After any failure *out holds nothing to free. */
+typedef struct gm_pair_mapping {     /* 12 x 32 bits + 8 doubles = 112 bytes, no padding */
+  int32_t pair;
+  int32_t hit[2];                    /* the mates' hits, as indices into the PAIR's OWN slices: hits[m][hit_off[m][pair] + hit[m]] */
+  int32_t score, pct_score, key;     /* compute_paired_hit's sums; an improper pair: score = the sum of the two AS, pct_score = key = 0 */
+  int32_t insert_size;               /* signed as compute_paired_hit signs it; an improper pair: 0 */
+  int32_t mapq[2], as[2];            /* MAPQ and AS of the two records */
+  int32_t improper;                  /* 1: the pair of two unpaired winners --single-best-mapping --all-contigs prints (FLAG without 0x2); hit[] then name rescue hits */
+  double  z[2][4];                   /* per mate, the values of the Z tags its record prints: proper Z2 Z3 Z4 Z6; improper Z0 Z1 Z4 Z5.  0 without mapping qualities */
+} gm_pair_mapping_t;
+typedef struct gm_pair_mappings {
+  int32_t  n_pairs, has_edit;
+  uint64_t n_hits[2], n_pmaps, n_umaps[2], cigar_len[2], edit_len[2], ops_len[2];
+  gm_pass1_hit_t    *hits[2];  uint64_t *hit_off[2];  uint8_t *hit_kind[2];
+  gm_sw_full_rec_t  *recs[2];
+  gm_pair_mapping_t *pmaps;    uint64_t *pmap_off;
+  gm_mapping_t      *umaps[2]; uint64_t *umap_off[2]; double *umap_z45[2];
+  char *cigar[2]; uint64_t *cigar_off[2];
+  char *edit[2];  uint64_t *edit_off[2];
+  uint8_t *ops[2];
+} gm_pair_mappings_t;
+int  gm_pair_mapping_size(void);         /* sizeof(gm_pair_mapping_t), for the Python mirror */
+int  gm_pair_mappings_size(void);        /* sizeof(gm_pair_mappings_t), for the Python mirror */
+int  gm_pair_mappings(gm_session_t *s, int n_pairs, int len1, const uint32_t *mates1_packed, int len2, const uint32_t *mates2_packed,
+                      const gm_pair_opts_t *opts, int want_ops, gm_pair_mappings_t *out, gm_map_stats_t *stats);
+void gm_pair_mappings_free(gm_pair_mappings_t *out);
+/* test hook: the device pair selection of gm_pair_mappings beside the host loop of gm_map_pairs on hand-made candidate lists, under the session's num_outputs, strata,
+ * max_alignments and sw_full_threshold.  wins0 / wins1: 9 x int32 a window (cn, gen_st, genome_start, rmapped, deletions, insertions, score_full, score_max, sort_idx),
+ * pair pr's cnt0[pr] / cnt1[pr] windows one after the other; plist[pr * 64 ..]: its pcnt[pr] candidates (window of mate 1 << 8) | window of mate 2.  dev_out / host_out:
+ * n_pairs x 64 words in the same form, dev_cnt / host_cnt: n_pairs counts. */
+int  gm_debug_pair_select(gm_session_t *s, int pair_mode, int n_pairs, const uint32_t *cnt0, const int32_t *wins0, const uint32_t *cnt1, const int32_t *wins1,
+                          const uint32_t *plist, const uint32_t *pcnt, uint32_t *dev_out, uint32_t *dev_cnt, uint32_t *host_out, uint32_t *host_cnt);
 
 /* time of the dominant kernel (seed lookup) during the last gm_map_* call, from HIP events on the
  * session's own stream, and the algorithmic bytes it moved */

@@ -1475,3 +1475,4 @@ extern "C" int gm_debug_tophits_cs(gm_session_t* s, int n_reads, int n_colours, 
 #include "gm_host_text.inc"
 #include "gm_host_pass2.inc"
 #include "gm_host_pass2_cs.inc"
+#include "gm_host_pair_mappings.inc"

@@ -349,6 +349,17 @@ static PairPlan plan_pair_output(const gm_params_t& P, FHit* const HP[2], const 
   return p;
 }
 
+// What readpair_output settles for pair pr before it prints (ref: output.c:1070-1235): the mates' unpaired selection (t.U afterwards), the paired mapping qualities, the
+// plan.  emit_pair prints from it; gm_pair_mappings (gm_host_pair_mappings.inc) hands the same out as arrays.
+static PairPlan settle_pair(const PairCall& c, PairOut& b, int pr, PairScratch& t) {
+  const gm_params_t& P = c.s->P;
+  FHit* HP[2] = {b.fhP[0].data() + b.offP[0][pr], b.fhP[1].data() + b.offP[1][pr]};
+  std::vector<FHit*>* const U = t.U;
+  for (int m = 0; m < 2; m++) b.F[m].select_hits(b.cntU[m][pr] ? &b.resU[m][b.offU[m][pr]] : nullptr, b.opsU[m].data(), (int)b.cntU[m][pr], t.fhU[m], U[m]);
+  const PPair* fp = &b.fpairs[(size_t)pr * b.NO]; const int nfp = b.fcnt[pr];
+  if (gm_mqv_on(P)) compute_paired_mqv(c.C, HP, fp, nfp, U);                  // --local / --no-mapping-qualities: none (ref: gmapper.c:2258,2325-2328, output.c:1092)
+  return plan_pair_output(P, HP, fp, nfp, U);
+}
 // readpair_output for pair pr of the sub-batch (ref: output.c:1070-1291): the mates' unpaired selection, the paired mapping qualities, the text.  Returns the number of
 // records; t.U holds the unpaired mappings afterwards.
 static uint64_t emit_pair(const PairCall& c, PairOut& b, int pr, std::string& o, PairScratch& t) {
@@ -356,10 +367,8 @@ static uint64_t emit_pair(const PairCall& c, PairOut& b, int pr, std::string& o,
   const long gp = (long)b.base + pr;
   FHit* HP[2] = {b.fhP[0].data() + b.offP[0][pr], b.fhP[1].data() + b.offP[1][pr]};
   std::vector<FHit*>* const U = t.U;
-  for (int m = 0; m < 2; m++) b.F[m].select_hits(b.cntU[m][pr] ? &b.resU[m][b.offU[m][pr]] : nullptr, b.opsU[m].data(), (int)b.cntU[m][pr], t.fhU[m], U[m]);
   const PPair* fp = &b.fpairs[(size_t)pr * b.NO]; const int nfp = b.fcnt[pr];
-  if (gm_mqv_on(P)) compute_paired_mqv(c.C, HP, fp, nfp, U);                  // --local / --no-mapping-qualities: none (ref: gmapper.c:2258,2325-2328, output.c:1092)
-  const PairPlan p = plan_pair_output(P, HP, fp, nfp, U);
+  const PairPlan p = settle_pair(c, b, pr, t);
   // QNAME = common prefix of the two names, minus a trailing ':' or '/' (ref: output.c:365-378)
   const char* qn; size_t qnl; char qbuf[40];
   if (c.named) {
@@ -683,19 +692,7 @@ struct PairRun : PairCall {
   }
   // host: pair selection (readpair_pass2 per pair) on the host threads; the windows of the final pairs are saved from the rescue
   void select_pairs_host(PairOut& b, PairSel& t) {
-    b.nchunks = (b.n + b.chunk - 1) / b.chunk;
-    b.fhP[0].resize(t.n_work[0]); b.fhP[1].resize(t.n_work[1]);
-    b.NO = std::max(1, s->P.num_outputs);
-    b.fpairs.resize((size_t)b.n * b.NO); b.fcnt.assign(b.n, 0);
-    t.saved_chunks[0].resize(b.nchunks); t.saved_chunks[1].resize(b.nchunks);
-    for (int m = 0; m < 2; m++) { b.F[m] = HitScorer(); b.F[m].s = s; b.F[m].read_len = len[m]; b.F[m].read_words = rwords[m]; }
-    if (cs) {   // post_sw needs the colours and the primer letter of each read (ref: sw-post.c:448-528)
-      for (int m = 0; m < 2; m++) {
-        HitScorer& F = b.F[m];
-        F.reads = mates[m] + (size_t)b.base * rwords[m]; F.initbp = initbp_in[m] + b.base; F.ops_half = S[m]->ops_stride / 2; F.csk = cs_post_consts(s);
-        if (quals) { F.qual_ptr = qptr[m].data() + b.base; F.qual_delta = qual_delta; }      // post_sw with the reads' QVs (ref: sw-post.c:486-491)
-      }
-    }
+    select_setup(b, t);
     parallel_chunks(b.nchunks, [&](int c) {
       std::vector<PPair> v;
       for (int pr = c * b.chunk; pr < std::min(b.n, (c + 1) * b.chunk); pr++) {
@@ -710,6 +707,22 @@ struct PairRun : PairCall {
       }
     });
     lap("host pair select");
+  }
+  // the sizes of the selection's results and the mates' scorers (shared with gm_pair_mappings, whose selection runs on the device)
+  void select_setup(PairOut& b, PairSel& t) {
+    b.nchunks = (b.n + b.chunk - 1) / b.chunk;
+    b.fhP[0].resize(t.n_work[0]); b.fhP[1].resize(t.n_work[1]);
+    b.NO = std::max(1, s->P.num_outputs);
+    b.fpairs.resize((size_t)b.n * b.NO); b.fcnt.assign(b.n, 0);
+    t.saved_chunks[0].resize(b.nchunks); t.saved_chunks[1].resize(b.nchunks);
+    for (int m = 0; m < 2; m++) { b.F[m] = HitScorer(); b.F[m].s = s; b.F[m].read_len = len[m]; b.F[m].read_words = rwords[m]; }
+    if (cs) {   // post_sw needs the colours and the primer letter of each read (ref: sw-post.c:448-528)
+      for (int m = 0; m < 2; m++) {
+        HitScorer& F = b.F[m];
+        F.reads = mates[m] + (size_t)b.base * rwords[m]; F.initbp = initbp_in[m] + b.base; F.ops_half = S[m]->ops_stride / 2; F.csk = cs_post_consts(s);
+        if (quals) { F.qual_ptr = qptr[m].data() + b.base; F.qual_delta = qual_delta; }      // post_sw with the reads' QVs (ref: sw-post.c:486-491)
+      }
+    }
   }
   // device: half-paired fall-back -- handle_read per mate with the windows already there (ref: mapping.c:2598-2625, gmapper.c:2700-2714)
   int rescue(PairOut& b, PairSel& t) {

@@ -192,6 +192,16 @@ int gm_launch_pass1(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* 
 
 // K4a top-K selection (ref: read_get_vector_hits), one thread per read; K4b pass 2, one wave per selected hit
 #define GM_SEL_MAX 64
+// The pair selection of paired pass 2 on the device (gm_pair_mappings, gm_pair_select.hip; gm_map_pairs* keeps its host loop).
+//   gm_launch_pair_sel_items: d_items[i] from the paired pass 2's record d_res[i] and the host's score_full of it.
+//   gm_launch_sel_pair_pass2: a wave a pair over its d_pcnt[pr] candidate pairs d_plist[pr * GM_SEL_MAX ..] = (a << 8) | b, a / b windows of the pair's slices
+//                             d_items{0,1}[d_off{0,1}[pr] .. + d_cnt{0,1}[pr]): d_out[pr * GM_SEL_MAX + k] = the k-th final pair in the same form, d_cnt[pr] their number.
+//                             d_thr_tab[s], s < thr_n: the integer threshold for two windows whose score_max sum to s; abs_key: the key is the score, not its percentage.
+struct GmPairSelItem { int32_t grp, start, endkey, score_full, score_max, sort_idx; };      // grp = cn * 2 + gen_st
+int gm_launch_pair_sel_items(int n, const GmFullRes* d_res, const int32_t* d_score_full, GmPairSelItem* d_items, hipStream_t stream);
+int gm_launch_sel_pair_pass2(int n_pairs, int abs_key, int num_outputs, int strata, int max_alignments, const int* d_thr_tab, int thr_n, const uint32_t* d_plist,
+                             const uint32_t* d_pcnt, const GmPairSelItem* d_items0, const uint32_t* d_off0, const uint32_t* d_cnt0, const GmPairSelItem* d_items1,
+                             const uint32_t* d_off1, const uint32_t* d_cnt1, uint32_t* d_out, uint32_t* d_cnt, hipStream_t stream);
 int gm_launch_select(const GmScoreDev& sc, int n_reads, int read_len, const GmHit* d_hits, const uint16_t* d_perm,
                      const uint32_t* d_hit_cnt, int hcap, int32_t* d_sel, uint32_t* d_sel_cnt, uint32_t* d_sel_off,
                      uint32_t* d_work, uint32_t* d_n_work, hipStream_t stream, const uint8_t* d_saved = nullptr);

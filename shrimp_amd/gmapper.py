@@ -151,12 +151,25 @@ class ReadMappingsCsResult(C.Structure):   # gm_read_mappings_cs_t: ReadMappings
     _fields_ = ReadMappingsResult._fields_ + [("post_quals_len", C.c_uint64), ("post", C.c_void_p), ("post_quals", C.c_void_p), ("qralign", C.c_void_p)]
 
 
+class PairMapping(C.Structure):     # gm_pair_mapping_t: one paired mapping of gm_pair_mappings (checked against gm_pair_mapping_size())
+    _fields_ = [("pair", C.c_int32), ("hit", C.c_int32 * 2), ("score", C.c_int32), ("pct_score", C.c_int32), ("key", C.c_int32), ("insert_size", C.c_int32),
+                ("mapq", C.c_int32 * 2), ("as", C.c_int32 * 2), ("improper", C.c_int32), ("z", (C.c_double * 4) * 2)]
+
+
+class PairMappingsResult(C.Structure):   # gm_pair_mappings_t: what gm_pair_mappings fills (checked against gm_pair_mappings_size())
+    _fields_ = [("n_pairs", C.c_int32), ("has_edit", C.c_int32), ("n_hits", C.c_uint64 * 2), ("n_pmaps", C.c_uint64), ("n_umaps", C.c_uint64 * 2), ("cigar_len", C.c_uint64 * 2),
+                ("edit_len", C.c_uint64 * 2), ("ops_len", C.c_uint64 * 2), ("hits", C.c_void_p * 2), ("hit_off", C.c_void_p * 2), ("hit_kind", C.c_void_p * 2),
+                ("recs", C.c_void_p * 2), ("pmaps", C.c_void_p), ("pmap_off", C.c_void_p), ("umaps", C.c_void_p * 2), ("umap_off", C.c_void_p * 2), ("umap_z45", C.c_void_p * 2),
+                ("cigar", C.c_void_p * 2), ("cigar_off", C.c_void_p * 2), ("edit", C.c_void_p * 2), ("edit_off", C.c_void_p * 2), ("ops", C.c_void_p * 2)]
+
+
 SW_FULL_REC_DTYPE = np.dtype(SwFullRec)      # the structured numpy view of an array of them
 POST_REC_DTYPE = np.dtype(PostRec)
 ANCHOR_DTYPE = np.dtype(Anchor)
 READ_WINDOW_DTYPE = np.dtype(ReadWindow)
 PASS1_HIT_DTYPE = np.dtype(Pass1Hit)
 MAPPING_DTYPE = np.dtype(Mapping)
+PAIR_MAPPING_DTYPE = np.dtype(PairMapping)
 # one row of ReadMappings.table(): a mapping as a SAM record states it
 MAPPING_TABLE_DTYPE = np.dtype([("read", np.int32), ("contig", np.int32), ("strand", np.int32), ("pos", np.uint32), ("mapq", np.int32), ("as", np.int32), ("nm", np.int32),
                                 ("hit", np.int32)])
@@ -222,6 +235,31 @@ class ReadMappingsCs(ReadMappings):
         a = int(self.post["qual_off"][i]); return self.post_quals[a:a + int(self.post["qual_len"][i])]
 
 
+class PairMappings:
+    """What Session.pair_mappings returns: the arrays of gm_pair_mappings_t as numpy arrays.  Per mate m (0 / 1), as lists of two: hits (PASS1_HIT_DTYPE), hit_off,
+    hit_kind (0 a hit of the paired pass, 1 of the half-paired rescue), recs (SW_FULL_REC_DTYPE), umaps (MAPPING_DTYPE; hit: the index in hits[m]), umap_off, umap_z45
+    ([n, 2]: the Z4 and Z5 values), cigar_buf / cigar_off, edit_buf / edit_off (None unless the session prints edit strings), ops (want_ops only, else None).  For the
+    pair: pmaps (PAIR_MAPPING_DTYPE; hit[m]: the index within the pair's own slice of hits[m]), pmap_off."""
+    def __init__(self, n_pairs, hits, hit_off, hit_kind, recs, pmaps, pmap_off, umaps, umap_off, umap_z45, cigar_buf, cigar_off, edit_buf, edit_off, ops, contig_len):
+        self.n_pairs, self.hits, self.hit_off, self.hit_kind, self.recs, self.pmaps, self.pmap_off = n_pairs, hits, hit_off, hit_kind, recs, pmaps, pmap_off
+        self.umaps, self.umap_off, self.umap_z45, self.cigar_buf, self.cigar_off, self.edit_buf, self.edit_off = umaps, umap_off, umap_z45, cigar_buf, cigar_off, edit_buf, edit_off
+        self.ops, self.contig_len = ops, contig_len
+
+    def cigar(self, m, i): return self.cigar_buf[m][int(self.cigar_off[m][i]):int(self.cigar_off[m][i + 1])]
+
+    def edit(self, m, i):
+        if self.edit_off[m] is None: raise GmError("pair_mappings: the session prints no edit strings (extra_sam_fields)")
+        return self.edit_buf[m][int(self.edit_off[m][i]):int(self.edit_off[m][i + 1])]
+
+    def pair_hit(self, m, k):
+        """the index in hits[m] / recs[m] of mate m's hit of paired mapping k"""
+        return int(self.hit_off[m][int(self.pmaps["pair"][k])]) + int(self.pmaps["hit"][k][m])
+
+    def positions(self, m, hit_index):
+        """POS of mate m's mappings on the hits `hit_index`, as the SAM records print it"""
+        return mapping_positions(self.hits[m], self.recs[m], self.contig_len, hit_index)
+
+
 # every entry point include/gmapper_hip.h declares
 EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", "gm_preprocess_read_text", "gm_map_pairs_cs_fastq", "gm_map_reads_file", "gm_merge_options_default", "gm_merge_sam", "gm_release_cache", "gm_map_pairs_cs", "gm_last_error", "gm_device_count", "gm_params_default", "gm_params_default_cs", "gm_index_build", "gm_index_build_fasta", "gm_index_n_contigs", "gm_index_contig", "gm_sam_header", "gm_index_build_timing", "gm_index_free", "gm_index_list_cutoff",
            "gm_index_save", "gm_index_load", "gm_index_bytes", "gm_index_n_slabs", "gm_index_has_buckets", "gm_index_get_list", "gm_index_device_array", "gm_index_meta", "gm_index_alloc_like",
@@ -237,6 +275,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_read_windows", "gm_read_window_size", "gm_select_pass1", "gm_pass1_hit_size", "gm_select_pass2", "gm_mapping_size", "gm_score_windows", "gm_select_pass1_f1", "gm_read_hits", "gm_sam_records", "gm_sam_input_size", "gm_read_mappings", "gm_read_mappings_free", "gm_read_mappings_size",
            "gm_read_mappings_cs", "gm_read_mappings_cs_free", "gm_read_mappings_cs_size",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
+           "gm_pair_mappings", "gm_pair_mappings_free", "gm_pair_mappings_size", "gm_pair_mapping_size", "gm_debug_pair_select",
            "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
 
 _lib = None
@@ -362,6 +401,14 @@ def lib():
     L.gm_read_mappings_free.argtypes = [C.POINTER(ReadMappingsResult)]; L.gm_read_mappings_free.restype = None
     if L.gm_read_mappings_size() != C.sizeof(ReadMappingsResult):
         raise GmError("gm_read_mappings_t is %d bytes in the library, %d in ReadMappingsResult" % (L.gm_read_mappings_size(), C.sizeof(ReadMappingsResult)))
+    L.gm_pair_mapping_size.argtypes = []; L.gm_pair_mapping_size.restype = C.c_int
+    L.gm_pair_mappings_size.argtypes = []; L.gm_pair_mappings_size.restype = C.c_int
+    L.gm_pair_mappings.argtypes = [vp, C.c_int, C.c_int, u32p, C.c_int, u32p, C.POINTER(PairOpts), C.c_int, C.POINTER(PairMappingsResult), C.POINTER(MapStats)]
+    L.gm_pair_mappings_free.argtypes = [C.POINTER(PairMappingsResult)]; L.gm_pair_mappings_free.restype = None
+    L.gm_debug_pair_select.argtypes = [vp, C.c_int, C.c_int, u32p, C.POINTER(C.c_int32), u32p, C.POINTER(C.c_int32), u32p, u32p, u32p, u32p, u32p, u32p]
+    for fn, size, what in ((L.gm_pair_mapping_size, PAIR_MAPPING_DTYPE.itemsize, "gm_pair_mapping_t"), (L.gm_pair_mappings_size, C.sizeof(PairMappingsResult), "gm_pair_mappings_t")):
+        if fn() != size:
+            raise GmError("%s is %d bytes in the library, %d in its Python mirror" % (what, fn(), size))
     L.gm_read_mappings_cs_size.argtypes = []; L.gm_read_mappings_cs_size.restype = C.c_int
     L.gm_read_mappings_cs.argtypes = [vp, C.c_int, C.c_int, u32p, u8p, C.c_char_p, C.c_int, C.c_int, C.POINTER(ReadMappingsCsResult), C.POINTER(MapStats)]
     L.gm_read_mappings_cs_free.argtypes = [C.POINTER(ReadMappingsCsResult)]; L.gm_read_mappings_cs_free.restype = None
@@ -1054,6 +1101,59 @@ class Session:
             L.gm_read_mappings_free(C.byref(R))
         self.stats = st.as_dict(); self._windows_read_len = Lr
         return res
+
+    def pair_mappings(self, mates1, mates2, opts=None, want_ops=False):
+        """A chunk of read pairs to mapping arrays in one call (gm_pair_mappings: the pipeline of map_pairs with the pair selection on the device and arrays in place
+        of SAM text): mates1 [n, L1], mates2 [n, L2] uint8 codes, opts a PairOpts (None: the defaults) -> PairMappings.  Letter space; match_mode 4 and 3.  want_ops: the
+        edit operations of the records come down too.  The stage counters of the call are left in self.stats."""
+        from .synth import pack_reads
+        m1 = np.ascontiguousarray(mates1, dtype=np.uint8); m2 = np.ascontiguousarray(mates2, dtype=np.uint8)
+        if m1.ndim != 2 or m2.ndim != 2 or m1.shape[0] != m2.shape[0]:
+            raise ValueError("pair_mappings: mates1 [n, L1] and mates2 [n, L2] must hold the same number of reads")
+        n = m1.shape[0]
+        p1 = np.ascontiguousarray(pack_reads(m1)); p2 = np.ascontiguousarray(pack_reads(m2))
+        o = opts if opts is not None else PairOpts.default()
+        L = lib(); R = PairMappingsResult(); st = MapStats(); u32p = C.POINTER(C.c_uint32)
+        _check(L.gm_pair_mappings(self.h, n, m1.shape[1], p1.ctypes.data_as(u32p), m2.shape[1], p2.ctypes.data_as(u32p), C.byref(o), 1 if want_ops else 0, C.byref(R), C.byref(st)),
+               "gm_pair_mappings")
+        try:
+            def take(p, count, dtype):
+                a = np.zeros(count, dtype=dtype)
+                if count and p: C.memmove(a.ctypes.data, p, count * a.dtype.itemsize)
+                return a
+            text = lambda p, k: C.string_at(p, int(k)) if p else b""
+            nh = [int(R.n_hits[m]) for m in (0, 1)]; nu = [int(R.n_umaps[m]) for m in (0, 1)]
+            res = PairMappings(n, [take(R.hits[m], nh[m], PASS1_HIT_DTYPE) for m in (0, 1)], [take(R.hit_off[m], n + 1, np.uint64) for m in (0, 1)],
+                               [take(R.hit_kind[m], nh[m], np.uint8) for m in (0, 1)], [take(R.recs[m], nh[m], SW_FULL_REC_DTYPE) for m in (0, 1)],
+                               take(R.pmaps, int(R.n_pmaps), PAIR_MAPPING_DTYPE), take(R.pmap_off, n + 1, np.uint64),
+                               [take(R.umaps[m], nu[m], MAPPING_DTYPE) for m in (0, 1)], [take(R.umap_off[m], n + 1, np.uint64) for m in (0, 1)],
+                               [take(R.umap_z45[m], 2 * nu[m], np.float64).reshape(nu[m], 2) for m in (0, 1)],
+                               [text(R.cigar[m], R.cigar_len[m]) for m in (0, 1)], [take(R.cigar_off[m], nh[m] + 1, np.uint64) for m in (0, 1)],
+                               [text(R.edit[m], R.edit_len[m]) if R.has_edit else None for m in (0, 1)],
+                               [take(R.edit_off[m], nh[m] + 1, np.uint64) if R.has_edit else None for m in (0, 1)],
+                               [take(R.ops[m], int(R.ops_len[m]), np.uint8) if want_ops else None for m in (0, 1)], self.index.contig_lengths())
+        finally:
+            L.gm_pair_mappings_free(C.byref(R))
+        self.stats = st.as_dict()
+        return res
+
+    def debug_pair_select(self, pair_mode, cnt0, wins0, cnt1, wins1, plist, pcnt):
+        """Test hook (gm_debug_pair_select): the device pair selection of pair_mappings beside the host loop of map_pairs on hand-made candidate lists, under this
+        session's num_outputs, strata, max_alignments and sw_full_threshold.  wins0 / wins1: [sum(cnt), 9] int32 rows (cn, gen_st, genome_start, rmapped, deletions,
+        insertions, score_full, score_max, sort_idx); plist [n, 64] uint32 candidates (a << 8) | b, pcnt [n].  -> (device pairs per pair, host pairs per pair), each a list
+        of lists of (a, b)."""
+        cnt0 = np.ascontiguousarray(cnt0, dtype=np.uint32); cnt1 = np.ascontiguousarray(cnt1, dtype=np.uint32); pcnt = np.ascontiguousarray(pcnt, dtype=np.uint32)
+        wins0 = np.ascontiguousarray(wins0, dtype=np.int32).reshape(-1, 9); wins1 = np.ascontiguousarray(wins1, dtype=np.int32).reshape(-1, 9)
+        plist = np.ascontiguousarray(plist, dtype=np.uint32)
+        n = cnt0.shape[0]
+        if cnt1.shape[0] != n or pcnt.shape[0] != n or plist.shape != (n, 64) or wins0.shape[0] != int(cnt0.sum()) or wins1.shape[0] != int(cnt1.sum()):
+            raise ValueError("debug_pair_select: the arrays do not agree")
+        out = [np.zeros((n, 64), dtype=np.uint32) for _ in range(2)]; oc = [np.zeros(n, dtype=np.uint32) for _ in range(2)]
+        u32p, i32p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+        _check(lib().gm_debug_pair_select(self.h, int(pair_mode), n, cnt0.ctypes.data_as(u32p), wins0.ctypes.data_as(i32p), cnt1.ctypes.data_as(u32p), wins1.ctypes.data_as(i32p),
+                                          plist.ctypes.data_as(u32p), pcnt.ctypes.data_as(u32p), out[0].ctypes.data_as(u32p), oc[0].ctypes.data_as(u32p),
+                                          out[1].ctypes.data_as(u32p), oc[1].ctypes.data_as(u32p)), "gm_debug_pair_select")
+        return tuple([[(int(v) >> 8, int(v) & 0xff) for v in out[k][pr, :int(oc[k][pr])]] for pr in range(n)] for k in range(2))
 
     def read_mappings_cs(self, reads_codes, initbp=None, quals=None, qual_delta=33, want_ops=False):
         """Colour reads to mappings in one call (gm_read_mappings_cs: read_hits, then per hit sw_full_cs, post_sw under the session's constants with the host re-dos and
