@@ -1073,6 +1073,9 @@ int  gm_debug_pair_select(gm_session_t *s, int pair_mode, int n_pairs, const uin
 int gm_last_lookup_timing(gm_session_t *s, double *ms, uint64_t *alg_bytes, int *launches);
 /* name of the seed-lookup kernel the last mapping call launched (k_lookup_bkt / k_lookup_v4 / k_lookup_v3 / k_lookup): what the roofline figures refer to */
 const char *gm_last_lookup_kernel(void);
+/* name of the pass-2 (full alignment) kernel the calling thread's last launch chose: letter space k_pass2_g4<16,int> (four windows a wave), k_pass2_g4<8,int16_t> (tuning
+ * builds) or k_pass2 (one window); colour space k_pass2_cs_g4<8,int16_t>, k_pass2_cs_g4<16,int> or k_pass2_cs.  "" before the first launch. */
+const char *gm_last_pass2_kernel(void);
 
 #ifdef __cplusplus
 }

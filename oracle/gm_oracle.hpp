@@ -119,6 +119,9 @@ struct Params {
   bool colour = false;
   int crossover_score = -20, indel_taboo_len = 0;
   double pr_xover = 0.03, pr_mismatch = .01, pr_del_open = 0, pr_del_extend = 0, pr_ins_open = 0, pr_ins_extend = 0;
+  // sensitivity checks (tests/test_long_reads.py), not options of the reference: the vector filter sees only the read's first test_vector_rows positions, the anchor
+  // list of a read-strand is cut behind its first test_anchor_cap entries; 0: off
+  int test_vector_rows = 0, test_anchor_cap = 0;
 };
 
 #define GMO_IS_ABSOLUTE(x) ((x) < 0)
@@ -473,6 +476,7 @@ static inline int sw_vector(const Params& P, const uint32_t* genome, llint goff,
   std::vector<int8_t> db(glen);
   for (int j = 0; j < glen; j++) db[j] = (int8_t)EXTRACT(genome, goff + j);
   int score = 0;
+  if (P.test_vector_rows > 0) rlen = std::min(rlen, P.test_vector_rows);
   for (int i = 0; i < rlen; i++) {
     int q = EXTRACT(read, i);
     int hdiag = 0;          // H(i-1, -1)
@@ -525,6 +529,7 @@ static inline int sw_vector_cs(const Params& P, int mismatch, const uint32_t* ge
   const int b_go = -P.b_gap_open_score, b_ge = -P.b_gap_extend_score;
   std::vector<int> H(glen + 1, 0), B(glen + 1, -b_go);
   int score = 0;
+  if (P.test_vector_rows > 0) rlen = std::min(rlen, P.test_vector_rows);
   for (int i = 0; i < rlen; i++) {
     const int q = EXTRACT(read, i);
     int hdiag = 0, hleft = 0, a = -a_go;
@@ -1323,6 +1328,7 @@ struct Mapper {
       if (idx[off] < len) { h.replace_min({l[idx[off]], off}); idx[off]++; }
       else h.extract_min();
     }
+    if (P.test_anchor_cap > 0 && A.size() > (size_t)P.test_anchor_cap) A.resize((size_t)P.test_anchor_cap);
   }
 
   // read_get_hit_list_per_strand (mapping.c:1025-1229), gapless = false, match_mode 1 or 2

@@ -314,7 +314,8 @@ static void apply_opts(Params& P, const char* opts) {
     else if (k == "match-window") P.window_len = d; else if (k == "cmw-overlap") P.window_overlap = d;
     else if (k == "cmw-threshold") P.window_gen_threshold = d; else if (k == "vec-threshold") P.sw_vect_threshold = d;
     else if (k == "full-threshold") P.sw_full_threshold = d; else if (k == "cmw-mode") P.match_mode = (int)d;
-    else if (k == "report") P.num_outputs = (int)d; else if (k == "anchor-width") P.anchor_width = (int)d;
+    else if (k == "report") { P.num_outputs = (int)d; P.num_tmp_outputs = 20 + (int)d; }      // -o N: pass 1 keeps 20 + N (gmapper.c:1915-1918)
+    else if (k == "anchor-width") P.anchor_width = (int)d;
     else if (k == "cutoff") P.list_cutoff = (uint32_t)d; else if (k == "strata") P.strata = d != 0;
     else if (k == "max-alignments") P.max_alignments = (int)d;
     else if (k == "region-bits") P.region_bits = (int)d; else if (k == "region-overlap") P.region_overlap = (int)d;
@@ -333,6 +334,7 @@ static void apply_opts(Params& P, const char* opts) {
     else if (k == "hash-spaced-kmers") P.Hflag = d != 0;     // -H
     else if (k == "extra-sam-fields") P.extra_sam_fields = d != 0;
     else if (k == "crossover") P.crossover_score = (int)d; else if (k == "indel-taboo-len") P.indel_taboo_len = (int)d;
+    else if (k == "test-vector-rows") P.test_vector_rows = (int)d; else if (k == "test-anchor-cap") P.test_anchor_cap = (int)d;      // sensitivity checks, see Params
     else if (k == "seeds") {
       P.seeds.clear(); P.max_seed_span = 0; P.min_seed_span = 64;
       size_t a = 0; while (a < v.size()) { size_t b = v.find(',', a); if (b == std::string::npos) b = v.size(); add_spaced_seed(P, v.substr(a, b - a).c_str()); a = b + 1; }

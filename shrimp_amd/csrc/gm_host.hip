@@ -632,7 +632,7 @@ static int alloc_buffers(gm_session* s, DevSet& D, int read_len, bool paired = f
 
 // pair_mode: the paired match mode when called for pairs (0: unpaired).  Modes 3 and 2 have no prune rules (a single k-mer match can open a window) and K2 takes
 // the lookup's rows directly: its LDS tier holds 4096 keys; mode 2 keeps every list entry
-static void choose_caps(gm_session* s, DevSet& D, int read_len, int pair_mode = 0) {
+static void choose_caps(const gm_session* s, DevSet& D, int read_len, int pair_mode = 0) {
   const gm_index* ix = s->ix;
   const int max_n_kmers = std::max(0, read_len - ix->min_seed_span + 1);
   double lists = 0, avg_len = 0;
@@ -1089,8 +1089,21 @@ static int ensure_host_genome(gm_session* s) {
   GM_HIP(hipMemcpy(s->h_genome.data(), s->ix->d_genome, s->ix->genome_words * 4, hipMemcpyDeviceToHost));
   return GM_OK;
 }
-static int check_read_len(const gm_session* s, int read_len) {
+// The front's own limit on the read length.  K1b's list-mode kernel (k_prune, gm_launch_prune) takes gm_prune_lds bytes of LDS for twice the survivor capacity choose_caps
+// gives reads of this length; beyond a CU's LDS its launch fails in the middle of the front.  The same arithmetic here, before anything is uploaded: on a small index
+// this binds long before the alignment kernel's LDS does.  0: the session's front runs no K1b (pair_mode as choose_caps takes it).
+static size_t pass2_front_prune_lds(const gm_session* s, int read_len, int pair_mode = 0) {
+  DevSet D; choose_caps(s, D, read_len, pair_mode);
+  if (D.scap2 <= 0) return 0;
+  return gm_prune_lds(D.scap, s->ix->n_slabs);      // (every buffer set has its d_surv_seg: the launcher's segments are the slabs)
+}
+static int check_read_len(const gm_session* s, int read_len, int pair_mode = 0) {
   if (read_len > s->P.longest_read_len || read_len >= 32768 / std::max(1, s->P.match_score)) { gm_set_error("read length %d out of range (ref: sw-vector.c:393-398)", read_len); return GM_E_RANGE; }
+  const size_t prune_lds = pass2_front_prune_lds(s, read_len, pair_mode);
+  if (prune_lds > GM_SWF_LDS_LIMIT) {
+    gm_set_error("reads of %d positions: the front's prune kernel needs %zu bytes of LDS on this index and seed set, beyond the %zu of a CU", read_len, prune_lds, (size_t)GM_SWF_LDS_LIMIT);
+    return GM_E_RANGE;
+  }
   // the window of these reads (window_len_of, before its cut to 16 bits) against what pass 2 can take: nothing is uploaded for a window beyond it
   const double w = s->P.window_len < 0 ? -s->P.window_len : read_len * (s->P.window_len / 100.0);
   const int w_max = gm_pass2_max_window(s->P.colour_space ? 1 : 0, s->P.local_alignment ? 1 : 0, read_len);

@@ -235,7 +235,7 @@ struct PairCall {
     scp = s->sc; scp.match_mode = pmode == 4 ? 2 : (pmode == 3 ? 3 : 1); scp.min_matches = pmode == 4 ? 2 : 1;      // hit_list.match_mode, pass1.min_matches of the paired set
     scr = s->sc; scr.min_matches = 2;                                                                                // the half-paired rescue's pass 1
     len[0] = len1; len[1] = len2; mates[0] = m1; mates[1] = m2;
-    for (int m = 0; m < 2; m++) { rc = check_read_len(s, len[m]); if (rc) return rc; }
+    for (int m = 0; m < 2; m++) { rc = check_read_len(s, len[m], pmode); if (rc) return rc; }
     GM_HIP(hipSetDevice(s->ix->device));
     if (stats) memset(stats, 0, sizeof *stats);
     s->last_lookup_ms = 0; s->last_lookup_bytes = 0; s->last_lookup_launches = 0;

@@ -28,17 +28,7 @@ extern "C" void gm_read_mappings_cs_free(gm_read_mappings_cs_t* out) {
   memset(out, 0, sizeof *out);
 }
 
-// The front's own limit on the read length.  K1b's list-mode kernel (k_prune, gm_launch_prune) takes 8 << hbits bytes of LDS for twice the survivor capacity choose_caps
-// gives reads of this length; beyond a CU's LDS its launch fails in the middle of the front (gm_read_hits alike).  The same arithmetic here, before anything is uploaded:
-// on a small index this binds long before the alignment kernel's LDS does.  0: the session's front runs no K1b.
-static size_t pass2_front_prune_lds(gm_session_t* s, int read_len) {
-  DevSet D; choose_caps(s, D, read_len);
-  if (D.scap2 <= 0) return 0;
-  const int segs = std::max(1, s->ix->n_slabs);
-  int hbits = 8; while ((1 << hbits) < 2 * std::max(128, (segs > 1 ? (2 * D.scap) / segs : D.scap))) hbits++;
-  return (size_t)8 << hbits;
-}
-
+// (the front's own limit on the read length: pass2_front_prune_lds, beside check_read_len in gm_host.hip)
 namespace {
 // one sub-batch of gm_read_mappings_cs behind its records: post_sw's answers per hit and the host re-dos
 struct Pass2CsBatch {

@@ -215,11 +215,8 @@ int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc, const uint32_t* 
                     const int32_t* d_sel_sidx = nullptr, int input_strand = 0, int write_back = 0,
                     uint32_t* d_order = nullptr, uint32_t* d_cls_cnt = nullptr);        // the work items listed by kind (as many words as d_work), four counter words; without them: the one-window kernel
 
-// The longest window pass 2 takes beside reads of read_len: what the kernel gm_launch_pass2 / gm_launch_pass2_cs choose fits into GM_SWF_LDS_LIMIT, and no more than the
-// 16 bits of GmHit.w_len.  gm_map_reads / gm_map_pairs refuse a longer window (GM_E_RANGE) before they upload anything.
-int gm_pass2_max_window(int colour, int local, int read_len);
-size_t gm_pass2_g4_lds(int ng, int read_len, int window_len);      // letter space, ng = 4 / 8 windows a wave
-size_t gm_pass2_cs_lds(int ng, int read_len, int window_len);      // colour space, ng = 1 / 4 / 8
+// gm_pass2_max_window, gm_pass2_g4_lds (letter space, ng = 4 / 8 windows a wave), gm_pass2_cs_lds (colour space, ng = 1 / 4 / 8), gm_prune_lds, GM_SWF_LDS_LIMIT
+#include "gm_pass2_sizes.h"
 
 // colour-space pass 2 (sw_full_cs per selected window); ops_stride bytes per result: backtrace bytes, then (genome << 4 | read) codes
 // colour-space post_sw on the device (gm_post.hip): constants = CsPostConsts of gm_host.hip (logs taken on the host), one record per pass-2 result
@@ -299,7 +296,6 @@ int gm_launch_sw_vector_batch_cs(const GmScoreDev& sc, int n, const uint32_t* d_
 struct GmFullItem { long long goff, ax, ay; unsigned long long ops_off; int glen, rlen, alen, awidth, thresh, maxscore, flags, initbp, ops_cap, idx; };
 // v[0..10] = score read_start rmapped genome_start (window-relative) gmapped matches mismatches insertions deletions crossovers n_ops
 struct GmFullOut { int v[12]; };
-static const size_t GM_SWF_LDS_LIMIT = 160 * 1024;      // LDS of a CU: what one wave of the batch kernels may take; the admission test of the host entries and the launchers share it
 size_t gm_sw_full_batch_lds(int max_g, int max_r);
 size_t gm_sw_full_cs_batch_lds(int max_g, int max_r);
 // items[first .. first + n) by `grid` waves; wave b owns back-pointer scratch d_back + b * back_stride (bytes; colour space: uint32 words)

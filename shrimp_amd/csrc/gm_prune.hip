@@ -275,8 +275,8 @@ int gm_launch_prune(int n_reads, int read_len, int window_len, int e_max, int n_
   if (bin_bits > 12) { gm_set_error("prune: D = %u does not fit the 12-bit bin offsets", D); return GM_E_ARG; }
   // table for one slab's segment: twice the expected share of the survivor capacity (segments beyond half the table go to the heavy tier)
   const int segs = d_surv_seg ? std::max(1, n_slabs) : 1;
-  int hbits = 8; while ((1 << hbits) < 2 * std::max(128, (segs > 1 ? (2 * scap) / segs : scap))) hbits++;
-  const size_t lds = (size_t)8 << hbits;
+  const int hbits = gm_prune_hbits(scap, segs);
+  const size_t lds = gm_prune_lds(scap, segs);
   GM_HIP(gm_lds_at_least((const void*)k_prune, lds));
   // latency-bound (hash probes): as many lanes per read-strand as a segment has work for
   const int pthreads = gm_tune("GM_PRUNE_THREADS") ? atoi(gm_tune("GM_PRUNE_THREADS")) : std::min(1024, std::max(128, (1 << hbits) / 8));

@@ -1317,11 +1317,10 @@ int gm_launch_build_work(int n_reads, const uint32_t* d_sel_cnt, uint32_t* d_sel
   return GM_OK;
 }
 
-// LDS of the letter-space pass-2 kernels of NG windows a wave (k_pass2_g4: NG = 4 with int carry rows, 8 with int16_t ones): reads, windows, three carry values a column
-size_t gm_pass2_g4_lds(int ng, int read_len, int window_len) {
-  const size_t r16 = (size_t)((read_len + 15) & ~15), w16 = (size_t)((window_len + 15) & ~15);
-  return ng * r16 + ng * w16 + ng * (size_t)window_len * 3 * (ng == 8 ? sizeof(int16_t) : sizeof(int)) + 64;
-}
+static thread_local const char* g_p2_name = "";      // the kernel of the calling thread's last gm_launch_pass2 / gm_launch_pass2_cs
+extern "C" const char* gm_last_pass2_kernel(void) { return g_p2_name; }
+
+// (the LDS of the kernels of NG windows a wave: gm_pass2_g4_lds, gm_pass2_sizes.h)
 int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc_in, const uint32_t* d_reads, int n_reads, int read_len, int read_words,
                     int window_len, GmHit* d_hits, const uint16_t* d_perm, int hcap, const int32_t* d_sel, const uint32_t* d_sel_cnt,
                     const uint32_t* d_work, const uint32_t* d_n_work, GmFullRes* d_res, uint8_t* d_ops, int ops_stride,
@@ -1370,7 +1369,8 @@ int gm_launch_pass2(const GmIndexDev& ix, const GmScoreDev& sc_in, const uint32_
 #endif
     { if (sc.local) GM_P2_G4L(16, int, true); else GM_P2_G4L(16, int, false); }
 #undef GM_P2_G4L
-  } else { if (sc.local) GM_P2_LAUNCH(true); else GM_P2_LAUNCH(false); }
+    g_p2_name = g8 ? "k_pass2_g4<8,int16_t>" : "k_pass2_g4<16,int>";
+  } else { if (sc.local) GM_P2_LAUNCH(true); else GM_P2_LAUNCH(false); g_p2_name = "k_pass2"; }
 #undef GM_P2_LAUNCH
   GM_HIP(hipGetLastError());
   return GM_OK;
@@ -2076,12 +2076,7 @@ k_pass2_cs_g4(GmIndexDev ix, GmScoreDev sc, GmCsDev P, const uint32_t* __restric
   if (lane == 0) { GS_ADD(stats, GS_FULL_CALLS, fcalls); GS_ADD(stats, GS_FULL_CELLS, fcells); }
 }
 
-// LDS of the colour-space pass-2 kernels: one window a wave (ng = 1, k_pass2_cs), or NG (k_pass2_cs_g4: 4 with int carry rows, 8 with int16_t ones) -- the colours and the
-// four translations of a read, the window, twelve carry values a column
-size_t gm_pass2_cs_lds(int ng, int read_len, int window_len) {
-  const size_t q16 = (size_t)((read_len + 15) & ~15), w16 = (size_t)((window_len + 15) & ~15);
-  return ng * 5 * q16 + ng * w16 + ng * (size_t)window_len * 12 * (ng == 8 ? sizeof(int16_t) : sizeof(int)) + 64;
-}
+// (the LDS of the colour-space pass-2 kernels: gm_pass2_cs_lds, gm_pass2_sizes.h)
 int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs_params9, const uint32_t* d_reads, const uint8_t* d_initbp, int n_reads,
                        int read_len, int read_words, int window_len, GmHit* d_hits, int hcap, const int32_t* d_sel, const uint32_t* d_work,
                        const uint32_t* d_n_work, GmFullRes* d_res, uint8_t* d_ops, int ops_stride, uint32_t* d_back, size_t back_words, int grid,
@@ -2126,6 +2121,7 @@ int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs
       else { if (sc.local) GM_P2CS_GN(false, true); else GM_P2CS_GN(false, false); }
 #undef GM_P2CS_GN
 #undef GM_P2CS_G4
+      g_p2_name = g8 ? "k_pass2_cs_g4<8,int16_t>" : "k_pass2_cs_g4<16,int>";
       GM_HIP(hipGetLastError());
       return GM_OK;
     }
@@ -2137,18 +2133,9 @@ int gm_launch_pass2_cs(const GmIndexDev& ix, const GmScoreDev& sc, const int* cs
   else
   hipLaunchKernelGGL(k_pass2_cs<false>, dim3(grid), dim3(GM_WAVE), lds, stream, ix, sc, P, d_reads, d_initbp, n_reads, read_len, read_words, d_hits, hcap, d_sel,
                      d_work, d_n_work, d_res, d_ops, ops_stride, d_back, back_words, window_len, d_stats, d_xover, d_sel_sidx);
+  g_p2_name = "k_pass2_cs";
   GM_HIP(hipGetLastError());
   return GM_OK;
-}
-
-// (by the launchers' own size functions.  Letter space: the four-window kernel, which every mapping call gets; colour space: the one-window kernel, which global alignment
-// falls back to when the four-window one does not fit, and the four-window one with int carry rows, which local alignment needs -- the eight-window shape, taken only
-// within 64 KB, fits wherever that one does)
-int gm_pass2_max_window(int colour, int local, int read_len) {
-  auto lds = [&](int W) -> size_t { return !colour ? gm_pass2_g4_lds(4, read_len, W) : gm_pass2_cs_lds(local ? 4 : 1, read_len, W); };
-  int lo = 0, hi = 65535;
-  while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (lds(mid) <= GM_SWF_LDS_LIMIT) lo = mid; else hi = mid - 1; }
-  return lo;
 }
 
 // S1's ungapped filter at the seam (ref: common/sw-gapless.c:57-117): call i scores the diagonal of its own genome bitfield (window i starts at word

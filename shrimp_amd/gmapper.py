@@ -276,7 +276,7 @@ EXPORTS = ["gm_map_pairs_file", "gm_map_reads_file_cb", "gm_map_pairs_file_cb", 
            "gm_read_mappings_cs", "gm_read_mappings_cs_free", "gm_read_mappings_cs_size",
            "gm_pair_opts_default", "gm_map_pairs", "gm_map_pairs_fastq",
            "gm_pair_mappings", "gm_pair_mappings_free", "gm_pair_mappings_size", "gm_pair_mapping_size", "gm_debug_pair_select",
-           "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_abi_sizeof"]
+           "gm_last_lookup_timing", "gm_last_lookup_kernel", "gm_last_pass2_kernel", "gm_abi_sizeof"]
 
 _lib = None
 
@@ -292,6 +292,7 @@ def lib():
     u32p, vp = C.POINTER(C.c_uint32), C.c_void_p
     L.gm_last_error.restype = C.c_char_p
     L.gm_last_lookup_kernel.restype = C.c_char_p
+    L.gm_last_pass2_kernel.restype = C.c_char_p
     L.gm_device_count.restype = C.c_int
     L.gm_params_default.argtypes = [C.POINTER(Params)]
     L.gm_params_default_cs.argtypes = [C.POINTER(Params)]

@@ -87,6 +87,26 @@ static const Row ROWS[] = {
   {"default seeds, 184-base reads on a bucket-sized genome: 513 lists: no bucket kernel", 2000000, 0, 0, 11, 184, 4096, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=10704", 0, nullptr},
   {"default seeds, 187-base reads on a bucket-sized genome: 522 lists", 2000000, 0, 0, 11, 187, 4096, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=10896", 0, nullptr},
   {"default seeds, 188-base reads on a bucket-sized genome: 525 lists", 2000000, 0, 0, 11, 188, 4096, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=10960", 0, nullptr},
+  // Long reads on the 148 323 bases of tests/golden/long_genome.npz (tests/test_long_reads.py), recorded through the query mode below: the bucket kernel up to 183 bases
+  // (3 x 170 = 510 lists), v3 from 184 on -- 2 961 lists at 1 000 bases, 3 932 under the weight-16 -H set -- and the slab sweep where no region counts or mate-pair counts run
+  {"long genome, 128 bases", 148323, 0, 0, 11, 128, 200, 1, 0, "", "k_lookup_bkt", "bkt persistent=1 threads=384 lds=160 lds_p=288", 0, nullptr},
+  {"long genome, 129 bases", 148323, 0, 0, 11, 129, 200, 1, 0, "", "k_lookup_bkt", "bkt persistent=1 threads=384 lds=176 lds_p=320", 0, nullptr},
+  {"long genome, 183 bases: the last length with the bucket kernel", 148323, 0, 0, 11, 183, 200, 1, 0, "", "k_lookup_bkt", "bkt persistent=1 threads=512 lds=224 lds_p=416", 0, nullptr},
+  {"long genome, 184 bases: 513 lists, v3", 148323, 0, 0, 11, 184, 200, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=10480", 0, nullptr},
+  {"long genome, 184 bases, -n 1: the slab sweep", 148323, 0, 0, 11, 184, 200, 1, 8, "", "k_lookup", "sweep mp=6 threads=576 lds=12544", 6, nullptr},
+  {"long genome, 257 bases", 148323, 0, 0, 11, 257, 200, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=14944", 0, nullptr},
+  {"long genome, 257 bases, the weight-16 -H set: 960 lists", 148323, 0, 1, 11, 257, 200, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=19504", 0, SEEDS_REF_W16H},
+  {"long genome, 400 bases: 1 161 lists", 148323, 0, 0, 11, 400, 100, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=23664", 0, nullptr},
+  {"long genome, 400 bases, -n 1", 148323, 0, 0, 11, 400, 100, 1, 8, "", "k_lookup", "sweep mp=6 threads=1024 lds=28304", 6, nullptr},
+  {"long genome, 1 000 bases: 2 961 lists", 148323, 0, 0, 11, 1000, 40, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=60256", 0, nullptr},
+  {"long genome, 1 000 bases, the weight-16 -H set: 3 932 lists", 148323, 0, 1, 11, 1000, 40, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=79680", 0, SEEDS_REF_W16H},
+  {"long genome, 204 colours", 148323, 1, 0, 11, 204, 200, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=11712", 0, nullptr},
+  {"long genome, 205 colours", 148323, 1, 0, 11, 205, 200, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=11776", 0, nullptr},
+  {"long genome, 1 000 colours", 148323, 1, 0, 11, 1000, 30, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=60256", 0, nullptr},
+  {"long genome, mates of 250 bases, unpaired form", 148323, 0, 0, 11, 250, 100, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=14512", 0, nullptr},
+  {"long genome, mates of 250 bases, mate-pair mode 1", 148323, 0, 0, 11, 250, 100, 1, 1, "", "k_lookup", "sweep mp=1 threads=768 lds=82896", 0, nullptr},
+  {"long genome, mates of 700 bases, unpaired form", 148323, 0, 0, 11, 700, 40, 1, 0, "", "k_lookup_v3", "v3 threads=768 lds=41968", 0, nullptr},
+  {"long genome, mates of 700 bases, mate-pair mode 1", 148323, 0, 0, 11, 700, 40, 1, 1, "", "k_lookup", "sweep mp=1 threads=1024 lds=115744", 0, nullptr},
 };
 
 static std::map<std::string, std::string> g_env;

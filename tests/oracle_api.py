@@ -259,17 +259,18 @@ def sam_mapped_share_and_indels(body, n_reads):
 
 # Non-default option sets whose reference output is committed as <base>@<tag>.sam.gz (tools/make_golden.py OPTION_CASES):
 # tag -> (base golden, oracle option string (the reference's long option names), product gm_params_t fields, seeds, sam_unaligned)
+# (-o N sets num_outputs = N and num_tmp_outputs = 20 + N, gmapper.c:1915-1918: the fields name both)
 OPTION_CASES = {
     "strata": ("stress_60bp", "strata=1", dict(strata=1), None),
-    "max3_o5": ("stress_60bp", "max-alignments=3;report=5", dict(max_alignments=3, num_outputs=5), None),
+    "max3_o5": ("stress_60bp", "max-alignments=3;report=5", dict(max_alignments=3, num_outputs=5, num_tmp_outputs=25), None),
     "scores": ("stress_100bp_unal", "match=8;mismatch=-12;open-r=-30;open-q=-28;ext-r=-5;ext-q=-4;full-threshold=60;vec-threshold=60;"
                "match-window=150;cmw-overlap=80;cmw-threshold=50;report=6;anchor-width=10",
                dict(match_score=8, mismatch_score=-12, a_gap_open_score=-30, b_gap_open_score=-28, a_gap_extend_score=-5, b_gap_extend_score=-4,
                     sw_full_threshold=60.0, sw_vect_threshold=60.0, window_len=150.0, window_overlap=80.0, window_gen_threshold=50.0,
-                    num_outputs=6, anchor_width=10, sam_unaligned=1), None),
+                    num_outputs=6, num_tmp_outputs=26, anchor_width=10, sam_unaligned=1), None),
     "seeds": ("cfg2s_100bp_2Mbp", "seeds=1111101111,110110110110111,1110100111010111;cutoff=40", dict(list_cutoff=40),
               ["1111101111", "110110110110111", "1110100111010111"]),
-    "pairs_strata": ("stress_pairs_2x100", "strata=1;report=4", dict(strata=1, num_outputs=4), None),
+    "pairs_strata": ("stress_pairs_2x100", "strata=1;report=4", dict(strata=1, num_outputs=4, num_tmp_outputs=24), None),
     # --local: sw_full_ls with local_alignment = 1 (soft clips), no mapping qualities (MAPQ 255, no Z0/Z1)
     "local": ("stress_100bp_unal", "local=1", dict(local_alignment=1, sam_unaligned=1), None),
     "local60": ("stress_60bp", "local=1;full-threshold=40;vec-threshold=40", dict(local_alignment=1, sw_full_threshold=40.0, sw_vect_threshold=40.0), None),
@@ -309,7 +310,7 @@ OPTION_CASES = {
     "hashed": ("stress_60bp", "hash-spaced-kmers=1", dict(hash_seeds=1), None),
     "hashed_w16": ("cfg2s_100bp_2Mbp", "hash-spaced-kmers=1;seeds=11111111101111111,1111110111011101111,111101110010000101111011", dict(hash_seeds=1),
                    ["11111111101111111", "1111110111011101111", "111101110010000101111011"]),
-    "pairs_hashed": ("stress_pairs_2x100", "hash-spaced-kmers=1;report=3", dict(hash_seeds=1, num_outputs=3), None),
+    "pairs_hashed": ("stress_pairs_2x100", "hash-spaced-kmers=1;report=3", dict(hash_seeds=1, num_outputs=3, num_tmp_outputs=23), None),
     "pairs_local": ("stress_pairs_2x100", "local=1", dict(local_alignment=1), None),
     "pairs_ungapped": ("stress_pairs_2x100", "local=1;ungapped=1", dict(local_alignment=1, ungapped=1, anchor_width=0, a_gap_open_score=-255, b_gap_open_score=-255,
                                                                         hash_filter_calls=0), None),
@@ -541,6 +542,190 @@ def sam_distance(body, other):
     """records of `body` that are not records of `other`"""
     have = set(other.split(b"\n"))
     return sum(1 for l in body.split(b"\n") if l and l not in have)
+
+
+# Reads of 128 to 1 000 bases and colours (tools/make_golden.py --long-only, tests/test_long_reads.py).  One genome for all of them, stored once as long_genome.npz
+# (long_stress_genome of the generator: contig0, contig1 and `repeat`, the bounds of contig 0's repeat part); an input is long_<name>.npz (reads, or mates1 / mates2 /
+# names1 / names2 / mode / ins) and names the genome; the reference's body under an option set is long_<name>@<set>.sam.gz ("default" for none), made with --sam-unaligned.
+GM_SWF_LDS_LIMIT = 160 * 1024
+
+
+def gm_pass2_g4_lds(ng, read_len, window_len):
+    """shrimp_amd/csrc/gm_pass2_sizes.h restated (tests/host/pass2_sizes_main.cpp holds the two together)"""
+    r16 = (read_len + 15) & ~15; w16 = (window_len + 15) & ~15
+    return ng * r16 + ng * w16 + ng * window_len * 3 * (2 if ng == 8 else 4) + 64
+
+
+def gm_pass2_cs_lds(ng, read_len, window_len):
+    q16 = (read_len + 15) & ~15; w16 = (window_len + 15) & ~15
+    return ng * 5 * q16 + ng * w16 + ng * window_len * 12 * (2 if ng == 8 else 4) + 64
+
+
+def gm_pass2_max_window(colour, local, read_len):
+    lds = (lambda W: gm_pass2_g4_lds(4, read_len, W)) if not colour else (lambda W: gm_pass2_cs_lds(4 if local else 1, read_len, W))
+    lo, hi = 0, 65535
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if lds(mid) <= GM_SWF_LDS_LIMIT: lo = mid
+        else: hi = mid - 1
+    return lo
+
+
+def default_window(read_len):
+    """window_len_of at -w 140 %"""
+    return int(read_len * (140.0 / 100.0)) & 0xFFFF
+
+
+def pass2_kernel(colour, read_len, local=False, big=None):
+    """the kernel gm_launch_pass2 / gm_launch_pass2_cs choose for reads of read_len under default windows and scores (big: the largest change of the score a move can
+    make, 40 + 20 at the colour-space defaults), as gm_last_pass2_kernel() names it"""
+    W = default_window(read_len)
+    if not colour: return "k_pass2_g4<16,int>"
+    reach = (read_len + W) * (big or 60)
+    if reach < 16000 and gm_pass2_cs_lds(8, read_len, W) <= 64 * 1024: return "k_pass2_cs_g4<8,int16_t>"
+    if gm_pass2_cs_lds(4, read_len, W) <= GM_SWF_LDS_LIMIT: return "k_pass2_cs_g4<16,int>"
+    assert not local
+    return "k_pass2_cs"
+
+
+def _last_true(pred, lo, hi):
+    """the largest L in [lo, hi] with pred(L), pred true at lo and monotone"""
+    assert pred(lo)
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if pred(mid): lo = mid
+        else: hi = mid - 1
+    return lo
+
+
+# the last read length the four-window colour-space kernel takes at default windows, and the last one colour-space --local is admitted at (check_read_len)
+LONG_CS_G4_LAST = _last_true(lambda L: gm_pass2_cs_lds(4, L, default_window(L)) <= GM_SWF_LDS_LIMIT, 100, 1000)
+LONG_CS_LOCAL_LAST = _last_true(lambda L: L * (140.0 / 100.0) <= gm_pass2_max_window(1, 1, L), 100, 1000)
+
+_W16H = SEED_SETS["ref_w16H"][0]
+_LONG_SETS = {      # set -> (the reference's options, the oracle's, gm_params_t fields ("pair_": gm_pair_opts_t), seed strings or None)
+    "default": ([], "", {}, None),
+    "local": (["--local"], "local=1", dict(local_alignment=1), None),
+    "n1": (["-n", "1"], "cmw-mode=1", dict(match_mode=1), None),
+    "w16H": (["-H", "-s", ",".join(_W16H)], "hash-spaced-kmers=1;seeds=" + ",".join(_W16H), dict(hash_seeds=1), _W16H),
+    "extra": (["--extra-sam-fields"], "extra-sam-fields=1", dict(extra_sam_fields=1), None),
+    "w110": (["-w", "110%"], "match-window=110", dict(window_len=110.0), None),
+    "o5_strata": (["-o", "5", "--strata"], "report=5;strata=1", dict(num_outputs=5, num_tmp_outputs=25, strata=1), None),
+    "ungapped": (["--local", "-U"], "local=1;ungapped=1", dict(local_alignment=1, ungapped=1, anchor_width=0, a_gap_open_score=-255, b_gap_open_score=-255, hash_filter_calls=0), None),
+    # (colour space at unit scores: a move changes the score by 3 at the most, so `reach` stays far below 16 000 and the eight-window kernel's 64 KB decide at 204 / 205)
+    "unit": (["-m", "1", "-i", "-1", "-g", "-1", "-e", "-1", "-q", "-1", "-f", "-1", "-x", "-1"], _score_opts("unit", True), _score_fields("unit", True), None),
+    # FASTQ input with PHRED+33 qualities (letter space: --qv-offset 33; csfastq is PHRED+33 by default): the QUAL strings come with the input, not with the options
+    "fq": (["--qv-offset", "33"], "", {}, None),
+    "csfq": ([], "", {}, None),
+    "nhp": (["--no-half-paired"], "half-paired=0", dict(pair_half_paired=0), None),
+    "n3": (["-n", "3"], "mp-match-mode=3", dict(pair_match_mode=3), None),
+}
+
+
+def long_reads_of(length):
+    """reads of an unpaired input: 200 up to 257 bases or colours, 100 up to 557, 60 at 700, 40 letter-space or 30 colour-space reads at 1 000 (long_inputs)"""
+    return 200 if length <= 257 else (100 if length <= max(557, LONG_CS_G4_LAST + 1) else (60 if length < 1000 else 40))
+
+
+def _long_inputs():
+    """name -> dict(kind, length(s), n, seed, sets, and for pairs mode and ins)"""
+    d = {}
+    ls = {128: [], 129: ["local", "extra"], 183: [], 184: ["n1"], 256: [], 257: ["w16H", "extra"], 385: [], 400: ["local", "n1", "o5_strata"], 700: ["extra"], 1000: ["local", "w16H", "w110"]}
+    for k, (L, more) in enumerate(sorted(ls.items())):
+        d["ls_%d" % L] = dict(kind="ls", len=L, n=long_reads_of(L), seed=4117 if L == 1000 else 4100 + k, sets=["default"] + more, clean="extra" in more)
+    cs = {129: ["local"], 204: ["unit"], 205: ["unit"], LONG_CS_G4_LAST: [], LONG_CS_G4_LAST + 1: [], 400: ["local", "ungapped"], 1000: []}
+    for k, (L, more) in enumerate(sorted(cs.items())):
+        d["cs_%d" % L] = dict(kind="cs", len=L, n=30 if L == 1000 else long_reads_of(L), seed=4200 + k, sets=["default"] + more)
+    # FASTQ at 400 bases (QUAL lines of that length), csfastq at 200 colours (per-position crossover rows of that length)
+    d["ls_400q"] = dict(kind="ls", len=400, n=100, seed=4150, sets=["fq"], fq=33)
+    d["cs_200q"] = dict(kind="cs", len=200, n=200, seed=4250, sets=["csfq"], fq=33)
+    d["cs_%d" % LONG_CS_LOCAL_LAST] = dict(kind="cs", len=LONG_CS_LOCAL_LAST, n=60, seed=4290, sets=["local"])
+    pr = [("pairs_2x250_opp-in", (250, 250), 100, "opp-in", (200, 1200), ["default", "nhp", "n3"]),
+          ("pairs_400_100_col-fw", (400, 100), 100, "col-fw", (200, 1500), ["default", "nhp"]),
+          ("pairs_400_100_col-bw", (400, 100), 100, "col-bw", (200, 1500), ["default", "nhp"]),
+          ("pairs_2x250_opp-out", (250, 250), 100, "opp-out", (200, 1200), ["default", "nhp"]),
+          ("pairs_2x700_opp-in", (700, 700), 40, "opp-in", (700, 3000), ["default", "nhp"]),
+          ("cs_pairs_2x150_opp-in", (150, 150), 100, "opp-in", (200, 1200), ["default", "nhp"])]
+    # (share: of the pairs drawn from the repeat part.  Under --no-half-paired the reference loses a quarter of the 400 + 100 pairs that lie in unique sequence and none of
+    # those in the repeats; with half of the pairs there fewer than 90 % of the mates keep a record, with four fifths they do -- on one draw of the col-bw pairs in eight: 83 to 87 of 100 pairs stay paired on the others, 91 on seed 4312)
+    for k, (name, lens, n, mode, ins, sets) in enumerate(pr):
+        d[name] = dict(kind="cs_pairs" if name.startswith("cs_") else "pairs", len=lens, n=n, seed=4312 if mode == "col-bw" else 4300 + k, sets=sets, mode=mode, ins=ins, share=0.8 if lens == (400, 100) else 0.5)
+    return d
+
+
+LONG_INPUTS = _long_inputs()
+# tag "<input>:<set>" -> (input, the reference's options, the oracle's options, fields, seeds)
+LONG_CASES = {"%s:%s" % (name, st): (name,) + _LONG_SETS[st] for name, inp in LONG_INPUTS.items() for st in inp["sets"]}
+# (-U aligns without gaps: no record of it can hold an I or a D)
+LONG_NO_INDELS = ("cs_400:ungapped",)
+# (--strata prints the mappings of a read's best score alone: a read has a second record only where two places tie, which 3 % substitutions leave to a few reads)
+LONG_NO_MULTI = ("ls_400:o5_strata",)
+# what every fixture holds at the least (tools/make_golden.py asserts it when it writes them, tests/test_long_reads.py on the committed files): shares of the reads with a
+# mapped record and with more than one, of the records on the reverse strand and with an I or a D in the CIGAR; pairs: the properly paired share of the pairs and, with
+# half-paired mappings allowed, the share of the records that are half-paired or unpaired
+LONG_MIN = dict(mapped=0.90, multi=0.10, reverse=0.30, indel=0.50, proper=0.60, loose=0.05)
+
+
+def long_file(tag):
+    name, st = tag.split(":")
+    return "long_%s@%s.sam.gz" % (name, st)
+
+
+def load_long_sam(tag):
+    with gzip.open(os.path.join(ROOT, "tests", "golden", long_file(tag)), "rb") as f:
+        return f.read()
+
+
+_long_genome = []
+def load_long_genome():
+    """(contigs, (lo, hi) of the repeat part of contig 0)"""
+    if not _long_genome:
+        z = np.load(os.path.join(ROOT, "tests", "golden", "long_genome.npz"))
+        _long_genome.append(([z["contig0"], z["contig1"]], tuple(int(x) for x in z["repeat"])))
+    return _long_genome[0]
+
+
+def load_long_input(name):
+    """the genome's contigs beside an input's arrays: reads, or m1 / m2 / names1 / names2 / mode / ins"""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "long_%s.npz" % name))
+    assert str(z["genome"]) == "long_genome"
+    g = dict(contigs=load_long_genome()[0], contig_names=[b"contig1", b"contig2"])
+    if "reads" in z.files:
+        g["reads"] = z["reads"]
+        if "quals" in z.files: g["quals"] = [bytes(q) for q in z["quals"]]; g["qual_delta"] = int(z["qual_delta"])
+    else: g.update(m1=z["mates1"], m2=z["mates2"], names1=[bytes(x) for x in z["names1"]], names2=[bytes(x) for x in z["names2"]], mode=str(z["mode"]), ins=tuple(int(x) for x in z["ins"]))
+    return g
+
+
+def long_counts(body, n, pairs=False):
+    """the counts LONG_MIN speaks of, from a SAM body without header lines: n reads (pairs: n pairs, a mate a read)"""
+    per = {}; recs = rev = indel = loose = 0; proper = set()
+    for l in body.split(b"\n"):
+        if not l or l.startswith(b"@"): continue
+        t = l.split(b"\t"); fl = int(t[1])
+        if fl & 4: continue
+        key = (t[0], fl & 0xC0); per[key] = per.get(key, 0) + 1
+        recs += 1; rev += bool(fl & 16); indel += (b"I" in t[5] or b"D" in t[5])
+        if pairs:
+            if fl & 2: proper.add(t[0])
+            else: loose += 1
+    reads = 2 * n if pairs else n
+    d = dict(reads=reads, records=recs, mapped=len(per), multi=sum(1 for v in per.values() if v > 1), reverse=rev, indel=indel)
+    if pairs: d.update(pairs=n, proper=len(proper), loose=loose)
+    return d
+
+
+def long_conditions(tag, c):
+    """the conditions of LONG_MIN a fixture with the counts c misses (an empty list: none)"""
+    m = LONG_MIN; bad = []
+    if c["mapped"] < m["mapped"] * c["reads"]: bad.append("mapped")
+    if tag not in LONG_NO_MULTI and c["multi"] < m["multi"] * c["reads"]: bad.append("multi")
+    if c["reverse"] < m["reverse"] * c["records"]: bad.append("reverse")
+    if tag not in LONG_NO_INDELS and c["indel"] < m["indel"] * c["records"]: bad.append("indel")
+    if "pairs" in c:
+        if c["proper"] < m["proper"] * c["pairs"]: bad.append("proper")
+        if not tag.endswith(":nhp") and c["loose"] < m["loose"] * c["records"]: bad.append("loose")
+    return bad
 
 
 def load_kat_anchors(colour=False):

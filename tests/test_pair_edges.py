@@ -18,7 +18,7 @@ PAIR_MODES = ["opp-in", "opp-out", "col-fw", "col-bw"]
 SHIFT = {"opp-in": 0, "opp-out": 100, "col-fw": 60, "col-bw": 40}           # the reference pairs a fragment iff 180 + SHIFT <= f <= 420 + SHIFT
 # tag -> (oracle options, gm_pair_opts_t fields, gm_params_t fields)
 OPTS = {None: ("", {}, {}), "pe_nhp": ("half-paired=0", dict(half_paired=0), {}), "pe_n3": ("mp-match-mode=3", dict(match_mode=3), {}),
-        "pe_n3_nhp": ("mp-match-mode=3;half-paired=0", dict(match_mode=3, half_paired=0), {}), "ph_o3_strata": ("strata=1;report=3", {}, dict(strata=1, num_outputs=3))}
+        "pe_n3_nhp": ("mp-match-mode=3;half-paired=0", dict(match_mode=3, half_paired=0), {}), "ph_o3_strata": ("strata=1;report=3", {}, dict(strata=1, num_outputs=3, num_tmp_outputs=23))}
 LS_RUNS = [("pair_edges_" + m, t) for m in PAIR_MODES for t in (None, "pe_nhp", "pe_n3", "pe_n3_nhp")]
 CS_RUNS = [("pair_edges_cs_" + m, t) for m in ("opp-in", "col-bw") for t in (None, "pe_nhp")]
 HEAP_RUNS = [(b, t) for b in ("pair_heap_tandem", "pair_heap_ties") for t in (None, "ph_o3_strata")]

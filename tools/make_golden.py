@@ -1617,8 +1617,143 @@ def anchor_kat_cases():
         print("%s: %d bytes;" % (name, os.path.getsize(path)), "; ".join("%s: %s" % (k, ", ".join("%d %s" % (c, t) for t, c in sorted(v.items()))) for k, v in per.items()))
 
 
+# Reads of 128 to 1 000 bases and colours (tests/oracle_api.py LONG_INPUTS / LONG_CASES, tests/test_long_reads.py)
+def long_stress_genome(seed=2025):
+    """Two contigs of about 150 kbp together, for long reads.  Contig 1: 20 kbp, then the repeat part -- eight copies of a 1 500-base family at 2 % divergence with spacers
+    of 300 to 2 000 bases between them, six copies in tandem of a 700-base unit at 1.4 % -- then 15 kbp, a 9-mer in tandem x 300, 10 kbp, a run of 200 N, 20 kbp.
+    Contig 2: 25 kbp, a reverse-complement copy of the family, 8 kbp, a forward copy, 22 kbp.  Returns (contigs, (lo, hi): the repeat part of contig 1)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    def rnd(n): return rng.integers(0, 4, size=n, dtype=np.uint8)
+    def copy_of(x, div):
+        y = x.copy(); k = rng.random(len(x)) < div
+        y[k] = (y[k] + rng.integers(1, 4, int(k.sum()))) & 3
+        return y.astype(np.uint8)
+    fam = rnd(1500); unit = rnd(700)
+    c1 = [rnd(20000)]; lo = 20000
+    for _ in range(8): c1 += [copy_of(fam, 0.02), rnd(int(rng.integers(300, 2001)))]
+    c1 += [copy_of(unit, 0.014) for _ in range(6)] + [rnd(500)]
+    hi = sum(len(x) for x in c1)
+    c1 += [rnd(15000), np.tile(np.array([0, 1, 2, 3, 3, 2, 1, 0, 2], dtype=np.uint8), 300), rnd(10000), np.full(200, 15, dtype=np.uint8), rnd(20000)]
+    c2 = [rnd(25000), synth.COMPLEMENT[copy_of(fam, 0.02)[::-1]], rnd(8000), copy_of(fam, 0.02), rnd(22000)]
+    return [np.concatenate(c1).astype(np.uint8), np.concatenate(c2).astype(np.uint8)], (lo, hi)
+
+
+def _long_mutate(src, L, rng, p_sub=0.03, p_ins=0.004, p_del=0.004):
+    """synth.make_reads' walk along source rows of at least L + 16 bases: substitutions, insertions and deletions per base"""
+    n, margin = src.shape; out = np.empty((n, L), dtype=np.uint8); ptr = np.zeros(n, dtype=np.int64); rows = np.arange(n)
+    for j in range(L):
+        r = rng.random(n); ins = r < p_ins; dele = (~ins) & (r < p_ins + p_del)
+        ptr = np.minimum(ptr + dele, margin - 1)
+        b = src[rows, ptr]
+        sub = (~ins) & (rng.random(n) < p_sub)
+        b = np.where(sub & (b < 4), (b + rng.integers(1, 4, size=n, dtype=np.uint8)) & 3, b)
+        b = np.where(ins, rng.integers(0, 4, size=n, dtype=np.uint8), b)
+        out[:, j] = b
+        ptr = np.minimum(ptr + (~ins), margin - 1)
+    return out
+
+
+def long_reads(contigs, rep, inp):
+    """the reads of an unpaired input: every second one from the repeat part.  Letter space: 3 % substitutions, 0.4 % insertions and deletions; colour space: an indel of one to
+    three bases a read, 3 % colour errors, 0.4 % skipped cycles.  clean: no N in a read (the reference does not return from --extra-sam-fields on one)"""
+    part = [contigs[0][rep[0]:rep[1]]]; n = inp["n"]; L = inp["len"]; k = n // 2
+    if inp["kind"] == "cs":
+        a = synth.make_cs_reads(part, k, L, inp["seed"], p_col=0.03, p_dot=0.004)[0]; b = synth.make_cs_reads(contigs, n - k, L, inp["seed"] + 50, p_col=0.03, p_dot=0.004)[0]
+    else:
+        a = synth.make_reads(part, k, L, inp["seed"], p_sub=0.03, p_ins=0.004, p_del=0.004)[0]; b = synth.make_reads(contigs, n - k, L, inp["seed"] + 50, p_sub=0.03, p_ins=0.004, p_del=0.004)[0]
+    reads = np.empty((n, a.shape[1]), dtype=np.uint8)
+    reads[0:2 * k:2] = a; reads[1:2 * k:2] = b[:k]; reads[2 * k:] = b[k:]
+    if inp.get("clean"):
+        rng = np.random.Generator(np.random.PCG64(inp["seed"] + 99)); bad = reads > 3
+        reads = np.where(bad, rng.integers(0, 4, size=reads.shape, dtype=np.uint8), reads).astype(np.uint8)
+    return reads
+
+
+def long_pairs(contigs, rep, inp):
+    """the mates of a paired input (letter codes): fragments whose insert size, as the pair mode measures it, is drawn about the middle of -I (every twentieth pair: 1 000
+    beyond its upper bound, so that its mates map on their own), the share inp["share"] of the fragments from the repeat part, from either strand; each mate walks its end of the fragment
+    with 3 % substitutions and 0.4 % insertions and deletions, then the pair mode turns the mates (as pe_mates)"""
+    rng = np.random.Generator(np.random.PCG64(inp["seed"])); n = inp["n"]; L1, L2 = inp["len"]; lo, hi = inp["ins"]; mode = inp["mode"]
+    shift = {"opp-in": 0, "opp-out": L1 + L2, "col-fw": L2, "col-bw": L1}[mode]
+    A = np.empty((n, L1 + 16), dtype=np.uint8); B = np.empty((n, L2 + 16), dtype=np.uint8)
+    for i in range(n):
+        f = int(np.rint(rng.normal((lo + hi) / 2 + shift, (hi - lo) / 16)))
+        if i % 20 == 19: f = hi + shift + 1000
+        f = max(f, max(L1, L2) + 16)
+        if int((i + 1) * inp["share"]) > int(i * inp["share"]): c = contigs[0]; p = int(rng.integers(rep[0], rep[1] - f))
+        else: c = contigs[int(rng.integers(0, 2))]; p = int(rng.integers(0, len(c) - f))
+        frag = c[p:p + f]
+        if rng.random() < 0.5: frag = _rc(frag)
+        frag = np.where(frag > 3, rng.integers(0, 4, size=len(frag), dtype=np.uint8), frag).astype(np.uint8)
+        A[i] = frag[:L1 + 16]; B[i] = _rc(frag)[:L2 + 16]
+    a = _long_mutate(A, L1, rng); b = _long_mutate(B, L2, rng)
+    if mode == "opp-out": a, b = synth.COMPLEMENT[a[:, ::-1]], synth.COMPLEMENT[b[:, ::-1]]
+    elif mode == "col-fw": b = synth.COMPLEMENT[b[:, ::-1]]
+    elif mode == "col-bw": a = synth.COMPLEMENT[a[:, ::-1]]
+    return np.ascontiguousarray(a, dtype=np.uint8), np.ascontiguousarray(b, dtype=np.uint8)
+
+
+def _long_ref_body(d, cs, args, limit=300, rfile=None):
+    """the reference on d/g.fa and d/r.*, under a time limit: its SAM text without the @PG / @RG lines"""
+    exe = os.path.join(ROOT, "oracle", "_ref", "gmapper-cs" if cs else "gmapper-ls")
+    p = subprocess.run(["timeout", "-k", "5", str(limit), exe, "-N", "4", "--sam-unaligned", *args, os.path.join(d, rfile or ("r.csfasta" if cs else "r.fa")), os.path.join(d, "g.fa")], capture_output=True)
+    assert p.returncode == 0, (args, p.returncode, p.stderr[-2000:])
+    return b"".join(l + b"\n" for l in p.stdout.split(b"\n") if l and not l.startswith(b"@PG") and not l.startswith(b"@RG"))
+
+
+def long_cases():
+    """--long-only: long_genome.npz, the inputs of LONG_INPUTS and the reference's bodies of LONG_CASES.  Prints every fixture's counts and asserts LONG_MIN on them."""
+    from tests import oracle_api as oa
+    contigs, rep = long_stress_genome(); cn = [b"contig1", b"contig2"]
+    _npz_fixed(os.path.join(OUT, "long_genome.npz"), contig0=contigs[0], contig1=contigs[1], repeat=np.array(rep))
+    print("long_genome: contigs of %d and %d bases, repeat part [%d, %d) of contig1, %d bytes" % (len(contigs[0]), len(contigs[1]), rep[0], rep[1], os.path.getsize(os.path.join(OUT, "long_genome.npz"))))
+    total = 0; missed = []
+    for name, inp in oa.LONG_INPUTS.items():
+        cs = inp["kind"].startswith("cs"); pairs = inp["kind"].endswith("pairs")
+        with tempfile.TemporaryDirectory() as d:
+            write_fa_codes(os.path.join(d, "g.fa"), cn, contigs)
+            if pairs:
+                m1, m2 = long_pairs(contigs, rep, inp)
+                if cs: m1 = synth.cs_from_letters(m1, inp["seed"] + 1, p_col=0.03); m2 = synth.cs_from_letters(m2, inp["seed"] + 2, p_col=0.03)
+                n1 = [b"p%d/1" % i for i in range(inp["n"])]; n2 = [b"p%d/2" % i for i in range(inp["n"])]
+                names = [x for pair in zip(n1, n2) for x in pair]; rows = [x for pair in zip(list(m1), list(m2)) for x in pair]
+                if cs:
+                    with open(os.path.join(d, "r.csfasta"), "wb") as f:
+                        for nm, row in zip(names, rows): f.write(b">" + nm + b"\n" + b"ACGT"[row[0]:row[0] + 1] + bytes(b"0123"[c] if c < 4 else ord(".") for c in row[1:]) + b"\n")
+                else: write_fa_codes(os.path.join(d, "r.fa"), names, rows)
+                _npz_fixed(os.path.join(OUT, "long_%s.npz" % name), genome=np.array("long_genome"), mates1=m1, mates2=m2, names1=np.array(n1), names2=np.array(n2), mode=np.array(inp["mode"]), ins=np.array(inp["ins"]))
+                more = ["-p", inp["mode"], "-I", "%d,%d" % inp["ins"]]
+            else:
+                reads = long_reads(contigs, rep, inp)
+                if inp.get("fq"):                                       # FASTQ / csfastq input, PHRED+33: a quality of 2 to 40 a base or colour
+                    q = (np.random.default_rng(inp["seed"] + 7).integers(2, 41, size=(len(reads), inp["len"])) + 33).astype(np.uint8)
+                    T = np.frombuffer(b"ACGTUMRWSYKVHDBN", dtype=np.uint8); tab = np.full(16, ord("."), dtype=np.uint8); tab[:4] = np.frombuffer(b"0123", dtype=np.uint8)
+                    with open(os.path.join(d, "r.csfastq" if cs else "r.fq"), "wb") as f:
+                        for i in range(len(reads)):
+                            seq = b"ACGT"[reads[i, 0]:reads[i, 0] + 1] + tab[reads[i, 1:]].tobytes() if cs else T[reads[i]].tobytes()
+                            f.write(b"@r%d\n" % i + seq + b"\n+\n" + q[i].tobytes() + b"\n")
+                    _npz_fixed(os.path.join(OUT, "long_%s.npz" % name), genome=np.array("long_genome"), reads=reads, quals=q, qual_delta=np.array(33))
+                else:
+                    if cs: synth.write_csfasta_reads(os.path.join(d, "r.csfasta"), reads)
+                    else: write_fa_codes(os.path.join(d, "r.fa"), [b"r%d" % i for i in range(len(reads))], list(reads))
+                    _npz_fixed(os.path.join(OUT, "long_%s.npz" % name), genome=np.array("long_genome"), reads=reads)
+                more = []
+            for st in inp["sets"]:
+                tag = "%s:%s" % (name, st)
+                body = _long_ref_body(d, cs, more + oa.LONG_CASES[tag][1], rfile=("r.csfastq" if cs else "r.fq") if inp.get("fq") else None)
+                path = os.path.join(OUT, oa.long_file(tag)); _gz_fixed(path, body)
+                c = oa.long_counts(body, inp["n"], pairs); bad = oa.long_conditions(tag, c); size = os.path.getsize(path); total += size
+                print("%-32s %s, %d bytes%s" % (tag, ", ".join("%s %d" % kv for kv in c.items()), size, "  MISSES " + ",".join(bad) if bad else ""))
+                if bad: missed.append((tag, bad))
+                assert size <= 200_000, (tag, size)
+    print("long goldens: %d cases, %d bytes" % (len(oa.LONG_CASES), total))
+    assert not missed, missed
+
+
 if __name__ == "__main__":
-    if "--geometry-only" in sys.argv:
+    if "--long-only" in sys.argv:
+        os.makedirs(OUT, exist_ok=True); long_cases()
+    elif "--geometry-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); geometry_cases()
     elif "--anchor-kat-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True); anchor_kat_cases()
